@@ -15,8 +15,17 @@ launch per phase -- because a launch lasts as long as its slowest chain, and the
 other twenty times instead of twice (same draws either way; 650 k against 625 k leapfrogs/s, profiles/r06_launch_size.txt).
 `--launch-steps 1` is rounds 1-6's one launch per step.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--config 1|2|3|4] [--full] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+
+A plain run sets up, warms up, times the K steps and prints the line.  --full adds everything else the benchmark measures, after the
+timed region: the CPU port on the host cores (cpu_baseline; configs[0]: beside every call), the 256-chain saturated point, and the side
+measurements (configs[0], configs[3], the configs[4] presets, configs[1] under two more seeds; with N > 1 the single-process run).
+--no-cpu-baseline, --no-saturated and --no-side leave parts of that out again.
+
+--dump-outputs DIR  after the timed steps, what the timed path handed its caller at the end of its last step, as float64 .npy files under
+              DIR (dump_outputs lists them; at most 64 MiB in all, larger outputs as a fixed seeded sample of their columns).  The inputs are
+              fixed by the arguments (committed data, seeded inits), so two builds can be compared file for file.
 
 `python bench.py --gpus N` with N > 1 and no launcher around it (WORLD_SIZE unset) starts its own N ranks -- it re-executes itself
 under `python -m torch.distributed.run --nnodes=1 --nproc-per-node N` on 127.0.0.1 with a free port, one rank per GPU over the "nccl"
@@ -27,7 +36,7 @@ these boxes only supports dmabuf IPC and RCCL's intra-node transport fails witho
 --config 1/2  2016 backtest, C = 8 chains per GPU (configs[1]; with N GPUs configs[2]: 8 N chains, one RCCL all-gather
               of the draws-of-interest for pooled R-hat / ESS, device buffers end to end)
 --config 0    the reference's own sampler calls as scripted (6 chains x (500 + 500), seed 1843: final_2016.R, final_2012.R, final_2008.R;
-              BASELINE's 4 x 500), each run to completion on the GPU and on the CPU port, side by side (one GPU)
+              BASELINE's 4 x 500), each run to completion on the GPU (one GPU); with --full the CPU port runs each as well, side by side
 --config 3    2008 + 2012 + 2016 backtests concurrently, 4 chains of each per GPU (32 each over 8 GPUs), three
               posteriors advancing together under potus_run_many
 --config 4    synthetic stress posterior (51 states x 600 days x 10 000 polls, D = 41 610), dense metric
@@ -87,6 +96,89 @@ def measured_traffic(kernel, sides=1):
         if d.get("kernel") == kernel and (kernel != "k_cl_run" or ("two clusters" in d.get("command", "")) == (sides == 2)):
             best = (f.name, d)
     return best
+
+
+# ------------------------------------------------------------------------------------------------ --dump-outputs
+DUMP_BUDGET_BYTES = 64 * 2 ** 20        # all files of one run together
+DUMP_SAMPLE_COLUMNS = 4096              # draws_sample: at most this many of the write array's model columns
+
+
+def _seeded_sample(n, k):
+    """k of range(n), sorted: the same k for the same (n, k) in every run and every build."""
+    return np.sort(np.random.default_rng(0).choice(n, size=k, replace=False)) if k < n else np.arange(n)
+
+
+def _fit(a, budget):
+    """`a` as float64; when it would take more than `budget` bytes, a fixed seeded sample of its last axis."""
+    a = np.ascontiguousarray(a, dtype=np.float64)
+    rows = a.size // max(a.shape[-1], 1)
+    k = max(int(budget // (8 * max(rows, 1))), 1)
+    return a if k >= a.shape[-1] else np.ascontiguousarray(a[..., _seeded_sample(a.shape[-1], k)])
+
+
+def _last_draws(h, cols, n_saved, n_last):
+    """[chains, n_last, len(cols)]: the write-array columns `cols` (sorted) of a handle's last n_last saved draws, taken on the device in
+    blocks of at most 256 MB (potus_write_array_device covers every saved draw of a column range) -- only the selection crosses to the host."""
+    import torch
+    dev, C_ = torch.device("cuda", h.opts.device), h.opts.chains
+    block = max(1, int(256e6 // (8 * n_saved * C_)))
+    out = []
+    for cb in range(int(cols[0]), int(cols[-1]) + 1, block):
+        ce = min(cb + block, int(cols[-1]) + 1)
+        sel = cols[(cols >= cb) & (cols < ce)] - cb
+        if len(sel) == 0:
+            continue
+        t = torch.empty((n_saved, C_, ce - cb), dtype=torch.float64, device=dev)
+        h.write_array_device(cb, ce, t)
+        out.append(t[n_saved - n_last:, :, torch.as_tensor(sel, device=dev)].cpu().numpy())
+        del t
+    return np.concatenate(out, axis=2).transpose(1, 0, 2)
+
+
+def dump_outputs(out_dir, handles, n_saved, n_last, diag=None, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: what the timed path handed its caller at the end of its last step, as float64 <name>.npy files in `out_dir`.
+    `handles` = [(prefix, handle)]; every handle writes
+      <prefix>sampler_params     [chains, draws, 7]  lp__, accept_stat__, stepsize__, treedepth__, n_leapfrog__, divergent__, energy__
+      <prefix>mu_b_T             [chains, draws, S]  mu_b[:, T] (stan:73)
+      <prefix>predicted_score_T  [chains, draws, S]  predicted_score[T, :] (stan:135)
+      <prefix>draws_sample       [chains, draws, k]  a fixed seeded sample of k of the write array's model columns (all of them if they fit)
+      <prefix>stepsize, <prefix>inv_metric  [chains], [chains, D]  the adaptation the warm-up left (the diagonal under a dense metric)
+    -- draws = the last n_last saved draws (the last step's; none when the run saved none) -- and `diag` = {prefix: (rhat, ess_bulk)} adds
+    <prefix>rhat and <prefix>ess_bulk.  Every file fits its share of `budget` (_fit); returns the bytes written."""
+    out_dir = Path(out_dir)
+    out_dir.mkdir(parents=True, exist_ok=True)
+    diag = diag or {}
+    share = budget / (len(handles) + len(diag))
+    draws = n_saved > 0 and n_last > 0
+    written = 0
+
+    def save(name, a, cap):
+        nonlocal written
+        a = _fit(a, cap)
+        np.save(out_dir / f"{name}.npy", a)
+        written += a.nbytes
+        return a.nbytes
+
+    for prefix, h in handles:
+        left = share
+        eps, minv = h.adaptation()
+        left -= save(prefix + "stepsize", eps, left)
+        if draws:
+            S, T = int(h.data["S"]), int(h.data["T"])
+            a_mu, a_ps = h.layout["mu_b"][0], h.layout["predicted_score"][0]
+            left -= save(prefix + "sampler_params", _last_draws(h, np.arange(7), n_saved, n_last), left)
+            left -= save(prefix + "mu_b_T", _last_draws(h, a_mu + S * (T - 1) + np.arange(S), n_saved, n_last), left)
+            left -= save(prefix + "predicted_score_T", _last_draws(h, a_ps + (T - 1) + T * np.arange(S), n_saved, n_last), left)
+        left -= save(prefix + "inv_metric", minv, left / 2 if draws else left)       # (the other half for the sample below)
+        if draws:
+            model_cols = h.n_cols - 7
+            k = min(model_cols, DUMP_SAMPLE_COLUMNS, int(left // (8 * h.opts.chains * n_last)))
+            if k > 0:
+                save(prefix + "draws_sample", _last_draws(h, 7 + _seeded_sample(model_cols, k), n_saved, n_last), left)
+    for prefix, (rh, es) in diag.items():
+        save(prefix + "rhat", rh, share / 2)
+        save(prefix + "ess_bulk", es, share / 2)
+    return written
 
 
 # ------------------------------------------------------------------------------------------------ N ranks
@@ -323,7 +415,7 @@ def single_process_line(args):
         done += g
         if done == warm_steps:
             t_warm_end = time.perf_counter()
-    ess, rhat, diag_s = None, None, 0.0
+    ess, rhat, diag_s, diag = None, None, 0.0, {}
     if ns >= 8:
         S, T = int(data["S"]), int(data["T"])
         a_mu, a_ps = hs[0].layout["mu_b"][0], hs[0].layout["predicted_score"][0]
@@ -333,8 +425,11 @@ def single_process_line(args):
                 a_ps + (T - 1) + T * (S - 1) + 1)             # predicted_score[T, s]: every T-th column
         parts.append((rp[::T], ep[::T]))
         diag_s = time.perf_counter() - td0
-        rhat, ess = float(np.nanmax(np.concatenate([p_[0] for p_ in parts]))), float(np.nanmin(np.concatenate([p_[1] for p_ in parts])))
+        diag = {f"{name}_": (np.concatenate([p_[0] for p_ in parts]), np.concatenate([p_[1] for p_ in parts]))}
+        rhat, ess = float(np.nanmax(diag[f"{name}_"][0])), float(np.nanmin(diag[f"{name}_"][1]))
     t1 = time.perf_counter()
+    if args.dump_outputs:       # lp__, mu_b[:, T], predicted_score[T, :] of the pooled chains: the columns the diagnostics ran on
+        dump_outputs(args.dump_outputs, [(f"{name}_handle{i}_", h) for i, h in enumerate(hs)], ns, min(chunk, ns), diag)
     elapsed, samp = t1 - t0, t1 - (t_warm_end or t0)
     lf = [h.total_leapfrogs() for h in hs]
     bpl = algorithmic_bytes_per_leapfrog(data, variant)
@@ -601,11 +696,20 @@ def main():
             help="ONE process, --gpus N handles on N devices under potus_run_many: the R-facing multi-GPU path")
     ap.add_argument("--no-side", action="store_true",
             help="skip the side measurements of configs[0], configs[3] and the configs[4] preset (default line only)")
+    ap.add_argument("--full", action="store_true",
+            help="after the timed region, also the CPU baseline, the saturated point and the side measurements (off: the headline only)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+            help="write what the timed path computed in its last step to DIR/<name>.npy (float64, at most 64 MiB; see dump_outputs)")
     args = ap.parse_args()
+    # a plain run does what its headline needs; --full adds the rest (the --no-* switches still leave parts of it out)
+    if not args.full:
+        args.no_cpu_baseline = args.no_saturated = args.no_side = True
 
     os.environ.setdefault("HSA_ENABLE_IPC_MODE_LEGACY", "0")      # before the first HIP call (module docstring)
     if args.gpus < 1:
         raise SystemExit("--gpus must be at least 1")
+    if args.dump_outputs and args.config == 0:
+        raise SystemExit("--dump-outputs: --config 0 runs the reference's calls one after another, there is no one timed path to dump")
     if args.single_process:
         if args.config not in (1, 2):
             raise SystemExit("--single-process runs configs[1] / configs[2]")
@@ -671,7 +775,7 @@ def main():
                           "config": {"workload": "configs[0]: the reference's sampler calls as scripted (final_2016.R:533-541: 6 chains "
                                                  "x (500 + 500), seed 1843; final_2012.R, "
                                                  "final_2008.R likewise; BASELINE's 4 x 500), each run to completion on the "
-                                                         "MI355X and on the CPU port; value = the 2016 call on the GPU; "
+                                                         f"MI355X{'' if args.no_cpu_baseline else ' and on the CPU port'}; value = the 2016 call on the GPU; "
                                                  "a step = `refresh` = 50 transitions"},
                           "runs": runs}), flush=True)
         parallel.barrier()
@@ -811,6 +915,11 @@ def main():
     kernel_ms_max = parallel.max_over_ranks(kernel_ms, coll_dev)
     samp_time = parallel.max_over_ranks(t1 - (t_warm_end or t0), coll_dev)
     status = [h.chain_status() for h in hs]
+    if args.dump_outputs:       # every rank its own chains (a rank suffix when there are several), the pooled diagnostics from rank 0
+        tag = f"rank{rank}_" if world > 1 else ""
+        dump_outputs(args.dump_outputs, [(f"{w[0]}_{tag}", h) for w, h in zip(work, hs)], ns, min(chunk, ns),
+                     {f"{w[0]}_": (dd["rhat"], dd["ess_bulk"]) for w, dd in zip(work, dev_diag) if dd is not None and rank == 0},
+                     DUMP_BUDGET_BYTES / world)
 
     if rank == 0:
         per_post = {}

@@ -467,7 +467,8 @@ def test_bench_single_process_gives_the_pooled_diagnostics_of_the_two_rank_run(t
     # ... and the two-rank run carries the single-process run as side.single_process (rank 0 starts it once both ranks have closed their samplers; the other
     # rank waits on the job's TCP store, not inside a collective: an RCCL barrier would hold compute units the child's cluster launches need)
     env = dict(os.environ, POTUS_DIST_BACKEND="gloo", MASTER_ADDR="127.0.0.1", MASTER_PORT="29543", POTUS_BENCH_FORCE_SP_SIDE="1", POTUS_BENCH_DEVICES=f"0,{second_device()}")
-    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", "29543", str(ROOT / "bench.py")] + common
+    cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node=2", "--master-addr", "127.0.0.1", "--master-port", "29543", str(ROOT / "bench.py")] + \
+          common + ["--full"]                                   # the side measurements run with --full only
     out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=600, cwd=str(ROOT))
     assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
     mp_ = json.loads([ln for ln in out.stdout.splitlines() if ln.startswith("{")][0])
@@ -501,6 +502,66 @@ def test_bench_starts_its_own_ranks(tmp_path):
     d = json.loads(lines[0])
     assert d["n_gpus"] == 2 and d["config"]["total_chains"] == 16 and d["config"]["baseline_config_index"] == 2 and "configs[2]" in d["config"]["workload"]
     assert d["config"]["posteriors"]["2016"]["pooled_draws"] == 16 * 10 and d["leapfrogs"] > 0
+
+
+def test_bench_dump_outputs_hold_the_last_steps_draws(cases, tmp_path):
+    """bench.dump_outputs on a handle of the small posterior: every per-draw file holds the LAST n_last saved draws of its columns -- equal to the
+    handle's own write_array (host path) of those rows, and not to its first ones -- and the adaptation files equal potus_get_adaptation."""
+    import importlib.util
+    from conftest import ROOT
+    spec = importlib.util.spec_from_file_location("bench_dump", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    data, variant = cases["small_full"]
+    h = Handle(data, variant, chains=3, num_warmup=10, num_samples=20, seed=1843)
+    h.init()
+    h.run(30)
+    bench.dump_outputs(tmp_path, [("s_", h)], 20, 10)
+    host = h.write_array(0, h.n_cols, 20).transpose(1, 0, 2)                     # [chain, draw, column]
+    S, T = int(data["S"]), int(data["T"])
+    a_mu, a_ps = h.layout["mu_b"][0], h.layout["predicted_score"][0]
+    k = np.load(tmp_path / "s_draws_sample.npy").shape[2]
+    for name, cols in (("sampler_params", np.arange(7)), ("mu_b_T", a_mu + S * (T - 1) + np.arange(S)),
+                       ("predicted_score_T", a_ps + (T - 1) + T * np.arange(S)), ("draws_sample", 7 + bench._seeded_sample(h.n_cols - 7, k))):
+        got = np.load(tmp_path / f"s_{name}.npy")
+        assert np.array_equal(got, host[:, 10:, cols]), name
+        assert not np.array_equal(got, host[:, :10, cols]), name
+    eps, minv = h.adaptation()
+    assert np.array_equal(np.load(tmp_path / "s_stepsize.npy"), eps) and np.array_equal(np.load(tmp_path / "s_inv_metric.npy"), minv)
+    h.close()
+
+
+def test_bench_plain_run_is_lean_and_dumps_the_same_outputs_twice(tmp_path):
+    """`bench.py --gpus 1 --steps K --warmup W` without --full: the headline line and nothing measured beside it (no CPU baseline, saturated point or
+    side runs); --steps sets the timed steps and ms_per_step is their time per step.  --dump-outputs: float64 .npy files within 64 MiB, the same bytes
+    from two runs of the same command, predicted_score[T, :] the inverse logit of mu_b[:, T] draw for draw (stan:137)."""
+    import json
+    import subprocess
+    import sys
+    from conftest import ROOT
+    env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "POTUS_DIST_BACKEND")}
+    lines, dirs = [], [tmp_path / "a", tmp_path / "b"]
+    for d in dirs:
+        cmd = [sys.executable, str(ROOT / "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--chunk", "10", "--dump-outputs", str(d)]
+        out = subprocess.run(cmd, capture_output=True, text=True, env=env, timeout=300, cwd=str(ROOT))
+        assert out.returncode == 0, out.stdout[-2000:] + out.stderr[-2000:]
+        got = [ln for ln in out.stdout.splitlines() if ln.startswith("{")]
+        assert len(got) == 1
+        lines.append(json.loads(got[0]))
+    line = lines[0]
+    assert line["metric"] == "leapfrog_steps_per_sec" and line["unit"] == "leapfrogs/s" and line["higher_is_better"] is True and line["dtype"] == "f64"
+    assert line["steps"] == 3 and line["config"]["iter_warmup"] == 10 and line["config"]["iter_sampling"] == 20
+    assert abs(line["ms_per_step"] - 1e3 * line["seconds"] / 3) <= 1e-9 * line["ms_per_step"]
+    assert not {"cpu_baseline", "saturated", "side"} & set(line) and line["leapfrogs"] == lines[1]["leapfrogs"]
+    names = sorted(p.name for p in dirs[0].glob("*.npy"))
+    assert names == sorted(p.name for p in dirs[1].glob("*.npy")) and "2016_draws_sample.npy" in names and "2016_rhat.npy" in names
+    assert sum((dirs[0] / n).stat().st_size for n in names) <= 64 * 2 ** 20
+    for n in names:
+        a, b = np.load(dirs[0] / n), np.load(dirs[1] / n)
+        assert a.dtype == np.float64 and a.tobytes() == b.tobytes(), n
+    sp, mu, ps = (np.load(dirs[0] / f"2016_{n}.npy") for n in ("sampler_params", "mu_b_T", "predicted_score_T"))
+    assert sp.shape == (8, 10, 7) and mu.shape == ps.shape == (8, 10, 51) and np.isfinite(sp).all()
+    assert np.allclose(ps, 1.0 / (1.0 + np.exp(-mu)), rtol=1e-10, atol=0)
 
 
 def test_rccl_collectives_on_device_buffers_one_rank():

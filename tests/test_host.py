@@ -49,23 +49,6 @@ def test_backtest_fixtures(cases, year, sizes):
     assert 0.48 < nat < 0.56                                                       # Obama two-party prior
 
 
-@pytest.mark.skipif(not Path("/root/reference/data").exists(), reason="reference CSVs only exist in the build container")
-@pytest.mark.parametrize("year", [2012, 2008])
-def test_dataprep_reproduces_backtest_fixtures(cases, year):
-    from us_potus_model_amd import dataprep
-    d = dataprep.build_backtest("/root/reference/data", year)["data"]
-    for k, v in cases[str(year)][0].items():
-        assert np.allclose(np.asarray(d[k], dtype=float), np.asarray(v, dtype=float), rtol=1e-12, atol=1e-14), k
-
-
-@pytest.mark.skipif(not Path("/root/reference/data").exists(), reason="reference CSVs only exist in the build container")
-def test_dataprep_reproduces_fixture(data_2016):
-    from us_potus_model_amd import dataprep
-    d = dataprep.build_2016("/root/reference/data")["data"]
-    for k, v in data_2016.items():
-        assert np.allclose(np.asarray(d[k], dtype=float), np.asarray(v, dtype=float), rtol=1e-12, atol=1e-14), k
-
-
 def test_make_positive_definite_and_cov_matrix():
     from us_potus_model_amd import dataprep
     m = dataprep.cov_matrix(4, 0.04, 0.9)
@@ -377,3 +360,48 @@ def test_side_measurements_keep_the_line_alive(monkeypatch):
     out = bench.side_measurements(1843, budget_s=10.0)                    # nothing fits a budget of ten seconds
     assert calls == [] and all("skipped" in out[k] for k in ("configs[0]", "configs[3]", "seed_1844", "seed_1845", "configs[4]_preset", "configs[4]_pooled",
                                                          "configs[4]_pooled_f32")) and "seeds" not in out
+
+
+def test_bench_dump_outputs_files_and_budget(tmp_path, monkeypatch):
+    """bench.py --dump-outputs without a GPU (the device-side reads of the write array faked, values that name their column, draw and chain): the files
+    of one handle, float64 and the same bytes from two calls; the last step's draws of the columns each file names; every file within its share of the
+    budget, a larger output as a fixed seeded sample of its columns; a run that saved no draws writes the adaptation only."""
+    import importlib.util
+    from types import SimpleNamespace
+    from conftest import GOLD
+    from us_potus_model_amd import dataprep
+    spec = importlib.util.spec_from_file_location("bench_mod3", ROOT / "bench.py")
+    bench = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(bench)
+    data = dataprep.load_npz(GOLD / "data_2016.npz")["data"]
+    lay, ncols = _abi.column_layout(data, "full")
+    C_, D, S, T = 8, _abi.num_params(data, "full"), int(data["S"]), int(data["T"])
+    h = SimpleNamespace(data=data, layout=lay, n_cols=ncols, opts=SimpleNamespace(chains=C_, device=0),
+                        adaptation=lambda: (np.full(C_, 0.1), np.arange(C_ * D, dtype=float).reshape(C_, D)))
+
+    def fake_last_draws(h_, cols, n_saved, n_last):       # column + draw / 1e4 + chain * 1e6
+        return (np.asarray(cols, float)[None, None, :] + 1e-4 * np.arange(n_saved - n_last, n_saved)[None, :, None]
+                + 1e6 * np.arange(C_)[:, None, None])
+
+    monkeypatch.setattr(bench, "_last_draws", fake_last_draws)
+    diag = {"2016_": (np.linspace(1.0, 1.01, 1 + S * T + S), np.linspace(100.0, 900.0, 1 + S * T + S))}
+    written = [bench.dump_outputs(tmp_path / d, [("2016_", h)], 1000, 100, diag) for d in ("a", "b")]
+    names = {f"2016_{n}.npy" for n in ("sampler_params", "mu_b_T", "predicted_score_T", "draws_sample", "stepsize", "inv_metric", "rhat", "ess_bulk")}
+    assert {p.name for p in (tmp_path / "a").glob("*.npy")} == names and written[0] == written[1] <= bench.DUMP_BUDGET_BYTES
+    for n in names:
+        a, b = np.load(tmp_path / "a" / n), np.load(tmp_path / "b" / n)
+        assert a.dtype == np.float64 and a.tobytes() == b.tobytes(), n
+    first = lambda n: np.round(np.load(tmp_path / "a" / n)[0, 0] - 0.09).astype(int)        # chain 0, draw 900: the columns a file holds
+    assert np.load(tmp_path / "a" / "2016_sampler_params.npy").shape == (C_, 100, 7) and (first("2016_sampler_params.npy") == np.arange(7)).all()
+    assert (first("2016_mu_b_T.npy") == lay["mu_b"][0] + S * (T - 1) + np.arange(S)).all()
+    assert (first("2016_predicted_score_T.npy") == lay["predicted_score"][0] + (T - 1) + T * np.arange(S)).all()
+    k = np.load(tmp_path / "a" / "2016_draws_sample.npy").shape[2]
+    assert 0 < k <= bench.DUMP_SAMPLE_COLUMNS and (first("2016_draws_sample.npy") == 7 + bench._seeded_sample(ncols - 7, k)).all()
+    assert np.array_equal(np.load(tmp_path / "a" / "2016_rhat.npy"), diag["2016_"][0]) and np.load(tmp_path / "a" / "2016_inv_metric.npy").shape == (C_, D)
+    # a budget of 1 MiB: the inverse metric as a seeded sample of its columns, the draws sample smaller still, the whole within the budget
+    assert bench.dump_outputs(tmp_path / "c", [("x_", h)], 1000, 100, None, budget=2 ** 20) <= 2 ** 20
+    im = np.load(tmp_path / "c" / "x_inv_metric.npy")
+    assert im.shape[1] < D and (im[0] == bench._seeded_sample(D, im.shape[1])).all()
+    assert np.load(tmp_path / "c" / "x_draws_sample.npy").shape[2] < k
+    bench.dump_outputs(tmp_path / "d", [("x_", h)], 0, 0)
+    assert {p.name for p in (tmp_path / "d").glob("*.npy")} == {"x_stepsize.npy", "x_inv_metric.npy"}
