@@ -36,6 +36,30 @@ potus_load <- function(path, call_path = NULL) {
   }
 }
 
+# potus_R_create on an R data list; iopts / dopts as in include/potus_hmc.h.  Returns the .C() result (handle, status).
+.potus_create <- function(data, variant, iopts, dopts) {
+  full <- variant == "full"
+  iv <- function(x, n) if (is.null(x)) integer(max(n, 1)) else as.integer(x)
+  dv <- function(x, n) if (is.null(x)) double(max(n, 1)) else as.double(x)
+  Ns <- as.integer(data$N_state_polls); Nn <- as.integer(data$N_national_polls)
+  dims <- as.integer(c(Nn, Ns, data$T, data$S, data$P, if (full) data$M else 0L, if (full) data$Pop else 0L,
+                       if (full) 0L else 1L))
+  scalars <- as.double(c(data$sigma_c, if (full) data$sigma_m else 0, if (full) data$sigma_pop else 0,
+                         data$sigma_measure_noise_national, data$sigma_measure_noise_state,
+                         if (full) data$sigma_e_bias else 0, data$random_walk_scale, data$mu_b_T_scale,
+                         data$polling_bias_scale))
+  .C("potus_R_create", dims,
+     iv(data$state, Ns), iv(data$day_state, Ns), iv(data$day_national, Nn), iv(data$poll_state, Ns),
+     iv(data$poll_national, Nn), iv(data$poll_mode_state, Ns), iv(data$poll_mode_national, Nn),
+     iv(data$poll_pop_state, Ns), iv(data$poll_pop_national, Nn),
+     iv(data$n_democrat_national, Nn), iv(data$n_two_share_national, Nn),
+     iv(data$n_democrat_state, Ns), iv(data$n_two_share_state, Ns),
+     dv(data$unadjusted_national, Nn), dv(data$unadjusted_state, Ns),
+     as.double(data$mu_b_prior), as.double(data$state_weights), scalars,
+     as.double(data$state_covariance_0),           # column-major, as R stores it
+     as.integer(iopts), as.double(dopts), handle = integer(1), status = integer(1))
+}
+
 # gpus: device ids; the chains are dealt to them in contiguous blocks (chain ids, hence RNG streams and draws, do not
 # depend on the number of GPUs) and all devices advance together under potus_R_run_many.
 potus_sample <- function(data, variant = c("full", "no_mode_adjustment"), seed = 1843, chains = 4,
@@ -53,35 +77,17 @@ potus_sample <- function(data, variant = c("full", "no_mode_adjustment"), seed =
   metric <- match.arg(metric)
   variant <- match.arg(variant)
   full <- variant == "full"
-  iv <- function(x, n) if (is.null(x)) integer(max(n, 1)) else as.integer(x)
-  dv <- function(x, n) if (is.null(x)) double(max(n, 1)) else as.double(x)
-  Ns <- as.integer(data$N_state_polls); Nn <- as.integer(data$N_national_polls)
-  dims <- as.integer(c(Nn, Ns, data$T, data$S, data$P, if (full) data$M else 0L, if (full) data$Pop else 0L,
-                       if (full) 0L else 1L))
-  scalars <- as.double(c(data$sigma_c, if (full) data$sigma_m else 0, if (full) data$sigma_pop else 0,
-                         data$sigma_measure_noise_national, data$sigma_measure_noise_state,
-                         if (full) data$sigma_e_bias else 0, data$random_walk_scale, data$mu_b_T_scale,
-                         data$polling_bias_scale))
   gpus <- as.integer(gpus)
   per <- rep(chains %/% length(gpus), length(gpus)) + (seq_along(gpus) <= chains %% length(gpus))   # chains per device
   first <- cumsum(c(0L, per))[seq_along(per)]
   handles <- integer(0); counts <- integer(0)
   for (g in seq_along(gpus)) {
     if (per[g] == 0L) next
-    res <- .C("potus_R_create", dims,
-              iv(data$state, Ns), iv(data$day_state, Ns), iv(data$day_national, Nn), iv(data$poll_state, Ns),
-              iv(data$poll_national, Nn), iv(data$poll_mode_state, Ns), iv(data$poll_mode_national, Nn),
-              iv(data$poll_pop_state, Ns), iv(data$poll_pop_national, Nn),
-              iv(data$n_democrat_national, Nn), iv(data$n_two_share_national, Nn),
-              iv(data$n_democrat_state, Ns), iv(data$n_two_share_state, Ns),
-              dv(data$unadjusted_national, Nn), dv(data$unadjusted_state, Ns),
-              as.double(data$mu_b_prior), as.double(data$state_weights), scalars,
-              as.double(data$state_covariance_0),           # column-major, as R stores it
-              as.integer(c(per[g], chain_id_offset + first[g], iter_warmup, iter_sampling, max_treedepth, gpus[g],
-                           as.integer(save_warmup), cus_per_chain, if (metric == "dense_e") 1L else 0L, twin,
-                           if (metric_storage == "f32") 1L else 0L, if (isTRUE(pooled_metric)) 1L else 0L)),
-              as.double(c(adapt_delta, 0.05, 0.75, 10, 1, init, seed)),   # the seed as a double: exact to 2^53
-              handle = integer(1), status = integer(1))
+    res <- .potus_create(data, variant,
+                         as.integer(c(per[g], chain_id_offset + first[g], iter_warmup, iter_sampling, max_treedepth, gpus[g],
+                                      as.integer(save_warmup), cus_per_chain, if (metric == "dense_e") 1L else 0L, twin,
+                                      if (metric_storage == "f32") 1L else 0L, if (isTRUE(pooled_metric)) 1L else 0L)),
+                         as.double(c(adapt_delta, 0.05, 0.75, 10, 1, init, seed)))   # the seed as a double: exact to 2^53
     .potus_check(res$status)
     .potus_check(.C("potus_R_init", res$handle, status = integer(1))$status)
     handles <- c(handles, res$handle); counts <- c(counts, per[g])
@@ -211,3 +217,53 @@ potus_backtest_scores <- function(fit, summary, ev, won, day = 0L) {
 }
 
 potus_free <- function(fit) invisible(lapply(fit$handles, function(h) .C("potus_R_destroy", h, status = integer(1))))
+
+# ---- simulation-based calibration (us_potus_model_amd/sbc.py is the same workflow in Python) ----
+# Prior predictive simulation of `data`'s design: list(q = [n_sims, D] unconstrained draws, n_democrat_state = [n_sims, N_state_polls],
+# n_democrat_national = [n_sims, N_national_polls]); simulation i is the same whatever n_sims / sim_offset it is asked with.
+potus_simulate_prior <- function(data, variant = c("full", "no_mode_adjustment"), n_sims = 100, seed = 1843, sim_offset = 0, device = 0) {
+  variant <- match.arg(variant)
+  res <- .potus_create(data, variant, c(1L, 0L, 0L, 0L, 10L, as.integer(device), 0L, 0L, 0L, -1L, 0L, 0L), c(0.8, 0.05, 0.75, 10, 1, 2, seed))
+  .potus_check(res$status)
+  on.exit(.C("potus_R_destroy", res$handle, status = integer(1)))
+  info <- .C("potus_R_num_columns", res$handle, D = integer(1), n_cols = integer(1), status = integer(1))
+  .potus_check(info$status)
+  Ns <- as.integer(data$N_state_polls); Nn <- as.integer(data$N_national_polls)
+  r <- .C("potus_R_simulate_prior", res$handle, as.double(seed), as.integer(c(n_sims, sim_offset)), q = double(n_sims * info$D),
+          ys = integer(max(n_sims * Ns, 1)), yn = integer(max(n_sims * Nn, 1)), status = integer(1))
+  .potus_check(r$status)
+  list(q = matrix(r$q, n_sims, info$D, byrow = TRUE), n_democrat_state = matrix(r$ys[seq_len(n_sims * Ns)], n_sims, Ns, byrow = TRUE),
+       n_democrat_national = matrix(r$yn[seq_len(n_sims * Nn)], n_sims, Nn, byrow = TRUE), D = info$D, n_cols = info$n_cols)
+}
+
+# SBC (Talts et al. 2018): n_sims replicates simulated from the prior, fitted as chains_per_sim chains each of ONE handle (one workgroup per
+# chain, diagonal metric), ranked on the device.  columns: 0-based output-row columns (>= 7), e.g. .potus_layout(fit)$mu_b$begin + ...
+# Returns list(ranks [n_sims, columns] (ties broken uniformly with R's RNG), L, failed [n_sims]: every count zero, i.e. no draw kept; with one
+# column a truth below every draw looks the same) -- test the ranks of the other replicates for uniformity, e.g. with chisq.test.
+potus_sbc <- function(data, variant = c("full", "no_mode_adjustment"), columns, n_sims = 100, chains_per_sim = 2, iter_warmup = 1000,
+                      iter_sampling = 1000, thin = 10, seed = 1843, device = 0) {
+  variant <- match.arg(variant)
+  sims <- potus_simulate_prior(data, variant, n_sims, seed, 0, device)
+  a <- min(columns); e <- max(columns) + 1L
+  cr <- .potus_create(data, variant, c(1L, 0L, 0L, 0L, 10L, as.integer(device), 0L, 0L, 0L, -1L, 0L, 0L), c(0.8, 0.05, 0.75, 10, 1, 2, seed))
+  .potus_check(cr$status)
+  tr <- .C("potus_R_constrain", cr$handle, as.double(t(sims$q)), as.integer(n_sims), as.integer(c(a, e)), out = double(n_sims * (e - a)), status = integer(1))
+  .C("potus_R_destroy", cr$handle, status = integer(1))
+  .potus_check(tr$status)
+  res <- .potus_create(data, variant, c(n_sims * chains_per_sim, 0L, iter_warmup, iter_sampling, 10L, as.integer(device), 0L, 1L, 0L, 0L, 0L, 0L),
+                       c(0.8, 0.05, 0.75, 10, 1, 2, seed))
+  .potus_check(res$status)
+  on.exit(.C("potus_R_destroy", res$handle, status = integer(1)))
+  .potus_check(.C("potus_R_set_datasets", res$handle, as.integer(n_sims), as.integer(t(sims$n_democrat_state)),
+                  as.integer(t(sims$n_democrat_national)), status = integer(1))$status)
+  .potus_check(.C("potus_R_init", res$handle, status = integer(1))$status)
+  .potus_check(.C("potus_R_run", res$handle, as.integer(iter_warmup + iter_sampling), status = integer(1))$status)
+  rk <- .C("potus_R_sbc_ranks", res$handle, tr$out, as.integer(c(a, e, thin)), less = integer(n_sims * (e - a)), equal = integer(n_sims * (e - a)),
+           L = integer(1), status = integer(1))
+  .potus_check(rk$status)
+  less <- matrix(rk$less, n_sims, e - a, byrow = TRUE)[, columns - a + 1L, drop = FALSE]
+  equal <- matrix(rk$equal, n_sims, e - a, byrow = TRUE)[, columns - a + 1L, drop = FALSE]
+  # a replicate whose chains failed (step-size search, initialisation) adds no draws: all its counts are zero
+  failed <- rowSums(less + equal) == 0
+  list(ranks = less + floor(runif(length(less)) * (equal + 1)), L = rk$L, failed = failed)
+}

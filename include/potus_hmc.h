@@ -314,6 +314,38 @@ int potus_dense_pool_finish(int handle, double n_total);
  * its passes are not part of potus_dense_timing's counts. */
 int potus_dense_check(int handle, int chain, int n_probe, double *out /*[2]*/);
 
+/* ---- simulation-based calibration (Talts et al. 2018; DESIGN.md "Simulation-based calibration") ----
+ * Many data sets in one handle: after potus_create and before potus_init, give n_datasets outcome vectors of the handle's polls
+ * ([n][N_state_polls] and [n][N_national_polls], caller's order, 0 <= y <= n_two_share); everything else in the data is shared.
+ * Chain c fits data set c / (chains / n_datasets).  Needs chains % n_datasets == 0, one workgroup per chain (cus_per_chain = 1,
+ * twin = 0) and the diagonal metric.  Per-chain calls (potus_get_draws, potus_write_array[_device], potus_chain_status,
+ * potus_get_adaptation, potus_draws_device_ptr) work unchanged; calls that pool all chains (potus_posterior_summary[_many],
+ * potus_diagnostics, potus_check_convergence, potus_extract_matrix, potus_write_stan_csv) refuse with POTUS_ERR_STATE.  A chain
+ * whose initialisation or step-size search fails does not fail potus_init / potus_run: potus_chain_status reports it, the
+ * iteration and saved-draw counts are those of the other chains. */
+int potus_set_datasets(int handle, int n_datasets, const int32_t *n_democrat_state, const int32_t *n_democrat_national);
+/* Prior predictive simulation: n_sims draws theta ~ prior (poll_model_2020.stan:116-128) on the unconstrained scale (q_out [n_sims][D];
+ * rho_e_bias ~ normal(0.7, 0.1) restricted to (0, 1), stored as logit(rho)) and y ~ binomial(n_two_share, inv_logit(logit_pi(theta)))
+ * (stan:85-113; exact sampler: inversion when n min(p, 1 - p) < 10, BTRS above) in the caller's poll order.  Any output may be null.
+ * Philox4x32-10 as the sampler's (counter = {index, purpose | aux << 8, iter, chain}, key = seed), purpose 6, chain = sim_offset + i + 1
+ * for simulation i, so a simulation's bytes do not depend on how simulations are batched:
+ *   standard normals   coordinates 2j, 2j+1 = the Box-Muller pair of (iter 0, aux 0, index j)
+ *   rho_e_bias         attempt a = 0, 1, ...: z = first normal of (iter 0, aux 1, index a), accepted when 0 < 0.7 + 0.1 z < 1
+ *                      (replaces coordinate rho_e_bias of the line above)
+ *   outcome of poll k  (k = state poll index, or N_state_polls + national poll index) attempt a: u = uniform (iter a, aux 2, index k);
+ *                      BTRS also v = uniform (iter a, aux 3, index k) */
+int potus_simulate_prior(int handle, uint64_t seed, int n_sims, int sim_offset, double *q_out /*[n_sims][D]*/,
+                         int32_t *n_democrat_state_out /*[n_sims][N_state_polls]*/, int32_t *n_democrat_national_out /*[n_sims][N_national_polls]*/);
+/* CmdStan output rows of arbitrary unconstrained points (rstan's constrain_pars): out [n][col_end - col_begin]; the sampler columns
+ * 0-6 of these rows are NaN. */
+int potus_constrain(int handle, const double *q /*[n][D]*/, int n, int col_begin, int col_end, double *out);
+/* SBC ranks on the device: for every data set d (a handle without potus_set_datasets is one) and column k of [col_begin, col_end)
+ * (col_begin >= POTUS_N_SAMPLER_COLS), less[d][k] / equal[d][k] = how many of the compared draws are below / equal to truth[d][k];
+ * the compared draws are every thin-th post-warm-up saved draw (the first, the (thin+1)-th, ...) of every chain of the data set, *L of
+ * them per data set.  Chains that failed (potus_chain_status != 0) add nothing.  No draws x columns block is built. */
+int potus_sbc_ranks(int handle, const double *truth /*[n_datasets][ncols]*/, int col_begin, int col_end, int thin, int32_t *less /*[n_datasets][ncols]*/,
+                    int32_t *equal, int *L);
+
 /* ---- .C()-callable wrappers (int* / double* / char** only) ---- */
 void potus_R_create(int *dims /*[8]: N_nat,N_state,T,S,P,M,Pop,variant*/,
                     int *state, int *day_state, int *day_national, int *poll_state,
@@ -344,6 +376,11 @@ void potus_R_check_convergence(int *handles, int *n_handles, double *limits /*[2
 void potus_R_backtest_scores(double *state_out, int *dims /*[3]: T, S, day*/, double *ev, int *won, double *out /*[3]*/, int *status);
 void potus_R_last_error(char **buf, int *len);
 void potus_R_destroy(int *handle, int *status);
+void potus_R_set_datasets(int *handle, int *n_datasets, int *n_democrat_state, int *n_democrat_national, int *status);
+void potus_R_simulate_prior(int *handle, double *seed, int *dims /*[2]: n_sims, sim_offset*/, double *q_out, int *n_democrat_state_out,
+                            int *n_democrat_national_out, int *status);
+void potus_R_sbc_ranks(int *handle, double *truth, int *cols /*[3]: col_begin, col_end, thin*/, int *less, int *equal, int *L, int *status);
+void potus_R_constrain(int *handle, double *q, int *n, int *cols /*[2]: col_begin, col_end*/, double *out, int *status);
 
 #ifdef __cplusplus
 }

@@ -834,77 +834,280 @@ struct WAParams {
   double sigma_ns, sigma_nn;
   int out_stride;
 };
-__global__ __launch_bounds__(256) void k_write_array(const DevModel *Mg, WAParams W) {
-  const DevModel M = *Mg;
-  __shared__ double s_bT[64], s_pb[64], s_misc[4];
+// One full CmdStan output row (ncols doubles) from a draw's sampler columns and unconstrained point src[0 .. 7 + D); src must not
+// alias row.  Called by every thread of a 256-thread workgroup; s_bT / s_pb hold 64 doubles, s_misc 4 (LDS).  Shared by
+// k_write_array, k_simulate_prior and k_sbc_ranks.
+__device__ __forceinline__ void wa_build_row(const DevModel &M, const double *src, double *row, double *s_bT, double *s_pb, double *s_misc) {
   const int tid = threadIdx.x, S = M.S, T = M.T, D = M.D;
-  double *row = W.scratch + (size_t)blockIdx.x * W.ncols;
   const int o_par = POTUS_N_SAMPLER_COLS;
   const int o_mub = o_par + D, o_muc = o_mub + S * T;
   const int o_mum = o_muc + M.P, o_mupop = o_mum + (M.full ? M.M : 0), o_eb = o_mupop + (M.full ? M.Pop : 0);
   const int o_pb = o_eb + (M.full ? T : 0), o_nat = o_pb + S, o_natpb = o_nat + T, o_srho = o_natpb + 1;
   const int o_etas = o_srho + (M.full ? 1 : 0), o_etan = o_etas + M.Ns, o_gq = o_etan + M.Nn;
+  const double *q = src + POTUS_N_SAMPLER_COLS;
+  for (int i = tid; i < POTUS_N_SAMPLER_COLS + D; i += 256) row[i] = src[i];
+  __syncthreads();
+  double *Ct = row + o_gq; // suffix sums, staged where predicted_score will go
+  if (tid < S) {
+    double run = 0.0;
+    Ct[tid + S * (T - 1)] = 0.0;
+    for (int t = T - 2; t >= 0; t--) { run += q[M.o_Z + tid + S * t]; Ct[tid + S * t] = run; }
+    double bT = M.mat[M.m_prior + tid], pb = 0.0;
+    for (int k = 0; k <= tid; k++) { bT += M.mat[M.m_LT + tid * S + k] * q[M.o_zT + k]; pb += M.mat[M.m_LB + tid * S + k] * q[M.o_zb + k]; }
+    s_bT[tid] = bT; s_pb[tid] = pb; row[o_pb + tid] = pb;
+  }
+  if (tid == 64 && M.full) {
+    const double mue = 0.02 * q[M.o_mue], rho = d_inv_logit(q[M.o_rho]), srho = sqrt(1.0 - rho * rho) * M.sigma_e;
+    row[o_par + M.o_mue] = mue; row[o_par + M.o_rho] = rho; row[o_srho] = srho;
+    double e = q[M.o_ze] * M.sigma_e;
+    row[o_eb] = e;
+    for (int t = 1; t < T; t++) { e = mue + rho * (e - mue) + q[M.o_ze + t] * srho; row[o_eb + t] = e; }
+  }
+  for (int i = tid; i < M.P; i += 256) row[o_muc + i] = q[M.o_c + i] * M.sigma_c;
+  if (M.full) {
+    for (int i = tid; i < M.M; i += 256) row[o_mum + i] = q[M.o_m + i] * M.sigma_m;
+    for (int i = tid; i < M.Pop; i += 256) row[o_mupop + i] = q[M.o_pop + i] * M.sigma_pop;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < S * T; idx += 256) {
+    const int s = idx % S, t = idx / S;
+    double a = s_bT[s];
+    const double *Lrow = M.mat + s * M.SP, *Cc = Ct + S * t;
+    for (int k = 0; k <= s; k++) a += Lrow[k] * Cc[k];
+    row[o_mub + idx] = a;
+  }
+  if (tid == 0) { double a = 0.0; for (int s = 0; s < S; s++) a += s_pb[s] * M.mat[M.m_w + s]; s_misc[0] = a; row[o_natpb] = a; }
+  __syncthreads();
+  for (int t = tid; t < T; t += 256) {
+    double a = 0.0;
+    for (int s = 0; s < S; s++) a += row[o_mub + s + S * t] * M.mat[M.m_w + s];
+    row[o_nat + t] = a;
+  }
+  __syncthreads();
+  for (int i = tid; i < M.Npoll; i += 256) {
+    const int s = M.pi[i], t = M.pi[M.Npad + i], qi = M.pi[5 * M.Npad + i];
+    const bool nat = s == S;
+    double eta = (nat ? row[o_nat + t] : row[o_mub + s + S * t]) + row[o_muc + M.pi[2 * M.Npad + i]];
+    if (M.full) eta += row[o_mum + M.pi[3 * M.Npad + i]] + row[o_mupop + M.pi[4 * M.Npad + i]] + M.pd[2 * M.Npad + i] * row[o_eb + t];
+    eta += q[qi] * M.pd[3 * M.Npad + i] + (nat ? s_misc[0] : s_pb[s]);
+    if (nat) row[o_etan + (qi - M.o_nn)] = eta; else row[o_etas + (qi - M.o_ns)] = eta;
+  }
+  __syncthreads();
+  for (int idx = tid; idx < S * T; idx += 256) { // predicted_score[t,s] = inv_logit(mu_b[s,t]) (stan:135-139)
+    const int t = idx % T, s = idx / T;
+    row[o_gq + idx] = d_inv_logit(row[o_mub + s + S * t]);
+  }
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(256) void k_write_array(const DevModel *Mg, WAParams W) {
+  const DevModel M = *Mg;
+  __shared__ double s_bT[64], s_pb[64], s_misc[4];
+  const int tid = threadIdx.x;
+  double *row = W.scratch + (size_t)blockIdx.x * W.ncols;
   for (int d = blockIdx.x; d < W.n_saved * W.chains; d += gridDim.x) {
     const int iter = d / W.chains, chain = d % W.chains;
     const double *src = W.draws + ((size_t)chain * W.n_save_max + iter) * W.row;
-    const double *q = src + POTUS_N_SAMPLER_COLS;
-    for (int i = tid; i < POTUS_N_SAMPLER_COLS + D; i += 256) row[i] = src[i];
-    __syncthreads();
-    double *Ct = row + o_gq; // suffix sums, staged where predicted_score will go
-    if (tid < S) {
-      double run = 0.0;
-      Ct[tid + S * (T - 1)] = 0.0;
-      for (int t = T - 2; t >= 0; t--) { run += q[M.o_Z + tid + S * t]; Ct[tid + S * t] = run; }
-      double bT = M.mat[M.m_prior + tid], pb = 0.0;
-      for (int k = 0; k <= tid; k++) { bT += M.mat[M.m_LT + tid * S + k] * q[M.o_zT + k]; pb += M.mat[M.m_LB + tid * S + k] * q[M.o_zb + k]; }
-      s_bT[tid] = bT; s_pb[tid] = pb; row[o_pb + tid] = pb;
-    }
-    if (tid == 64 && M.full) {
-      const double mue = 0.02 * q[M.o_mue], rho = d_inv_logit(q[M.o_rho]), srho = sqrt(1.0 - rho * rho) * M.sigma_e;
-      row[o_par + M.o_mue] = mue; row[o_par + M.o_rho] = rho; row[o_srho] = srho;
-      double e = q[M.o_ze] * M.sigma_e;
-      row[o_eb] = e;
-      for (int t = 1; t < T; t++) { e = mue + rho * (e - mue) + q[M.o_ze + t] * srho; row[o_eb + t] = e; }
-    }
-    for (int i = tid; i < M.P; i += 256) row[o_muc + i] = q[M.o_c + i] * M.sigma_c;
-    if (M.full) {
-      for (int i = tid; i < M.M; i += 256) row[o_mum + i] = q[M.o_m + i] * M.sigma_m;
-      for (int i = tid; i < M.Pop; i += 256) row[o_mupop + i] = q[M.o_pop + i] * M.sigma_pop;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < S * T; idx += 256) {
-      const int s = idx % S, t = idx / S;
-      double a = s_bT[s];
-      const double *Lrow = M.mat + s * M.SP, *Cc = Ct + S * t;
-      for (int k = 0; k <= s; k++) a += Lrow[k] * Cc[k];
-      row[o_mub + idx] = a;
-    }
-    if (tid == 0) { double a = 0.0; for (int s = 0; s < S; s++) a += s_pb[s] * M.mat[M.m_w + s]; s_misc[0] = a; row[o_natpb] = a; }
-    __syncthreads();
-    for (int t = tid; t < T; t += 256) {
-      double a = 0.0;
-      for (int s = 0; s < S; s++) a += row[o_mub + s + S * t] * M.mat[M.m_w + s];
-      row[o_nat + t] = a;
-    }
-    __syncthreads();
-    for (int i = tid; i < M.Npoll; i += 256) {
-      const int s = M.pi[i], t = M.pi[M.Npad + i], qi = M.pi[5 * M.Npad + i];
-      const bool nat = s == S;
-      double eta = (nat ? row[o_nat + t] : row[o_mub + s + S * t]) + row[o_muc + M.pi[2 * M.Npad + i]];
-      if (M.full) eta += row[o_mum + M.pi[3 * M.Npad + i]] + row[o_mupop + M.pi[4 * M.Npad + i]] + M.pd[2 * M.Npad + i] * row[o_eb + t];
-      eta += q[qi] * M.pd[3 * M.Npad + i] + (nat ? s_misc[0] : s_pb[s]);
-      if (nat) row[o_etan + (qi - M.o_nn)] = eta; else row[o_etas + (qi - M.o_ns)] = eta;
-    }
-    __syncthreads();
-    for (int idx = tid; idx < S * T; idx += 256) { // predicted_score[t,s] = inv_logit(mu_b[s,t]) (stan:135-139)
-      const int t = idx % T, s = idx / T;
-      row[o_gq + idx] = d_inv_logit(row[o_mub + s + S * t]);
-    }
-    __syncthreads();
+    wa_build_row(M, src, row, s_bT, s_pb, s_misc);
     const int nsel = W.col_end - W.col_begin;
     double *dst = W.out + (size_t)d * W.out_stride;
     for (int i = tid; i < nsel; i += 256) dst[i] = row[W.col_begin + i];
     __syncthreads();
+  }
+}
+
+// ------------------------------------------------------------------------ prior predictive simulation and SBC ranks
+// Offsets of the two logit_pi blocks in an output row (wa_build_row's layout).
+__device__ __forceinline__ int wa_o_etas(const DevModel &M) {
+  return POTUS_N_SAMPLER_COLS + M.D + M.S * M.T + M.P + (M.full ? M.M + M.Pop + M.T : 0) + M.S + M.T + 1 + (M.full ? 1 : 0);
+}
+
+// y ~ binomial(n, p) with p = inv_logit(eta), exactly: inversion (sequential search from 0) when n min(p, 1 - p) < 10, else BTRS (Hoermann
+// 1993, "The generation of binomial random variates", with the exact log-ratio lgamma form of its acceptance bound).  Uniforms of attempt a
+// come from Philox counter (iter a, RNG_PRIOR, aux 2 / 3, index idx).
+__device__ int binomial_logit_draw(const RngKey &key, uint32_t idx, int n, double eta) {
+  if (n <= 0) return 0;
+  const double e = exp(-fabs(eta));
+  const double p = e / (1.0 + e), q = 1.0 / (1.0 + e);          // p = min(pi, 1 - pi), computed without cancellation
+  const bool flip = eta > 0;
+  int k = 0;
+  if ((double)n * p < 10.0) {
+    const double s = p / q, a = (n + 1) * s, r0 = pow(q, (double)n);
+    for (uint32_t att = 0; att < 64; att++) {
+      double u = rng_uniform(key, att, RNG_PRIOR, 2, idx), r = r0;
+      int x = 0;
+      while (u > r && x <= n) { u -= r; x++; r *= a / x - s; }
+      k = x;
+      if (x <= n) break;                                            // (x > n: the rounding of the cumulative sum ran out; draw again)
+    }
+    k = min(k, n);
+  } else {
+    const double spq = sqrt(n * p * q), b = 1.15 + 2.53 * spq, a = -0.0873 + 0.0248 * b + 0.01 * p, c = n * p + 0.5;
+    const double vr = 0.92 - 4.2 / b, alpha = (2.83 + 5.1 / b) * spq, lpq = log(p / q), m = floor((n + 1) * p);
+    const double h = lgamma(m + 1.0) + lgamma(n - m + 1.0);
+    for (uint32_t att = 0; att < 4096; att++) {
+      const double u = rng_uniform(key, att, RNG_PRIOR, 2, idx) - 0.5, v0 = rng_uniform(key, att, RNG_PRIOR, 3, idx);
+      const double us = 0.5 - fabs(u), kk = floor((2.0 * a / us + b) * u + c);
+      if (kk < 0.0 || kk > (double)n) continue;
+      k = (int)kk;
+      if (us >= 0.07 && v0 <= vr) break;
+      const double v = log(v0 * alpha / (a / (us * us) + b));
+      if (v <= h - lgamma(kk + 1.0) - lgamma(n - kk + 1.0) + (kk - m) * lpq) break;
+    }
+  }
+  return flip ? n - k : k;
+}
+
+struct SimParams {
+  double *qrow;        // [n][7 + D]: sampler columns zero, then the drawn unconstrained point
+  double *scratch;     // [gridDim.x][ncols]
+  int *y;              // [n][Ns + Nn]: state polls, then national polls, in the caller's order
+  int n, ncols, sim_offset;
+  unsigned seed_lo, seed_hi;
+};
+// One workgroup per simulation: theta ~ prior (stan:116-128 on the unconstrained scale), logit_pi by the row builder, y ~ binomial.
+// Counters (key chain field = sim_offset + sim + 1, so a simulation's bytes do not depend on the batching) are listed in potus_hmc.h.
+__global__ __launch_bounds__(256) void k_simulate_prior(const DevModel *Mg, SimParams P) {
+  const DevModel M = *Mg;
+  __shared__ double s_bT[64], s_pb[64], s_misc[4];
+  const int tid = threadIdx.x, D = M.D, Ns = M.Ns;
+  const int o_etas = wa_o_etas(M), o_etan = o_etas + Ns;
+  double *row = P.scratch + (size_t)blockIdx.x * P.ncols;
+  for (int sim = blockIdx.x; sim < P.n; sim += gridDim.x) {
+    const RngKey key{P.seed_lo, P.seed_hi, (uint32_t)(P.sim_offset + sim + 1)};
+    double *src = P.qrow + (size_t)sim * (POTUS_N_SAMPLER_COLS + D);
+    double *q = src + POTUS_N_SAMPLER_COLS;
+    if (tid < POTUS_N_SAMPLER_COLS) src[tid] = 0.0;
+    for (int j = tid; 2 * j < D; j += 256) {
+      double z0, z1;
+      rng_normal_pair(key, 0, RNG_PRIOR, 0, (uint32_t)j, z0, z1);
+      q[2 * j] = z0;
+      if (2 * j + 1 < D) q[2 * j + 1] = z1;
+    }
+    __syncthreads();
+    if (M.full && tid == 0) {   // rho_e_bias ~ normal(0.7, 0.1) restricted to (0, 1): rejection; P(reject) = 1.3e-3
+      double rho = 0.7;
+      for (uint32_t att = 0; att < 256; att++) {
+        double z0, z1;
+        rng_normal_pair(key, 0, RNG_PRIOR, 1, att, z0, z1);
+        const double r = 0.7 + 0.1 * z0;
+        if (r > 0.0 && r < 1.0) { rho = r; break; }
+      }
+      q[M.o_rho] = log(rho / (1.0 - rho));
+    }
+    __syncthreads();
+    wa_build_row(M, src, row, s_bT, s_pb, s_misc);
+    for (int i = tid; i < M.Npoll; i += 256) {
+      const int qi = M.pi[5 * M.Npad + i];
+      const bool nat = M.pi[i] == M.S;
+      const int j = nat ? qi - M.o_nn : qi - M.o_ns;
+      const uint32_t idx = (uint32_t)(nat ? Ns + j : j);
+      P.y[(size_t)sim * M.Npoll + idx] = binomial_logit_draw(key, idx, (int)M.pd[M.Npad + i], row[nat ? o_etan + j : o_etas + j]);
+    }
+    __syncthreads();
+  }
+}
+
+struct RankParams {
+  const double *draws; // [chains][n_save_max][row]
+  int chains, n_save_max, row, ncols, col_begin, col_end;
+  int first, thin, L, chains_per_ds;   // saved draws first, first + thin, ... (L of them) of every chain
+  const double *truth; // [n_datasets][col_end - col_begin]
+  const int *skip;     // [chains]: nonzero = the chain failed, its counts stay zero
+  double *scratch;     // [gridDim.x][ncols]
+  int *less, *equal;   // [chains][col_end - col_begin]
+};
+// One workgroup per chain: each compared draw's output row is rebuilt (wa_build_row) and compared with the truth of the chain's data
+// set; a thread owns the same columns for the whole launch, so its counts are plain loads and stores.
+__global__ __launch_bounds__(256) void k_sbc_ranks(const DevModel *Mg, RankParams P) {
+  const DevModel M = *Mg;
+  __shared__ double s_bT[64], s_pb[64], s_misc[4];
+  const int tid = threadIdx.x, nsel = P.col_end - P.col_begin;
+  double *row = P.scratch + (size_t)blockIdx.x * P.ncols;
+  for (int chain = blockIdx.x; chain < P.chains; chain += gridDim.x) {
+    const double *tr = P.truth + (size_t)(chain / P.chains_per_ds) * nsel;
+    int *ls = P.less + (size_t)chain * nsel, *eq = P.equal + (size_t)chain * nsel;
+    for (int i = tid; i < nsel; i += 256) { ls[i] = 0; eq[i] = 0; }
+    if (P.skip[chain]) continue;
+    for (int j = 0; j < P.L; j++) {
+      const double *src = P.draws + ((size_t)chain * P.n_save_max + P.first + (size_t)j * P.thin) * P.row;
+      wa_build_row(M, src, row, s_bT, s_pb, s_misc);
+      for (int i = tid; i < nsel; i += 256) {
+        const double v = row[P.col_begin + i], t = tr[i];
+        ls[i] += v < t ? 1 : 0;
+        eq[i] += v == t ? 1 : 0;
+      }
+      __syncthreads();
+    }
+  }
+}
+// Counts per data set: [n_datasets][nsel] = sum over the data set's chains.
+__global__ __launch_bounds__(256) void k_sbc_reduce(const int *less, const int *equal, int n_ds, int chains_per_ds, int nsel, int *less_out, int *equal_out) {
+  for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < (long long)n_ds * nsel; k += (long long)gridDim.x * 256) {
+    const int ds = (int)(k / nsel), i = (int)(k % nsel);
+    int a = 0, b = 0;
+    for (int c = ds * chains_per_ds; c < (ds + 1) * chains_per_ds; c++) { a += less[(size_t)c * nsel + i]; b += equal[(size_t)c * nsel + i]; }
+    less_out[k] = a; equal_out[k] = b;
+  }
+}
+
+// Many data sets in one handle (potus_set_datasets): Mg = [n_datasets] models that differ only in the poll outcomes (pd), chain c
+// uses data set c / chains_per_ds.  One workgroup per chain, diagonal metric.  The bodies are those of k_init / k_run line for line
+// with the chain's model in place of Mg: written out rather than shared, so that k_init and k_run stay the instructions they were.
+__global__ __launch_bounds__(PT_THREADS) void k_init_ds(const DevModel *Mg, const RunParams *Rg, const double *q0, int chains_per_ds) {
+  const int chain = blockIdx.x;
+  CMp M = (CMp)(Mg + chain / chains_per_ds);
+  CRp R = (CRp)Rg;
+  Chain c = make_chain(M, R, chain);
+  c.pst = model_setup_lds(M, c.lds);
+  const int tid = c.tid;
+  gdp Q0 = c.vec(V_QC), G0 = c.vec(V_GC), minv = c.vec(V_MINV), mean = c.vec(V_WMEAN), m2 = c.vec(V_WM2);
+  for (int i = tid; i < c.D; i += PT_THREADS) { minv[i] = 1.0; mean[i] = 0.0; m2[i] = 0.0; }
+  if (tid == 0) {
+    gsc sc = c.sc;
+    sc->nom_eps = R->stepsize; sc->mu = log(10.0 * R->stepsize); sc->s_bar = 0; sc->x_bar = 0; sc->ad_counter = 0;
+    sc->wf_n = 0; sc->total_leapfrogs = 0; sc->iter = 0; sc->status = 0; sc->n_divergent = 0; sc->saved = 0; sc->leaves_run = 0; sc->spec_limit = 0x7f7f7f7f;
+    sc->win_counter = 0; sc->win_size = R->window; sc->win_next = R->init_buffer + R->window - 1;
+  }
+  __syncthreads();
+  bool ok = false;
+  const double radius = R->init_radius;
+  for (uint32_t attempt = 0; attempt < 100 && !ok; attempt++) {
+    for (int i = tid; i < c.D; i += PT_THREADS) {
+      if (q0) Q0[i] = as_g(q0)[(size_t)chain * c.D + i];
+      else Q0[i] = radius * (2.0 * rng_uniform(c.key, PT_ITER_PRE, RNG_INITS, attempt, (uint32_t)i) - 1.0);
+    }
+    __syncthreads();
+    PlainPolicy pol{c.st, c.st, c.soff(V_QC), c.soff(V_GC), {0}};
+    const double lp = model_pass(M, c.lds, c.pst, pol);
+    double bad[1] = {0.0};
+    for (int i = tid; i < c.D; i += PT_THREADS) bad[0] += isfinite(G0[i]) ? 0.0 : 1.0;
+    block_sum(bad, c.red(), tid);
+    ok = isfinite(lp) && bad[0] == 0.0;
+    if (tid == 0 && ok) c.sc->lp_cur = lp;
+    __syncthreads();
+    if (q0) break;
+  }
+  if (!ok) { if (tid == 0) c.sc->status = POTUS_ERR_INIT; return; }
+  init_stepsize(c, PT_ITER_PRE);
+  if (tid == 0 && R->num_warmup == 0) c.sc->nom_eps = exp(c.sc->x_bar); // engage+disengage: complete_adaptation
+}
+
+__global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, const RunParams *Rg, int n_iter, int chains_per_ds) {
+  const int chain = blockIdx.x;
+  const DevModel *Mg = Mg_all + chain / chains_per_ds;
+  CMp M = (CMp)Mg;
+  CRp R = (CRp)Rg;
+  Chain c = make_chain(M, R, chain);
+  if (c.sc->status != 0) return;
+  c.pst = model_setup_lds(M, c.lds);
+  const int total = R->num_warmup + R->num_samples;
+  for (int k = 0; k < n_iter; k++) {
+    const int it = c.sc->iter;
+    if (it >= total) break;
+    cold_transition_begin(Mg, Rg, chain, (uint32_t)it);
+    transition_tree(c, (uint32_t)it);
+    cold_transition_end(Mg, Rg, chain, (uint32_t)it);
   }
 }
 
@@ -1070,6 +1273,10 @@ struct Sampler {
   long long mv_calls = 0, mv_bytes = 0, dn_rounds = 0, dn_pass_bytes[2] = {0, 0};   // bytes per pass at DN_RB rows per workgroup / at the handle's DnParams::rb
   double we_cov_ms = 0, we_chol_ms = 0, we_eps_ms = 0;   // window ends: covariance, factorisation, init_stepsize (host clock around synchronised sections)
   int we_count = 0;
+  // potus_set_datasets: n_ds models that differ only in the poll outcomes (0: one data set, dM)
+  int n_ds = 0;
+  DevModel *dMs = nullptr;
+  int chains_per_ds() const { return n_ds ? R.chains / n_ds : R.chains; }
 };
 
 std::mutex g_mu;
@@ -1100,6 +1307,14 @@ Sampler *get(int h) {
   std::lock_guard<std::mutex> lk(g_mu);
   if (h < 0 || h >= (int)g_handles.size()) return nullptr;
   return g_handles[h];
+}
+
+// Calls that pool every chain of a handle into one posterior: a handle with several data sets holds several posteriors
+int refuse_many_datasets(const Sampler *sp, const char *what) {
+  if (!sp->n_ds) return 0;
+  return fail(POTUS_ERR_STATE, "%s pools all chains of a handle, which holds %d data sets (potus_set_datasets): slice the chains per data set "
+                               "(potus_get_draws / potus_write_array, chains d * %d .. (d + 1) * %d - 1) or use potus_sbc_ranks", what, sp->n_ds,
+              sp->chains_per_ds(), sp->chains_per_ds());
 }
 
 // One owner for every temporary device buffer of a call: freed on every return path.
@@ -1319,6 +1534,8 @@ int set_lds_attr(Sampler *sp) {
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_init), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp->lds_bytes));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_run), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp->lds_bytes));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_run_twin), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp->lds_bytes));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_init_ds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp->lds_bytes));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_run_ds), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp->lds_bytes));
   return 0;
 }
 
@@ -1633,6 +1850,8 @@ int check_chains(Sampler *sp) {
     }
   }
   for (int c = 0; c < sp->R.chains; c++) {
+    // many data sets: a replicate whose chain found no start or step size is reported by potus_chain_status, the others go on
+    if (sp->n_ds && (sc[c].status == POTUS_ERR_INIT || sc[c].status == POTUS_ERR_STEPSIZE)) continue;
     if (sc[c].status == POTUS_ERR_INIT) return fail(POTUS_ERR_INIT, "chain %d: no finite initial log density/gradient after 100 attempts", c + 1);
     if (sc[c].status == POTUS_ERR_STEPSIZE) return fail(POTUS_ERR_STEPSIZE, "chain %d: the step-size search left (0, 1e7) -- the posterior is improper or the gradient is wrong (Stan throws here)", c + 1);
     if (sc[c].status == POTUS_ERR_WATCHDOG) return fail(POTUS_ERR_WATCHDOG, "chain %d: cluster launch abandoned (watchdog)", c + 1);
@@ -2409,7 +2628,10 @@ int potus_init(int handle, const double *q0) {
                                            (const ClModel *)sp->dCL, (const RunParams *)sp->dR, (const double *)dq0, lid)
     CL_DISPATCH(sp->cl_dw, POTUS_CALL);
 #undef POTUS_CALL
-  } else
+  } else if (sp->n_ds)
+    hipLaunchKernelGGL(k_init_ds, dim3(sp->R.chains), dim3(PT_THREADS), sp->lds_bytes, sp->stream, (const DevModel *)sp->dMs, (const RunParams *)sp->dR, (const double *)dq0,
+                       sp->chains_per_ds());
+  else
     hipLaunchKernelGGL(k_init, dim3(sp->R.chains * sp->sides()), dim3(PT_THREADS), sp->lds_bytes, sp->stream, (const DevModel *)sp->dM, (const RunParams *)sp->dR, (const double *)dq0);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(sp->stream));
@@ -2442,6 +2664,9 @@ int run_launch(RunTicket &t, int n_iter) {
   } else if (sp->twin)
     hipLaunchKernelGGL(k_run_twin, dim3(2 * sp->R.chains), dim3(PT_THREADS), sp->lds_bytes, sp->stream, (const DevModel *)sp->dM, (const RunParams *)sp->dR, n_iter,
                        ++sp->launch_id);
+  else if (sp->n_ds)
+    hipLaunchKernelGGL(k_run_ds, dim3(sp->R.chains), dim3(PT_THREADS), sp->lds_bytes, sp->stream, (const DevModel *)sp->dMs, (const RunParams *)sp->dR, n_iter,
+                       sp->chains_per_ds());
   else
     hipLaunchKernelGGL(k_run, dim3(sp->R.chains), dim3(PT_THREADS), sp->lds_bytes, sp->stream, (const DevModel *)sp->dM, (const RunParams *)sp->dR, n_iter);
   HIP_TRY(hipGetLastError());
@@ -2543,9 +2768,9 @@ int potus_iterations_done(int handle, int *n) {
   HIP_TRY(hipSetDevice(sp->device));
   std::vector<ChainScalars> sc;
   { const int rc_ = read_scalars(sp, sc); if (rc_) return rc_; }
-  int m = sc[0].iter;
-  for (auto &s : sc) m = std::min(m, s.iter);
-  *n = m;
+  int m = -1;   // (many data sets: over the chains that have not failed)
+  for (auto &s : sc) if (!sp->n_ds || s.status == 0) m = m < 0 ? s.iter : std::min(m, s.iter);
+  *n = std::max(m, 0);
   return 0;
 }
 
@@ -2773,9 +2998,9 @@ int potus_dense_check(int handle, int chain, int n_probe, double *out) {
 static int saved_count(Sampler *sp, int *n_saved) {
   std::vector<ChainScalars> sc;
   { const int rc_ = read_scalars(sp, sc); if (rc_) return rc_; }
-  int m = sc[0].saved;
-  for (auto &s : sc) m = std::min(m, s.saved);
-  *n_saved = m;
+  int m = -1;   // (many data sets: over the chains that have not failed)
+  for (auto &s : sc) if (!sp->n_ds || s.status == 0) m = m < 0 ? s.saved : std::min(m, s.saved);
+  *n_saved = std::max(m, 0);
   return 0;
 }
 
@@ -2864,6 +3089,7 @@ int potus_extract_matrix(const int *handles, int n_handles, int col_begin, int c
   for (int i = 0; i < n_handles; i++) {
     Sampler *sp = get(handles[i]);
     if (!sp) return fail(POTUS_ERR_STATE, "potus_extract_matrix: bad handle %d", handles[i]);
+    if (const int rc_ = refuse_many_datasets(sp, "potus_extract_matrix")) return rc_;
     for (int j = 0; j < i; j++) if (handles[j] == handles[i]) return fail(POTUS_ERR_ARG, "potus_extract_matrix: handle %d listed twice", handles[i]);
     if (i > 0 && sp->L.ncols != sps[0]->L.ncols) return fail(POTUS_ERR_ARG, "potus_extract_matrix: the handles hold different posteriors");
     sps.push_back(sp); devs.push_back(sp->device);
@@ -2932,6 +3158,7 @@ int potus_posterior_summary_many(const int *handles, int n_handles, const double
   for (int i = 0; i < n_handles; i++) {
     Sampler *sp = get(handles[i]);
     if (!sp) return fail(POTUS_ERR_STATE, "potus_posterior_summary: bad handle %d", handles[i]);
+    if (const int rc_ = refuse_many_datasets(sp, "potus_posterior_summary")) return rc_;
     devs.push_back(sp->device);
   }
   DeviceGuard guard;                                   // whatever happens below, the caller's device comes back
@@ -3135,6 +3362,7 @@ static int diagnostics_impl(const int *handles, int n_handles, int col_begin, in
 // that advances the sampler in chunks of `refresh` transitions may stop once *converged is set; nothing the sampler does depends on it (same
 // draws up to that point as an uninterrupted run).  A deviation from Stan, which always runs num_samples iterations: off unless the host asks.
 int potus_diagnostics(const int *handles, int n_handles, int col_begin, int col_end, double *rhat_out, double *ess_bulk_out) {
+  for (int i = 0; handles && i < n_handles; i++) { Sampler *sp = get(handles[i]); if (sp) { if (const int rc_ = refuse_many_datasets(sp, "potus_diagnostics")) return rc_; } }
   return diagnostics_impl(handles, n_handles, col_begin, col_end, rhat_out, ess_bulk_out, false);
 }
 
@@ -3143,7 +3371,12 @@ int potus_check_convergence(const int *handles, int n_handles, double rhat_below
   Sampler *s0 = get(handles[0]);
   if (!s0) return fail(POTUS_ERR_STATE, "bad handle %d", handles[0]);
   std::vector<int> devs;
-  for (int i = 0; i < n_handles; i++) { Sampler *sp = get(handles[i]); if (!sp) return fail(POTUS_ERR_STATE, "bad handle %d", handles[i]); devs.push_back(sp->device); }
+  for (int i = 0; i < n_handles; i++) {
+    Sampler *sp = get(handles[i]);
+    if (!sp) return fail(POTUS_ERR_STATE, "bad handle %d", handles[i]);
+    if (const int rc_ = refuse_many_datasets(sp, "potus_check_convergence")) return rc_;
+    devs.push_back(sp->device);
+  }
   DeviceLocks lock(devs);                            // one set of locks for the count and both column ranges
   const int S = s0->M.S, T = s0->M.T, a_mu = POTUS_N_SAMPLER_COLS + s0->L.D + S * (T - 1);
   std::vector<double> rh(1 + S), es(1 + S);
@@ -3195,6 +3428,7 @@ int potus_last_run_timing(int handle, double *ms, long long *leapfrogs) {
 int potus_write_stan_csv(int handle, const char *dir, const char *basename) {
   Sampler *sp = get(handle);
   if (!sp || !dir || !basename) return fail(POTUS_ERR_STATE, "bad handle or null path");
+  if (const int rc_ = refuse_many_datasets(sp, "potus_write_stan_csv")) return rc_;
   int n_saved = 0, rc = 0;
   { DeviceLocks lock0(sp->device); HIP_TRY(hipSetDevice(sp->device)); rc = saved_count(sp, &n_saved); }
   if (rc) return rc;
@@ -3308,6 +3542,141 @@ int potus_write_stan_csv(int handle, const char *dir, const char *basename) {
 
 // Development aid (POTUS_PROF builds only; not part of include/potus_hmc.h): per-chain cycle
 // counters of the kernel phases.  Returns the number of slots written per chain, 0 otherwise.
+// ------------------------------------------------------------------------ simulation-based calibration (DESIGN.md "Simulation-based calibration")
+int potus_set_datasets(int handle, int n_datasets, const int32_t *n_democrat_state, const int32_t *n_democrat_national) {
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  const int Ns = sp->M.Ns, Nn = sp->M.Nn, Np = Ns + Nn, Npad = sp->M.Npad;
+  if (n_datasets < 1) return fail(POTUS_ERR_ARG, "potus_set_datasets: n_datasets = %d, at least 1", n_datasets);
+  if ((Ns && !n_democrat_state) || (Nn && !n_democrat_national)) return fail(POTUS_ERR_ARG, "potus_set_datasets: null outcome array");
+  if (sp->inited) return fail(POTUS_ERR_STATE, "potus_set_datasets: the handle is already initialised (call it between potus_create and potus_init)");
+  if (sp->n_ds) return fail(POTUS_ERR_STATE, "potus_set_datasets: the handle already holds %d data sets", sp->n_ds);
+  if (sp->dense) return fail(POTUS_ERR_UNSUPPORTED, "potus_set_datasets: the dense metric is not supported (metric = POTUS_METRIC_DIAG only)");
+  if (sp->K != 1 || sp->twin) return fail(POTUS_ERR_UNSUPPORTED, "potus_set_datasets: needs one workgroup per chain (cus_per_chain = 1, twin = 0); this handle runs %d x %d", sp->K, sp->sides());
+  if (sp->R.chains % n_datasets) return fail(POTUS_ERR_ARG, "potus_set_datasets: chains = %d is not a multiple of n_datasets = %d", sp->R.chains, n_datasets);
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  std::vector<double> base((size_t)4 * Npad);
+  HIP_TRY(hipMemcpy(base.data(), sp->M.pd, base.size() * 8, hipMemcpyDeviceToHost));
+  std::vector<double> pd((size_t)n_datasets * 4 * Npad);
+  for (int k = 0; k < n_datasets; k++) {
+    double *blk = pd.data() + (size_t)k * 4 * Npad;
+    std::copy(base.begin(), base.end(), blk);
+    for (int i = 0; i < Np; i++) {   // day-sorted poll i is state poll qidx - o_ns or national poll qidx - o_nn (build_model)
+      const int qi = sp->h_pq[i];
+      const bool nat = sp->h_ps[i] == sp->M.S;
+      const int j = nat ? qi - sp->M.o_nn : qi - sp->M.o_ns;
+      const int y = nat ? n_democrat_national[(size_t)k * Nn + j] : n_democrat_state[(size_t)k * Ns + j];
+      const double n = base[(size_t)Npad + i];
+      if (y < 0 || y > n) return fail(POTUS_ERR_ARG, "potus_set_datasets: data set %d: n_democrat_%s[%d] = %d outside [0,%d]", k + 1, nat ? "national" : "state", j + 1, y, (int)n);
+      blk[i] = (double)y;
+    }
+  }
+  const double *dpd = nullptr;
+  if (const int rc = upload(sp, pd, &dpd)) return rc;
+  std::vector<DevModel> ms(n_datasets, sp->M);
+  for (int k = 0; k < n_datasets; k++) ms[k].pd = dpd + (size_t)k * 4 * Npad;
+  const DevModel *dms = nullptr;
+  if (const int rc = upload(sp, ms, &dms)) return rc;
+  sp->dMs = const_cast<DevModel *>(dms);
+  sp->n_ds = n_datasets;
+  return 0;
+}
+
+int potus_simulate_prior(int handle, uint64_t seed, int n_sims, int sim_offset, double *q_out, int32_t *n_democrat_state_out, int32_t *n_democrat_national_out) {
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  if (n_sims < 0 || sim_offset < 0 || (long long)sim_offset + n_sims >= 0xFFFFFFFFll) return fail(POTUS_ERR_ARG, "potus_simulate_prior: n_sims = %d, sim_offset = %d", n_sims, sim_offset);
+  if (n_sims == 0) return 0;
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  const int D = sp->L.D, row = POTUS_N_SAMPLER_COLS + D, Ns = sp->M.Ns, Np = sp->M.Npoll;
+  const int grid = std::min(n_sims, 512);
+  DevBufs tmp;
+  double *qrow = nullptr, *scratch = nullptr;
+  int *y = nullptr;
+  HIP_TRY(tmp.alloc(&qrow, (size_t)n_sims * row * 8)); HIP_TRY(tmp.alloc(&scratch, (size_t)grid * sp->L.ncols * 8));
+  HIP_TRY(tmp.alloc(&y, (size_t)n_sims * std::max(Np, 1) * 4));
+  SimParams P{qrow, scratch, y, n_sims, sp->L.ncols, sim_offset, (unsigned)(seed & 0xFFFFFFFFu), (unsigned)(seed >> 32)};
+  hipLaunchKernelGGL(k_simulate_prior, dim3(grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, P);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> hq((size_t)n_sims * row);
+  std::vector<int32_t> hy((size_t)n_sims * Np);
+  HIP_TRY(hipMemcpyAsync(hq.data(), qrow, hq.size() * 8, hipMemcpyDeviceToHost, sp->stream));
+  if (Np) HIP_TRY(hipMemcpyAsync(hy.data(), y, hy.size() * 4, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  for (int i = 0; i < n_sims; i++) {
+    if (q_out) std::copy(hq.begin() + (size_t)i * row + POTUS_N_SAMPLER_COLS, hq.begin() + (size_t)(i + 1) * row, q_out + (size_t)i * D);
+    if (n_democrat_state_out) std::copy(hy.begin() + (size_t)i * Np, hy.begin() + (size_t)i * Np + Ns, n_democrat_state_out + (size_t)i * Ns);
+    if (n_democrat_national_out) std::copy(hy.begin() + (size_t)i * Np + Ns, hy.begin() + (size_t)(i + 1) * Np, n_democrat_national_out + (size_t)i * (Np - Ns));
+  }
+  return 0;
+}
+
+int potus_constrain(int handle, const double *q, int n, int col_begin, int col_end, double *out) {
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  if (n < 0 || (n > 0 && (!q || !out))) return fail(POTUS_ERR_ARG, "potus_constrain: null argument");
+  if (col_begin < 0 || col_end > sp->L.ncols || col_begin >= col_end) return fail(POTUS_ERR_ARG, "bad column range [%d,%d) of %d", col_begin, col_end, sp->L.ncols);
+  if (n == 0) return 0;
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  const int D = sp->L.D, row = POTUS_N_SAMPLER_COLS + D, nsel = col_end - col_begin;
+  std::vector<double> blk((size_t)n * row, NAN);   // the sampler columns of these rows are NaN
+  for (int i = 0; i < n; i++) std::copy(q + (size_t)i * D, q + (size_t)(i + 1) * D, blk.begin() + (size_t)i * row + POTUS_N_SAMPLER_COLS);
+  const int grid = std::min(n, 512);
+  DevBufs tmp;
+  double *dblk = nullptr, *scratch = nullptr, *dout = nullptr;
+  HIP_TRY(tmp.alloc(&dblk, blk.size() * 8)); HIP_TRY(tmp.alloc(&scratch, (size_t)grid * sp->L.ncols * 8)); HIP_TRY(tmp.alloc(&dout, (size_t)n * nsel * 8));
+  HIP_TRY(hipMemcpyAsync(dblk, blk.data(), blk.size() * 8, hipMemcpyHostToDevice, sp->stream));
+  WAParams W{dblk, 1, n, n, row, sp->L.ncols, col_begin, col_end, scratch, dout, sp->sigma_ns, sp->sigma_nn, nsel};   // n draws of one chain
+  hipLaunchKernelGGL(k_write_array, dim3(grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, W);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, dout, (size_t)n * nsel * 8, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  return 0;
+}
+
+int potus_sbc_ranks(int handle, const double *truth, int col_begin, int col_end, int thin, int32_t *less, int32_t *equal, int *L) {
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  if (!truth || !less || !equal || !L) return fail(POTUS_ERR_ARG, "potus_sbc_ranks: null argument");
+  if (col_begin < POTUS_N_SAMPLER_COLS || col_end > sp->L.ncols || col_begin >= col_end)
+    return fail(POTUS_ERR_ARG, "potus_sbc_ranks: bad column range [%d,%d) (columns %d .. %d)", col_begin, col_end, POTUS_N_SAMPLER_COLS, sp->L.ncols);
+  if (thin < 1) return fail(POTUS_ERR_ARG, "potus_sbc_ranks: thin = %d, at least 1", thin);
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  std::vector<ChainScalars> sc;
+  if (const int rc = read_scalars(sp, sc)) return rc;
+  int n_saved = 0;
+  if (const int rc = saved_count(sp, &n_saved)) return rc;
+  const int first = sp->R.save_warmup ? sp->R.num_warmup : 0, n_post = n_saved - first;
+  if (n_post < 1) return fail(POTUS_ERR_STATE, "potus_sbc_ranks: no post-warm-up draws saved yet (%d saved, %d of them warm-up)", n_saved, std::min(n_saved, first));
+  const int nL = (n_post + thin - 1) / thin, chains = sp->R.chains, n_ds = std::max(sp->n_ds, 1), cpd = sp->chains_per_ds(), nsel = col_end - col_begin;
+  std::vector<int> skip(chains);
+  for (int c = 0; c < chains; c++) skip[c] = sc[c].status != 0;
+  const int grid = std::min(chains, 1024);
+  DevBufs tmp;
+  double *dtruth = nullptr, *scratch = nullptr;
+  int *dskip = nullptr, *cl = nullptr, *ce = nullptr, *dl = nullptr, *de = nullptr;
+  HIP_TRY(tmp.alloc(&dtruth, (size_t)n_ds * nsel * 8)); HIP_TRY(tmp.alloc(&scratch, (size_t)grid * sp->L.ncols * 8)); HIP_TRY(tmp.alloc(&dskip, (size_t)chains * 4));
+  HIP_TRY(tmp.alloc(&cl, (size_t)chains * nsel * 4)); HIP_TRY(tmp.alloc(&ce, (size_t)chains * nsel * 4));
+  HIP_TRY(tmp.alloc(&dl, (size_t)n_ds * nsel * 4)); HIP_TRY(tmp.alloc(&de, (size_t)n_ds * nsel * 4));
+  HIP_TRY(hipMemcpyAsync(dtruth, truth, (size_t)n_ds * nsel * 8, hipMemcpyHostToDevice, sp->stream));
+  HIP_TRY(hipMemcpyAsync(dskip, skip.data(), (size_t)chains * 4, hipMemcpyHostToDevice, sp->stream));
+  RankParams P{sp->R.draws, chains, sp->R.n_save_max, sp->R.row, sp->L.ncols, col_begin, col_end, first, thin, nL, cpd, dtruth, dskip, scratch, cl, ce};
+  hipLaunchKernelGGL(k_sbc_ranks, dim3(grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, P);
+  HIP_TRY(hipGetLastError());
+  const int rgrid = (int)std::min<long long>(((long long)n_ds * nsel + 255) / 256, 1024);
+  hipLaunchKernelGGL(k_sbc_reduce, dim3(rgrid), dim3(256), 0, sp->stream, (const int *)cl, (const int *)ce, n_ds, cpd, nsel, dl, de);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(less, dl, (size_t)n_ds * nsel * 4, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipMemcpyAsync(equal, de, (size_t)n_ds * nsel * 4, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  *L = nL * cpd;
+  return 0;
+}
+
 int potus_debug_profile(int handle, double *out) {
   Sampler *sp = get(handle);
   if (!sp || !sp->R.prof || !out) return 0;
@@ -3606,5 +3975,19 @@ void potus_R_backtest_scores(double *state_out, int *dims /*[3]: T, S, day*/, do
 void potus_R_saved_count(int *handle, int *n_saved, int *status) { *status = potus_get_draws(*handle, nullptr, n_saved); }
 void potus_R_last_error(char **buf, int *len) { potus_last_error(buf[0], *len); }
 void potus_R_destroy(int *handle, int *status) { *status = potus_destroy(*handle); }
+void potus_R_set_datasets(int *handle, int *n_datasets, int *n_democrat_state, int *n_democrat_national, int *status) {
+  *status = potus_set_datasets(*handle, *n_datasets, n_democrat_state, n_democrat_national);
+}
+void potus_R_simulate_prior(int *handle, double *seed, int *dims /*[2]: n_sims, sim_offset*/, double *q_out, int *n_democrat_state_out, int *n_democrat_national_out,
+                            int *status) {
+  if (!(seed[0] >= 0) || seed[0] > 9007199254740992.0 || seed[0] != std::floor(seed[0])) { *status = fail(POTUS_ERR_ARG, "seed must be a non-negative integer below 2^53"); return; }
+  *status = potus_simulate_prior(*handle, (uint64_t)seed[0], dims[0], dims[1], q_out, n_democrat_state_out, n_democrat_national_out);
+}
+void potus_R_sbc_ranks(int *handle, double *truth, int *cols /*[3]: col_begin, col_end, thin*/, int *less, int *equal, int *L, int *status) {
+  *status = potus_sbc_ranks(*handle, truth, cols[0], cols[1], cols[2], less, equal, L);
+}
+void potus_R_constrain(int *handle, double *q, int *n, int *cols /*[2]: col_begin, col_end*/, double *out, int *status) {
+  *status = potus_constrain(*handle, q, *n, cols[0], cols[1], out);
+}
 
 } // extern "C"

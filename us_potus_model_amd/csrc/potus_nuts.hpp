@@ -33,7 +33,8 @@ extern __shared__ __attribute__((aligned(16))) double lds_dyn[];
 #define PT_NPP (2 * PT_MAXD + 6)
 #define PT_NPQ (PT_MAXD + 6)
 
-enum { RNG_MOMENTUM = 0, RNG_DIRECTION = 1, RNG_TOP_ACCEPT = 2, RNG_SUB_ACCEPT = 3, RNG_INIT_EPS = 4, RNG_INITS = 5 };
+enum { RNG_MOMENTUM = 0, RNG_DIRECTION = 1, RNG_TOP_ACCEPT = 2, RNG_SUB_ACCEPT = 3, RNG_INIT_EPS = 4, RNG_INITS = 5,
+       RNG_PRIOR = 6 /* potus_simulate_prior (potus_hmc.h documents its counters) */ };
 #define PT_ITER_PRE 0xFFFFFFFFu
 
 // vector slots of one chain's state block (each Dpad doubles).

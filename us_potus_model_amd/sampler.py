@@ -90,6 +90,12 @@ def load_library():
     L.potus_plan_cus_per_chain.argtypes = [C.c_int] * 7 + [ip, ip]
     L.potus_plan_sides.argtypes = [C.c_int] * 7 + [ip]
     L.potus_twin_stats.argtypes = [C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_longlong), C.POINTER(C.c_longlong)]
+    if hasattr(L, "potus_sbc_ranks"):                   # simulation-based calibration (sbc.py)
+        i32p = C.POINTER(C.c_int32)
+        L.potus_set_datasets.argtypes = [C.c_int, C.c_int, i32p, i32p]
+        L.potus_simulate_prior.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_int, dp, i32p, i32p]
+        L.potus_constrain.argtypes = [C.c_int, dp, C.c_int, C.c_int, C.c_int, dp]
+        L.potus_sbc_ranks.argtypes = [C.c_int, dp, C.c_int, C.c_int, C.c_int, i32p, i32p, ip]
     _LIB = L
     return L
 
@@ -101,13 +107,19 @@ EXPORTS = [
     "potus_get_dense_metric", "potus_dense_timing", "potus_dense_adapt_timing", "potus_dense_pool_window", "potus_dense_pool_finish", "potus_dense_check", "potus_get_draws", "potus_draws_device_ptr", "potus_write_array", "potus_write_array_device", "potus_extract_matrix", "potus_write_stan_csv",
     "potus_last_run_timing", "potus_posterior_summary", "potus_posterior_summary_many", "potus_backtest_scores",
     "potus_diagnostics", "potus_diagnostics_device", "potus_check_convergence",
+    "potus_set_datasets", "potus_simulate_prior", "potus_constrain", "potus_sbc_ranks",
     "potus_R_create", "potus_R_init", "potus_R_run", "potus_R_run_many", "potus_R_num_columns", "potus_R_saved_count",
     "potus_R_write_array", "potus_R_write_stan_csv", "potus_R_posterior_summary", "potus_R_diagnostics", "potus_R_check_convergence", "potus_R_backtest_scores", "potus_R_last_error", "potus_R_destroy",
+    "potus_R_set_datasets", "potus_R_simulate_prior", "potus_R_sbc_ranks", "potus_R_constrain",
 ]
 
 
 def _dp(a):
     return a.ctypes.data_as(C.POINTER(C.c_double))
+
+
+def _ip(a):
+    return a.ctypes.data_as(C.POINTER(C.c_int32))
 
 
 def _check(L, rc):
@@ -309,6 +321,44 @@ class Handle:
         if n_saved:
             _check(self.L, self.L.potus_write_array(self.h, col_begin, col_end, _dp(out)))
         return out
+
+    def set_datasets(self, n_democrat_state, n_democrat_national):
+        """potus_set_datasets: [n, N_state_polls] and [n, N_national_polls] poll outcomes, one data set per chains / n consecutive chains
+        (before init(); one workgroup per chain, diagonal metric)."""
+        Ns, Nn = int(self.data["N_state_polls"]), int(self.data["N_national_polls"])
+        ys = np.ascontiguousarray(np.asarray(n_democrat_state, dtype=np.int32).reshape(-1, Ns) if Ns else np.zeros((0, 0), np.int32))
+        yn = np.ascontiguousarray(np.asarray(n_democrat_national, dtype=np.int32).reshape(-1, Nn) if Nn else np.zeros((0, 0), np.int32))
+        n = ys.shape[0] if Ns else yn.shape[0]
+        if Ns and Nn and ys.shape[0] != yn.shape[0]:
+            raise ValueError(f"{ys.shape[0]} state and {yn.shape[0]} national outcome vectors")
+        _check(self.L, self.L.potus_set_datasets(self.h, n, _ip(ys), _ip(yn)))
+        self.n_datasets = n
+
+    def simulate_prior(self, seed, n_sims, sim_offset=0):
+        """potus_simulate_prior: (q [n_sims, D], n_democrat_state [n_sims, Ns], n_democrat_national [n_sims, Nn]) drawn from the prior
+        predictive distribution of this handle's design (its poll outcomes are not used)."""
+        Ns, Nn = int(self.data["N_state_polls"]), int(self.data["N_national_polls"])
+        q = np.zeros((n_sims, self.D))
+        ys, yn = np.zeros((n_sims, Ns), np.int32), np.zeros((n_sims, Nn), np.int32)
+        _check(self.L, self.L.potus_simulate_prior(self.h, C.c_uint64(int(seed)), int(n_sims), int(sim_offset), _dp(q), _ip(ys), _ip(yn)))
+        return q, ys, yn
+
+    def constrain(self, q, col_begin=_abi.N_SAMPLER_COLS, col_end=None):
+        """potus_constrain: output-row columns [col_begin, col_end) of unconstrained points q [n, D] (sampler columns are NaN)."""
+        q = np.ascontiguousarray(np.atleast_2d(q), dtype=np.float64)
+        assert q.shape[1] == self.D
+        col_end = self.n_cols if col_end is None else int(col_end)
+        out = np.zeros((q.shape[0], col_end - col_begin))
+        _check(self.L, self.L.potus_constrain(self.h, _dp(q), q.shape[0], int(col_begin), col_end, _dp(out)))
+        return out
+
+    def sbc_ranks(self, truth, col_begin, col_end, thin=1):
+        """potus_sbc_ranks: (less, equal) [n_datasets, col_end - col_begin] and L, the draws compared per data set."""
+        nc = int(col_end) - int(col_begin)
+        truth = np.ascontiguousarray(np.asarray(truth, dtype=np.float64).reshape(-1, nc))
+        less, equal, L = np.zeros(truth.shape, np.int32), np.zeros(truth.shape, np.int32), C.c_int()
+        _check(self.L, self.L.potus_sbc_ranks(self.h, _dp(truth), int(col_begin), int(col_end), int(thin), _ip(less), _ip(equal), C.byref(L)))
+        return less, equal, L.value
 
     def write_stan_csv(self, directory, basename="poll_model_2020"):
         os.makedirs(directory, exist_ok=True)
