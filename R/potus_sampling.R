@@ -267,3 +267,43 @@ potus_sbc <- function(data, variant = c("full", "no_mode_adjustment"), columns, 
   failed <- rowSums(less + equal) == 0
   list(ranks = less + floor(runif(length(less)) * (equal + 1)), L = rk$L, failed = failed)
 }
+
+# ---- PSIS-LOO (us_potus_model_amd/loo.py is the same in Python; DESIGN.md section 4e) ----
+# What fit$loo() gives a cmdstanr user with a log_lik generated quantity, computed on the device over every chain of the fit (post-warm-up
+# draws).  integrate = TRUE integrates each poll's own noise coordinate out of its likelihood (plain PSIS-LOO meets high Pareto k there, since
+# every poll has a parameter of its own).  r_eff: one value per poll, or NULL (computed as loo::relative_eff does).
+# Returns list(estimates = [3, 2] (elpd_loo, p_loo, looic) x (Estimate, SE), pointwise = [polls, 5], diagnostics = list(pareto_k)); polls are
+# numbered state polls first, then national polls.
+potus_loo <- function(fit, integrate = TRUE, r_eff = NULL) {
+  N <- as.integer(fit$data$N_state_polls) + as.integer(fit$data$N_national_polls)
+  r <- .C("potus_R_loo", as.integer(fit$handles), length(fit$handles), as.integer(c(isTRUE(integrate), !is.null(r_eff))),
+          as.double(if (is.null(r_eff)) 0 else r_eff), pointwise = double(N * 5), estimates = double(6), status = integer(1))
+  .potus_check(r$status)
+  pw <- matrix(r$pointwise, N, 5, byrow = TRUE, dimnames = list(NULL, c("elpd_loo", "p_loo", "looic", "pareto_k", "r_eff")))
+  est <- matrix(r$estimates, 3, 2, byrow = TRUE, dimnames = list(c("elpd_loo", "p_loo", "looic"), c("Estimate", "SE")))
+  structure(list(estimates = est, pointwise = pw, diagnostics = list(pareto_k = pw[, "pareto_k"]),
+                 y = c(fit$data$n_democrat_state, fit$data$n_democrat_national), n = c(fit$data$n_two_share_state, fit$data$n_two_share_national)),
+            class = "potus_loo")
+}
+
+# loo::loo_compare: rows sorted by elpd_loo, elpd_diff against the best and se_diff = sqrt(N) sd(pointwise differences).  The fits must be
+# of the same polls (e.g. potus_loo_compare(full = potus_loo(fit_full), no_mode = potus_loo(fit_no_mode))).
+potus_loo_compare <- function(...) {
+  loos <- list(...)
+  nm <- names(loos)
+  if (is.null(nm) || any(nm == "")) nm <- paste0("model", seq_along(loos))
+  N <- nrow(loos[[1]]$pointwise)
+  for (l in loos[-1])
+    if (nrow(l$pointwise) != N || !identical(as.numeric(l$y), as.numeric(loos[[1]]$y)) || !identical(as.numeric(l$n), as.numeric(loos[[1]]$n)))
+      stop("potus_loo_compare: the fits were not fitted to the same polls")
+  ord <- order(sapply(loos, function(l) l$estimates["elpd_loo", "Estimate"]), decreasing = TRUE)
+  best <- loos[[ord[1]]]$pointwise[, "elpd_loo"]
+  out <- t(sapply(seq_along(ord), function(r) {
+    l <- loos[[ord[r]]]
+    d <- l$pointwise[, "elpd_loo"] - best
+    c(elpd_diff = sum(d), se_diff = if (r == 1) 0 else sqrt(N) * sd(d), elpd_loo = l$estimates[1, 1], se_elpd_loo = l$estimates[1, 2],
+      p_loo = l$estimates[2, 1], se_p_loo = l$estimates[2, 2], looic = l$estimates[3, 1], se_looic = l$estimates[3, 2])
+  }))
+  rownames(out) <- nm[ord]
+  out
+}

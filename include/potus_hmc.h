@@ -320,7 +320,8 @@ int potus_dense_check(int handle, int chain, int n_probe, double *out /*[2]*/);
  * Chain c fits data set c / (chains / n_datasets).  Needs chains % n_datasets == 0, one workgroup per chain (cus_per_chain = 1,
  * twin = 0) and the diagonal metric.  Per-chain calls (potus_get_draws, potus_write_array[_device], potus_chain_status,
  * potus_get_adaptation, potus_draws_device_ptr) work unchanged; calls that pool all chains (potus_posterior_summary[_many],
- * potus_diagnostics, potus_check_convergence, potus_extract_matrix, potus_write_stan_csv) refuse with POTUS_ERR_STATE.  A chain
+ * potus_diagnostics, potus_check_convergence, potus_extract_matrix, potus_write_stan_csv, potus_loo, potus_log_lik_device) refuse with
+ * POTUS_ERR_STATE.  A chain
  * whose initialisation or step-size search fails does not fail potus_init / potus_run: potus_chain_status reports it, the
  * iteration and saved-draw counts are those of the other chains. */
 int potus_set_datasets(int handle, int n_datasets, const int32_t *n_democrat_state, const int32_t *n_democrat_national);
@@ -345,6 +346,22 @@ int potus_constrain(int handle, const double *q /*[n][D]*/, int n, int col_begin
  * them per data set.  Chains that failed (potus_chain_status != 0) add nothing.  No draws x columns block is built. */
 int potus_sbc_ranks(int handle, const double *truth /*[n_datasets][ncols]*/, int col_begin, int col_end, int thin, int32_t *less /*[n_datasets][ncols]*/,
                     int32_t *equal, int *L);
+
+/* ---- PSIS-LOO (Vehtari, Gelman, Gabry 2017): what fit$loo() computes from a log_lik generated quantity ----
+ * Polls are numbered as the output row numbers them: state polls in data order, then national polls.  integrate = 0: the plain
+ * binomial_logit_lpmf(y | n, logit_pi) of each poll at the draw (log C(n, y) included); integrate = 1: the poll's own noise coordinate
+ * raw_measure_noise_* integrated out of its likelihood, log int Binomial(y | n, inv_logit(eta + sigma z)) phi(z) dz (adaptive Gauss-Hermite,
+ * 16 nodes), where plain PSIS-LOO meets high Pareto k because every poll has a parameter of its own.  Warm-up rows (save_warmup = 1) are left out. */
+/* per-poll log-likelihood of the saved post-warm-up draws, on the handle's device: out_device [poll_end - poll_begin][chains][n_post] */
+int potus_log_lik_device(int handle, int poll_begin, int poll_end, int integrate, void *out_device);
+/* PSIS-LOO of a [n_polls][n_chains][n_draws] log-likelihood block already on `device`; r_eff [n_polls] or NULL (computed);
+ * pointwise_out [n_polls][5] = elpd_loo, p_loo, looic, pareto_k, r_eff; estimates_out [3][2] = (elpd_loo, p_loo, looic) x (estimate, se) */
+int potus_loo_device(int device, const void *log_lik, int n_polls, int n_chains, long long n_draws, const double *r_eff,
+                     double *pointwise_out, double *estimates_out);
+/* the same over the pooled post-warm-up draws of handles that hold one posterior (the pooling rules of potus_diagnostics; at least four
+ * post-warm-up draws per chain); handles on other GPUs are brought to the first handle's by peer copies.  Polls go in blocks whose
+ * temporaries stay within 256 MB; r_eff as loo::relative_eff (not split) when NULL. */
+int potus_loo(const int *handles, int n_handles, int integrate, const double *r_eff, double *pointwise_out, double *estimates_out);
 
 /* ---- .C()-callable wrappers (int* / double* / char** only) ---- */
 void potus_R_create(int *dims /*[8]: N_nat,N_state,T,S,P,M,Pop,variant*/,
@@ -381,6 +398,8 @@ void potus_R_simulate_prior(int *handle, double *seed, int *dims /*[2]: n_sims, 
                             int *n_democrat_national_out, int *status);
 void potus_R_sbc_ranks(int *handle, double *truth, int *cols /*[3]: col_begin, col_end, thin*/, int *less, int *equal, int *L, int *status);
 void potus_R_constrain(int *handle, double *q, int *n, int *cols /*[2]: col_begin, col_end*/, double *out, int *status);
+void potus_R_loo(int *handles, int *n_handles, int *iopts /*[2]: integrate, r_eff given*/, double *r_eff, double *pointwise_out /*[n_polls][5]*/,
+                 double *estimates_out /*[3][2]*/, int *status);
 
 #ifdef __cplusplus
 }

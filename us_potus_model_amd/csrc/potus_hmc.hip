@@ -1111,6 +1111,8 @@ __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, c
   }
 }
 
+#include "potus_loo.hpp"   // per-poll log-likelihoods and PSIS-LOO (after wa_build_row, which it shares)
+
 // ======================================================================== host
 namespace {
 
@@ -3366,6 +3368,244 @@ int potus_diagnostics(const int *handles, int n_handles, int col_begin, int col_
   return diagnostics_impl(handles, n_handles, col_begin, col_end, rhat_out, ess_bulk_out, false);
 }
 
+// ---------------------------------------------------------------------------------------------- PSIS-LOO (potus_loo.hpp)
+extern "C++" {   // (the helpers are templates)
+namespace {
+constexpr size_t LOO_BLOCK_BUDGET = 256ull << 20;   // a call's log-likelihood blocks (half) and PSIS scratch (half)
+constexpr size_t LOO_ROW_BUDGET = 64ull << 20;      // k_loo_loglik's rebuilt output rows, per handle
+
+template <class T> int loo_alloc(DevBufs &b, T **p, size_t bytes, const char *what) {
+  if (b.alloc(p, bytes) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(POTUS_ERR_DEVICE, "%s: hipMalloc of %zu bytes (%.1f MB) failed", what, bytes, bytes / 1048576.0);
+  }
+  return 0;
+}
+
+// per handle: log C(n, y) of its polls in the model's order, and the row scratch of k_loo_loglik
+struct LooRows { double *lc = nullptr, *scratch = nullptr; int grid = 1; };
+int loo_rows_setup(Sampler *sp, long long ndraw, DevBufs &keep, LooRows &r, const char *what) {
+  HIP_TRY(hipSetDevice(sp->device));
+  const int Np = sp->M.Npoll, Npad = sp->M.Npad;
+  std::vector<double> pd((size_t)2 * Npad), lc(std::max(Np, 1), 0.0);
+  HIP_TRY(hipMemcpy(pd.data(), sp->M.pd, pd.size() * 8, hipMemcpyDeviceToHost));
+  for (int i = 0; i < Np; i++) {
+    const long double y = pd[i], n = pd[Npad + i];
+    lc[i] = (double)(lgammal(n + 1) - lgammal(y + 1) - lgammal(n - y + 1));
+  }
+  int rc;
+  if ((rc = loo_alloc(keep, &r.lc, lc.size() * 8, what))) return rc;
+  HIP_TRY(hipMemcpy(r.lc, lc.data(), lc.size() * 8, hipMemcpyHostToDevice));
+  r.grid = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(ndraw, 512), (long long)(LOO_ROW_BUDGET / ((size_t)sp->L.ncols * 8))));
+  return loo_alloc(keep, &r.scratch, (size_t)r.grid * sp->L.ncols * 8, what);
+}
+
+// log-likelihoods of polls [b0, b1) of the handle's post-warm-up draws -> out [n_post][chains][b1 - b0], on the handle's device and stream
+int loo_loglik(Sampler *sp, const LooRows &r, int first, int n_post, int b0, int b1, int integrate, double *out) {
+  LlParams P{sp->R.draws, sp->R.chains, sp->R.n_save_max, sp->R.row, sp->L.ncols, first, n_post, b0, b1, integrate, r.lc, r.scratch, out};
+  hipLaunchKernelGGL(k_loo_loglik, dim3(r.grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, P);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// polls per block: blocks of bytes_per_poll each within half the budget
+int loo_block_polls(size_t bytes_per_poll, int n) {
+  return (int)std::max<size_t>(1, std::min<size_t>((size_t)n, LOO_BLOCK_BUDGET / 2 / std::max<size_t>(bytes_per_poll, 1)));
+}
+
+// PSIS-LOO of ll [NP][C][n] on the current device -> pointwise [NP][LOO_NPW] on the host (r_eff: host [NP] or null)
+int loo_psis(hipStream_t st, const double *ll, int NP, int C, long long n, const double *r_eff, double *pw, const char *what) {
+  const long long S = (long long)C * n;
+  const int mmax = 32 + (int)std::sqrt(0.2 * (double)S + 1.0);
+  const size_t wsd_n = 2 * (size_t)S + 2 * (size_t)mmax;
+  const size_t per_wg = wsd_n * 8 + (size_t)S * 4 + (S > DG_RUN ? (size_t)S * 12 : 0);
+  const int grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(NP, 1024), LOO_BLOCK_BUDGET / 2 / per_wg));
+  DevBufs tmp;
+  double *wsd = nullptr, *dre = nullptr, *dout = nullptr;
+  int *wsi = nullptr;
+  unsigned long long *rkey = nullptr;
+  unsigned *ridx = nullptr;
+  int rc;
+  if ((rc = loo_alloc(tmp, &wsd, (size_t)grid * wsd_n * 8, what)) || (rc = loo_alloc(tmp, &wsi, (size_t)grid * S * 4, what)) ||
+      (rc = loo_alloc(tmp, &dout, (size_t)NP * LOO_NPW * 8, what)))
+    return rc;
+  if (S > DG_RUN && ((rc = loo_alloc(tmp, &rkey, (size_t)grid * S * 8, what)) || (rc = loo_alloc(tmp, &ridx, (size_t)grid * S * 4, what)))) return rc;
+  if (r_eff) {
+    if ((rc = loo_alloc(tmp, &dre, (size_t)NP * 8, what))) return rc;
+    HIP_TRY(hipMemcpyAsync(dre, r_eff, (size_t)NP * 8, hipMemcpyHostToDevice, st));
+  }
+  int npad = 1;
+  while (npad < S && npad < DG_RUN) npad <<= 1;
+  const size_t lds = (size_t)npad * 12;                // keys + indices of one sorted run
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_loo_psis), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  PsisParams P{ll, dre, wsd, wsi, rkey, ridx, dout, n, C, NP, mmax};
+  hipLaunchKernelGGL(k_loo_psis, dim3(grid), dim3(DG_THREADS), lds, st, P);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(pw, dout, (size_t)NP * LOO_NPW * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  return 0;
+}
+
+// [3][2] = (elpd_loo, p_loo, looic) x (sum, sqrt(N) sd) over the polls, in poll order
+void loo_estimates(const double *pw, int N, double *est) {
+  for (int k = 0; k < 3; k++) {
+    double s = 0.0, q = 0.0;
+    for (int i = 0; i < N; i++) s += pw[(size_t)i * LOO_NPW + k];
+    const double m = s / N;
+    for (int i = 0; i < N; i++) { const double d = pw[(size_t)i * LOO_NPW + k] - m; q += d * d; }
+    est[2 * k] = s;
+    est[2 * k + 1] = std::sqrt((double)N) * std::sqrt(q / (N - 1));
+  }
+}
+
+int loo_check_r_eff(const double *r_eff, int n, const char *what) {
+  for (int i = 0; r_eff && i < n; i++)
+    if (!(std::isfinite(r_eff[i]) && r_eff[i] > 0)) return fail(POTUS_ERR_ARG, "%s: r_eff[%d] = %g (finite and > 0 expected)", what, i, r_eff[i]);
+  return 0;
+}
+} // namespace
+} // extern "C++"
+
+int potus_log_lik_device(int handle, int poll_begin, int poll_end, int integrate, void *out_device) {
+  Sampler *sp = get(handle);
+  if (!sp || !out_device) return fail(POTUS_ERR_STATE, "bad handle or null output");
+  if (const int rc_ = refuse_many_datasets(sp, "potus_log_lik_device")) return rc_;
+  if (integrate != 0 && integrate != 1) return fail(POTUS_ERR_ARG, "potus_log_lik_device: integrate = %d (0: plain, 1: noise coordinate integrated out)", integrate);
+  const int Np = sp->M.Npoll;
+  if (poll_begin < 0 || poll_end > Np || poll_begin >= poll_end) return fail(POTUS_ERR_ARG, "potus_log_lik_device: polls [%d, %d) of %d", poll_begin, poll_end, Np);
+  DeviceGuard guard;
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, out_device) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != sp->device) {
+    (void)hipGetLastError();
+    return fail(POTUS_ERR_ARG, "potus_log_lik_device: the output is not device memory of GPU %d", sp->device);
+  }
+  int n_saved = 0, rc = saved_count(sp, &n_saved);
+  if (rc) return rc;
+  const int first = sp->opts.save_warmup ? std::min(n_saved, sp->R.num_warmup) : 0, n_post = n_saved - first, C = sp->R.chains;
+  if (n_post < 1) return fail(POTUS_ERR_STATE, "potus_log_lik_device: no post-warm-up draws saved (%d saved, %d of them warm-up)", n_saved, first);
+  DevBufs keep;
+  LooRows r;
+  if ((rc = loo_rows_setup(sp, (long long)n_post * C, keep, r, "potus_log_lik_device"))) return rc;
+  const int nb = loo_block_polls((size_t)n_post * C * 8, poll_end - poll_begin);
+  double *blk = nullptr, *out = (double *)out_device;
+  if ((rc = loo_alloc(keep, &blk, (size_t)n_post * C * nb * 8, "potus_log_lik_device"))) return rc;
+  for (int b0 = poll_begin; b0 < poll_end; b0 += nb) {
+    const int b1 = std::min(b0 + nb, poll_end);
+    if ((rc = loo_loglik(sp, r, first, n_post, b0, b1, integrate, blk))) return rc;
+    hipLaunchKernelGGL(k_dg_transpose, dim3((b1 - b0 + 63) / 64, (unsigned)((n_post + 63) / 64), C), dim3(256), 0, sp->stream, (const double *)blk,
+                       out + (size_t)(b0 - poll_begin) * C * n_post, (long long)n_post, C, b1 - b0, C, 0);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  return 0;
+}
+
+int potus_loo_device(int device, const void *log_lik, int n_polls, int n_chains, long long n_draws, const double *r_eff, double *pointwise_out,
+                     double *estimates_out) {
+  if (!log_lik || !pointwise_out || !estimates_out || n_polls < 1 || n_chains < 1) return fail(POTUS_ERR_ARG, "potus_loo_device: bad argument");
+  if (n_draws < 4) return fail(POTUS_ERR_ARG, "potus_loo_device: %lld draws per chain (at least 4)", n_draws);
+  if (2 * n_chains > DG_MAXCH) return fail(POTUS_ERR_UNSUPPORTED, "potus_loo_device: %d chains pooled (at most %d)", n_chains, DG_MAXCH / 2);
+  if ((long long)n_chains * n_draws > 0x7fffffffll) return fail(POTUS_ERR_UNSUPPORTED, "potus_loo_device: %lld draws per poll (at most 2^31 - 1)", (long long)n_chains * n_draws);
+  if (const int rc_ = loo_check_r_eff(r_eff, n_polls, "potus_loo_device")) return rc_;
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(POTUS_ERR_DEVICE, "potus_loo_device: no HIP device %d", device);
+  DeviceGuard guard;
+  DeviceLocks lock(device);
+  HIP_TRY(hipSetDevice(device));
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, log_lik) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
+    (void)hipGetLastError();
+    return fail(POTUS_ERR_ARG, "potus_loo_device: the block is not device memory of GPU %d", device);
+  }
+  const int rc = loo_psis(0, (const double *)log_lik, n_polls, n_chains, n_draws, r_eff, pointwise_out, "potus_loo_device");
+  if (rc) return rc;
+  loo_estimates(pointwise_out, n_polls, estimates_out);
+  return 0;
+}
+
+int potus_loo(const int *handles, int n_handles, int integrate, const double *r_eff, double *pointwise_out, double *estimates_out) {
+  if (!handles || n_handles < 1 || !pointwise_out || !estimates_out) return fail(POTUS_ERR_ARG, "potus_loo: null argument");
+  std::vector<Sampler *> sps;
+  std::vector<int> devs;
+  for (int i = 0; i < n_handles; i++) {
+    Sampler *sp = get(handles[i]);
+    if (!sp) return fail(POTUS_ERR_STATE, "bad handle %d", handles[i]);
+    if (const int rc_ = refuse_many_datasets(sp, "potus_loo")) return rc_;
+    for (int j = 0; j < i; j++) if (handles[j] == handles[i]) return fail(POTUS_ERR_ARG, "potus_loo: handle %d listed twice", handles[i]);
+    if (i > 0 && (sp->L.ncols != sps[0]->L.ncols || sp->M.full != sps[0]->M.full || sp->data_hash != sps[0]->data_hash))
+      return fail(POTUS_ERR_ARG, "potus_loo: handle %d holds another posterior than handle %d (LOO pools the chains of one)", handles[i], handles[0]);
+    sps.push_back(sp); devs.push_back(sp->device);
+  }
+  Sampler *s0 = sps[0];
+  const int Np = s0->M.Npoll;
+  if (integrate != 0 && integrate != 1) return fail(POTUS_ERR_ARG, "potus_loo: integrate = %d (0: plain, 1: noise coordinate integrated out)", integrate);
+  if (Np < 1) return fail(POTUS_ERR_ARG, "potus_loo: the data hold no polls");
+  if (const int rc_ = loo_check_r_eff(r_eff, Np, "potus_loo")) return rc_;
+  DeviceGuard guard;
+  DeviceLocks lock(devs);
+  int n_saved = -1, Ctot = 0;
+  for (size_t i = 0; i < sps.size(); i++) {
+    Sampler *sp = sps[i];
+    HIP_TRY(hipSetDevice(sp->device));
+    int ns = 0, rc = saved_count(sp, &ns);
+    if (rc) return rc;
+    if (n_saved >= 0 && ns != n_saved) return fail(POTUS_ERR_STATE, "potus_loo: handle %d has saved %d draws per chain, handle %d has %d", handles[i], ns, handles[0], n_saved);
+    n_saved = ns; Ctot += sp->R.chains;
+  }
+  if (2 * Ctot > DG_MAXCH) return fail(POTUS_ERR_UNSUPPORTED, "potus_loo: %d chains pooled (at most %d)", Ctot, DG_MAXCH / 2);
+  const int first = s0->opts.save_warmup ? std::min(n_saved, s0->R.num_warmup) : 0;
+  for (Sampler *sp : sps)
+    if ((sp->opts.save_warmup ? std::min(n_saved, sp->R.num_warmup) : 0) != first) return fail(POTUS_ERR_ARG, "potus_loo: the handles saved different numbers of warm-up rows");
+  const int n_post = n_saved - first;
+  if (n_post < 4) return fail(POTUS_ERR_STATE, "potus_loo: PSIS-LOO needs at least four saved post-warm-up draws per chain (%d saved, %d of them warm-up)", n_saved, first);
+  DevBufs keep;
+  std::vector<LooRows> rows(sps.size());
+  int rc;
+  for (size_t i = 0; i < sps.size(); i++)
+    if ((rc = loo_rows_setup(sps[i], (long long)n_post * sps[i]->R.chains, keep, rows[i], "potus_loo"))) return rc;
+  const long long S = (long long)n_post * Ctot;
+  const int nb = loo_block_polls((size_t)S * 16, Np);    // the pooled block, and one handle's block before its transpose
+  HIP_TRY(hipSetDevice(s0->device));
+  double *cols = nullptr;
+  if ((rc = loo_alloc(keep, &cols, (size_t)S * nb * 8, "potus_loo"))) return rc;
+  for (int b0 = 0; b0 < Np; b0 += nb) {
+    const int b1 = std::min(b0 + nb, Np), nbk = b1 - b0;
+    int coff = 0;
+    for (size_t i = 0; i < sps.size(); i++) {
+      Sampler *sp = sps[i];
+      const int C = sp->R.chains;
+      const size_t bytes = (size_t)n_post * C * nbk * 8;
+      DevBufs blkbuf;
+      double *blk = nullptr;
+      HIP_TRY(hipSetDevice(s0->device));
+      if ((rc = loo_alloc(blkbuf, &blk, bytes, "potus_loo"))) return rc;
+      if (sp->device == s0->device) {
+        if ((rc = loo_loglik(sp, rows[i], first, n_post, b0, b1, integrate, blk))) return rc;
+        HIP_TRY(hipStreamSynchronize(sp->stream));
+      } else {
+        HIP_TRY(hipSetDevice(sp->device));
+        DevBufs far;
+        double *fb = nullptr;
+        if ((rc = loo_alloc(far, &fb, bytes, "potus_loo"))) return rc;
+        if ((rc = loo_loglik(sp, rows[i], first, n_post, b0, b1, integrate, fb))) return rc;
+        HIP_TRY(hipStreamSynchronize(sp->stream));
+        HIP_TRY(hipMemcpyPeer(blk, s0->device, fb, sp->device, bytes));
+        HIP_TRY(hipSetDevice(s0->device));
+      }
+      hipLaunchKernelGGL(k_dg_transpose, dim3((nbk + 63) / 64, (unsigned)((n_post + 63) / 64), C), dim3(256), 0, s0->stream, (const double *)blk, cols,
+                         (long long)n_post, C, nbk, Ctot, coff);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipStreamSynchronize(s0->stream));
+      coff += C;
+    }
+    if ((rc = loo_psis(s0->stream, cols, nbk, Ctot, n_post, r_eff ? r_eff + b0 : nullptr, pointwise_out + (size_t)b0 * LOO_NPW, "potus_loo"))) return rc;
+  }
+  loo_estimates(pointwise_out, Np, estimates_out);
+  return 0;
+}
+
 int potus_check_convergence(const int *handles, int n_handles, double rhat_below, double ess_at_least, int *converged, double *rhat_max, double *ess_bulk_min) {
   if (!handles || n_handles < 1 || !converged || !rhat_max || !ess_bulk_min) return fail(POTUS_ERR_ARG, "potus_check_convergence: null argument");
   Sampler *s0 = get(handles[0]);
@@ -3988,6 +4228,10 @@ void potus_R_sbc_ranks(int *handle, double *truth, int *cols /*[3]: col_begin, c
 }
 void potus_R_constrain(int *handle, double *q, int *n, int *cols /*[2]: col_begin, col_end*/, double *out, int *status) {
   *status = potus_constrain(*handle, q, *n, cols[0], cols[1], out);
+}
+void potus_R_loo(int *handles, int *n_handles, int *iopts /*[2]: integrate, r_eff given*/, double *r_eff, double *pointwise_out, double *estimates_out,
+                 int *status) {
+  *status = potus_loo(handles, *n_handles, iopts[0], iopts[1] ? r_eff : nullptr, pointwise_out, estimates_out);
 }
 
 } // extern "C"

@@ -1,0 +1,325 @@
+// potus_loo.hpp -- per-poll log-likelihoods of the saved draws and PSIS-LOO (Vehtari, Gelman, Gabry 2017; loo 2.x), on the device.
+//
+// Polls are numbered as the output row numbers them: state polls in data order, then national polls (logit_pi_democrat_state, then
+// logit_pi_democrat_national).  For poll i with outcome y of n and noise scale sigma_i (psig), eta_i is logit_pi_i without its noise term
+// raw_measure_noise_i * sigma_i (stan:102, stan:111), computed directly from the output row:
+//   plain       log C(n, y) + y x - n softplus(x),  x = eta_i + sigma_i z_i (the draw's own noise coordinate): binomial_logit_lpmf
+//   integrated  log int Binomial(y | n, inv_logit(eta_i + sigma_i z)) phi(z) dz: the poll's own noise coordinate integrated out
+//               (Vehtari et al. 2016, JMLR 17, "integrated importance sampling"), by adaptive Gauss-Hermite quadrature: Newton steps
+//               from z = 0 to the mode of the strictly concave f(z) = y x - n softplus(x) - z^2 / 2, nodes scaled by sqrt(2 / -f''(mode)).
+// Kernels:
+//   1. k_loo_loglik: one 256-thread workgroup per saved draw rebuilds the output row (wa_build_row, as k_sbc_ranks does) and writes the
+//      log-likelihoods of a block of polls as one row [draw][chain][poll]; k_dg_transpose turns the block into [poll][chain][draw]
+//      (coalesced stores on both sides);
+//   2. k_loo_psis: one workgroup per poll over its S pooled draws: r_eff (loo::relative_eff: Geyer's initial positive, then monotone
+//      sequence of the chain-averaged autocorrelations of exp(ll - max ll), lag by lag as far as the sequence reads them), the tail of the
+//      largest importance ratios by the order statistics of potus_diag.hpp (sorted runs, ranks by binary search: any S up to 512 pooled
+//      chains), gpdfit (Zhang & Stephens 2009 with loo's prior), the smoothed and truncated tail, self-normalised weights and
+//      elpd_loo_i, p_loo_i, looic_i, k-hat_i.  Every sum runs in a fixed order (lane-strided, then a DPP tree, then the waves in order):
+//      same block, same bytes.
+#pragma once
+#include <float.h>
+#include "potus_diag.hpp"
+
+#define LOO_GH 16             // Gauss-Hermite nodes of the integrated form (the error against scipy.integrate.quad)
+#define LOO_NEWTON 8          // Newton steps to the mode
+#define LOO_NPW 5             // pointwise outputs: elpd_loo, p_loo, looic, pareto_k, r_eff
+
+// physicists' Gauss-Hermite nodes x_k and log(w_k) + x_k^2 (numpy.polynomial.hermite.hermgauss(16))
+__constant__ double loo_gh_x[LOO_GH] = {
+    -4.688738939305819, -3.869447904860123, -3.176999161979956, -2.5462021578474814, -1.9517879909162539, -1.3802585391988809,
+    -0.8229514491446559, -0.27348104613815244, 0.27348104613815244, 0.8229514491446559, 1.3802585391988809, 1.9517879909162539,
+    2.5462021578474814, 3.176999161979956, 3.869447904860123, 4.688738939305819};
+__constant__ double loo_gh_lw[LOO_GH] = {
+    -0.0652059514099399, -0.3034786882399878, -0.4219670092986956, -0.4947276307888995, -0.5425790095739411, -0.5740888178776504,
+    -0.5934069056473787, -0.6026207792767783, -0.6026207792767783, -0.5934069056473787, -0.5740888178776504, -0.5425790095739411,
+    -0.4947276307888995, -0.4219670092986956, -0.3034786882399878, -0.0652059514099399};
+
+__device__ __forceinline__ double loo_softplus(double x) { return fmax(x, 0.0) + log1p(exp(-fabs(x))); }
+__device__ __forceinline__ double loo_inv_logit(double x) { return 1.0 / (1.0 + exp(-x)); }
+
+// log p(y | n, eta, sigma) without log C(n, y): plain at the draw's noise coordinate z, or z integrated out (sigma = 0: plain at z = 0)
+__device__ double loo_poll_ll(double y, double n, double eta, double sig, double z, int integrate) {
+  if (!integrate || sig == 0.0) {
+    const double x = integrate ? eta : eta + sig * z;
+    return y * x - n * loo_softplus(x);
+  }
+  double m = 0.0;
+  for (int it = 0; it < LOO_NEWTON; it++) {
+    const double p = loo_inv_logit(eta + sig * m);
+    m -= (sig * (y - n * p) - m) / (-sig * sig * n * p * (1.0 - p) - 1.0);
+  }
+  const double p = loo_inv_logit(eta + sig * m);
+  const double s = sqrt(2.0 / (sig * sig * n * p * (1.0 - p) + 1.0));
+  double f[LOO_GH], fm = -INFINITY;
+#pragma unroll
+  for (int k = 0; k < LOO_GH; k++) {
+    const double zk = m + s * loo_gh_x[k], x = eta + sig * zk;
+    f[k] = y * x - n * loo_softplus(x) - 0.5 * zk * zk + loo_gh_lw[k];
+    fm = fmax(fm, f[k]);
+  }
+  double a = 0.0;
+#pragma unroll
+  for (int k = 0; k < LOO_GH; k++) a += exp(f[k] - fm);
+  return fm + log(a) + log(s) - 0.91893853320467274178;   // - log(2 pi) / 2
+}
+
+struct LlParams {
+  const double *draws;  // [chains][n_save_max][row]
+  int chains, n_save_max, row, ncols;
+  int first, n_post;    // saved draws first .. first + n_post - 1 of every chain (the post-warm-up ones)
+  int p0, p1, integrate;
+  const double *lc;     // [Npoll] log C(n, y) in the model's (day-sorted) poll order
+  double *scratch;      // [gridDim.x][ncols]
+  double *out;          // [n_post][chains][p1 - p0]
+};
+__global__ __launch_bounds__(256) void k_loo_loglik(const DevModel *Mg, LlParams P) {
+  const DevModel M = *Mg;
+  __shared__ double s_bT[64], s_pb[64], s_misc[4];
+  const int tid = threadIdx.x, S = M.S, T = M.T, nb = P.p1 - P.p0, Np = M.Npad;
+  // wa_build_row's column blocks
+  const int o_mub = POTUS_N_SAMPLER_COLS + M.D, o_muc = o_mub + S * T, o_mum = o_muc + M.P, o_mupop = o_mum + (M.full ? M.M : 0);
+  const int o_eb = o_mupop + (M.full ? M.Pop : 0), o_pb = o_eb + (M.full ? T : 0), o_nat = o_pb + S, o_natpb = o_nat + T;
+  double *row = P.scratch + (size_t)blockIdx.x * P.ncols;
+  for (long long d = blockIdx.x; d < (long long)P.n_post * P.chains; d += gridDim.x) {
+    const int iter = (int)(d / P.chains), chain = (int)(d % P.chains);
+    const double *src = P.draws + ((size_t)chain * P.n_save_max + P.first + iter) * P.row;
+    wa_build_row(M, src, row, s_bT, s_pb, s_misc);
+    const double *q = src + POTUS_N_SAMPLER_COLS;
+    double *dst = P.out + (size_t)d * nb;
+    for (int i = tid; i < M.Npoll; i += 256) {
+      const int s = M.pi[i], t = M.pi[Np + i], qi = M.pi[5 * Np + i];
+      const bool nat = s == S;
+      const int k = nat ? M.Ns + (qi - M.o_nn) : qi - M.o_ns;
+      if (k < P.p0 || k >= P.p1) continue;
+      double eta = (nat ? row[o_nat + t] : row[o_mub + s + S * t]) + row[o_muc + M.pi[2 * Np + i]];
+      if (M.full) eta += row[o_mum + M.pi[3 * Np + i]] + row[o_mupop + M.pi[4 * Np + i]] + M.pd[2 * Np + i] * row[o_eb + t];
+      eta += nat ? row[o_natpb] : row[o_pb + s];
+      dst[k - P.p0] = P.lc[i] + loo_poll_ll(M.pd[i], M.pd[Np + i], eta, M.pd[3 * Np + i], q[qi], P.integrate);
+    }
+    __syncthreads();
+  }
+}
+
+// ---- reductions over the DG_THREADS threads of a workgroup in a fixed order (every thread gets the result)
+__device__ __forceinline__ double loo_block_sum(double v, double *red) {
+  const double s = dpp_wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  double t = 0.0;
+  for (int w = 0; w < DG_THREADS / 64; w++) t += red[w];
+  __syncthreads();
+  return t;
+}
+__device__ __forceinline__ double loo_block_max(double v, double *red) {
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = -INFINITY;
+  for (int w = 0; w < DG_THREADS / 64; w++) t = fmax(t, red[w]);
+  __syncthreads();
+  return t;
+}
+
+struct PsisParams {
+  const double *ll;           // [NP][C][n]
+  const double *r_eff;        // [NP], or null: computed
+  double *wsd;                // [gridDim.x][2 S + 2 mmax]: centred weights, then gpdfit's sample | tail | grid of theta | profile log-likelihoods
+  int *wsi;                   // [gridDim.x][S] ranks of the draws among the ratios
+  unsigned long long *rkey;   // [gridDim.x][S] sorted runs when S > DG_RUN
+  unsigned *ridx;
+  double *out;                // [NP][LOO_NPW]
+  long long n;                // draws per chain
+  int C, NP, mmax;
+};
+
+__global__ __launch_bounds__(DG_THREADS) void k_loo_psis(PsisParams P) {
+  extern __shared__ __attribute__((aligned(16))) unsigned long long xk[];   // as k_dg_column: min(npad, DG_RUN) keys, then the indices
+  __shared__ double cmean[DG_MAXCH / 2], cvar[DG_MAXCH / 2], rho[DG_LAGS];
+  __shared__ double red[DG_THREADS / 64], sc[8];
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, C = P.C;
+  const long long n = P.n, S = (long long)C * n;
+  double *xc = P.wsd + (size_t)blockIdx.x * (2 * (size_t)S + 2 * (size_t)P.mmax), *tail = xc + S, *th = tail + S, *lth = th + P.mmax;
+  int *rnk = P.wsi + (size_t)blockIdx.x * (size_t)S;
+  unsigned long long *rkey = P.rkey ? P.rkey + (size_t)blockIdx.x * (size_t)S : nullptr;
+  unsigned *ridx = P.ridx ? P.ridx + (size_t)blockIdx.x * (size_t)S : nullptr;
+  int npad_all = 1;
+  while (npad_all < S && npad_all < DG_RUN) npad_all <<= 1;
+  unsigned *xi = (unsigned *)(xk + npad_all);
+  for (int p = blockIdx.x; p < P.NP; p += gridDim.x) {
+    const double *ll = P.ll + (size_t)p * S;
+    double *o = P.out + (size_t)p * LOO_NPW;
+    {
+      int bad = 0;
+      for (long long j = tid; j < S; j += DG_THREADS) bad |= !isfinite(ll[j]);
+      if (__syncthreads_or(bad)) {
+        if (tid == 0) { for (int k = 0; k < 4; k++) o[k] = NAN; o[4] = P.r_eff ? P.r_eff[p] : NAN; }
+        continue;
+      }
+    }
+    double mx = -INFINITY, mn = INFINITY;
+    for (long long j = tid; j < S; j += DG_THREADS) { mx = fmax(mx, ll[j]); mn = fmin(mn, ll[j]); }
+    mx = loo_block_max(mx, red);
+    mn = -loo_block_max(-mn, red);
+    // ---- r_eff = ESS / S of x = exp(ll - max ll), chains not split
+    double reff;
+    if (P.r_eff) reff = P.r_eff[p];
+    else {
+      for (long long j = tid; j < S; j += DG_THREADS) xc[j] = exp(ll[j] - mx);
+      __threadfence_block();
+      __syncthreads();
+      for (int c = w; c < C; c += DG_THREADS / 64) {       // one wave per chain: mean, biased autocovariance at lag 0
+        double s = 0.0;
+        for (long long i = lane; i < n; i += 64) s += xc[(size_t)c * n + i];
+        const double m = dpp_wave_sum(s) / (double)n;
+        double q = 0.0;
+        for (long long i = lane; i < n; i += 64) { const double d = xc[(size_t)c * n + i] - m; q += d * d; }
+        const double v = dpp_wave_sum(q) / (double)n;
+        if (lane == 0) { cmean[c] = m; cvar[c] = v; }
+      }
+      __syncthreads();
+      for (long long j = tid; j < S; j += DG_THREADS) xc[j] -= cmean[j / n];
+      if (tid == 0) {
+        double a = 0.0, mm = 0.0;
+        for (int c = 0; c < C; c++) { a += cvar[c]; mm += cmean[c]; }
+        const double mean_var = a / C * (double)n / (double)(n - 1);
+        double var_plus = mean_var * (double)(n - 1) / (double)n;
+        if (C > 1) {
+          mm /= C;
+          double b = 0.0;
+          for (int c = 0; c < C; c++) b += (cmean[c] - mm) * (cmean[c] - mm);
+          var_plus += b / (C - 1);
+        }
+        sc[0] = mean_var; sc[1] = var_plus;
+        sc[2] = 0.0; sc[3] = 0.0; sc[4] = 0.0; sc[5] = 0.0;   // sum of rho over lags < max_t, previous pair, rho(max_t), done
+      }
+      __threadfence_block();
+      __syncthreads();
+      const double mean_var = sc[0], var_plus = sc[1];
+      for (long long t0 = 0; t0 < n; t0 += DG_LAGS) {
+        for (int lg = w; lg < DG_LAGS; lg += DG_THREADS / 64) {
+          const long long t = t0 + lg;
+          double s = 0.0;
+          if (t < n)
+            for (int c = 0; c < C; c++) {
+              const double *xcc = xc + (size_t)c * n;
+              double a = 0.0;
+              for (long long i = lane; i + t < n; i += 64) a += xcc[i] * xcc[i + t];
+              s += dpp_wave_sum(a) / (double)n;                // biased autocovariance of chain c at lag t
+            }
+          if (lane == 0) rho[lg] = t < n ? 1.0 - (mean_var - s / C) / var_plus : NAN;
+        }
+        __syncthreads();
+        if (tid == 0) {
+          double tsum = sc[2], prev = sc[3];
+          for (int lg = 0; lg < DG_LAGS; lg += 2) {
+            const long long t = t0 + lg;
+            const double even = t == 0 ? 1.0 : rho[lg], odd = rho[lg + 1], pair = even + odd;
+            if (t < n - 5 && pair > 0) {                   // not the last pair: kept, then made monotone
+              double e = even, od = odd;
+              if (t >= 2 && pair > prev) { e = prev / 2; od = e; }
+              tsum += e; tsum += od;
+              prev = e + od;
+            } else {                                       // the last pair: max_t = t
+              sc[4] = (t == 0 || pair >= 0 || even > 0) ? even : 0.0;
+              sc[5] = 1.0;
+              break;
+            }
+          }
+          sc[2] = tsum; sc[3] = prev;
+        }
+        __syncthreads();
+        if (sc[5] != 0.0) break;
+      }
+      if (tid == 0) {
+        double tau = -1.0 + 2.0 * sc[2] + sc[4];
+        tau = fmax(tau, 1.0 / log10((double)S));
+        sc[6] = ((double)S / tau) / (double)S;
+      }
+      __syncthreads();
+      reff = sc[6];
+      __syncthreads();
+    }
+    // ---- PSIS of the ratios r = -ll: lw = r - max r
+    const double rmax = -mn;
+    auto lwv = [&](long long j) { return -ll[j] - rmax + 0.0; };
+    const long long Mt = (long long)ceil(fmin(0.2 * (double)S, 3.0 * sqrt((double)S / reff)));
+    double khat = INFINITY;
+    bool smooth = false;
+    double *tl = tail + 1;                                  // tail[0] = the cutoff, tail[1 .. M] = the M largest lw, ascending
+    if (Mt >= 5) {
+      dg_sort_runs(lwv, S, xk, xi, rkey, ridx);
+      for (long long j = tid; j < S; j += DG_THREADS) {
+        const double v = lwv(j);
+        const long long r0 = dg_rank(v, j, S, xk, xi, rkey, ridx) - 1;
+        rnk[j] = (int)r0;
+        if (r0 >= S - Mt - 1) tail[r0 - (S - Mt - 1)] = v;
+      }
+      __threadfence_block();
+      __syncthreads();
+      if (tl[Mt - 1] - tl[0] >= DBL_EPSILON / 100) {
+        smooth = true;
+        const int N = (int)Mt, m = 30 + (int)floor(sqrt((double)N));
+        const double ec = exp(tail[0]);
+        double *xs = xc;                                   // gpdfit's sample exp(tail) - exp(cutoff), ascending
+        for (int j = tid; j < N; j += DG_THREADS) xs[j] = exp(tl[j]) - ec;
+        __threadfence_block();
+        __syncthreads();
+        const double xstar = xs[(int)floor(N / 4.0 + 0.5) - 1];
+        for (int jj = w; jj < m; jj += DG_THREADS / 64) {  // one wave per grid point theta_j
+          const double theta = 1.0 / xs[N - 1] + (1.0 - sqrt((double)m / (jj + 0.5))) / 3.0 / xstar;
+          double a = 0.0;
+          for (int i = lane; i < N; i += 64) a += log1p(-theta * xs[i]);
+          const double kj = dpp_wave_sum(a) / N;
+          if (lane == 0) { th[jj] = theta; lth[jj] = N * (log(-theta / kj) - kj - 1.0); }
+        }
+        __threadfence_block();
+        __syncthreads();
+        if (tid == 0) {                                    // theta-hat = sum_j softmax(l)_j theta_j
+          double lm = -INFINITY;
+          for (int jj = 0; jj < m; jj++) lm = fmax(lm, lth[jj]);
+          double s = 0.0;
+          for (int jj = 0; jj < m; jj++) s += exp(lth[jj] - lm);
+          const double lse = lm + log(s);
+          double thh = 0.0;
+          for (int jj = 0; jj < m; jj++) thh += th[jj] * exp(lth[jj] - lse);
+          sc[7] = thh;
+        }
+        __syncthreads();
+        const double thh = sc[7];
+        double a = 0.0;
+        for (int j = tid; j < N; j += DG_THREADS) a += log1p(-thh * xs[j]);
+        double k = loo_block_sum(a, red) / N;
+        const double sigma = -k / thh;
+        k = k * N / (N + 10) + 10 * 0.5 / (N + 10);     // loo's weakly informative prior
+        if (isnan(k)) k = INFINITY;
+        khat = k;
+        if (isfinite(k))
+          for (int j = tid; j < N; j += DG_THREADS) tl[j] = log(sigma * expm1(-k * log1p(-(j + 0.5) / N)) / k + ec);
+        __threadfence_block();
+        __syncthreads();
+      }
+    }
+    auto lwf = [&](long long j) {                          // smoothed, then truncated at max lw = 0
+      double v = lwv(j);
+      if (smooth && rnk[j] >= S - Mt) v = tl[rnk[j] - (S - Mt)];
+      return fmin(v, 0.0);
+    };
+    // ---- self-normalised weights; elpd_loo_i = logsumexp(ll + lw), lpd_i = logsumexp(ll) - log S
+    double m1 = -INFINITY;
+    for (long long j = tid; j < S; j += DG_THREADS) m1 = fmax(m1, lwf(j));
+    m1 = loo_block_max(m1, red);
+    double s1 = 0.0, s3 = 0.0;
+    for (long long j = tid; j < S; j += DG_THREADS) { s1 += exp(lwf(j) - m1); s3 += exp(ll[j] - mx); }
+    const double lse_w = m1 + log(loo_block_sum(s1, red));
+    const double lpd = mx + log(loo_block_sum(s3, red)) - log((double)S);
+    double m2 = -INFINITY;
+    for (long long j = tid; j < S; j += DG_THREADS) m2 = fmax(m2, ll[j] + (lwf(j) - lse_w));
+    m2 = loo_block_max(m2, red);
+    double s2 = 0.0;
+    for (long long j = tid; j < S; j += DG_THREADS) s2 += exp(ll[j] + (lwf(j) - lse_w) - m2);
+    const double elpd = m2 + log(loo_block_sum(s2, red));
+    if (tid == 0) { o[0] = elpd; o[1] = lpd - elpd; o[2] = -2.0 * elpd; o[3] = khat; o[4] = reff; }
+    __syncthreads();
+  }
+}

@@ -1,0 +1,148 @@
+"""PSIS-LOO cross-validation of the poll models on the GPU (Vehtari, Gelman, Gabry 2017), what `fit$loo()` gives a cmdstanr user with a
+`log_lik` generated quantity, and `loo_compare` to choose between the two variants fitted to the same polls.
+
+    1. per-poll log-likelihood       potus_log_lik_device (k_loo_loglik: rows rebuilt per draw, no draws x columns block)
+    2. PSIS per poll                 potus_loo / potus_loo_device (k_loo_psis: r_eff, generalized-Pareto tail, weights, elpd_loo_i)
+    3. comparison                    loo_compare (host: the pointwise differences)
+
+integrate=True (the default) integrates each poll's own noise coordinate raw_measure_noise_* out of its likelihood (integrated
+importance sampling, Vehtari et al. 2016): every poll has a parameter of its own, so leaving it out moves that parameter from posterior
+to prior, which plain PSIS-LOO (integrate=False) meets with high Pareto k.  DESIGN.md section 4e states the definitions.
+"""
+from __future__ import annotations
+
+import ctypes as C
+
+import numpy as np
+
+from .sampler import _check, _dp, load_library
+
+POINTWISE = ("elpd_loo", "p_loo", "looic", "pareto_k", "r_eff")
+ESTIMATES = ("elpd_loo", "p_loo", "looic")
+
+
+def poll_vectors(data):
+    """(outcomes, trials) of every poll: state polls, then national polls."""
+    y = np.concatenate([np.asarray(data["n_democrat_state"]), np.asarray(data["n_democrat_national"])]).astype(np.int64)
+    n = np.concatenate([np.asarray(data["n_two_share_state"]), np.asarray(data["n_two_share_national"])]).astype(np.int64)
+    return y, n
+
+
+class Loo:
+    """One fit's PSIS-LOO: estimates [3, 2] (elpd_loo, p_loo, looic) x (Estimate, SE), pointwise [N, 5] (POINTWISE), and the Pareto k table."""
+
+    def __init__(self, pointwise, estimates, n_draws, name=None, y=None, n=None, integrate=None):
+        self.pointwise = np.asarray(pointwise, dtype=np.float64)
+        self.estimates = np.asarray(estimates, dtype=np.float64).reshape(3, 2)
+        self.n_draws = int(n_draws)
+        self.name, self.integrate = name, integrate
+        self.y = None if y is None else np.asarray(y)
+        self.n = None if n is None else np.asarray(n)
+
+    @property
+    def pareto_k(self):
+        return self.pointwise[:, 3]
+
+    @property
+    def r_eff(self):
+        return self.pointwise[:, 4]
+
+    @property
+    def elpd_loo(self):
+        return float(self.estimates[0, 0])
+
+    @property
+    def se_elpd_loo(self):
+        return float(self.estimates[0, 1])
+
+    def k_threshold(self):
+        """loo 2.x: k-hat up to min(1 - 1 / log10 S, 0.7) is good."""
+        return min(1.0 - 1.0 / np.log10(self.n_draws), 0.7)
+
+    def pareto_k_table(self):
+        """{"good": count, "bad": count, "very bad": count}: k <= threshold, threshold < k <= 1, k > 1 (an infinite k-hat is very bad)."""
+        k, t = self.pareto_k, self.k_threshold()
+        return {"good": int((k <= t).sum()), "bad": int(((k > t) & (k <= 1)).sum()), "very bad": int((k > 1).sum())}
+
+    def __str__(self):
+        N = self.pointwise.shape[0]
+        form = {None: "", True: " (noise coordinate integrated out)", False: " (plain)"}[self.integrate]
+        lines = [f"Computed from {self.n_draws} by {N} log-likelihood matrix{form}", "", f"{'':10s}{'Estimate':>10s}{'SE':>8s}"]
+        for i, nm in enumerate(ESTIMATES):
+            lines.append(f"{nm:10s}{self.estimates[i, 0]:10.1f}{self.estimates[i, 1]:8.1f}")
+        t = self.k_threshold()
+        tab = self.pareto_k_table()
+        lines += ["", "Pareto k diagnostic values:", f"{'':28s}{'Count':>6s}{'Pct.':>8s}"]
+        for rng, lab in ((f"(-Inf, {t:.2f}]", "good"), (f"({t:.2f}, 1]", "bad"), ("(1, Inf)", "very bad")):
+            lines.append(f"{rng:>14s}  {'(' + lab + ')':12s}{tab[lab]:6d}{100.0 * tab[lab] / N:7.1f}%")
+        return "\n".join(lines)
+
+
+def loo(handles, integrate=True, r_eff=None, name=None):
+    """potus_loo over the pooled post-warm-up draws of the listed handles (one posterior, one GPU or several).  r_eff: [N polls], or None
+    (computed per poll as loo::relative_eff)."""
+    hs = list(handles) if isinstance(handles, (list, tuple)) else [handles]
+    h0 = hs[0]
+    N = h0.n_polls
+    pw, est = np.zeros((N, 5)), np.zeros((3, 2))
+    re = None if r_eff is None else np.ascontiguousarray(r_eff, dtype=np.float64).reshape(N)
+    ids = (C.c_int * len(hs))(*[h.h for h in hs])
+    _check(h0.L, h0.L.potus_loo(ids, len(hs), int(bool(integrate)), None if re is None else _dp(re), _dp(pw), _dp(est)))
+    y, n = poll_vectors(h0.data)
+    S = h0.post_warmup_saved() * sum(h.opts.chains for h in hs)
+    return Loo(pw, est, S, name if name is not None else h0.variant, y, n, bool(integrate))
+
+
+def loo_of_block(block, r_eff=None, name=None, y=None, n=None):
+    """potus_loo_device on a torch tensor [polls, chains, draws] (float64, contiguous, on a GPU) of log-likelihoods."""
+    import torch
+    if not (block.is_cuda and block.dtype == torch.float64 and block.is_contiguous() and block.dim() == 3):
+        raise TypeError("loo_of_block needs a contiguous float64 [polls, chains, draws] tensor on the GPU")
+    L = load_library()
+    N, ch, nd = (int(x) for x in block.shape)
+    pw, est = np.zeros((N, 5)), np.zeros((3, 2))
+    re = None if r_eff is None else np.ascontiguousarray(r_eff, dtype=np.float64).reshape(N)
+    torch.cuda.current_stream(block.device).synchronize()
+    _check(L, L.potus_loo_device(int(block.device.index or 0), C.c_void_p(block.data_ptr()), N, ch, nd, None if re is None else _dp(re),
+                                 _dp(pw), _dp(est)))
+    return Loo(pw, est, ch * nd, name, y, n)
+
+
+def loo_compare(*loos):
+    """loo::loo_compare: rows sorted by elpd_loo (best first), each a dict with name, elpd_diff (against the best) and
+    se_diff = sqrt(N) sd(elpd_loo_i - elpd_loo_i of the best) (n - 1 in sd), then elpd_loo, se_elpd_loo, p_loo, se_p_loo, looic, se_looic.
+    Refuses fits of different polls (outcomes or trials differ)."""
+    if len(loos) == 1 and isinstance(loos[0], (list, tuple)):
+        loos = tuple(loos[0])
+    if len(loos) < 2:
+        raise ValueError("loo_compare needs at least two fits")
+    l0 = loos[0]
+    N = l0.pointwise.shape[0]
+    for lo in loos[1:]:
+        same = lo.pointwise.shape[0] == N and (lo.y is None) == (l0.y is None)
+        if same and l0.y is not None:
+            same = np.array_equal(lo.y, l0.y) and np.array_equal(lo.n, l0.n)
+        if not same:
+            raise ValueError("loo_compare: the fits were not fitted to the same polls (their outcome or trial vectors differ)")
+    order = sorted(range(len(loos)), key=lambda i: -loos[i].elpd_loo)
+    best = loos[order[0]].pointwise[:, 0]
+    rows = []
+    for r, i in enumerate(order):
+        lo = loos[i]
+        d = lo.pointwise[:, 0] - best
+        row = {"name": lo.name if lo.name is not None else f"model{i + 1}", "elpd_diff": float(d.sum()),
+               "se_diff": 0.0 if r == 0 else float(np.sqrt(N) * np.std(d, ddof=1))}
+        for k, nm in enumerate(ESTIMATES):
+            row[nm] = float(lo.estimates[k, 0])
+            row["se_" + nm] = float(lo.estimates[k, 1])
+        rows.append(row)
+    return rows
+
+
+def format_compare(rows):
+    keys = ("elpd_diff", "se_diff", "elpd_loo", "se_elpd_loo", "p_loo", "se_p_loo", "looic", "se_looic")
+    w = max(len(r["name"]) for r in rows) + 2
+    out = [" " * w + "".join(f"{k:>12s}" for k in keys)]
+    for r in rows:
+        out.append(f"{r['name']:{w}s}" + "".join(f"{r[k]:12.1f}" for k in keys))
+    return "\n".join(out)

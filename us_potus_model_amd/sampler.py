@@ -96,6 +96,10 @@ def load_library():
         L.potus_simulate_prior.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_int, dp, i32p, i32p]
         L.potus_constrain.argtypes = [C.c_int, dp, C.c_int, C.c_int, C.c_int, dp]
         L.potus_sbc_ranks.argtypes = [C.c_int, dp, C.c_int, C.c_int, C.c_int, i32p, i32p, ip]
+    if hasattr(L, "potus_loo"):                         # PSIS-LOO (loo.py)
+        L.potus_log_lik_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.potus_loo_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_longlong, dp, dp, dp]
+        L.potus_loo.argtypes = [ip, C.c_int, C.c_int, dp, dp, dp]
     _LIB = L
     return L
 
@@ -108,9 +112,10 @@ EXPORTS = [
     "potus_last_run_timing", "potus_posterior_summary", "potus_posterior_summary_many", "potus_backtest_scores",
     "potus_diagnostics", "potus_diagnostics_device", "potus_check_convergence",
     "potus_set_datasets", "potus_simulate_prior", "potus_constrain", "potus_sbc_ranks",
+    "potus_log_lik_device", "potus_loo_device", "potus_loo",
     "potus_R_create", "potus_R_init", "potus_R_run", "potus_R_run_many", "potus_R_num_columns", "potus_R_saved_count",
     "potus_R_write_array", "potus_R_write_stan_csv", "potus_R_posterior_summary", "potus_R_diagnostics", "potus_R_check_convergence", "potus_R_backtest_scores", "potus_R_last_error", "potus_R_destroy",
-    "potus_R_set_datasets", "potus_R_simulate_prior", "potus_R_sbc_ranks", "potus_R_constrain",
+    "potus_R_set_datasets", "potus_R_simulate_prior", "potus_R_sbc_ranks", "potus_R_constrain", "potus_R_loo",
 ]
 
 
@@ -360,6 +365,29 @@ class Handle:
         _check(self.L, self.L.potus_sbc_ranks(self.h, _dp(truth), int(col_begin), int(col_end), int(thin), _ip(less), _ip(equal), C.byref(L)))
         return less, equal, L.value
 
+    @property
+    def n_polls(self):
+        """Polls of the data: state polls, then national polls (the order of the logit_pi_democrat_* columns)."""
+        return int(self.data["N_state_polls"]) + int(self.data["N_national_polls"])
+
+    def post_warmup_saved(self):
+        """Saved draws per chain that are not warm-up rows (save_warmup = 1 saves those too)."""
+        n = self.draws_saved()
+        return n - (min(n, self.opts.num_warmup) if self.opts.save_warmup else 0)
+
+    def log_lik_device(self, poll_begin, poll_end, out, integrate=True):
+        """potus_log_lik_device: per-poll log-likelihoods of the post-warm-up draws into a torch tensor on this handle's GPU
+        ([poll_end - poll_begin, chains, draws], float64, contiguous).  integrate: each poll's own noise coordinate integrated out."""
+        import torch
+        if not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()):
+            raise TypeError("log_lik_device needs a contiguous float64 tensor on the GPU")
+        want = (int(poll_end) - int(poll_begin)) * self.opts.chains * self.post_warmup_saved()
+        if out.numel() != want:
+            raise ValueError(f"tensor has {out.numel()} elements, {want} expected")
+        torch.cuda.current_stream(out.device).synchronize()
+        _check(self.L, self.L.potus_log_lik_device(self.h, int(poll_begin), int(poll_end), int(bool(integrate)), C.c_void_p(out.data_ptr())))
+        return out
+
     def write_stan_csv(self, directory, basename="poll_model_2020"):
         os.makedirs(directory, exist_ok=True)
         _check(self.L, self.L.potus_write_stan_csv(self.h, str(directory).encode(), basename.encode()))
@@ -528,6 +556,11 @@ class StanFit:
     def summary(self, ev):
         """Device-side posterior summaries over all chains of the fit (see posterior_summary)."""
         return posterior_summary(self._hs, ev)
+
+    def loo(self, integrate=True, r_eff=None):
+        """fit$loo(): PSIS-LOO of the polls over every chain of the fit, on the device (us_potus_model_amd.loo)."""
+        from .loo import loo
+        return loo(self._hs, integrate=integrate, r_eff=r_eff, name=self.model_name)
 
     def extract(self, pars, permuted=False):
         """rstan::extract(out, pars=)[[1]]: array [draws, ...dims], chains merged.
