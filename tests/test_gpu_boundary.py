@@ -705,6 +705,69 @@ def test_device_diagnostics_over_the_chains_of_several_handles(cases):
 
 
 @pytest.mark.gpu
+def test_pooled_entry_points_accept_and_refuse_the_same_handle_lists(cases):
+    """What every call that pools the chains of several handles does with a list of handles: `a` and `b` hold chains 1-2 and 3-4 of one posterior
+    (b on `second_device()`), `g` the other variant (another number of columns), `o` other poll counts (same columns), `short` the posterior of
+    `a` with fewer saved draws, `few` fewer than four.  [a, b] is pooled; [a, a] is refused as listed twice, [a, g] and [a, o] as another
+    posterior (potus_extract_matrix only looks at the number of columns, in its own words), [a, short] for its unequal counts except by the
+    summary, which pools whatever is saved; potus_check_convergence says "not yet" before it looks at the list while the first handle holds
+    fewer than four draws.  (PSIS-LOO's own refusals: tests/test_gpu_loo.py.)"""
+    from conftest import second_device
+    from us_potus_model_amd import check_convergence, device_diagnostics, loo as loo_mod, synthetic
+    from us_potus_model_amd.sampler import PotusError
+    data, variant = cases["small_full"]
+    kw = dict(num_warmup=30, num_samples=20, seed=11, cus_per_chain=1, twin=0)
+
+    def fit(d, v, n_iter, **more):
+        h = Handle(d, v, chains=2, **kw, **more)
+        h.init(); h.run(n_iter)
+        return h
+
+    a = fit(data, variant, 50)
+    b = fit(data, variant, 50, chain_id_offset=2, device=second_device())
+    g = fit(*cases["small_nomode"], 50)
+    o = fit(dict(data, n_democrat_state=np.asarray(data["n_democrat_state"]) // 2), variant, 50)
+    short = fit(data, variant, 40, chain_id_offset=2)
+    few = fit(data, variant, 32, chain_id_offset=2)
+    S = int(data["S"])
+    L = a.L
+    L.potus_extract_matrix.argtypes = [IP, C.c_int, C.c_int, C.c_int, DP, C.c_longlong, C.POINTER(C.c_longlong)]
+
+    def extract(hs):
+        ids, rows = (C.c_int * len(hs))(*[h.h for h in hs]), C.c_longlong()
+        sampler._check(L, L.potus_extract_matrix(ids, len(hs), 0, 3, None, 0, C.byref(rows)))
+        out = np.zeros((3, rows.value))
+        sampler._check(L, L.potus_extract_matrix(ids, len(hs), 0, 3, out.ctypes.data_as(DP), rows.value, None))
+        return out
+
+    calls = {"extract": extract, "summary": lambda hs: posterior_summary(hs, np.ones(S)), "diagnostics": lambda hs: device_diagnostics(hs, 0, 3),
+             "check_convergence": check_convergence, "loo": loo_mod.loo}
+    for name, call in calls.items():
+        call([a, b])
+        with pytest.raises(PotusError, match="twice"):
+            call([a, a])
+        with pytest.raises(PotusError, match="different posteriors" if name == "extract" else "another posterior"):
+            call([a, g])
+        if name == "extract":
+            assert call([a, o]).shape == (3, 80)                       # same columns: taken
+        else:
+            with pytest.raises(PotusError, match="another posterior"):
+                call([a, o])
+        if name == "summary":
+            call([a, short])                                           # 2 x 20 + 2 x 10 draws
+        else:
+            with pytest.raises(PotusError, match="libpotus_hmc error 4.*saved"):
+                call([a, short])
+    assert extract([a, b]).shape == (3, 80)
+    assert np.array_equal(extract([a, b])[:, :40], extract([a]))
+    assert check_convergence([few, few]) == (False, pytest.approx(np.nan, nan_ok=True), pytest.approx(np.nan, nan_ok=True))
+    with pytest.raises(PotusError, match="at least four"):
+        device_diagnostics([few], 0, 3)
+    for h in (a, b, g, o, short, few):
+        h.close()
+
+
+@pytest.mark.gpu
 def test_bench_two_ranks_over_rccl_on_two_gpus():
     """bench.py --gpus 2 exactly as the driver launches it -- torch.distributed.run, one rank per GPU, backend "nccl" (= RCCL over
     xGMI): chains sharded by global chain id, the device-side all-gather of lp__ + mu_b, pooled R-hat / ESS on the device, ONE JSON

@@ -105,3 +105,26 @@ def test_new_entry_points_fail_cleanly_on_a_bad_handle():
     st.value = 0
     L.potus_R_constrain(C.byref(h), dp, C.byref(C.c_int(1)), two, dp, C.byref(st))
     assert st.value == 4 and _err(L) == "bad handle"
+
+
+def test_pooled_entry_points_refuse_a_null_list_and_an_unknown_handle():
+    """Every entry point that takes a list of handles: a null list is an argument error (1) and handle 12345 a state error (4) whose message
+    names the handle -- decided on the host, before any HIP call (this machine may have no GPU)."""
+    L = sampler.load_library()
+    f64 = np.zeros(64)
+    dp = f64.ctypes.data_as(C.POINTER(C.c_double))
+    ip = C.POINTER(C.c_int)
+    n, ll = C.c_int(), C.c_longlong()
+    L.potus_extract_matrix.argtypes = [ip, C.c_int, C.c_int, C.c_int, C.POINTER(C.c_double), C.c_longlong, C.POINTER(C.c_longlong)]
+    calls = {
+        "potus_extract_matrix": lambda h, k: L.potus_extract_matrix(h, k, 0, 1, None, 0, C.byref(ll)),
+        "potus_posterior_summary_many": lambda h, k: L.potus_posterior_summary_many(h, k, dp, dp, dp, dp),
+        "potus_diagnostics": lambda h, k: L.potus_diagnostics(h, k, 0, 1, dp, dp),
+        "potus_check_convergence": lambda h, k: L.potus_check_convergence(h, k, 1.01, 400.0, C.byref(n), dp, dp),
+        "potus_loo": lambda h, k: L.potus_loo(h, k, 0, None, dp, dp),
+        "potus_run_many": lambda h, k: L.potus_run_many(h, k, 5),
+    }
+    bad = (C.c_int * 1)(12345)
+    for name, call in calls.items():
+        assert call(None, 1) == 1 and "null" in _err(L), (name, _err(L))
+        assert call(bad, 1) == 4 and "bad handle 12345" in _err(L), (name, _err(L))

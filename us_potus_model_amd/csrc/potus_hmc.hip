@@ -2282,6 +2282,125 @@ int dense_import_init(Sampler *sp) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------- pooled calls
+// Calls that take a list of handles and treat their chains as the chains of ONE posterior ("The pooling contract").
+int saved_count(Sampler *sp, int *n_saved) {
+  std::vector<ChainScalars> sc;
+  { const int rc_ = read_scalars(sp, sc); if (rc_) return rc_; }
+  int m = -1;   // (many data sets: over the chains that have not failed)
+  for (auto &s : sc) if (!sp->n_ds || s.status == 0) m = m < 0 ? s.saved : std::min(m, s.saved);
+  *n_saved = std::max(m, 0);
+  return 0;
+}
+
+// warm-up rows among the first n_saved rows of a handle (save_warmup = 1): not draws from the posterior -- rstan::monitor and extract() drop them
+int warm_rows(const Sampler *sp, int n_saved) { return sp->opts.save_warmup ? std::min(n_saved, sp->R.num_warmup) : 0; }
+
+int check_cols(const Sampler *sp, int col_begin, int col_end) {
+  if (col_begin < 0 || col_end > sp->L.ncols || col_begin >= col_end) return fail(POTUS_ERR_ARG, "bad column range [%d,%d) of %d", col_begin, col_end, sp->L.ncols);
+  return 0;
+}
+
+// The listed handles, resolved.  Everything down to same_posterior() needs no device and is done before the first HIP call; count() runs
+// under the caller's DeviceLocks(devs), which the caller holds from there to the last synchronise of the call.
+struct Pool {
+  const char *what = "";
+  const int *handles = nullptr;
+  std::vector<Sampler *> sps;
+  std::vector<int> devs, saved;   // per handle: its device; its saved rows per chain (count())
+  Sampler *s0 = nullptr;          // the first handle: the pooled work runs on its GPU
+  int chains = 0;                 // count(): chains of all handles
+  long long draws = 0;            //          ... and the rows they have saved
+
+  int lookup(const int *h, int n, const char *what_) {
+    what = what_; handles = h;
+    if (!h || n < 1) return fail(POTUS_ERR_ARG, "%s: null handle list", what);
+    for (int i = 0; i < n; i++) {
+      Sampler *sp = get(h[i]);
+      if (!sp) return fail(POTUS_ERR_STATE, "%s: bad handle %d", what, h[i]);
+      sps.push_back(sp); devs.push_back(sp->device);
+    }
+    s0 = sps[0];
+    return 0;
+  }
+  int single_dataset() const {
+    for (const Sampler *sp : sps) if (const int rc = refuse_many_datasets(sp, what)) return rc;
+    return 0;
+  }
+  int distinct() const {
+    for (size_t i = 0; i < sps.size(); i++)
+      for (size_t j = 0; j < i; j++) if (handles[j] == handles[i]) return fail(POTUS_ERR_ARG, "%s: handle %d listed twice", what, handles[i]);
+    return 0;
+  }
+  // what a call that pools chains starts with
+  int resolve(const int *h, int n, const char *what_) {
+    if (const int rc = lookup(h, n, what_)) return rc;
+    if (const int rc = single_dataset()) return rc;
+    return distinct();
+  }
+  // same columns, same variant, same data (hash_data covers the sizes, S and T among them)
+  int same_posterior(const char *why) const {
+    for (size_t i = 1; i < sps.size(); i++)
+      if (sps[i]->L.ncols != s0->L.ncols || sps[i]->M.full != s0->M.full || sps[i]->data_hash != s0->data_hash)
+        return fail(POTUS_ERR_ARG, "%s: handle %d holds another posterior than handle %d (%s)", what, handles[i], handles[0], why);
+    return 0;
+  }
+  int count() {
+    saved.assign(sps.size(), 0); chains = 0; draws = 0;
+    for (size_t i = 0; i < sps.size(); i++) {
+      HIP_TRY(hipSetDevice(sps[i]->device));
+      if (const int rc = saved_count(sps[i], &saved[i])) return rc;
+      chains += sps[i]->R.chains; draws += (long long)saved[i] * sps[i]->R.chains;
+    }
+    return 0;
+  }
+  int equal_counts() const {
+    for (size_t i = 1; i < sps.size(); i++)
+      if (saved[i] != saved[0]) return fail(POTUS_ERR_STATE, "%s: handle %d has saved %d draws per chain, handle %d has %d", what, handles[i], saved[i], handles[0], saved[0]);
+    return 0;
+  }
+  // after equal_counts(): the first post-warm-up row of every handle and the draws per chain from there on
+  int post_warmup(int *first, int *n_post) const {
+    *first = warm_rows(s0, saved[0]); *n_post = saved[0] - *first;
+    for (const Sampler *sp : sps) if (warm_rows(sp, saved[0]) != *first) return fail(POTUS_ERR_ARG, "%s: the handles saved different numbers of warm-up rows", what);
+    if (*n_post < 4) return fail(POTUS_ERR_STATE, "%s needs at least four saved post-warm-up draws per chain (%d saved, %d of them warm-up)", what, saved[0], *first);
+    return 0;
+  }
+};
+
+// One handle's block of a pooled call: made on the handle's own GPU -- produce(out) queues the work on sp's stream, sp's device current -- and
+// landed in dst on the first handle's.  On return the block is complete and s0's device is current.
+template <class Produce>
+int gather_block(Sampler *s0, Sampler *sp, size_t bytes, double *dst, Produce produce) {
+  HIP_TRY(hipSetDevice(sp->device));
+  DevBufs far;
+  double *blk = dst;
+  if (sp->device != s0->device) HIP_TRY(far.alloc(&blk, bytes));
+  if (const int rc = produce(blk)) return rc;
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  if (blk != dst) {
+    // (hipMemcpyPeer stages through the host when the two GPUs have no peer access; with it, the copy goes over xGMI)
+    int can = 0;
+    if (hipDeviceCanAccessPeer(&can, s0->device, sp->device) == hipSuccess && can) { (void)hipSetDevice(s0->device); (void)hipDeviceEnablePeerAccess(sp->device, 0); (void)hipGetLastError(); }
+    HIP_TRY(hipMemcpyPeer(dst, s0->device, blk, sp->device, bytes));
+  }
+  HIP_TRY(hipSetDevice(s0->device));
+  return 0;
+}
+
+// blk [n][C][ncol] -> the places of chains coff .. coff + C - 1 in cols [ncol][Ctot][n]
+int transpose_block(hipStream_t st, const double *blk, double *cols, long long n, int C, int ncol, int Ctot, int coff) {
+  hipLaunchKernelGGL(k_dg_transpose, dim3((ncol + 63) / 64, (unsigned)((n + 63) / 64), C), dim3(256), 0, st, blk, cols, n, C, ncol, Ctot, coff);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+// ... of one handle of a pool, on the first handle's GPU, finished on return (the caller frees blk next)
+int pool_transpose(Sampler *s0, const double *blk, double *cols, int n_post, int C, int ncol, int Ctot, int coff) {
+  if (const int rc = transpose_block(s0->stream, blk, cols, n_post, C, ncol, Ctot, coff)) return rc;
+  HIP_TRY(hipStreamSynchronize(s0->stream));
+  return 0;
+}
+
 } // namespace
 
 // ======================================================================== C ABI
@@ -2715,17 +2834,15 @@ int potus_run(int handle, int n_iter) {
 int potus_run_many(const int *handles, int n_handles, int n_iter) {
   if (!handles || n_handles < 0) return fail(POTUS_ERR_ARG, "potus_run_many: null handle list");
   if (n_iter <= 0 || n_handles == 0) return 0;
+  Pool P;   // (no chains are pooled here: handles with several data sets are welcome)
+  if (const int rc_ = P.lookup(handles, n_handles, "potus_run_many")) return rc_;
   std::vector<RunTicket> todo;
   for (int i = 0; i < n_handles; i++) {
-    Sampler *sp = get(handles[i]);
-    if (!sp) return fail(POTUS_ERR_STATE, "potus_run_many: bad handle %d", handles[i]);
-    if (!sp->inited) return fail(POTUS_ERR_STATE, "potus_init must be called before potus_run_many");
-    for (int j = 0; j < i; j++) if (handles[j] == handles[i]) return fail(POTUS_ERR_ARG, "potus_run_many: handle %d listed twice", handles[i]);
-    todo.push_back(RunTicket{sp, handles[i], 0, 0});
+    if (!P.sps[i]->inited) return fail(POTUS_ERR_STATE, "potus_init must be called before potus_run_many");
+    todo.push_back(RunTicket{P.sps[i], handles[i], 0, 0});
   }
-  std::vector<int> devs;
-  for (const RunTicket &t : todo) devs.push_back(t.sp->device);
-  DeviceLocks lock(devs);
+  if (const int rc_ = P.distinct()) return rc_;
+  DeviceLocks lock(P.devs);
   std::vector<char> done(todo.size(), 0);
   size_t n_done = 0;
   while (n_done < todo.size()) {
@@ -2997,15 +3114,6 @@ int potus_dense_check(int handle, int chain, int n_probe, double *out) {
   return 0;
 }
 
-static int saved_count(Sampler *sp, int *n_saved) {
-  std::vector<ChainScalars> sc;
-  { const int rc_ = read_scalars(sp, sc); if (rc_) return rc_; }
-  int m = -1;   // (many data sets: over the chains that have not failed)
-  for (auto &s : sc) if (!sp->n_ds || s.status == 0) m = m < 0 ? s.saved : std::min(m, s.saved);
-  *n_saved = std::max(m, 0);
-  return 0;
-}
-
 int potus_get_draws(int handle, double *out, int *n_saved) {
   Sampler *sp = get(handle);
   if (!sp || !n_saved) return fail(POTUS_ERR_STATE, "bad handle");
@@ -3051,7 +3159,7 @@ static int write_array_range(Sampler *sp, int n_saved, int col_begin, int col_en
 int potus_write_array(int handle, int col_begin, int col_end, double *out) {
   Sampler *sp = get(handle);
   if (!sp || !out) return fail(POTUS_ERR_STATE, "bad handle or null output");
-  if (col_begin < 0 || col_end > sp->L.ncols || col_begin >= col_end) return fail(POTUS_ERR_ARG, "bad column range [%d,%d) of %d", col_begin, col_end, sp->L.ncols);
+  if (const int rc_ = check_cols(sp, col_begin, col_end)) return rc_;
   DeviceLocks lock(sp->device);
   HIP_TRY(hipSetDevice(sp->device));
   int n_saved = 0, rc = saved_count(sp, &n_saved);
@@ -3084,28 +3192,18 @@ __global__ __launch_bounds__(256) void k_rows_to_r_matrix(const double *in, doub
   }
 }
 int potus_extract_matrix(const int *handles, int n_handles, int col_begin, int col_end, double *out, long long rows, long long *rows_out) {
-  if (!handles || n_handles < 1) return fail(POTUS_ERR_ARG, "potus_extract_matrix: null handle list");
-  std::vector<Sampler *> sps;
-  std::vector<int> saved(n_handles, 0), devs;
-  long long total = 0;
-  for (int i = 0; i < n_handles; i++) {
-    Sampler *sp = get(handles[i]);
-    if (!sp) return fail(POTUS_ERR_STATE, "potus_extract_matrix: bad handle %d", handles[i]);
-    if (const int rc_ = refuse_many_datasets(sp, "potus_extract_matrix")) return rc_;
-    for (int j = 0; j < i; j++) if (handles[j] == handles[i]) return fail(POTUS_ERR_ARG, "potus_extract_matrix: handle %d listed twice", handles[i]);
-    if (i > 0 && sp->L.ncols != sps[0]->L.ncols) return fail(POTUS_ERR_ARG, "potus_extract_matrix: the handles hold different posteriors");
-    sps.push_back(sp); devs.push_back(sp->device);
-  }
-  if (col_begin < 0 || col_end > sps[0]->L.ncols || col_begin >= col_end) return fail(POTUS_ERR_ARG, "bad column range [%d,%d) of %d", col_begin, col_end, sps[0]->L.ncols);
+  Pool P;
+  if (const int rc_ = P.resolve(handles, n_handles, "potus_extract_matrix")) return rc_;
+  for (const Sampler *sp : P.sps)   // (the columns alone: weaker than Pool::same_posterior)
+    if (sp->L.ncols != P.s0->L.ncols) return fail(POTUS_ERR_ARG, "potus_extract_matrix: the handles hold different posteriors");
+  if (const int rc_ = check_cols(P.s0, col_begin, col_end)) return rc_;
   DeviceGuard guard;
-  DeviceLocks lock(devs);
-  for (int i = 0; i < n_handles; i++) {
-    HIP_TRY(hipSetDevice(sps[i]->device));
-    const int rc = saved_count(sps[i], &saved[i]);
-    if (rc) return rc;
-    if (i > 0 && saved[i] != saved[0]) return fail(POTUS_ERR_STATE, "potus_extract_matrix: the handles have saved different numbers of draws (%d, %d)", saved[0], saved[i]);
-    total += (long long)saved[i] * sps[i]->R.chains;
-  }
+  DeviceLocks lock(P.devs);
+  if (const int rc_ = P.count()) return rc_;
+  if (const int rc_ = P.equal_counts()) return rc_;
+  const std::vector<Sampler *> &sps = P.sps;
+  const std::vector<int> &saved = P.saved;
+  const long long total = P.draws;
   if (rows_out) *rows_out = total;
   if (!out) return 0;
   if (rows != total) return fail(POTUS_ERR_ARG, "potus_extract_matrix: the result has %lld rows, the handles hold %lld draws", rows, total);
@@ -3136,7 +3234,7 @@ int potus_extract_matrix(const int *handles, int n_handles, int col_begin, int c
 int potus_write_array_device(int handle, int col_begin, int col_end, void *out_device) {
   Sampler *sp = get(handle);
   if (!sp || !out_device) return fail(POTUS_ERR_STATE, "bad handle or null output");
-  if (col_begin < 0 || col_end > sp->L.ncols || col_begin >= col_end) return fail(POTUS_ERR_ARG, "bad column range [%d,%d) of %d", col_begin, col_end, sp->L.ncols);
+  if (const int rc_ = check_cols(sp, col_begin, col_end)) return rc_;
   DeviceLocks lock(sp->device);
   HIP_TRY(hipSetDevice(sp->device));
   hipPointerAttribute_t at;
@@ -3154,32 +3252,15 @@ int potus_write_array_device(int handle, int col_begin, int col_end, void *out_d
 // predicted_score blocks of other GPUs are brought over with a peer copy.  Any number of draws (potus_summary.hpp).
 int potus_posterior_summary_many(const int *handles, int n_handles, const double *ev, double *state_out, double *natl_out, double *ev_out) {
   if (!handles || n_handles < 1 || !ev || !state_out || !natl_out || !ev_out) return fail(POTUS_ERR_ARG, "potus_posterior_summary: null argument");
-  std::vector<Sampler *> sps;
-  std::vector<int> n_saved(n_handles, 0), devs;
-  long long nd = 0;
-  for (int i = 0; i < n_handles; i++) {
-    Sampler *sp = get(handles[i]);
-    if (!sp) return fail(POTUS_ERR_STATE, "potus_posterior_summary: bad handle %d", handles[i]);
-    if (const int rc_ = refuse_many_datasets(sp, "potus_posterior_summary")) return rc_;
-    devs.push_back(sp->device);
-  }
+  Pool P;
+  if (const int rc_ = P.resolve(handles, n_handles, "potus_posterior_summary")) return rc_;
+  // (the first handle's state weights are the ones the national vote is taken with)
+  if (const int rc_ = P.same_posterior("pooled summaries are for the chains of one")) return rc_;
   DeviceGuard guard;                                   // whatever happens below, the caller's device comes back
-  DeviceLocks lock(devs);
-  for (int i = 0; i < n_handles; i++) {
-    Sampler *sp = get(handles[i]);
-    for (int j = 0; j < i; j++) if (handles[j] == handles[i]) return fail(POTUS_ERR_ARG, "potus_posterior_summary: handle %d listed twice", handles[i]);
-    // pooling is for the chains of ONE posterior: same shape, same variant, same data (its hash) -- the first handle's state
-    // weights are the ones the national vote is taken with
-    if (i > 0 && (sp->M.S != sps[0]->M.S || sp->M.T != sps[0]->M.T || sp->L.ncols != sps[0]->L.ncols || sp->M.full != sps[0]->M.full ||
-                  sp->data_hash != sps[0]->data_hash))
-      return fail(POTUS_ERR_ARG, "potus_posterior_summary: handle %d holds another posterior than handle %d (pooled summaries are for the chains of one)", handles[i], handles[0]);
-    HIP_TRY(hipSetDevice(sp->device));
-    int rc = saved_count(sp, &n_saved[i]);
-    if (rc) return rc;
-    nd += (long long)n_saved[i] * sp->R.chains;
-    sps.push_back(sp);
-  }
-  Sampler *s0 = sps[0];
+  DeviceLocks lock(P.devs);
+  if (const int rc_ = P.count()) return rc_;           // (the handles may have saved different numbers of draws: every one of them is pooled)
+  Sampler *s0 = P.s0;
+  const long long nd = P.draws;
   const int S = s0->M.S, T = s0->M.T, TS = S * T, NC = TS + 2 * T;
   if (nd < 2) return fail(POTUS_ERR_STATE, "posterior summaries need at least two saved draws");
   const int col_end = s0->L.ncols, col_begin = col_end - TS;   // predicted_score = the generated-quantities block
@@ -3192,28 +3273,15 @@ int potus_posterior_summary_many(const int *handles, int n_handles, const double
   HIP_TRY(tmp.alloc(&dout, ((size_t)TS * 4 + (size_t)T * 9) * 8));
   long long row0 = 0;
   for (int i = 0; i < n_handles; i++) {
-    Sampler *sp = sps[i];
-    const long long rows = (long long)n_saved[i] * sp->R.chains;
+    Sampler *sp = P.sps[i];
+    const int n_saved = P.saved[i];
+    const long long rows = (long long)n_saved * sp->R.chains;
     if (rows == 0) continue;
-    double *dst = full + (size_t)row0 * NC;
-    int rc;
-    if (sp->device == s0->device) {
-      if ((rc = write_array_range(sp, n_saved[i], col_begin, col_end, dst, true, NC))) return rc;
-    } else {
-      HIP_TRY(hipSetDevice(sp->device));
-      DevBufs far;                                     // freed on its own device before we go back
-      double *blk = nullptr;
-      HIP_TRY(far.alloc(&blk, (size_t)rows * NC * 8));
-      if ((rc = write_array_range(sp, n_saved[i], col_begin, col_end, blk, true, NC))) return rc;
-      // (hipMemcpyPeer stages through the host when the two GPUs have no peer access; with it, the copy goes over xGMI)
-      int can = 0;
-      if (hipDeviceCanAccessPeer(&can, s0->device, sp->device) == hipSuccess && can) { (void)hipSetDevice(s0->device); (void)hipDeviceEnablePeerAccess(sp->device, 0); (void)hipGetLastError(); (void)hipSetDevice(sp->device); }
-      HIP_TRY(hipMemcpyPeer(dst, s0->device, blk, sp->device, (size_t)rows * NC * 8));
-      HIP_TRY(hipSetDevice(s0->device));
-    }
+    const int rc = gather_block(s0, sp, (size_t)rows * NC * 8, full + (size_t)row0 * NC,
+                                [&](double *out) { return write_array_range(sp, n_saved, col_begin, col_end, out, true, NC); });
+    if (rc) return rc;
     row0 += rows;
   }
-  HIP_TRY(hipSetDevice(s0->device));
   HIP_TRY(hipMemcpyAsync(dw, s0->h_w.data(), (size_t)S * 8, hipMemcpyHostToDevice, s0->stream));
   HIP_TRY(hipMemcpyAsync(dev_, ev, (size_t)S * 8, hipMemcpyHostToDevice, s0->stream));
   hipLaunchKernelGGL(k_ps_derived, dim3((unsigned)std::min<long long>((nd * T + 255) / 256, 65535)), dim3(256), 0, s0->stream, full, nd, T, S,
@@ -3283,89 +3351,47 @@ int potus_diagnostics_device(int device, const void *block, long long n_draws, i
   DevBufs tmp;
   double *cols = nullptr;
   HIP_TRY(tmp.alloc(&cols, (size_t)n_draws * n_chains * n_cols * 8));
-  hipLaunchKernelGGL(k_dg_transpose, dim3((n_cols + 63) / 64, (unsigned)((n_draws + 63) / 64), n_chains), dim3(256), 0, 0, (const double *)block, cols, n_draws, n_chains,
-                     n_cols, n_chains, 0);
-  HIP_TRY(hipGetLastError());
+  if (const int rc_ = transpose_block(0, (const double *)block, cols, n_draws, n_chains, n_cols, n_chains, 0)) return rc_;
   return diagnostics_of_columns(0, cols, n_draws, n_chains, n_cols, rhat_out, ess_bulk_out);
 }
 
-// (have_locks: the caller already holds the device locks of every handle -- potus_check_convergence takes its two column ranges under ONE set of locks, so that
-//  no run on another host thread can add draws between them)
-static int diagnostics_impl(const int *handles, int n_handles, int col_begin, int col_end, double *rhat_out, double *ess_bulk_out, bool have_locks) {
-  if (!handles || n_handles < 1 || !rhat_out || !ess_bulk_out) return fail(POTUS_ERR_ARG, "potus_diagnostics: null argument");
-  std::vector<Sampler *> sps;
-  std::vector<int> devs;
-  for (int i = 0; i < n_handles; i++) {
-    Sampler *sp = get(handles[i]);
-    if (!sp) return fail(POTUS_ERR_STATE, "bad handle %d", handles[i]);
-    for (int j = 0; j < i; j++) if (handles[j] == handles[i]) return fail(POTUS_ERR_ARG, "potus_diagnostics: handle %d listed twice", handles[i]);
-    sps.push_back(sp); devs.push_back(sp->device);
-  }
-  Sampler *s0 = sps[0];
-  if (col_begin < 0 || col_end > s0->L.ncols || col_begin >= col_end) return fail(POTUS_ERR_ARG, "potus_diagnostics: columns [%d, %d) of %d", col_begin, col_end, s0->L.ncols);
-  DeviceGuard guard;
-  DeviceLocks lock(have_locks ? std::vector<int>{} : devs);
-  int n_saved = -1, Ctot = 0;
-  for (size_t i = 0; i < sps.size(); i++) {
-    Sampler *sp = sps[i];
-    if (i > 0 && (sp->L.ncols != s0->L.ncols || sp->M.full != s0->M.full || sp->data_hash != s0->data_hash))
-      return fail(POTUS_ERR_ARG, "potus_diagnostics: handle %d holds another posterior than handle %d (R-hat / ESS pool the chains of one)", handles[i], handles[0]);
-    HIP_TRY(hipSetDevice(sp->device));
-    int ns = 0, rc = saved_count(sp, &ns);
-    if (rc) return rc;
-    if (n_saved >= 0 && ns != n_saved) return fail(POTUS_ERR_STATE, "potus_diagnostics: handle %d has saved %d draws per chain, handle %d has %d", handles[i], ns, handles[0], n_saved);
-    n_saved = ns; Ctot += sp->R.chains;
-  }
+// R-hat / bulk ESS of columns [col_begin, col_end) over the pooled post-warm-up draws of a counted pool, under the caller's locks
+static int diagnostics_pooled(const Pool &P, int col_begin, int col_end, double *rhat_out, double *ess_bulk_out) {
+  Sampler *s0 = P.s0;
+  const int Ctot = P.chains, n_saved = P.saved[0], NC = col_end - col_begin;
   if (2 * Ctot > DG_MAXCH) return fail(POTUS_ERR_UNSUPPORTED, "potus_diagnostics: %d chains pooled (at most %d)", Ctot, DG_MAXCH / 2);
-  // warm-up rows (save_warmup = 1) are not draws from the posterior: rstan::monitor and extract() drop them, and so does this
-  const int n_warm_rows = s0->opts.save_warmup ? std::min(n_saved, s0->R.num_warmup) : 0;
-  for (Sampler *sp : sps)
-    if ((sp->opts.save_warmup ? std::min(n_saved, sp->R.num_warmup) : 0) != n_warm_rows) return fail(POTUS_ERR_ARG, "potus_diagnostics: the handles saved different numbers of warm-up rows");
-  const int n_post = n_saved - n_warm_rows;
-  if (n_post < 4) return fail(POTUS_ERR_STATE, "R-hat / ESS need at least four saved post-warm-up draws per chain (%d saved, %d of them warm-up)", n_saved, n_warm_rows);
-  const int NC = col_end - col_begin;
+  int n_warm_rows = 0, n_post = 0;
+  if (const int rc_ = P.post_warmup(&n_warm_rows, &n_post)) return rc_;
   HIP_TRY(hipSetDevice(s0->device));
   DevBufs tmp;
   double *cols = nullptr;
   HIP_TRY(tmp.alloc(&cols, (size_t)n_post * Ctot * NC * 8));
   int coff = 0;
-  for (size_t i = 0; i < sps.size(); i++) {
-    Sampler *sp = sps[i];
+  for (Sampler *sp : P.sps) {
     const int C = sp->R.chains;
+    const size_t bytes = (size_t)n_saved * C * NC * 8;
     DevBufs blkbuf;
     double *blk = nullptr;
     int rc;
-    HIP_TRY(hipSetDevice(s0->device));
-    HIP_TRY(blkbuf.alloc(&blk, (size_t)n_saved * C * NC * 8));
-    if (sp->device == s0->device) {
-      if ((rc = write_array_range(sp, n_saved, col_begin, col_end, blk, true, NC))) return rc;
-      HIP_TRY(hipStreamSynchronize(sp->stream));
-    } else {
-      HIP_TRY(hipSetDevice(sp->device));
-      DevBufs far;
-      double *fb = nullptr;
-      HIP_TRY(far.alloc(&fb, (size_t)n_saved * C * NC * 8));
-      if ((rc = write_array_range(sp, n_saved, col_begin, col_end, fb, true, NC))) return rc;
-      HIP_TRY(hipStreamSynchronize(sp->stream));
-      HIP_TRY(hipMemcpyPeer(blk, s0->device, fb, sp->device, (size_t)n_saved * C * NC * 8));
-      HIP_TRY(hipSetDevice(s0->device));
-    }
-    hipLaunchKernelGGL(k_dg_transpose, dim3((NC + 63) / 64, (unsigned)((n_post + 63) / 64), C), dim3(256), 0, s0->stream, (const double *)(blk + (size_t)n_warm_rows * C * NC), cols,
-                       (long long)n_post, C, NC, Ctot, coff);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s0->stream));
+    HIP_TRY(blkbuf.alloc(&blk, bytes));
+    if ((rc = gather_block(s0, sp, bytes, blk, [&](double *out) { return write_array_range(sp, n_saved, col_begin, col_end, out, true, NC); }))) return rc;
+    if ((rc = pool_transpose(s0, blk + (size_t)n_warm_rows * C * NC, cols, n_post, C, NC, Ctot, coff))) return rc;
     coff += C;
   }
   return diagnostics_of_columns(s0->stream, cols, n_post, Ctot, NC, rhat_out, ess_bulk_out);
 }
 
-// SURVEY 8(f4), "online R-hat-based early stop": the diagnostics of lp__ and mu_b[:, T] (the columns bench.py's ESS / s is defined on;
-// predicted_score[T, :] is their inverse logit) over the post-warm-up draws saved SO FAR by the pooled chains of the handles.  The host loop
-// that advances the sampler in chunks of `refresh` transitions may stop once *converged is set; nothing the sampler does depends on it (same
-// draws up to that point as an uninterrupted run).  A deviation from Stan, which always runs num_samples iterations: off unless the host asks.
 int potus_diagnostics(const int *handles, int n_handles, int col_begin, int col_end, double *rhat_out, double *ess_bulk_out) {
-  for (int i = 0; handles && i < n_handles; i++) { Sampler *sp = get(handles[i]); if (sp) { if (const int rc_ = refuse_many_datasets(sp, "potus_diagnostics")) return rc_; } }
-  return diagnostics_impl(handles, n_handles, col_begin, col_end, rhat_out, ess_bulk_out, false);
+  if (!handles || n_handles < 1 || !rhat_out || !ess_bulk_out) return fail(POTUS_ERR_ARG, "potus_diagnostics: null argument");
+  Pool P;
+  if (const int rc_ = P.resolve(handles, n_handles, "potus_diagnostics")) return rc_;
+  if (col_begin < 0 || col_end > P.s0->L.ncols || col_begin >= col_end) return fail(POTUS_ERR_ARG, "potus_diagnostics: columns [%d, %d) of %d", col_begin, col_end, P.s0->L.ncols);
+  if (const int rc_ = P.same_posterior("R-hat / ESS pool the chains of one")) return rc_;
+  DeviceGuard guard;
+  DeviceLocks lock(P.devs);
+  if (const int rc_ = P.count()) return rc_;
+  if (const int rc_ = P.equal_counts()) return rc_;
+  return diagnostics_pooled(P, col_begin, col_end, rhat_out, ess_bulk_out);
 }
 
 // ---------------------------------------------------------------------------------------------- PSIS-LOO (potus_loo.hpp)
@@ -3483,7 +3509,7 @@ int potus_log_lik_device(int handle, int poll_begin, int poll_end, int integrate
   }
   int n_saved = 0, rc = saved_count(sp, &n_saved);
   if (rc) return rc;
-  const int first = sp->opts.save_warmup ? std::min(n_saved, sp->R.num_warmup) : 0, n_post = n_saved - first, C = sp->R.chains;
+  const int first = warm_rows(sp, n_saved), n_post = n_saved - first, C = sp->R.chains;
   if (n_post < 1) return fail(POTUS_ERR_STATE, "potus_log_lik_device: no post-warm-up draws saved (%d saved, %d of them warm-up)", n_saved, first);
   DevBufs keep;
   LooRows r;
@@ -3494,9 +3520,7 @@ int potus_log_lik_device(int handle, int poll_begin, int poll_end, int integrate
   for (int b0 = poll_begin; b0 < poll_end; b0 += nb) {
     const int b1 = std::min(b0 + nb, poll_end);
     if ((rc = loo_loglik(sp, r, first, n_post, b0, b1, integrate, blk))) return rc;
-    hipLaunchKernelGGL(k_dg_transpose, dim3((b1 - b0 + 63) / 64, (unsigned)((n_post + 63) / 64), C), dim3(256), 0, sp->stream, (const double *)blk,
-                       out + (size_t)(b0 - poll_begin) * C * n_post, (long long)n_post, C, b1 - b0, C, 0);
-    HIP_TRY(hipGetLastError());
+    if ((rc = transpose_block(sp->stream, blk, out + (size_t)(b0 - poll_begin) * C * n_post, n_post, C, b1 - b0, C, 0))) return rc;
   }
   HIP_TRY(hipStreamSynchronize(sp->stream));
   return 0;
@@ -3527,39 +3551,23 @@ int potus_loo_device(int device, const void *log_lik, int n_polls, int n_chains,
 
 int potus_loo(const int *handles, int n_handles, int integrate, const double *r_eff, double *pointwise_out, double *estimates_out) {
   if (!handles || n_handles < 1 || !pointwise_out || !estimates_out) return fail(POTUS_ERR_ARG, "potus_loo: null argument");
-  std::vector<Sampler *> sps;
-  std::vector<int> devs;
-  for (int i = 0; i < n_handles; i++) {
-    Sampler *sp = get(handles[i]);
-    if (!sp) return fail(POTUS_ERR_STATE, "bad handle %d", handles[i]);
-    if (const int rc_ = refuse_many_datasets(sp, "potus_loo")) return rc_;
-    for (int j = 0; j < i; j++) if (handles[j] == handles[i]) return fail(POTUS_ERR_ARG, "potus_loo: handle %d listed twice", handles[i]);
-    if (i > 0 && (sp->L.ncols != sps[0]->L.ncols || sp->M.full != sps[0]->M.full || sp->data_hash != sps[0]->data_hash))
-      return fail(POTUS_ERR_ARG, "potus_loo: handle %d holds another posterior than handle %d (LOO pools the chains of one)", handles[i], handles[0]);
-    sps.push_back(sp); devs.push_back(sp->device);
-  }
-  Sampler *s0 = sps[0];
+  Pool P;
+  if (const int rc_ = P.resolve(handles, n_handles, "potus_loo")) return rc_;
+  if (const int rc_ = P.same_posterior("LOO pools the chains of one")) return rc_;
+  const std::vector<Sampler *> &sps = P.sps;
+  Sampler *s0 = P.s0;
   const int Np = s0->M.Npoll;
   if (integrate != 0 && integrate != 1) return fail(POTUS_ERR_ARG, "potus_loo: integrate = %d (0: plain, 1: noise coordinate integrated out)", integrate);
   if (Np < 1) return fail(POTUS_ERR_ARG, "potus_loo: the data hold no polls");
   if (const int rc_ = loo_check_r_eff(r_eff, Np, "potus_loo")) return rc_;
   DeviceGuard guard;
-  DeviceLocks lock(devs);
-  int n_saved = -1, Ctot = 0;
-  for (size_t i = 0; i < sps.size(); i++) {
-    Sampler *sp = sps[i];
-    HIP_TRY(hipSetDevice(sp->device));
-    int ns = 0, rc = saved_count(sp, &ns);
-    if (rc) return rc;
-    if (n_saved >= 0 && ns != n_saved) return fail(POTUS_ERR_STATE, "potus_loo: handle %d has saved %d draws per chain, handle %d has %d", handles[i], ns, handles[0], n_saved);
-    n_saved = ns; Ctot += sp->R.chains;
-  }
+  DeviceLocks lock(P.devs);
+  if (const int rc_ = P.count()) return rc_;
+  if (const int rc_ = P.equal_counts()) return rc_;
+  const int Ctot = P.chains;
   if (2 * Ctot > DG_MAXCH) return fail(POTUS_ERR_UNSUPPORTED, "potus_loo: %d chains pooled (at most %d)", Ctot, DG_MAXCH / 2);
-  const int first = s0->opts.save_warmup ? std::min(n_saved, s0->R.num_warmup) : 0;
-  for (Sampler *sp : sps)
-    if ((sp->opts.save_warmup ? std::min(n_saved, sp->R.num_warmup) : 0) != first) return fail(POTUS_ERR_ARG, "potus_loo: the handles saved different numbers of warm-up rows");
-  const int n_post = n_saved - first;
-  if (n_post < 4) return fail(POTUS_ERR_STATE, "potus_loo: PSIS-LOO needs at least four saved post-warm-up draws per chain (%d saved, %d of them warm-up)", n_saved, first);
+  int first = 0, n_post = 0;
+  if (const int rc_ = P.post_warmup(&first, &n_post)) return rc_;
   DevBufs keep;
   std::vector<LooRows> rows(sps.size());
   int rc;
@@ -3579,25 +3587,9 @@ int potus_loo(const int *handles, int n_handles, int integrate, const double *r_
       const size_t bytes = (size_t)n_post * C * nbk * 8;
       DevBufs blkbuf;
       double *blk = nullptr;
-      HIP_TRY(hipSetDevice(s0->device));
       if ((rc = loo_alloc(blkbuf, &blk, bytes, "potus_loo"))) return rc;
-      if (sp->device == s0->device) {
-        if ((rc = loo_loglik(sp, rows[i], first, n_post, b0, b1, integrate, blk))) return rc;
-        HIP_TRY(hipStreamSynchronize(sp->stream));
-      } else {
-        HIP_TRY(hipSetDevice(sp->device));
-        DevBufs far;
-        double *fb = nullptr;
-        if ((rc = loo_alloc(far, &fb, bytes, "potus_loo"))) return rc;
-        if ((rc = loo_loglik(sp, rows[i], first, n_post, b0, b1, integrate, fb))) return rc;
-        HIP_TRY(hipStreamSynchronize(sp->stream));
-        HIP_TRY(hipMemcpyPeer(blk, s0->device, fb, sp->device, bytes));
-        HIP_TRY(hipSetDevice(s0->device));
-      }
-      hipLaunchKernelGGL(k_dg_transpose, dim3((nbk + 63) / 64, (unsigned)((n_post + 63) / 64), C), dim3(256), 0, s0->stream, (const double *)blk, cols,
-                         (long long)n_post, C, nbk, Ctot, coff);
-      HIP_TRY(hipGetLastError());
-      HIP_TRY(hipStreamSynchronize(s0->stream));
+      if ((rc = gather_block(s0, sp, bytes, blk, [&](double *out) { return loo_loglik(sp, rows[i], first, n_post, b0, b1, integrate, out); }))) return rc;
+      if ((rc = pool_transpose(s0, blk, cols, n_post, C, nbk, Ctot, coff))) return rc;
       coff += C;
     }
     if ((rc = loo_psis(s0->stream, cols, nbk, Ctot, n_post, r_eff ? r_eff + b0 : nullptr, pointwise_out + (size_t)b0 * LOO_NPW, "potus_loo"))) return rc;
@@ -3606,27 +3598,27 @@ int potus_loo(const int *handles, int n_handles, int integrate, const double *r_
   return 0;
 }
 
+// SURVEY 8(f4), "online R-hat-based early stop": the diagnostics of lp__ and mu_b[:, T] (the columns bench.py's ESS / s is defined on;
+// predicted_score[T, :] is their inverse logit) over the post-warm-up draws saved SO FAR by the pooled chains of the handles.  The host loop
+// that advances the sampler in chunks of `refresh` transitions may stop once *converged is set; nothing the sampler does depends on it (same
+// draws up to that point as an uninterrupted run).  A deviation from Stan, which always runs num_samples iterations: off unless the host asks.
 int potus_check_convergence(const int *handles, int n_handles, double rhat_below, double ess_at_least, int *converged, double *rhat_max, double *ess_bulk_min) {
   if (!handles || n_handles < 1 || !converged || !rhat_max || !ess_bulk_min) return fail(POTUS_ERR_ARG, "potus_check_convergence: null argument");
-  Sampler *s0 = get(handles[0]);
-  if (!s0) return fail(POTUS_ERR_STATE, "bad handle %d", handles[0]);
-  std::vector<int> devs;
-  for (int i = 0; i < n_handles; i++) {
-    Sampler *sp = get(handles[i]);
-    if (!sp) return fail(POTUS_ERR_STATE, "bad handle %d", handles[i]);
-    if (const int rc_ = refuse_many_datasets(sp, "potus_check_convergence")) return rc_;
-    devs.push_back(sp->device);
-  }
-  DeviceLocks lock(devs);                            // one set of locks for the count and both column ranges
+  Pool P;
+  if (const int rc_ = P.lookup(handles, n_handles, "potus_check_convergence")) return rc_;
+  if (const int rc_ = P.single_dataset()) return rc_;
+  Sampler *s0 = P.s0;
+  DeviceGuard guard;
+  DeviceLocks lock(P.devs);                          // one set of locks for the count and both column ranges: no run on another host thread adds draws between them
   const int S = s0->M.S, T = s0->M.T, a_mu = POTUS_N_SAMPLER_COLS + s0->L.D + S * (T - 1);
   std::vector<double> rh(1 + S), es(1 + S);
   *converged = 0; *rhat_max = NAN; *ess_bulk_min = NAN;
-  int ns = 0;
-  { DeviceGuard guard; HIP_TRY(hipSetDevice(s0->device)); const int rc = saved_count(s0, &ns); if (rc) return rc; }
-  if (ns - (s0->opts.save_warmup ? std::min(ns, s0->R.num_warmup) : 0) < 4) return 0;      // too early to say anything: not converged, no error
   int rc;
-  if ((rc = diagnostics_impl(handles, n_handles, 0, 1, rh.data(), es.data(), true))) return rc;
-  if ((rc = diagnostics_impl(handles, n_handles, a_mu, a_mu + S, rh.data() + 1, es.data() + 1, true))) return rc;
+  if ((rc = P.count())) return rc;
+  if (P.saved[0] - warm_rows(s0, P.saved[0]) < 4) return 0;      // too early to say anything: not converged, no error (the list is looked at once there is something to say)
+  if ((rc = P.distinct()) || (rc = P.same_posterior("R-hat / ESS pool the chains of one")) || (rc = P.equal_counts())) return rc;
+  if ((rc = diagnostics_pooled(P, 0, 1, rh.data(), es.data()))) return rc;
+  if ((rc = diagnostics_pooled(P, a_mu, a_mu + S, rh.data() + 1, es.data() + 1))) return rc;
   double r = -INFINITY, e = INFINITY;
   bool bad = false;
   for (int i = 0; i <= S; i++) { bad = bad || std::isnan(rh[i]) || std::isnan(es[i]); r = std::max(r, rh[i]); e = std::min(e, es[i]); }
@@ -3736,7 +3728,7 @@ int potus_write_stan_csv(int handle, const char *dir, const char *basename) {
     }
   }
   auto adaptation_block = [&](int c) { fwrite(adapt_txt[c].data(), 1, adapt_txt[c].size(), fp[c]); };
-  const int n_warm_rows = sp->opts.save_warmup ? std::min(n_saved, sp->R.num_warmup) : 0;
+  const int n_warm_rows = warm_rows(sp, n_saved);
   if (n_warm_rows == 0) for (int c = 0; c < chains; c++) adaptation_block(c);
   // stream the rows in blocks of draws: rows come back as [iter][chain][ncols]
   const int blk = 32;
@@ -3857,7 +3849,7 @@ int potus_constrain(int handle, const double *q, int n, int col_begin, int col_e
   Sampler *sp = get(handle);
   if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
   if (n < 0 || (n > 0 && (!q || !out))) return fail(POTUS_ERR_ARG, "potus_constrain: null argument");
-  if (col_begin < 0 || col_end > sp->L.ncols || col_begin >= col_end) return fail(POTUS_ERR_ARG, "bad column range [%d,%d) of %d", col_begin, col_end, sp->L.ncols);
+  if (const int rc_ = check_cols(sp, col_begin, col_end)) return rc_;
   if (n == 0) return 0;
   DeviceLocks lock(sp->device);
   HIP_TRY(hipSetDevice(sp->device));
