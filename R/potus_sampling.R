@@ -307,3 +307,40 @@ potus_loo_compare <- function(...) {
   rownames(out) <- nm[ord]
   out
 }
+
+# ---- joint election outcomes (us_potus_model_amd/outcomes.py is the same in Python; DESIGN.md section 4f) ----
+# What the run scripts compute from the JOINT outcome of a draw, counted on the device over the post-warm-up draws of every chain of the fit:
+# the distribution of Democratic electoral votes (final_2016.R:904-920), the tipping-point state (final_2012.R:809-843), how often states i and j
+# are won together, and -- with `actual`, the certified two-party share per state -- how many draws fall below it (README.Rmd:481-502).
+# ev: integer electoral votes in state order; days: c(first, last) 1-based, NULL = every day.  Returns counts (exact doubles):
+# ev_hist [days, sum(ev) + 1], tipping [days, S + 1] (last column: no tipping point), joint [days, S + 2, S + 2] over the indicators
+# (state won ..., electoral-college win, popular-vote win), below_actual [days, S], n_draws, and p_value = (2 below + 1) / (2 n + 2).
+potus_outcomes <- function(fit, ev, actual = NULL, days = NULL, ev_to_win = 270L) {
+  S <- as.integer(fit$data$S); nT <- as.integer(fit$data$T)
+  if (any(ev != round(ev))) stop("potus_outcomes: electoral votes must be integers")
+  if (is.null(days)) days <- c(1L, nT)
+  n <- as.integer(days[2] - days[1] + 1L); K <- as.integer(sum(ev))
+  r <- .C("potus_R_outcomes", as.integer(fit$handles), length(fit$handles), as.integer(c(days[1] - 1L, days[2], ev_to_win, !is.null(actual))),
+          as.integer(ev), as.double(if (is.null(actual)) rep(0, S) else actual), ev_hist = double(max(n, 1L) * (K + 1L)),
+          tipping = double(max(n, 1L) * (S + 1L)), joint = double(max(n, 1L) * (S + 2L)^2), below = double(max(n, 1L) * S), n_draws = double(1),
+          status = integer(1))
+  .potus_check(r$status)
+  out <- list(ev_hist = matrix(r$ev_hist, n, K + 1L, byrow = TRUE), tipping = matrix(r$tipping, n, S + 1L, byrow = TRUE),
+              joint = aperm(array(r$joint, c(S + 2L, S + 2L, n)), c(3, 2, 1)), n_draws = r$n_draws, days = days, ev = ev, ev_to_win = ev_to_win)
+  if (!is.null(actual)) {
+    out$below_actual <- matrix(r$below, n, S, byrow = TRUE)
+    out$p_value <- (2 * out$below_actual + 1) / (2 * r$n_draws + 2)
+  }
+  out
+}
+
+# The tipping-point table of final_2012.R:836-843 on `day` of the range (default: its last day): state, prop, sorted by prop; states that
+# never tip are left out.
+potus_tipping_point <- function(outcomes, states = NULL, day = nrow(outcomes$tipping)) {
+  S <- ncol(outcomes$tipping) - 1L
+  cnt <- outcomes$tipping[day, seq_len(S)]
+  if (is.null(states)) states <- seq_len(S)
+  d <- data.frame(state = states, prop = cnt / sum(cnt))
+  d <- d[cnt > 0, , drop = FALSE]
+  d[order(-d$prop), , drop = FALSE]
+}

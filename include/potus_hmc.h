@@ -320,7 +320,7 @@ int potus_dense_check(int handle, int chain, int n_probe, double *out /*[2]*/);
  * Chain c fits data set c / (chains / n_datasets).  Needs chains % n_datasets == 0, one workgroup per chain (cus_per_chain = 1,
  * twin = 0) and the diagonal metric.  Per-chain calls (potus_get_draws, potus_write_array[_device], potus_chain_status,
  * potus_get_adaptation, potus_draws_device_ptr) work unchanged; calls that pool all chains (potus_posterior_summary[_many],
- * potus_diagnostics, potus_check_convergence, potus_extract_matrix, potus_write_stan_csv, potus_loo, potus_log_lik_device) refuse with
+ * potus_diagnostics, potus_check_convergence, potus_extract_matrix, potus_write_stan_csv, potus_loo, potus_log_lik_device, potus_outcomes) refuse with
  * POTUS_ERR_STATE.  A chain
  * whose initialisation or step-size search fails does not fail potus_init / potus_run: potus_chain_status reports it, the
  * iteration and saved-draw counts are those of the other chains. */
@@ -363,6 +363,38 @@ int potus_loo_device(int device, const void *log_lik, int n_polls, int n_chains,
  * temporaries stay within 256 MB; r_eff as loo::relative_eff (not split) when NULL. */
 int potus_loo(const int *handles, int n_handles, int integrate, const double *r_eff, double *pointwise_out, double *estimates_out);
 
+/* ---- joint election outcomes: what the run scripts compute from the JOINT outcome of a draw ----
+ * final_2016.R:904-920 (final_2012.R, final_2008.R, README.Rmd "Final electoral college histogram") the distribution of Democratic electoral
+ * votes; final_2012.R:809-839, final_2008.R:813-843 the tipping-point state; README.Rmd:481-502, :1638-1672 the p-value of the certified
+ * result among the draws; and the joint / conditional win probabilities none of the marginal tables can give.  For one draw and one day,
+ * x[s] = predicted_score[t, s], ev[s] non-negative integers, W = ev_to_win, w = the handle's normalised state weights:
+ *   dem_ev = sum_s ev[s] 1[x[s] > 0.5];  nat = sum_s w[s] x[s] (summed s = 0 .. S-1 in order);  pop_win = nat > 0.5
+ *   tipping point: states ordered by x descending when pop_win, ascending otherwise, equal x keeping the lower index first; the first state
+ *     whose cumulative ev is >= W (none when sum ev < W).  As in the reference the order follows the POPULAR-vote winner, not the
+ *     electoral-college winner.
+ *   indicators I_0..I_{S-1} = 1[x[s] > 0.5], I_S = 1[dem_ev >= W], I_{S+1} = pop_win
+ * Outputs are COUNTS over the draws, per day of [day_begin, day_end) (0-based), exact and independent of how the chains are split:
+ *   ev_hist      [days][sum(ev) + 1]   draws with dem_ev == k
+ *   tipping      [days][S + 1]         draws whose tipping point is state s; last slot: none
+ *   joint        [days][S + 2][S + 2]  draws with I_i and I_j (symmetric; the diagonal holds the marginal counts)
+ *   below_actual [days][S]             draws with x[s] < actual[s]; written only when actual is given
+ *   n_draws                            the draws counted
+ * Any output pointer may be NULL.  sum(ev) may be at most 2047 (the kernel's histogram), S at most 63.
+ * potus_outcomes pools the post-warm-up draws of handles that hold one posterior (they may have saved different numbers of draws); the
+ * counting runs on the first handle's GPU, blocks of other GPUs come over by peer copies.  Warm-up rows saved with save_warmup = 1 are LEFT
+ * OUT, as potus_loo and potus_diagnostics leave them out -- potus_posterior_summary pools every saved row, so the two agree only for
+ * save_warmup = 0.  predicted_score never visits the host. */
+int potus_outcomes(const int *handles, int n_handles, int day_begin, int day_end, const int32_t *ev, int ev_to_win, const double *actual /*[S] or NULL*/,
+                   long long *ev_hist, long long *tipping, long long *joint, long long *below_actual, long long *n_draws);
+/* The same for a block [n_draws][n_days][S] of doubles that already sits in DEVICE memory of GPU `device` (what a multi-rank job holds after its
+ * all-gather); w [S]: the weights of the national vote, used as given (normalise them to sum to one). */
+int potus_outcomes_device(int device, const void *block, long long n_draws, int n_days, int S, const double *w, const int32_t *ev, int ev_to_win,
+                          const double *actual /*[S] or NULL*/, long long *ev_hist, long long *tipping, long long *joint, long long *below_actual,
+                          long long *n_draws_out);
+/* Milliseconds of the calling thread's last potus_outcomes[_device]: ms[3] = producing and gathering predicted_score (host clock), cutting the
+ * day range out of it (host clock), the counting kernel (HIP events). */
+int potus_outcomes_timing(double *ms /*[3]*/);
+
 /* ---- .C()-callable wrappers (int* / double* / char** only) ---- */
 void potus_R_create(int *dims /*[8]: N_nat,N_state,T,S,P,M,Pop,variant*/,
                     int *state, int *day_state, int *day_national, int *poll_state,
@@ -400,6 +432,8 @@ void potus_R_sbc_ranks(int *handle, double *truth, int *cols /*[3]: col_begin, c
 void potus_R_constrain(int *handle, double *q, int *n, int *cols /*[2]: col_begin, col_end*/, double *out, int *status);
 void potus_R_loo(int *handles, int *n_handles, int *iopts /*[2]: integrate, r_eff given*/, double *r_eff, double *pointwise_out /*[n_polls][5]*/,
                  double *estimates_out /*[3][2]*/, int *status);
+void potus_R_outcomes(int *handles, int *n_handles, int *iopts /*[4]: day_begin, day_end, ev_to_win, actual given*/, int *ev, double *actual,
+                      double *ev_hist, double *tipping, double *joint, double *below_actual, double *n_draws, int *status);
 
 #ifdef __cplusplus
 }

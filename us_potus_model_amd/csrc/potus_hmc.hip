@@ -1112,6 +1112,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, c
 }
 
 #include "potus_loo.hpp"   // per-poll log-likelihoods and PSIS-LOO (after wa_build_row, which it shares)
+#include "potus_outcomes.hpp"   // joint election outcomes: EV histogram, tipping point, joint win counts
 
 // ======================================================================== host
 namespace {
@@ -3598,6 +3599,165 @@ int potus_loo(const int *handles, int n_handles, int integrate, const double *r_
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------- joint outcomes (potus_outcomes.hpp)
+namespace {
+thread_local double g_oc_ms[3] = {0.0, 0.0, 0.0};   // the last call of this thread: gather + produce, day-range reshape, counting kernel
+static_assert(sizeof(long long) == sizeof(unsigned long long), "the counts are copied out as they are");
+
+struct OcOut { long long *ev_hist, *tipping, *joint, *below_actual, *n_draws; };
+struct OcEvents {
+  hipEvent_t a = nullptr, b = nullptr;
+  ~OcEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+};
+
+// everything about ev, ev_to_win and actual: no device needed
+int oc_check(const char *what, int S, const int32_t *ev, int ev_to_win, const double *actual, int *ev_sum) {
+  if (S < 1 || S > OC_MAX_S) return fail(POTUS_ERR_UNSUPPORTED, "%s: S = %d (the kernel maps states to the lanes of a wave: 1 .. %d)", what, S, OC_MAX_S);
+  if (!ev) return fail(POTUS_ERR_ARG, "%s: ev is null", what);
+  long long sum = 0;
+  for (int s = 0; s < S; s++) {
+    if (ev[s] < 0) return fail(POTUS_ERR_ARG, "%s: ev[%d] = %d is negative", what, s, ev[s]);
+    sum += ev[s];
+  }
+  if (sum > OC_EV_CAP) return fail(POTUS_ERR_UNSUPPORTED, "%s: the electoral votes sum to %lld, the histogram holds at most %d", what, sum, OC_EV_CAP);
+  if (ev_to_win < 1) return fail(POTUS_ERR_ARG, "%s: ev_to_win = %d (at least 1)", what, ev_to_win);
+  if (actual)
+    for (int s = 0; s < S; s++)
+      if (!(actual[s] >= 0.0 && actual[s] <= 1.0)) return fail(POTUS_ERR_ARG, "%s: actual[%d] = %g outside [0, 1]", what, s, actual[s]);
+  *ev_sum = (int)sum;
+  return 0;
+}
+
+// items [nd][n_days][S] on the current device -> the counts, in the caller's host arrays (any of them may be null)
+int oc_count(hipStream_t st, const double *items, long long nd, int n_days, int S, const double *w, const int32_t *ev, int ev_to_win, const double *actual,
+             int ev_sum, const OcOut &o) {
+  const size_t n_hist = (size_t)n_days * (ev_sum + 1), n_tip = (size_t)n_days * (S + 1), n_joint = (size_t)n_days * (S + 2) * (S + 2),
+               n_below = (size_t)n_days * S;
+  DevBufs tmp;
+  double *dw = nullptr, *dact = nullptr;
+  int32_t *dev_ = nullptr;
+  unsigned long long *dout = nullptr;
+  HIP_TRY(tmp.alloc(&dw, (size_t)S * 8)); HIP_TRY(tmp.alloc(&dev_, (size_t)S * 4));
+  HIP_TRY(tmp.alloc(&dout, (n_hist + n_tip + n_joint + n_below) * 8));
+  HIP_TRY(hipMemcpyAsync(dw, w, (size_t)S * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dev_, ev, (size_t)S * 4, hipMemcpyHostToDevice, st));
+  if (actual) { HIP_TRY(tmp.alloc(&dact, (size_t)S * 8)); HIP_TRY(hipMemcpyAsync(dact, actual, (size_t)S * 8, hipMemcpyHostToDevice, st)); }
+  HIP_TRY(hipMemsetAsync(dout, 0, (n_hist + n_tip + n_joint + n_below) * 8, st));
+  // about 2048 workgroups over days x chunks of draws; a workgroup's own counters have 32 bits
+  long long chunks = std::min<long long>(std::max(1, 2048 / n_days), (nd + 63) / 64);
+  chunks = std::max(chunks, (nd + (1ll << 30) - 1) >> 30);
+  const long long chunk = (nd + chunks - 1) / chunks;
+  chunks = (nd + chunk - 1) / chunk;
+  OcParams P{items, nd, chunk, n_days, S, ev_to_win, ev_sum, dw, dev_, dact, dout, dout + n_hist, dout + n_hist + n_tip, dout + n_hist + n_tip + n_joint};
+  OcEvents e;
+  HIP_TRY(hipEventCreate(&e.a)); HIP_TRY(hipEventCreate(&e.b));
+  HIP_TRY(hipEventRecord(e.a, st));
+  hipLaunchKernelGGL(k_oc_count, dim3((unsigned)n_days, (unsigned)chunks), dim3(OC_THREADS), 0, st, P);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e.b, st));
+  if (o.ev_hist) HIP_TRY(hipMemcpyAsync(o.ev_hist, P.ev_hist, n_hist * 8, hipMemcpyDeviceToHost, st));
+  if (o.tipping) HIP_TRY(hipMemcpyAsync(o.tipping, P.tipping, n_tip * 8, hipMemcpyDeviceToHost, st));
+  if (o.joint) HIP_TRY(hipMemcpyAsync(o.joint, P.joint, n_joint * 8, hipMemcpyDeviceToHost, st));
+  if (o.below_actual && actual) HIP_TRY(hipMemcpyAsync(o.below_actual, P.below, n_below * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  float ms = 0.f;
+  if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) g_oc_ms[2] = ms;
+  if (o.n_draws) *o.n_draws = nd;
+  return 0;
+}
+} // namespace
+
+int potus_outcomes_device(int device, const void *block, long long n_draws, int n_days, int S, const double *w, const int32_t *ev, int ev_to_win,
+                          const double *actual, long long *ev_hist, long long *tipping, long long *joint, long long *below_actual, long long *n_draws_out) {
+  const char *what = "potus_outcomes_device";
+  if (!block || !w) return fail(POTUS_ERR_ARG, "%s: null block or weights", what);
+  if (n_draws < 1) return fail(POTUS_ERR_ARG, "%s: %lld draws (at least one)", what, n_draws);
+  if (n_draws > (1ll << 40)) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld draws (at most 2^40)", what, n_draws);
+  if (n_days < 1) return fail(POTUS_ERR_ARG, "%s: %d days (at least one)", what, n_days);
+  int ev_sum = 0;
+  if (const int rc_ = oc_check(what, S, ev, ev_to_win, actual, &ev_sum)) return rc_;
+  for (int s = 0; s < S; s++) if (!std::isfinite(w[s])) return fail(POTUS_ERR_ARG, "%s: w[%d] is not finite", what, s);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(POTUS_ERR_DEVICE, "%s: no HIP device %d", what, device);
+  DeviceGuard guard;
+  DeviceLocks lock(device);
+  HIP_TRY(hipSetDevice(device));
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, block) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
+    (void)hipGetLastError();
+    return fail(POTUS_ERR_ARG, "%s: the block is not device memory of GPU %d", what, device);
+  }
+  g_oc_ms[0] = g_oc_ms[1] = g_oc_ms[2] = 0.0;
+  return oc_count(0, (const double *)block, n_draws, n_days, S, w, ev, ev_to_win, actual, ev_sum, OcOut{ev_hist, tipping, joint, below_actual, n_draws_out});
+}
+
+// Pooled over the post-warm-up draws of every listed sampler (the rules of potus_posterior_summary_many for what may be pooled, of potus_loo for
+// the warm-up rows); the counting runs on the first handle's GPU, predicted_score blocks of other GPUs come over by peer copies.
+int potus_outcomes(const int *handles, int n_handles, int day_begin, int day_end, const int32_t *ev, int ev_to_win, const double *actual,
+                   long long *ev_hist, long long *tipping, long long *joint, long long *below_actual, long long *n_draws_out) {
+  const char *what = "potus_outcomes";
+  if (!handles || n_handles < 1) return fail(POTUS_ERR_ARG, "%s: null handle list", what);
+  Pool P;
+  if (const int rc_ = P.resolve(handles, n_handles, what)) return rc_;
+  if (const int rc_ = P.same_posterior("joint outcomes pool the chains of one")) return rc_;
+  Sampler *s0 = P.s0;
+  const int S = s0->M.S, T = s0->M.T, TS = S * T;
+  if (day_begin < 0 || day_end > T || day_begin >= day_end) return fail(POTUS_ERR_ARG, "%s: days [%d, %d) of %d", what, day_begin, day_end, T);
+  int ev_sum = 0;
+  if (const int rc_ = oc_check(what, S, ev, ev_to_win, actual, &ev_sum)) return rc_;
+  DeviceGuard guard;
+  DeviceLocks lock(P.devs);
+  if (const int rc_ = P.count()) return rc_;
+  std::vector<int> first(P.sps.size());
+  long long nd = 0;
+  for (size_t i = 0; i < P.sps.size(); i++) {
+    first[i] = warm_rows(P.sps[i], P.saved[i]);
+    nd += (long long)(P.saved[i] - first[i]) * P.sps[i]->R.chains;
+  }
+  if (nd < 1) return fail(POTUS_ERR_STATE, "%s needs at least one saved post-warm-up draw (%lld rows saved, all of them warm-up)", what, P.draws);
+  const int n_days = day_end - day_begin;
+  const int col_end = s0->L.ncols, col_begin = col_end - TS;   // predicted_score = the generated-quantities block
+  HIP_TRY(hipSetDevice(s0->device));
+  DevBufs tmp;
+  double *items = nullptr;
+  if (tmp.alloc(&items, (size_t)nd * n_days * S * 8) != hipSuccess) {
+    (void)hipGetLastError();
+    return fail(POTUS_ERR_DEVICE, "%s: no device memory for %lld draws x %d days x %d states", what, nd, n_days, S);
+  }
+  g_oc_ms[0] = g_oc_ms[1] = g_oc_ms[2] = 0.0;
+  long long row0 = 0;
+  for (size_t i = 0; i < P.sps.size(); i++) {
+    Sampler *sp = P.sps[i];
+    const int n_saved = P.saved[i], C = sp->R.chains;
+    const long long rows = (long long)(n_saved - first[i]) * C;
+    if (rows == 0) continue;
+    const size_t bytes = (size_t)n_saved * C * TS * 8;
+    DevBufs blkbuf;
+    double *blk = nullptr;
+    if (blkbuf.alloc(&blk, bytes) != hipSuccess) {
+      (void)hipGetLastError();
+      return fail(POTUS_ERR_DEVICE, "%s: no device memory for the predicted_score block of handle %d (%zu bytes)", what, handles[i], bytes);
+    }
+    const double t0 = dn_now();
+    if (const int rc = gather_block(s0, sp, bytes, blk, [&](double *out) { return write_array_range(sp, n_saved, col_begin, col_end, out, true, TS); })) return rc;
+    const double t1 = dn_now();
+    // the handle's post-warm-up rows (row = saved draw x chain), the days asked for, [draw][day][S]
+    hipLaunchKernelGGL(k_oc_days, dim3((n_days + 63) / 64, (unsigned)std::min<long long>(rows, 32768)), dim3(256), 0, s0->stream,
+                       (const double *)(blk + (size_t)first[i] * C * TS), (long long)TS, items + (size_t)row0 * n_days * S, rows, T, S, day_begin, day_end);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipStreamSynchronize(s0->stream));
+    g_oc_ms[0] += t1 - t0; g_oc_ms[1] += dn_now() - t1;
+    row0 += rows;
+  }
+  return oc_count(s0->stream, items, nd, n_days, S, s0->h_w.data(), ev, ev_to_win, actual, ev_sum, OcOut{ev_hist, tipping, joint, below_actual, n_draws_out});
+}
+
+int potus_outcomes_timing(double *ms) {
+  if (!ms) return fail(POTUS_ERR_ARG, "potus_outcomes_timing: null output");
+  for (int i = 0; i < 3; i++) ms[i] = g_oc_ms[i];
+  return 0;
+}
+
 // SURVEY 8(f4), "online R-hat-based early stop": the diagnostics of lp__ and mu_b[:, T] (the columns bench.py's ESS / s is defined on;
 // predicted_score[T, :] is their inverse logit) over the post-warm-up draws saved SO FAR by the pooled chains of the handles.  The host loop
 // that advances the sampler in chunks of `refresh` transitions may stop once *converged is set; nothing the sampler does depends on it (same
@@ -4224,6 +4384,26 @@ void potus_R_constrain(int *handle, double *q, int *n, int *cols /*[2]: col_begi
 void potus_R_loo(int *handles, int *n_handles, int *iopts /*[2]: integrate, r_eff given*/, double *r_eff, double *pointwise_out, double *estimates_out,
                  int *status) {
   *status = potus_loo(handles, *n_handles, iopts[0], iopts[1] ? r_eff : nullptr, pointwise_out, estimates_out);
+}
+// counts come back as doubles (exact below 2^53); below_actual is written only when actual is given
+void potus_R_outcomes(int *handles, int *n_handles, int *iopts /*[4]: day_begin, day_end, ev_to_win, actual given*/, int *ev, double *actual,
+                      double *ev_hist, double *tipping, double *joint, double *below_actual, double *n_draws, int *status) {
+  Sampler *sp = (handles && *n_handles >= 1) ? get(handles[0]) : nullptr;
+  if (!sp || !ev) { *status = fail(POTUS_ERR_STATE, "potus_R_outcomes: bad handle or null ev"); return; }
+  const int S = sp->M.S;
+  const size_t days = iopts[1] > iopts[0] ? (size_t)(iopts[1] - iopts[0]) : 0;
+  long long sum = 0;
+  for (int s = 0; s < S; s++) sum += ev[s] > 0 ? ev[s] : 0;
+  // (a refused call writes nothing: the sizes below only matter for the arguments potus_outcomes accepts)
+  std::vector<long long> h(days * (size_t)(sum <= OC_EV_CAP ? sum + 1 : 0)), t(days * (size_t)(S + 1)), j(days * (size_t)(S + 2) * (S + 2)), b(days * (size_t)S);
+  long long n = 0;
+  *status = potus_outcomes(handles, *n_handles, iopts[0], iopts[1], ev, iopts[2], iopts[3] ? actual : nullptr, h.data(), t.data(), j.data(), b.data(), &n);
+  if (*status) return;
+  for (size_t i = 0; i < h.size(); i++) ev_hist[i] = (double)h[i];
+  for (size_t i = 0; i < t.size(); i++) tipping[i] = (double)t[i];
+  for (size_t i = 0; i < j.size(); i++) joint[i] = (double)j[i];
+  if (iopts[3]) for (size_t i = 0; i < b.size(); i++) below_actual[i] = (double)b[i];
+  *n_draws = (double)n;
 }
 
 } // extern "C"

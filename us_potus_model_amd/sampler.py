@@ -100,6 +100,11 @@ def load_library():
         L.potus_log_lik_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.potus_loo_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_longlong, dp, dp, dp]
         L.potus_loo.argtypes = [ip, C.c_int, C.c_int, dp, dp, dp]
+    if hasattr(L, "potus_outcomes"):                    # joint election outcomes (outcomes.py)
+        i32p, llp = C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
+        L.potus_outcomes.argtypes = [ip, C.c_int, C.c_int, C.c_int, i32p, C.c_int, dp, llp, llp, llp, llp, llp]
+        L.potus_outcomes_device.argtypes = [C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int, dp, i32p, C.c_int, dp, llp, llp, llp, llp, llp]
+        L.potus_outcomes_timing.argtypes = [dp]
     _LIB = L
     return L
 
@@ -113,9 +118,10 @@ EXPORTS = [
     "potus_diagnostics", "potus_diagnostics_device", "potus_check_convergence",
     "potus_set_datasets", "potus_simulate_prior", "potus_constrain", "potus_sbc_ranks",
     "potus_log_lik_device", "potus_loo_device", "potus_loo",
+    "potus_outcomes", "potus_outcomes_device", "potus_outcomes_timing",
     "potus_R_create", "potus_R_init", "potus_R_run", "potus_R_run_many", "potus_R_num_columns", "potus_R_saved_count",
     "potus_R_write_array", "potus_R_write_stan_csv", "potus_R_posterior_summary", "potus_R_diagnostics", "potus_R_check_convergence", "potus_R_backtest_scores", "potus_R_last_error", "potus_R_destroy",
-    "potus_R_set_datasets", "potus_R_simulate_prior", "potus_R_sbc_ranks", "potus_R_constrain", "potus_R_loo",
+    "potus_R_set_datasets", "potus_R_simulate_prior", "potus_R_sbc_ranks", "potus_R_constrain", "potus_R_loo", "potus_R_outcomes",
 ]
 
 
@@ -388,6 +394,11 @@ class Handle:
         _check(self.L, self.L.potus_log_lik_device(self.h, int(poll_begin), int(poll_end), int(bool(integrate)), C.c_void_p(out.data_ptr())))
         return out
 
+    def outcomes(self, ev, actual=None, days=None, ev_to_win=270):
+        """Joint election outcomes of this handle's post-warm-up draws (us_potus_model_amd.outcomes)."""
+        from .outcomes import outcomes
+        return outcomes([self], ev, actual=actual, days=days, ev_to_win=ev_to_win)
+
     def write_stan_csv(self, directory, basename="poll_model_2020"):
         os.makedirs(directory, exist_ok=True)
         _check(self.L, self.L.potus_write_stan_csv(self.h, str(directory).encode(), basename.encode()))
@@ -561,6 +572,11 @@ class StanFit:
         """fit$loo(): PSIS-LOO of the polls over every chain of the fit, on the device (us_potus_model_amd.loo)."""
         from .loo import loo
         return loo(self._hs, integrate=integrate, r_eff=r_eff, name=self.model_name)
+
+    def outcomes(self, ev, actual=None, days=None, ev_to_win=270):
+        """EV histogram, tipping point, joint win counts and p-values over every chain of the fit, on the device (us_potus_model_amd.outcomes)."""
+        from .outcomes import outcomes
+        return outcomes(self._hs, ev, actual=actual, days=days, ev_to_win=ev_to_win)
 
     def extract(self, pars, permuted=False):
         """rstan::extract(out, pars=)[[1]]: array [draws, ...dims], chains merged.
