@@ -49,7 +49,8 @@ extern "C" {
 #define POTUS_OK 0
 #define POTUS_ERR_ARG 1      /* bad argument / Stan data-block constraint violated */
 #define POTUS_ERR_DEVICE 2   /* HIP runtime failure or no gfx950 device */
-#define POTUS_ERR_INIT 3     /* no finite initial point after 100 attempts */
+#define POTUS_ERR_INIT 3     /* no finite initial point after 100 attempts, or a user's initial point without a finite
+                                log density and gradient (it is tried once; Stan: "Rejecting initial value") */
 #define POTUS_ERR_STATE 4    /* call order / handle state */
 #define POTUS_ERR_IO 5
 #define POTUS_ERR_UNSUPPORTED 6
@@ -100,10 +101,13 @@ typedef struct potus_opts {
   int32_t num_warmup;      /* iter_warmup   (final_2016.R:538) */
   int32_t num_samples;     /* iter_sampling (final_2016.R:539) */
   int32_t max_depth;       /* 10 */
-  int32_t init_buffer, term_buffer, window; /* 75, 50, 25 */
-  double delta, gamma, kappa, t0;           /* 0.8, 0.05, 0.75, 10 */
-  double stepsize;         /* 1.0 */
-  double init_radius;      /* 2.0 : inits ~ U(-2,2) on the unconstrained scale */
+  int32_t init_buffer, term_buffer, window; /* 75, 50, 25; each >= 0 (rescaled to 15 % / 75 % / 10 % of num_warmup when
+                                               20 <= num_warmup < their sum, as windowed_adaptation does) */
+  double delta, gamma, kappa, t0;           /* 0.8, 0.05, 0.75, 10; 0 < delta < 1, the other three finite and > 0 */
+  double stepsize;         /* 1.0; finite and > 0 */
+  double init_radius;      /* 2.0 : inits ~ U(-2,2) on the unconstrained scale; finite and >= 0.
+                              potus_create refuses a value outside these ranges (CmdStan 2.24's argument bounds) with
+                              POTUS_ERR_ARG, before it touches the device. */
   uint64_t seed;           /* 1843 (final_2016.R:535) */
   int32_t device;          /* HIP device ordinal */
   int32_t save_warmup;     /* 0 */
@@ -194,7 +198,8 @@ int potus_log_prob_grad(int handle, const double *q, int n, double *lp, double *
 
 /* Initial values ~ U(-r,r) with retry (CmdStan semantics), then the initial
  * step-size search.  Must be called once before potus_run. Optional user inits:
- * q0 [chains][D] or NULL. */
+ * q0 [chains][D] or NULL; a row of q0 whose log density or gradient is not finite
+ * ends the call with POTUS_ERR_INIT. */
 int potus_init(int handle, const double *q0);
 
 /* Advance every chain by n_iter NUTS transitions (warmup transitions adapt).

@@ -1064,6 +1064,33 @@ static int learn_variance(sampler *sp, const double *q) {
   return 0;
 }
 
+/* windowed_adaptation's constructor: the three sizes, rescaled to 15 % / 75 % / 10 % when they do not fit the warm-up */
+static void set_window_params(sampler *sp, const oracle_opts *o) {
+  sp->nw = o->num_warmup; sp->ib = o->init_buffer; sp->tb = o->term_buffer; sp->bw = o->window;
+  if (sp->nw < 20) { /* windowed_adaptation::restart: no adaptation windows */ }
+  else if (sp->ib + sp->bw + sp->tb > sp->nw) {
+    sp->ib = (int)(0.15 * sp->nw); sp->tb = (int)(0.1 * sp->nw); sp->bw = sp->nw - (sp->ib + sp->tb);
+  }
+  sp->win_counter = 0; sp->win_size = sp->bw; sp->win_next = sp->ib + sp->win_size - 1;
+}
+
+/* The warm-up iterations after which sample_chain updates the metric, as its own counters find them (set_window_params,
+ * learn_variance's end_window test, compute_next_window): ends[0 .. returned count), at most max_ends of them written. */
+int oracle_window_ends(const oracle_opts *o, int *ends, int max_ends) {
+  sampler sp; memset(&sp, 0, sizeof(sp));
+  set_window_params(&sp, o);
+  int n = 0;
+  for (int it = 0; it < o->num_warmup && sp.nw >= 20; it++) {
+    if (sp.win_counter == sp.win_next && sp.win_counter != sp.nw) {
+      compute_next_window(&sp);
+      if (n < max_ends) ends[n] = it;
+      n++;
+    }
+    ++sp.win_counter;
+  }
+  return n;
+}
+
 void oracle_default_opts(oracle_opts *o) {
   memset(o, 0, sizeof(*o));
   o->num_warmup = 1000; o->num_samples = 1000; o->max_depth = 10;
@@ -1120,8 +1147,13 @@ static int sample_chain_impl(const oracle_model *m, const oracle_opts *o, int ch
   tree_pool *pool = (o->pooled && !sp.dense && o->max_depth < 16) ? pool_make(D, o->max_depth) : NULL;
   int rc = 0;
   /* stan::services::util::initialize: U(-R,R) on the unconstrained scale, up to 100 attempts */
-  if (q0) memcpy(sp.z.q, q0, sizeof(double) * (size_t)D);
-  else {
+  if (q0) { /* a user's initial point is evaluated once and refused like a failed draw ("Rejecting initial value") */
+    memcpy(sp.z.q, q0, sizeof(double) * (size_t)D);
+    double lp = sp.lpg(m, sp.z.q, sp.z.g);
+    int ok = isfinite(lp);
+    for (int i = 0; i < D && ok; i++) ok = isfinite(sp.z.g[i]);
+    if (!ok) { rc = POTUS_ERR_INIT; goto done; }
+  } else {
     int ok = 0;
     for (uint32_t attempt = 0; attempt < 100 && !ok; attempt++) {
       for (int i = 0; i < D; i++) {
@@ -1135,12 +1167,7 @@ static int sample_chain_impl(const oracle_model *m, const oracle_opts *o, int ch
     if (!ok) { rc = POTUS_ERR_INIT; goto done; }
   }
   /* hmc_nuts_diag_e_adapt: windows, mu = log(10*stepsize), then run_adaptive_sampler's init_stepsize */
-  sp.nw = o->num_warmup; sp.ib = o->init_buffer; sp.tb = o->term_buffer; sp.bw = o->window;
-  if (sp.nw < 20) { /* windowed_adaptation::restart: no adaptation windows */ }
-  else if (sp.ib + sp.bw + sp.tb > sp.nw) {
-    sp.ib = (int)(0.15 * sp.nw); sp.tb = (int)(0.1 * sp.nw); sp.bw = sp.nw - (sp.ib + sp.tb);
-  }
-  sp.win_counter = 0; sp.win_size = sp.bw; sp.win_next = sp.ib + sp.win_size - 1;
+  set_window_params(&sp, o);
   sp.nom_eps = o->stepsize;
   sp.mu = log(10.0 * o->stepsize); sp.s_bar = 0; sp.x_bar = 0; sp.ad_counter = 0;
   update_potential_gradient(&sp, &sp.z);

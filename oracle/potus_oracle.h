@@ -70,7 +70,8 @@ void oracle_rng_normal_pair(uint64_t seed, uint32_t chain, uint32_t iter, uint32
 
 /* One chain of adaptive NUTS.  draws: [n_saved][7 + D] row-major (unconstrained q);
  * adapt_out: [1 + D] = final step size, inverse metric.  Returns 0 on success.
- * q0: optional initial point (NULL -> U(-r,r) inits with retry). */
+ * q0: optional initial point (NULL -> U(-r,r) inits with retry); a q0 whose log density or gradient is not finite is
+ * refused with POTUS_ERR_INIT (3), as stan::services::util::initialize refuses it. */
 int oracle_sample_chain(const oracle_model *m, const oracle_opts *o, int chain_id,
                         const double *q0, double *draws, double *adapt_out,
                         long long *total_leapfrogs);
@@ -80,6 +81,10 @@ int oracle_sample_chain(const oracle_model *m, const oracle_opts *o, int chain_i
 int oracle_sample_chain_metric(const oracle_model *m, const oracle_opts *o, int chain_id,
                                const double *q0, double *draws, double *adapt_out,
                                long long *total_leapfrogs, double *metric_out);
+
+/* The warm-up iterations (0-based) after which oracle_sample_chain updates the metric under o's num_warmup, init_buffer,
+ * term_buffer and window: ends[0 .. returned count), at most max_ends of them written. */
+int oracle_window_ends(const oracle_opts *o, int *ends, int max_ends);
 
 /* bench.py's cpu_baseline: oracle_sample_chain with the wall-clock seconds and leapfrogs of the two phases,
  * timing[5] = {warm-up s, sampling s, warm-up leapfrogs, sampling leapfrogs, iterations done}; budget_s > 0 cuts the

@@ -65,9 +65,16 @@ def run_through_the_windows(h, n_total):
     return held
 
 
-def adaptation_replayed_from_the_device_rows(data, variant, h, chain, seed, replay_rows, held=None):
+def initial_point(m, seed, chain_id, radius, attempt=0):
+    """The point stan::services::util::initialize draws at its attempt-th try (0-based): U(-radius, radius), Philox index = Stan index."""
+    return np.array([radius * (2.0 * m.L.oracle_rng_uniform(seed, chain_id, 0xFFFFFFFF, 5, attempt, i) - 1.0) for i in range(m.D)])
+
+
+def adaptation_replayed_from_the_device_rows(data, variant, h, chain, seed, replay_rows, held=None, q0=None, attempt=0):
     """See the module docstring.  held: what run_through_the_windows returned (optional: without it only the last metric update is
-    compared with the device's, through potus_get_adaptation at the end)."""
+    compared with the device's, through potus_get_adaptation at the end).  q0: the point this chain was handed through potus_init
+    (default: the library's own draw); attempt: the try of `initialize` (0-based) whose draw was the first the model accepted.  A
+    replayed row 0 starts from that initial point."""
     o_ = h.opts
     nw = o_.num_warmup
     dense = o_.metric == _abi.METRIC_DENSE
@@ -79,7 +86,9 @@ def adaptation_replayed_from_the_device_rows(data, variant, h, chain, seed, repl
     minv_final = h.dense_metric(chain) if dense else np.asarray(minv_final[chain])
     D = h.D
     m = OracleModel(data, variant)
-    o = m.default_opts(num_warmup=nw, num_samples=o_.num_samples, seed=seed, fast_grad=1, max_depth=o_.max_depth, dense_metric=1 if dense else 0)
+    o = m.default_opts(num_warmup=nw, num_samples=o_.num_samples, seed=seed, fast_grad=1, max_depth=o_.max_depth, dense_metric=1 if dense else 0,
+                       init_buffer=o_.init_buffer, term_buffer=o_.term_buffer, window=o_.window,
+                       delta=o_.delta, gamma=o_.gamma, kappa=o_.kappa, t0=o_.t0, stepsize=o_.stepsize, init_radius=o_.init_radius)
     chain_id = o_.chain_id_offset + chain + 1
     windows = window_schedule(nw, o_.init_buffer, o_.term_buffer, o_.window)
     ends = {e: (s, i) for i, (s, e) in enumerate(windows)}
@@ -92,11 +101,12 @@ def adaptation_replayed_from_the_device_rows(data, variant, h, chain, seed, repl
             return (n / (n + 5.0)) * np.cov(np.array(w).T) + 1e-3 * (5.0 / (n + 5.0)) * np.eye(D)
         return (n / (n + 5.0)) * np.var(np.array(w), axis=0, ddof=1) + 1e-3 * (5.0 / (n + 5.0))   # var_adaptation::learn_variance
 
-    # the very first search: from the initial point (U(-2,2), Philox index = Stan index, first attempt) with the unit metric
-    q_init = np.array([o_.init_radius * (2.0 * m.L.oracle_rng_uniform(seed, chain_id, 0xFFFFFFFF, 5, 0, i) - 1.0) for i in range(D)])
+    # the very first search: from the initial point (the user's, or U(-r,r) of the attempt named) with the unit metric
+    q_init = initial_point(m, seed, chain_id, o_.init_radius, attempt) if q0 is None else np.asarray(q0, dtype=np.float64).reshape(D)
     minv = np.eye(D) if dense else np.ones(D)
     eps0 = m.init_stepsize_from(chain_id, o, 0xFFFFFFFF, q_init, o_.stepsize, minv, chol_of(minv))
-    assert d[0, 2] == eps0, (d[0, 2], eps0)
+    if nw > 0:                                                       # (without a warm-up complete_adaptation replaces it at once: exp(x_bar) = 1)
+        assert d[0, 2] == eps0, (d[0, 2], eps0)
     mu, s_bar, x_bar, cnt = np.log(10.0 * o_.stepsize), 0.0, 0.0, 0.0   # (services: set_mu(log(10 * stepsize)) precedes the first search)
     metric_at = {}                                                   # row -> metric it ran under
     next_eps = eps0
@@ -142,7 +152,7 @@ def adaptation_replayed_from_the_device_rows(data, variant, h, chain, seed, repl
             M_ = metric_at[it]
             if dense and id(M_) not in chols:
                 chols[id(M_)] = np.linalg.cholesky(M_)
-            ref = m.transitions_from(chain_id, o, it, d[it - 1, 7:], d[it, 2], M_, chols.get(id(M_)))[0]
+            ref = m.transitions_from(chain_id, o, it, d[it - 1, 7:] if it else q_init, d[it, 2], M_, chols.get(id(M_)))[0]
             assert np.array_equal(d[it, 3:6], ref[3:6]), (it, d[it, :7], ref[:7])                  # treedepth__, n_leapfrog__, divergent__
             assert np.allclose(d[it, [0, 1, 6]], ref[[0, 1, 6]], rtol=1e-6, atol=1e-8), (it, d[it, :7], ref[:7])
             assert np.allclose(d[it, 7:], ref[7:], rtol=1e-6, atol=1e-7), (it, np.abs(d[it, 7:] - ref[7:]).max())

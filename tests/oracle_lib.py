@@ -49,6 +49,7 @@ def lib():
                                           C.POINTER(C.c_longlong)]
         L.oracle_sample_chain_metric.argtypes = [C.c_void_p, C.POINTER(OracleOpts), C.c_int, dp, dp, dp,
                                                  C.POINTER(C.c_longlong), dp]
+        L.oracle_window_ends.argtypes = [C.POINTER(OracleOpts), C.POINTER(C.c_int), C.c_int]
         L.oracle_sample_chain_timed.argtypes = [C.c_void_p, C.POINTER(OracleOpts), C.c_int, dp, dp, dp, C.c_double]
         L.oracle_transitions_from.argtypes = [C.c_void_p, C.POINTER(OracleOpts), C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp]
         L.oracle_init_stepsize_from.restype = C.c_double
@@ -122,6 +123,13 @@ class OracleModel:
         if rc:
             raise RuntimeError(f"oracle_sample_chain failed rc={rc}")
         return draws, adapt, nl.value
+
+    def window_ends(self, opts):
+        """The warm-up iterations (0-based) after which sample_chain updates the metric under opts."""
+        ends = (C.c_int * 64)()
+        n = self.L.oracle_window_ends(C.byref(opts), ends, 64)
+        assert n <= 64
+        return list(ends[:n])
 
     def sample_chain_timed(self, chain_id, opts, budget_s=0.0):
         """sample_chain + (warm-up seconds, sampling seconds, warm-up leapfrogs, sampling leapfrogs, iterations done):

@@ -405,3 +405,27 @@ def test_bench_dump_outputs_files_and_budget(tmp_path, monkeypatch):
     assert np.load(tmp_path / "c" / "x_draws_sample.npy").shape[2] < k
     bench.dump_outputs(tmp_path / "d", [("x_", h)], 0, 0)
     assert {p.name for p in (tmp_path / "d").glob("*.npy")} == {"x_stepsize.npy", "x_inv_metric.npy"}
+
+
+def test_create_refuses_sampler_options_before_it_looks_for_a_device():
+    """potus_create holds delta, gamma, kappa, t0, stepsize, the init radius and the three window sizes to CmdStan 2.24's argument bounds and
+    answers POTUS_ERR_ARG with the field's name before it allocates or launches anything: the refusal comes first where there is no GPU at all
+    (there a handle with good options ends in POTUS_ERR_DEVICE), and is the same where there is one."""
+    from us_potus_model_amd import Handle, sampler
+    data = synthetic.small("full")
+    nan, inf = float("nan"), float("inf")
+    bad = ([("delta", v) for v in (0.0, 1.0, -0.2, 1.5, nan, inf)] + [(f, v) for f in ("gamma", "kappa", "t0", "stepsize") for v in (0.0, -1.0, nan, inf, -inf)] +
+           [("init_radius", v) for v in (-1e-9, nan, inf)] + [(f, v) for f in ("init_buffer", "term_buffer", "window") for v in (-1, -2 ** 31)])
+    for field, value in bad:
+        try:
+            h = Handle(data, "full", chains=1, num_warmup=10, num_samples=0, **{field: value})
+        except sampler.PotusError as e:
+            assert "error 1:" in str(e) and field in str(e), (field, value, str(e))
+            continue
+        h.close()                                                            # (never inited, never run)
+        pytest.fail(f"potus_create accepted {field} = {value!r}")
+    # the edges of the bounds pass the check: the only possible complaint is the missing device
+    try:
+        Handle(data, "full", chains=1, num_warmup=10, num_samples=0, init_radius=0.0, init_buffer=0, term_buffer=0, window=0, delta=1e-300, stepsize=1e-300).close()
+    except sampler.PotusError as e:
+        assert "error 2:" in str(e), str(e)

@@ -318,3 +318,61 @@ def test_the_replay_harness_accepts_the_oracles_own_chain(cases, nw, windows, de
                            dense_metric=lambda c: metric)
     n = adaptation_replayed_from_the_device_rows(data, variant, fake, 0, 11, [(1, 2)] + rows_around([e for _, e in windows], 2) + [(nw, 3)])
     assert n == len(windows)
+
+
+def test_window_schedule_against_the_oracles_own_counters():
+    """tests/adaptation_replay.window_schedule (the Python restatement the GPU suite replays warm-ups with) against the window ends the
+    oracle's own counters reach (oracle_window_ends: the constructor's rescaling, learn_variance's end-of-window test, compute_next_window)
+    over a sweep of warm-up lengths and window sizes: none below 20 iterations, 15 % / 75 % / 10 % where the sizes do not fit, doubling and the
+    stretched last window where they do."""
+    from adaptation_replay import window_schedule
+    from oracle_lib import OracleOpts, lib
+    L = lib()
+    sizes = [(75, 50, 25), (20, 10, 15), (0, 0, 30), (0, 0, 1), (10, 0, 5), (0, 7, 3), (5, 5, 5), (1, 1, 1), (100, 100, 100), (3, 2, 20)]
+    n_checked = 0
+    for ib, tb, bw in sizes:
+        for nw in list(range(0, 130)) + [150, 199, 200, 201, 280, 400, 500, 999, 1000, 1001, 2000]:
+            o = OracleOpts()
+            L.oracle_default_opts(o)
+            o.num_warmup, o.init_buffer, o.term_buffer, o.window = nw, ib, tb, bw
+            ends = (C.c_int * 64)()
+            n = L.oracle_window_ends(o, ends, 64)
+            got = window_schedule(nw, ib, tb, bw)
+            assert [e for _, e in got] == list(ends[:n]), (nw, ib, tb, bw, got, list(ends[:n]))
+            for (s0, e0), (s1, _) in zip(got, got[1:]):
+                assert s1 == e0 + 1                                            # the windows tile the slow phase
+            n_checked += 1
+    assert n_checked == len(sizes) * 141
+    assert window_schedule(60, 75, 50, 25) == [(9, 53)] and window_schedule(25, 75, 50, 25) == [(3, 22)] and window_schedule(19, 75, 50, 25) == []
+
+
+@pytest.mark.parametrize("fast", [0, 1])
+def test_oracle_refuses_a_user_init_without_a_finite_density_and_gradient(cases, fast):
+    """stan::services::util::initialize evaluates a user's initial point once and rejects it when the log density or a gradient component is
+    not finite; so does oracle_sample_chain (POTUS_ERR_INIT = 3) under both gradient forms -- the unconstrained rho_e_bias at 36.8 and above
+    (rho rounds to 1: density -inf, gradient not finite), at -746 (rho = 0: density -inf, the gradient finite), a NaN -- and the library's device
+    code gives the same verdicts (tests/test_gpu_options.py).  36.7 and -745 are accepted."""
+    data, variant = cases["small_full"]
+    m = OracleModel(data, variant)
+    layout, _ = _abi.column_layout(data, variant)
+    i_rho = layout["rho_e_bias"][0] - _abi.N_SAMPLER_COLS
+    o = m.default_opts(num_warmup=3, num_samples=0, save_warmup=1, seed=1, fast_grad=fast)
+    q = 0.1 * np.random.default_rng(0).standard_normal(m.D)
+    for value, finite_lp, finite_grad in ((36.7, True, True), (36.8, False, False), (40.0, False, False), (-745.0, True, True), (-746.0, False, True)):
+        q0 = q.copy()
+        q0[i_rho] = value
+        lp, g = m.log_prob_grad(q0, fast=bool(fast))
+        assert np.isfinite(lp) == finite_lp and np.isfinite(g).all() == finite_grad, (value, lp)
+        if finite_lp and finite_grad:
+            d = m.sample_chain(1, o, q0=q0)[0]
+            assert np.isfinite(d).all()
+            np.testing.assert_allclose(m.transitions_from(1, o, 0, q0, d[0, 2], np.ones(m.D))[0], d[0], rtol=1e-9, atol=1e-12)   # it starts from q0
+        else:
+            with pytest.raises(RuntimeError, match="rc=3"):
+                m.sample_chain(1, o, q0=q0)
+    q0 = q.copy()
+    q0[5] = np.nan
+    with pytest.raises(RuntimeError, match="rc=3"):
+        m.sample_chain(1, o, q0=q0)
+    with pytest.raises(RuntimeError, match="rc=3"):                            # no start in 100 attempts of U(-1e6, 1e6) either
+        m.sample_chain(1, m.default_opts(num_warmup=3, num_samples=0, seed=1843, init_radius=1e6, fast_grad=fast))

@@ -2528,6 +2528,16 @@ int potus_create(const potus_data *d, const potus_opts *o, int *handle) {
   if (o->pooled_metric < 0 || o->pooled_metric > 2) return fail(POTUS_ERR_ARG, "pooled_metric must be 0, 1 or 2");
   if (o->pooled_metric && o->metric != POTUS_METRIC_DENSE) return fail(POTUS_ERR_ARG, "pooled_metric applies to the dense metric (metric = POTUS_METRIC_DENSE)");
   if (o->metric_storage == POTUS_STORAGE_F32 && o->metric != POTUS_METRIC_DENSE) return fail(POTUS_ERR_ARG, "metric_storage = f32 applies to the dense metric only");
+  // CmdStan 2.24's argument bounds (arg_adapt_*, arg_stepsize, arg_init); written so that a NaN fails every one of them
+  if (!(o->delta > 0.0 && o->delta < 1.0)) return fail(POTUS_ERR_ARG, "delta must be in (0, 1), got %g", o->delta);
+  if (!(o->gamma > 0.0 && std::isfinite(o->gamma))) return fail(POTUS_ERR_ARG, "gamma must be finite and > 0, got %g", o->gamma);
+  if (!(o->kappa > 0.0 && std::isfinite(o->kappa))) return fail(POTUS_ERR_ARG, "kappa must be finite and > 0, got %g", o->kappa);
+  if (!(o->t0 > 0.0 && std::isfinite(o->t0))) return fail(POTUS_ERR_ARG, "t0 must be finite and > 0, got %g", o->t0);
+  if (!(o->stepsize > 0.0 && std::isfinite(o->stepsize))) return fail(POTUS_ERR_ARG, "stepsize must be finite and > 0, got %g", o->stepsize);
+  if (!(o->init_radius >= 0.0 && std::isfinite(o->init_radius))) return fail(POTUS_ERR_ARG, "init_radius must be finite and >= 0, got %g", o->init_radius);
+  if (o->init_buffer < 0) return fail(POTUS_ERR_ARG, "init_buffer must be >= 0, got %d", o->init_buffer);
+  if (o->term_buffer < 0) return fail(POTUS_ERR_ARG, "term_buffer must be >= 0, got %d", o->term_buffer);
+  if (o->window < 0) return fail(POTUS_ERR_ARG, "window must be >= 0, got %d", o->window);
   int ndev = 0;
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(POTUS_ERR_DEVICE, "no HIP device: libpotus_hmc needs an MI355X (gfx950)");
   if (o->device < 0 || o->device >= ndev) return fail(POTUS_ERR_DEVICE, "device %d out of range (have %d)", o->device, ndev);
@@ -2612,7 +2622,7 @@ int potus_create(const potus_data *d, const potus_opts *o, int *handle) {
   R.max_depth = o->max_depth; R.save_warmup = o->save_warmup;
   // windowed_adaptation::set_window_params
   int ib = o->init_buffer, tb = o->term_buffer, bw = o->window;
-  if (o->num_warmup >= 20 && ib + bw + tb > o->num_warmup) { ib = (int)(0.15 * o->num_warmup); tb = (int)(0.1 * o->num_warmup); bw = o->num_warmup - (ib + tb); }
+  if (o->num_warmup >= 20 && (long long)ib + bw + tb > o->num_warmup) { ib = (int)(0.15 * o->num_warmup); tb = (int)(0.1 * o->num_warmup); bw = o->num_warmup - (ib + tb); }
   R.init_buffer = ib; R.term_buffer = tb; R.window = bw;
   R.delta = o->delta; R.gamma = o->gamma; R.kappa = o->kappa; R.t0 = o->t0; R.stepsize = o->stepsize; R.init_radius = o->init_radius;
   R.seed_lo = (unsigned)(o->seed & 0xFFFFFFFFu); R.seed_hi = (unsigned)(o->seed >> 32);
@@ -2757,7 +2767,14 @@ int potus_init(int handle, const double *q0) {
     hipLaunchKernelGGL(k_init, dim3(sp->R.chains * sp->sides()), dim3(PT_THREADS), sp->lds_bytes, sp->stream, (const DevModel *)sp->dM, (const RunParams *)sp->dR, (const double *)dq0);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(sp->stream));
-  { const int rc_ = check_chains(sp); if (rc_) return rc_; }
+  {
+    const int rc_ = check_chains(sp);
+    if (rc_ == POTUS_ERR_INIT && q0) {   // a user's point is tried once: say so instead of "after 100 attempts"
+      const std::string chain = g_err.substr(0, g_err.find(':'));
+      return fail(POTUS_ERR_INIT, "%s: the initial point handed in has no finite log density and gradient (Stan: \"Rejecting initial value\")", chain.c_str());
+    }
+    if (rc_) return rc_;
+  }
   if (sp->dense) { const int rc_ = dense_import_init(sp); if (rc_) return rc_; }
   sp->inited = true;
   return 0;
