@@ -207,6 +207,44 @@ potus_diagnostics <- function(fit, col_begin, col_end) {
   data.frame(column = seq(col_begin, col_end - 1L), rhat = r$rhat, ess_bulk = r$ess)
 }
 
+# The posterior summary table -- rstan::summary(out, pars, probs)$summary / rstan::monitor -- formed on the device over every chain of the fit
+# (post-warm-up draws): what final_2016.R:556-705 tabulates right after extract() (mean_low_high of mu_b, mean +- 1.96 sd of mu_c, mu_m, mu_pop
+# and polling_bias, the means of e_bias) without the draws reaching R.  pars: names of the CmdStan row's blocks or "lp__"; NULL = the whole row.
+# Returns a matrix [columns, 8 + length(probs)] with rstan-style dimnames: rows "mu_c[1]", "mu_b[1,1]", ...; columns mean, sd, mad, se_mean,
+# Rhat, n_eff (bulk ESS), tail_eff, ess_mean, then "2.5%", ...  (us_potus_model_amd/monitor.py is the same in Python; DESIGN.md section 4g.)
+potus_monitor <- function(fit, pars = NULL, probs = c(.025, .25, .5, .75, .975)) {
+  lay <- .potus_layout(fit)
+  ncols <- max(sapply(lay, function(b) b$end))
+  sampler <- c("lp__", "accept_stat__", "stepsize__", "treedepth__", "n_leapfrog__", "divergent__", "energy__")
+  if (is.null(pars)) {
+    ranges <- list(list(begin = 0L, end = ncols))
+    pars <- c(sampler, names(lay))
+  } else {
+    ranges <- lapply(pars, function(nm) {
+      if (nm %in% sampler) return(list(begin = match(nm, sampler) - 1L, end = match(nm, sampler)))
+      if (is.null(lay[[nm]])) stop("unknown parameter ", nm)
+      lay[[nm]]
+    })
+  }
+  rn <- unlist(lapply(pars, function(nm) {
+    d <- lay[[nm]]$dims
+    if (nm %in% sampler || length(d) == 0) return(nm)
+    idx <- as.matrix(expand.grid(lapply(d, seq_len)))                       # first index fastest: CmdStan's column-major order
+    paste0(nm, "[", apply(idx, 1, paste, collapse = ","), "]")
+  }))
+  w <- 8L + length(probs)
+  rows <- lapply(ranges, function(b) {
+    n <- b$end - b$begin
+    r <- .C("potus_R_monitor", as.integer(fit$handles), length(fit$handles), as.integer(c(b$begin, b$end)), as.double(probs), length(probs),
+            out = double(n * w), status = integer(1))
+    .potus_check(r$status)
+    matrix(r$out, n, w, byrow = TRUE)
+  })
+  m <- do.call(rbind, rows)
+  dimnames(m) <- list(rn, c("mean", "sd", "mad", "se_mean", "Rhat", "n_eff", "tail_eff", "ess_mean", paste0(sapply(100 * probs, format), "%")))
+  m
+}
+
 # Backtest scores of final_2016.R:925-945: EV-weighted Brier, unweighted Brier, states called correctly on `day`
 # (1-based; 0 = the last day).  won: 1 where the Democrat carried the state, in state order.
 potus_backtest_scores <- function(fit, summary, ev, won, day = 0L) {

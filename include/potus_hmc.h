@@ -278,6 +278,26 @@ int potus_diagnostics(const int *handles, int n_handles, int col_begin, int col_
  * potus_write_array_device produces and an RCCL all-gather of it keeps.  rhat_out, ess_bulk_out: host arrays [n_cols]. */
 int potus_diagnostics_device(int device, const void *block, long long n_draws, int n_chains, int n_cols, double *rhat_out, double *ess_bulk_out);
 
+/* ---- the posterior summary table: what fit$summary() / print(stanfit) / rstan::monitor show, for any column ----
+ * What the run scripts tabulate right after extract() (final_2016.R:556-705: mean_low_high of mu_b, mean +- 1.96 sd of mu_c, mu_m, mu_pop and
+ * polling_bias, the means of e_bias), without the draws visiting the host.  Per column of [col_begin, col_end) a row of
+ * POTUS_MONITOR_NSTATS + n_probs doubles over the pooled post-warm-up draws:
+ *   0 mean   1 sd (ddof = 1)   2 mad = 1.4826 median|x - median(x)|   3 mcse_mean = sd / sqrt(ess_mean)
+ *   4 rhat and 5 ess_bulk, exactly potus_diagnostics' values   6 ess_tail (posterior::ess_tail: the smaller ESS of the split indicators
+ *   1[x <= Q(x, 0.05)], 1[x <= Q(x, 0.95)])   7 ess_mean (Geyer's ESS of the split draws, not rank-normalised)   8... R's type-7 quantiles at probs.
+ * mean, sd, mad and the quantiles are over ALL draws; slots 4-7 over the split draws (an odd number of draws per chain drops each chain's middle
+ * one).  A column with a NaN or an infinite draw: NaN in every slot.  A constant column: mean and quantiles the value, sd = mad = 0, slots 3-7
+ * NaN.  Fewer than four draws per half chain: the three ESS and mcse_mean NaN.  n_probs is 0 to 16, every prob finite and in [0, 1].
+ * potus_monitor pools as potus_diagnostics does (one posterior, equal counts, warm-up rows left out, at least four post-warm-up draws per chain, at
+ * most 512 chains, handles of other GPUs by peer copies) and works the column range in blocks whose gathered rows and transposed columns stay
+ * within 256 MB, so the whole output row can be asked for in one call.  Sums run in a fixed order: the same draws give the same bytes however
+ * the chains are spread over handles or the range over blocks. */
+#define POTUS_MONITOR_NSTATS 8
+int potus_monitor(const int *handles, int n_handles, int col_begin, int col_end, const double *probs, int n_probs,
+                  double *out /*[col_end - col_begin][POTUS_MONITOR_NSTATS + n_probs]*/);
+/* The same for a block [draw][chain][column] that already sits in DEVICE memory of GPU `device` (every row counts); out: host, [n_cols][8 + n_probs]. */
+int potus_monitor_device(int device, const void *block, long long n_draws, int n_chains, int n_cols, const double *probs, int n_probs, double *out);
+
 /* Online convergence check for a host loop that advances the sampler in chunks ("online R-hat-based early
  * stop"): rank-normalised split R-hat and bulk ESS of lp__ and mu_b[:, T] (what predicted_score[T, :], the quantity the scripts report, is a
  * monotone map of: final_2016.R:708-762) over the post-warm-up draws saved so far by the pooled chains of the handles.  *converged = 1 when
@@ -325,7 +345,7 @@ int potus_dense_check(int handle, int chain, int n_probe, double *out /*[2]*/);
  * Chain c fits data set c / (chains / n_datasets).  Needs chains % n_datasets == 0, one workgroup per chain (cus_per_chain = 1,
  * twin = 0) and the diagonal metric.  Per-chain calls (potus_get_draws, potus_write_array[_device], potus_chain_status,
  * potus_get_adaptation, potus_draws_device_ptr) work unchanged; calls that pool all chains (potus_posterior_summary[_many],
- * potus_diagnostics, potus_check_convergence, potus_extract_matrix, potus_write_stan_csv, potus_loo, potus_log_lik_device, potus_outcomes) refuse with
+ * potus_diagnostics, potus_check_convergence, potus_extract_matrix, potus_write_stan_csv, potus_loo, potus_log_lik_device, potus_outcomes, potus_monitor) refuse with
  * POTUS_ERR_STATE.  A chain
  * whose initialisation or step-size search fails does not fail potus_init / potus_run: potus_chain_status reports it, the
  * iteration and saved-draw counts are those of the other chains. */
@@ -425,6 +445,7 @@ void potus_R_write_stan_csv(int *handle, char **dir, char **basename, int *statu
 void potus_R_saved_count(int *handle, int *n_saved, int *status);
 void potus_R_posterior_summary(int *handles, int *n_handles, double *ev, double *state_out, double *natl_out, double *ev_out, int *status);
 void potus_R_diagnostics(int *handles, int *n_handles, int *cols /*[2]: col_begin, col_end*/, double *rhat_out, double *ess_bulk_out, int *status);
+void potus_R_monitor(int *handles, int *n_handles, int *cols /*[2]: col_begin, col_end*/, double *probs, int *n_probs, double *out, int *status);
 void potus_R_check_convergence(int *handles, int *n_handles, double *limits /*[2]: rhat_below, ess_at_least*/, int *converged, double *out /*[2]: rhat_max, ess_bulk_min*/,
                                 int *status);
 void potus_R_backtest_scores(double *state_out, int *dims /*[3]: T, S, day*/, double *ev, int *won, double *out /*[3]*/, int *status);

@@ -2,7 +2,7 @@
 
 Layout: csrc/ (HIP kernels + the C ABI of include/potus_hmc.h), sampler.py (host mirror of the
 reference's `$sample()` / `rstan::extract()` surface), dataprep.py / synthetic.py (Stan data
-lists), diagnostics.py (R-hat / ESS), outcomes.py (joint election outcomes: EV histogram, tipping point), _abi.py (ctypes structs).
+lists), diagnostics.py (R-hat / ESS), outcomes.py (joint election outcomes: EV histogram, tipping point), monitor.py (the posterior summary table), _abi.py (ctypes structs).
 """
 from . import _abi  # noqa: F401
 from .sampler import (Handle, PotusError, PotusModel, StanFit, backtest_scores, check_convergence, device_diagnostics, device_diagnostics_of_block,  # noqa: F401
@@ -10,3 +10,6 @@ from .sampler import (Handle, PotusError, PotusModel, StanFit, backtest_scores, 
 from . import outcomes  # noqa: F401,E402  (the module; its outcomes() is also available as joint_outcomes)
 from .outcomes import Outcomes, outcomes_of_block  # noqa: F401,E402
 from .outcomes import outcomes as joint_outcomes  # noqa: F401,E402
+from . import monitor  # noqa: F401,E402  (the module; its monitor() is also available as monitor_table)
+from .monitor import Monitor, monitor_of_block  # noqa: F401,E402
+from .monitor import monitor as monitor_table  # noqa: F401,E402

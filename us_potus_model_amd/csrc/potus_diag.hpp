@@ -133,11 +133,104 @@ __device__ __forceinline__ unsigned long long dg_select(const unsigned long long
   return lo;
 }
 
+// normal scores of the ranks of val(0 .. N-1) into zout, in the order of the split array: sorts the runs, then ranks every draw in them
+template <class F>
+__device__ __forceinline__ void dg_scores(F val, long long N, unsigned long long *xk, unsigned *xi, unsigned long long *rkey, unsigned *ridx, double *zout) {
+  for (long long j = threadIdx.x; j < N; j += DG_THREADS) {
+    const double v = val(j);
+    const long long r = dg_rank(v, j, N, xk, xi, rkey, ridx);
+    zout[j] = dg_normal_score(((double)r - 0.375) / ((double)N + 0.25));
+  }
+}
+
+// classic R-hat (rhat_basic) of the split chains zz [C2][h]: one wave per split chain, two passes (mean, then variance).  The chain means and
+// variances stay in cmean / cvar, their mean variance and the variance of the means in sc[3] / sc[4]: what dg_ess_basic starts from.
+__device__ __forceinline__ double dg_rhat_basic(const double *zz, int C2, long long h, double *cmean, double *cvar, double *sc) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  for (int cp = w; cp < C2; cp += DG_THREADS / 64) {
+    double s = 0.0;
+    for (long long i = lane; i < h; i += 64) s += zz[(size_t)cp * h + i];
+    const double m = dpp_wave_sum(s) / (double)h;
+    double q = 0.0;
+    for (long long i = lane; i < h; i += 64) { const double d = zz[(size_t)cp * h + i] - m; q += d * d; }
+    const double v = dpp_wave_sum(q) / (double)(h - 1);
+    if (lane == 0) { cmean[cp] = m; cvar[cp] = v; }
+  }
+  __syncthreads();
+  if (tid == 0) {
+    double wv = 0.0, mm = 0.0;
+    for (int cp = 0; cp < C2; cp++) { wv += cvar[cp]; mm += cmean[cp]; }
+    wv /= C2; mm /= C2;
+    double b = 0.0;
+    for (int cp = 0; cp < C2; cp++) b += (cmean[cp] - mm) * (cmean[cp] - mm);
+    const double bv = C2 > 1 ? b / (C2 - 1) : 0.0;                       // variance of the chain means (ddof = 1)
+    sc[1] = wv == 0.0 ? NAN : sqrt(((double)(h - 1) / (double)h * wv + bv) / wv);   // rhat_basic: B / n = var of the means
+    sc[3] = wv; sc[4] = bv;
+  }
+  __syncthreads();
+  return sc[1];
+}
+
+// Geyer's initial-monotone-sequence ESS (ess_basic) of the split chains z [C2][h] whose moments dg_rhat_basic has just left in cmean / sc[3] / sc[4]:
+// centres the chains in place, then forms the autocovariances lag by lag (DG_LAGS at a time) as far as the sequence reads them.  NaN below
+// four draws per split chain or without a positive var_plus.  z is free for the next quantity on return.
+__device__ __forceinline__ double dg_ess_basic(double *z, int C2, long long h, const double *cmean, double *rho, double *sc) {
+  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const long long N = (long long)C2 * h;
+  for (long long j = tid; j < N; j += DG_THREADS) z[j] -= cmean[j / h];
+  __threadfence_block();
+  __syncthreads();
+  // chain_var = acov[:, 0] * h / (h - 1) = cvar; mean_var = mean(cvar); var_plus = mean_var (h - 1) / h + var(means)
+  const double mean_var = sc[3], var_plus = mean_var * (double)(h - 1) / (double)h + (C2 > 1 ? sc[4] : 0.0);
+  double ess = NAN;
+  if (h >= 4 && isfinite(var_plus) && var_plus > 0.0) {
+    if (tid == 0) { sc[5] = 0.0; sc[6] = INFINITY; sc[7] = 0.0; }   // tau so far, previous pair, done flag
+    __syncthreads();
+    for (long long t0 = 0; t0 < h; t0 += DG_LAGS) {
+      for (int lg = w; lg < DG_LAGS; lg += DG_THREADS / 64) {
+        const long long t = t0 + lg;
+        double s = 0.0;
+        if (t < h)
+          for (int cp = 0; cp < C2; cp++) {
+            const double *zc = z + (size_t)cp * h;
+            double a = 0.0;
+            for (long long i = lane; i + t < h; i += 64) a += zc[i] * zc[i + t];
+            s += dpp_wave_sum(a) / (double)h;                                  // biased autocovariance of the chain
+          }
+        if (lane == 0) rho[lg] = t == 0 ? 1.0 : 1.0 - (mean_var - s / C2) / var_plus;
+      }
+      __syncthreads();
+      if (tid == 0) {
+        double tau = sc[5], prev = sc[6];
+        bool done = false;
+        for (int lg = 0; lg + 1 < DG_LAGS; lg += 2) {
+          if (t0 + lg + 1 >= h) { done = true; break; }
+          double pair = rho[lg] + rho[lg + 1];
+          if (pair < 0) { done = true; break; }
+          pair = fmin(pair, prev);
+          tau += 2.0 * pair;
+          prev = pair;
+        }
+        sc[5] = tau; sc[6] = prev; sc[7] = done ? 1.0 : 0.0;
+      }
+      __syncthreads();
+      if (sc[7] != 0.0) break;
+    }
+    double tau = sc[5] - 1.0;
+    tau = fmax(tau, 1.0 / log10((double)N));
+    ess = (double)N / tau;
+  }
+  __syncthreads();                                     // every read of z, rho and sc is behind this
+  return ess;
+}
+
+__device__ __forceinline__ double dg_nanmax(double a, double b) { return (isnan(a) && isnan(b)) ? NAN : fmax(isnan(a) ? -INFINITY : a, isnan(b) ? -INFINITY : b); }
+
 __global__ __launch_bounds__(DG_THREADS) void k_dg_column(DgParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long xk[];   // min(npad, DG_RUN) keys, then as many split indices
   __shared__ double cmean[DG_MAXCH], cvar[DG_MAXCH], rho[DG_LAGS];
   __shared__ double sc[8];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  const int tid = threadIdx.x;
   const long long n = P.n, h = n / 2;
   const int C = P.C, C2 = 2 * C;
   const long long N = (long long)C2 * h;
@@ -165,97 +258,23 @@ __global__ __launch_bounds__(DG_THREADS) void k_dg_column(DgParams P) {
       const double a = ps_unkey(N <= DG_RUN ? xk[k1] : dg_select(rkey, N, k1)), b = ps_unkey(N <= DG_RUN ? xk[k2] : dg_select(rkey, N, k2));
       sc[0] = 0.5 * (a + b);
     }
-    for (long long j = tid; j < N; j += DG_THREADS) {
-      const double v = val(j);
-      const long long r = dg_rank(v, j, N, xk, xi, rkey, ridx);
-      z[j] = dg_normal_score(((double)r - 0.375) / ((double)N + 0.25));
-    }
+    dg_scores(val, N, xk, xi, rkey, ridx, z);
     __syncthreads();
     const double med = sc[0];
     __syncthreads();
     // ---- folded: ranks of |x - median|
     auto fval = [&](long long j) { return fabs(dg_split_value(x, n, C, h, j) - med) + 0.0; };
     dg_sort_runs(fval, N, xk, xi, rkey, ridx);
-    for (long long j = tid; j < N; j += DG_THREADS) {
-      const double v = fval(j);
-      const long long r = dg_rank(v, j, N, xk, xi, rkey, ridx);
-      zf[j] = dg_normal_score(((double)r - 0.375) / ((double)N + 0.25));
-    }
+    dg_scores(fval, N, xk, xi, rkey, ridx, zf);
     __threadfence_block();
     __syncthreads();
-    // ---- classic R-hat of both (one wave per split chain, two passes: mean, then variance)
-    double rh[2];
-    for (int pass = 0; pass < 2; pass++) {
-      const double *zz = pass == 0 ? zf : z;          // bulk last: its chain means and variances stay for the ESS
-      for (int cp = w; cp < C2; cp += DG_THREADS / 64) {
-        double s = 0.0;
-        for (long long i = lane; i < h; i += 64) s += zz[(size_t)cp * h + i];
-        const double m = dpp_wave_sum(s) / (double)h;
-        double q = 0.0;
-        for (long long i = lane; i < h; i += 64) { const double d = zz[(size_t)cp * h + i] - m; q += d * d; }
-        const double v = dpp_wave_sum(q) / (double)(h - 1);
-        if (lane == 0) { cmean[cp] = m; cvar[cp] = v; }
-      }
-      __syncthreads();
-      if (tid == 0) {
-        double wv = 0.0, mm = 0.0;
-        for (int cp = 0; cp < C2; cp++) { wv += cvar[cp]; mm += cmean[cp]; }
-        wv /= C2; mm /= C2;
-        double b = 0.0;
-        for (int cp = 0; cp < C2; cp++) b += (cmean[cp] - mm) * (cmean[cp] - mm);
-        const double bv = C2 > 1 ? b / (C2 - 1) : 0.0;                       // variance of the chain means (ddof = 1)
-        sc[1 + pass] = wv == 0.0 ? NAN : sqrt(((double)(h - 1) / (double)h * wv + bv) / wv);   // rhat_basic: B / n = var of the means
-        sc[3] = wv; sc[4] = bv;
-      }
-      __syncthreads();
-      rh[pass] = sc[1 + pass];
-    }
-    // ---- bulk ESS (ess_basic of z): centre the chains, autocovariances lag by lag as far as Geyer's sequence needs them
-    for (long long j = tid; j < N; j += DG_THREADS) z[j] -= cmean[j / h];
-    __threadfence_block();
-    __syncthreads();
-    // chain_var = acov[:, 0] * h / (h - 1) = cvar; mean_var = mean(cvar); var_plus = mean_var (h - 1) / h + var(means)
-    const double mean_var = sc[3], var_plus = mean_var * (double)(h - 1) / (double)h + (C2 > 1 ? sc[4] : 0.0);
-    double ess = NAN;
-    if (h >= 4 && isfinite(var_plus) && var_plus > 0.0) {
-      if (tid == 0) { sc[5] = 0.0; sc[6] = INFINITY; sc[7] = 0.0; }   // tau so far, previous pair, done flag
-      __syncthreads();
-      for (long long t0 = 0; t0 < h; t0 += DG_LAGS) {
-        for (int lg = w; lg < DG_LAGS; lg += DG_THREADS / 64) {
-          const long long t = t0 + lg;
-          double s = 0.0;
-          if (t < h)
-            for (int cp = 0; cp < C2; cp++) {
-              const double *zc = z + (size_t)cp * h;
-              double a = 0.0;
-              for (long long i = lane; i + t < h; i += 64) a += zc[i] * zc[i + t];
-              s += dpp_wave_sum(a) / (double)h;                                  // biased autocovariance of the chain
-            }
-          if (lane == 0) rho[lg] = t == 0 ? 1.0 : 1.0 - (mean_var - s / C2) / var_plus;
-        }
-        __syncthreads();
-        if (tid == 0) {
-          double tau = sc[5], prev = sc[6];
-          bool done = false;
-          for (int lg = 0; lg + 1 < DG_LAGS; lg += 2) {
-            if (t0 + lg + 1 >= h) { done = true; break; }
-            double pair = rho[lg] + rho[lg + 1];
-            if (pair < 0) { done = true; break; }
-            pair = fmin(pair, prev);
-            tau += 2.0 * pair;
-            prev = pair;
-          }
-          sc[5] = tau; sc[6] = prev; sc[7] = done ? 1.0 : 0.0;
-        }
-        __syncthreads();
-        if (sc[7] != 0.0) break;
-      }
-      double tau = sc[5] - 1.0;
-      tau = fmax(tau, 1.0 / log10((double)N));
-      ess = (double)N / tau;
-    }
+    // ---- classic R-hat of both, bulk last: its chain means and variances stay for the ESS
+    const double rh_folded = dg_rhat_basic(zf, C2, h, cmean, cvar, sc);
+    const double rh_bulk = dg_rhat_basic(z, C2, h, cmean, cvar, sc);
+    // ---- bulk ESS (ess_basic of z)
+    const double ess = dg_ess_basic(z, C2, h, cmean, rho, sc);
     if (tid == 0) {
-      P.rhat[col] = (isnan(rh[0]) && isnan(rh[1])) ? NAN : fmax(isnan(rh[0]) ? -INFINITY : rh[0], isnan(rh[1]) ? -INFINITY : rh[1]);   // nanmax(bulk, folded)
+      P.rhat[col] = dg_nanmax(rh_folded, rh_bulk);   // nanmax(bulk, folded)
       P.ess[col] = ess;
     }
     __syncthreads();

@@ -10,6 +10,7 @@
 #include "potus_dense.hpp"
 #include "potus_summary.hpp"
 #include "potus_diag.hpp"
+#include "potus_monitor.hpp"
 
 #include <algorithm>
 #include <cmath>
@@ -3373,17 +3374,11 @@ int potus_diagnostics_device(int device, const void *block, long long n_draws, i
   return diagnostics_of_columns(0, cols, n_draws, n_chains, n_cols, rhat_out, ess_bulk_out);
 }
 
-// R-hat / bulk ESS of columns [col_begin, col_end) over the pooled post-warm-up draws of a counted pool, under the caller's locks
-static int diagnostics_pooled(const Pool &P, int col_begin, int col_end, double *rhat_out, double *ess_bulk_out) {
+// Columns [col_begin, col_end) of the post-warm-up draws of a counted pool, gathered handle by handle and transposed into cols [NC][chains][n_post] on
+// the first handle's GPU (its device current on return)
+static int gather_columns(const Pool &P, int col_begin, int col_end, int n_warm_rows, int n_post, double *cols) {
   Sampler *s0 = P.s0;
   const int Ctot = P.chains, n_saved = P.saved[0], NC = col_end - col_begin;
-  if (2 * Ctot > DG_MAXCH) return fail(POTUS_ERR_UNSUPPORTED, "potus_diagnostics: %d chains pooled (at most %d)", Ctot, DG_MAXCH / 2);
-  int n_warm_rows = 0, n_post = 0;
-  if (const int rc_ = P.post_warmup(&n_warm_rows, &n_post)) return rc_;
-  HIP_TRY(hipSetDevice(s0->device));
-  DevBufs tmp;
-  double *cols = nullptr;
-  HIP_TRY(tmp.alloc(&cols, (size_t)n_post * Ctot * NC * 8));
   int coff = 0;
   for (Sampler *sp : P.sps) {
     const int C = sp->R.chains;
@@ -3396,6 +3391,21 @@ static int diagnostics_pooled(const Pool &P, int col_begin, int col_end, double 
     if ((rc = pool_transpose(s0, blk + (size_t)n_warm_rows * C * NC, cols, n_post, C, NC, Ctot, coff))) return rc;
     coff += C;
   }
+  return 0;
+}
+
+// R-hat / bulk ESS of columns [col_begin, col_end) over the pooled post-warm-up draws of a counted pool, under the caller's locks
+static int diagnostics_pooled(const Pool &P, int col_begin, int col_end, double *rhat_out, double *ess_bulk_out) {
+  Sampler *s0 = P.s0;
+  const int Ctot = P.chains, NC = col_end - col_begin;
+  if (2 * Ctot > DG_MAXCH) return fail(POTUS_ERR_UNSUPPORTED, "potus_diagnostics: %d chains pooled (at most %d)", Ctot, DG_MAXCH / 2);
+  int n_warm_rows = 0, n_post = 0;
+  if (const int rc_ = P.post_warmup(&n_warm_rows, &n_post)) return rc_;
+  HIP_TRY(hipSetDevice(s0->device));
+  DevBufs tmp;
+  double *cols = nullptr;
+  HIP_TRY(tmp.alloc(&cols, (size_t)n_post * Ctot * NC * 8));
+  if (const int rc_ = gather_columns(P, col_begin, col_end, n_warm_rows, n_post, cols)) return rc_;
   return diagnostics_of_columns(s0->stream, cols, n_post, Ctot, NC, rhat_out, ess_bulk_out);
 }
 
@@ -3613,6 +3623,103 @@ int potus_loo(const int *handles, int n_handles, int integrate, const double *r_
     if ((rc = loo_psis(s0->stream, cols, nbk, Ctot, n_post, r_eff ? r_eff + b0 : nullptr, pointwise_out + (size_t)b0 * LOO_NPW, "potus_loo"))) return rc;
   }
   loo_estimates(pointwise_out, Np, estimates_out);
+  return 0;
+}
+
+// ---------------------------------------------------------------------------------------------- summary table (potus_monitor.hpp)
+namespace {
+// the gathered rows of one handle plus the transposed columns of one block of a potus_monitor call (POTUS_MONITOR_BLOCK_BUDGET, bytes: tests)
+constexpr size_t MONITOR_BLOCK_BUDGET = 256ull << 20;
+
+// what needs no device: the probabilities, the output, the pooled sizes
+int monitor_check(const char *what, const double *probs, int n_probs, const double *out, long long n, long long C) {
+  if (n_probs < 0 || n_probs > MN_MAXPROBS) return fail(POTUS_ERR_ARG, "%s: n_probs = %d (0 to %d)", what, n_probs, MN_MAXPROBS);
+  if (n_probs > 0 && !probs) return fail(POTUS_ERR_ARG, "%s: null probs", what);
+  for (int i = 0; i < n_probs; i++) if (!(probs[i] >= 0.0 && probs[i] <= 1.0)) return fail(POTUS_ERR_ARG, "%s: probs[%d] = %g outside [0, 1]", what, i, probs[i]);
+  if (!out) return fail(POTUS_ERR_ARG, "%s: null out", what);
+  if (2 * C > DG_MAXCH) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld chains pooled (at most %d)", what, C, DG_MAXCH / 2);
+  if (C * n > 0x7fffffffll) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld pooled draws (the sort's indices have 32 bits)", what, C * n);
+  return 0;
+}
+
+// cols [NC][C][n] on the current device -> out [NC][MN_NSTATS + n_probs] (host)
+int monitor_of_columns(hipStream_t stream, const double *cols, long long n, int C, int NC, const double *probs, int n_probs, double *out, const char *what) {
+  const long long N = std::max<long long>(2ll * C * (n / 2), 1), M = (long long)C * n;
+  const int W = MN_NSTATS + n_probs;
+  DevBufs tmp;
+  MnParams P{};
+  int rc;
+  // k_dg_column's scratch per workgroup (its runs hold the C middle draws too when n is odd) and its cap on the grid
+  const long long per_wg = N * 16 + (M > DG_RUN ? M * 12 : 0);
+  const int grid = (int)std::max<long long>(1, std::min<long long>(std::min(NC, 1024), (768ll << 20) / per_wg));
+  if ((rc = loo_alloc(tmp, &P.zbuf, (size_t)grid * 2 * (size_t)N * 8, what))) return rc;
+  if (M > DG_RUN) {
+    if ((rc = loo_alloc(tmp, &P.rkey, (size_t)grid * (size_t)M * 8, what))) return rc;
+    if ((rc = loo_alloc(tmp, &P.ridx, (size_t)grid * (size_t)M * 4, what))) return rc;
+  }
+  if ((rc = loo_alloc(tmp, &P.out, (size_t)NC * W * 8, what))) return rc;
+  int npad = 1;
+  while (npad < M && npad < DG_RUN) npad <<= 1;
+  const size_t lds = (size_t)npad * 12;                // keys + indices
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mn_column), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  P.cols = cols; P.n = n; P.C = C; P.NC = NC; P.n_probs = n_probs;
+  for (int i = 0; i < n_probs; i++) P.probs[i] = probs[i];
+  hipLaunchKernelGGL(k_mn_column, dim3(grid), dim3(DG_THREADS), lds, stream, P);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(out, P.out, (size_t)NC * W * 8, hipMemcpyDeviceToHost, stream));
+  HIP_TRY(hipStreamSynchronize(stream));
+  return 0;
+}
+} // namespace
+
+int potus_monitor_device(int device, const void *block, long long n_draws, int n_chains, int n_cols, const double *probs, int n_probs, double *out) {
+  if (!block || n_draws < 1 || n_chains < 1 || n_cols < 1) return fail(POTUS_ERR_ARG, "potus_monitor_device: bad argument");
+  if (const int rc_ = monitor_check("potus_monitor_device", probs, n_probs, out, n_draws, n_chains)) return rc_;   // before anything is allocated
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(POTUS_ERR_DEVICE, "potus_monitor_device: no HIP device %d", device);
+  DeviceGuard guard;
+  DeviceLocks lock(device);
+  HIP_TRY(hipSetDevice(device));
+  DevBufs tmp;
+  double *cols = nullptr;
+  if (const int rc_ = loo_alloc(tmp, &cols, (size_t)n_draws * n_chains * n_cols * 8, "potus_monitor_device")) return rc_;
+  if (const int rc_ = transpose_block(0, (const double *)block, cols, n_draws, n_chains, n_cols, n_chains, 0)) return rc_;
+  return monitor_of_columns(0, cols, n_draws, n_chains, n_cols, probs, n_probs, out, "potus_monitor_device");
+}
+
+int potus_monitor(const int *handles, int n_handles, int col_begin, int col_end, const double *probs, int n_probs, double *out) {
+  if (const int rc_ = monitor_check("potus_monitor", probs, n_probs, out, 0, 0)) return rc_;
+  if (col_begin < 0 || col_begin >= col_end) return fail(POTUS_ERR_ARG, "potus_monitor: columns [%d, %d)", col_begin, col_end);
+  Pool P;
+  if (const int rc_ = P.resolve(handles, n_handles, "potus_monitor")) return rc_;
+  if (col_end > P.s0->L.ncols) return fail(POTUS_ERR_ARG, "potus_monitor: columns [%d, %d) of %d", col_begin, col_end, P.s0->L.ncols);
+  if (const int rc_ = P.same_posterior("the table pools the chains of one")) return rc_;
+  long long Ctot = 0;
+  for (const Sampler *sp : P.sps) Ctot += sp->R.chains;
+  if (const int rc_ = monitor_check("potus_monitor", probs, n_probs, out, 0, Ctot)) return rc_;
+  DeviceGuard guard;
+  DeviceLocks lock(P.devs);
+  if (const int rc_ = P.count()) return rc_;
+  if (const int rc_ = P.equal_counts()) return rc_;
+  int n_warm_rows = 0, n_post = 0;
+  if (const int rc_ = P.post_warmup(&n_warm_rows, &n_post)) return rc_;
+  if (const int rc_ = monitor_check("potus_monitor", probs, n_probs, out, n_post, Ctot)) return rc_;
+  Sampler *s0 = P.s0;
+  HIP_TRY(hipSetDevice(s0->device));
+  // columns per block: one handle's gathered rows (at most all chains, warm-up rows included) and the block's transposed columns
+  size_t budget = MONITOR_BLOCK_BUDGET;
+  if (const char *e = getenv("POTUS_MONITOR_BLOCK_BUDGET")) budget = std::max<size_t>(1, (size_t)atoll(e));
+  const size_t per_col = ((size_t)P.saved[0] + (size_t)n_post) * (size_t)Ctot * 8;
+  const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)(col_end - col_begin), budget / per_col));
+  const int W = MN_NSTATS + n_probs;
+  DevBufs tmp;
+  double *cols = nullptr;
+  if (const int rc_ = loo_alloc(tmp, &cols, (size_t)n_post * Ctot * nb * 8, "potus_monitor")) return rc_;
+  for (int b0 = col_begin; b0 < col_end; b0 += nb) {
+    const int b1 = std::min(b0 + nb, col_end);
+    if (const int rc_ = gather_columns(P, b0, b1, n_warm_rows, n_post, cols)) return rc_;
+    if (const int rc_ = monitor_of_columns(s0->stream, cols, n_post, (int)Ctot, b1 - b0, probs, n_probs, out + (size_t)(b0 - col_begin) * W, "potus_monitor")) return rc_;
+  }
   return 0;
 }
 
@@ -4397,6 +4504,9 @@ void potus_R_sbc_ranks(int *handle, double *truth, int *cols /*[3]: col_begin, c
 }
 void potus_R_constrain(int *handle, double *q, int *n, int *cols /*[2]: col_begin, col_end*/, double *out, int *status) {
   *status = potus_constrain(*handle, q, *n, cols[0], cols[1], out);
+}
+void potus_R_monitor(int *handles, int *n_handles, int *cols /*[2]: col_begin, col_end*/, double *probs, int *n_probs, double *out, int *status) {
+  *status = potus_monitor(handles, *n_handles, cols[0], cols[1], probs, *n_probs, out);
 }
 void potus_R_loo(int *handles, int *n_handles, int *iopts /*[2]: integrate, r_eff given*/, double *r_eff, double *pointwise_out, double *estimates_out,
                  int *status) {

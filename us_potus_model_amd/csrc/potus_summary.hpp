@@ -85,6 +85,17 @@ __device__ __forceinline__ double ps_select(const double *runs, long long nd, lo
   return ps_unkey(lo);
 }
 
+// R's type-7 quantile of n sorted values at p: with h = (n - 1) p and lo = floor(h) it is x_(lo) + (h - lo) (x_(lo+1) - x_(lo)).
+// ps_q7_index gives the 0-based order statistic to fetch (upper = the second one, clamped to the last), ps_q7 combines the two.
+__device__ __forceinline__ long long ps_q7_index(long long n, double p, bool upper) {
+  const long long lo = (long long)floor((double)(n - 1) * p);
+  return upper ? (lo + 1 < n ? lo + 1 : n - 1) : lo;
+}
+__device__ __forceinline__ double ps_q7(long long n, double p, double x_lo, double x_hi) {
+  const double h = (double)(n - 1) * p;
+  return x_lo + (h - floor(h)) * (x_hi - x_lo);
+}
+
 // cols [NC][nd]; scratch [gridDim.x][nd] (only touched when nd > PS_RUN).
 // out_state [T*S][4] = low, high, mean, P(> 0.5); out_natl [T][4] the same; out_ev [T][5] = mean, median, high, low, P(>= 270)
 __global__ __launch_bounds__(PS_THREADS) void k_col_summary(const double *cols, double *scratch, long long nd, int T, int S,
@@ -135,9 +146,7 @@ __global__ __launch_bounds__(PS_THREADS) void k_col_summary(const double *cols, 
     // order statistics x_(lo), x_(hi) of the three type-7 quantiles 0.025, 0.975, 0.5: threads 0..5
     if (tid < 6) {
       const double p = tid < 2 ? 0.025 : tid < 4 ? 0.975 : 0.5;
-      const double h = (double)(nd - 1) * p;
-      const long long lo = (long long)floor(h);
-      const long long k = (tid & 1) ? (lo + 1 < nd ? lo + 1 : nd - 1) : lo;
+      const long long k = ps_q7_index(nd, p, tid & 1);
       qv[tid] = multi ? ps_select(runs, nd, k) : xs[k];
     }
     __syncthreads();
@@ -146,8 +155,7 @@ __global__ __launch_bounds__(PS_THREADS) void k_col_summary(const double *cols, 
       double q3[3];
       for (int j = 0; j < 3; j++) {
         const double p = j == 0 ? 0.025 : j == 1 ? 0.975 : 0.5;
-        const double h = (double)(nd - 1) * p;
-        q3[j] = qv[2 * j] + (h - floor(h)) * (qv[2 * j + 1] - qv[2 * j]);
+        q3[j] = ps_q7(nd, p, qv[2 * j], qv[2 * j + 1]);
       }
       if (kind == 0) { double *o = out_state + (size_t)col * 4; o[0] = q3[0]; o[1] = q3[1]; o[2] = mean; o[3] = prob; }
       else if (kind == 1) { double *o = out_natl + (size_t)(col - TS) * 4; o[0] = q3[0]; o[1] = q3[1]; o[2] = mean; o[3] = prob; }

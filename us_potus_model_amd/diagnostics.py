@@ -90,10 +90,68 @@ def ess_mean(x: np.ndarray) -> float:
     return ess_basic(_split(np.asarray(x, dtype=np.float64)))
 
 
-def summarise(draws: np.ndarray) -> dict:
-    """draws: [chains, n, k] -> per-column rhat, bulk ESS, mean, mcse."""
+def quantile7(x: np.ndarray, p: float) -> float:
+    """R's default (type 7) quantile over all entries of x: x_(lo) + (h - lo) (x_(lo+1) - x_(lo)) with h = (N - 1) p, lo = floor(h)."""
+    xs = np.sort(np.asarray(x, dtype=np.float64).reshape(-1))
+    if np.isnan(xs).any():
+        return np.nan
+    h = (xs.size - 1) * float(p)
+    lo = int(np.floor(h))
+    hi = min(lo + 1, xs.size - 1)
+    return float(xs[lo] + (h - lo) * (xs[hi] - xs[lo]))
+
+
+def mad(x: np.ndarray) -> float:
+    """1.4826 median|x - median(x)| over all entries (R's mad(); the medians are the mean of the two middle values)."""
+    x = np.asarray(x, dtype=np.float64).reshape(-1)
+    return float(1.4826 * np.median(np.abs(x - np.median(x))))
+
+
+def ess_quantile(x: np.ndarray, p: float) -> float:
+    """posterior::ess_quantile: ess_basic of the split indicator 1[x <= Q7(x, p)], the quantile over ALL draws. x: [chains, draws]."""
+    x = np.asarray(x, dtype=np.float64)
+    return ess_basic(_split((x <= quantile7(x, p)).astype(np.float64)))
+
+
+def ess_tail(x: np.ndarray) -> float:
+    """posterior::ess_tail: the smaller of ess_quantile at 5 % and at 95 % (NaN when either is)."""
+    return float(np.min([ess_quantile(x, 0.05), ess_quantile(x, 0.95)]))
+
+
+def mcse_mean(x: np.ndarray) -> float:
+    """posterior::mcse_mean: sd (ddof = 1, all draws) / sqrt(ess_mean)."""
+    x = np.asarray(x, dtype=np.float64)
+    return float(x.std(ddof=1) / np.sqrt(ess_mean(x)))
+
+
+MONITOR_STATS = ("mean", "sd", "mad", "mcse_mean", "rhat", "ess_bulk", "ess_tail", "ess_mean")
+
+
+def monitor_row(x: np.ndarray, probs=()) -> np.ndarray:
+    """What potus_monitor writes for one column, x: [chains, draws] -> [8 + len(probs)] = MONITOR_STATS, then the type-7 quantiles.
+    mean, sd, mad and quantiles over all draws, the rest over the split draws.  A non-finite draw: NaN everywhere.  A constant column:
+    sd = mad = 0 and nothing to diagnose -- slots 3-7 are NaN as in `posterior` (rhat() alone would rank the ties by position)."""
+    x = np.asarray(x, dtype=np.float64)
+    out = np.full(len(MONITOR_STATS) + len(probs), np.nan)
+    if not np.isfinite(x).all():
+        return out
+    out[8:] = [quantile7(x, p) for p in probs]
+    if x.min() == x.max():
+        out[0], out[1], out[2] = x.flat[0] + 0.0, 0.0, 0.0
+        return out
+    with np.errstate(invalid="ignore", divide="ignore"):
+        out[0], out[1], out[2] = x.mean(), x.std(ddof=1) if x.size > 1 else np.nan, mad(x)
+        if x.shape[1] >= 4:                                        # two draws per half: the least R-hat is defined for
+            out[4], out[5], out[6], out[7] = rhat(x), ess_bulk(x), ess_tail(x), ess_mean(x)
+        out[3] = out[1] / np.sqrt(out[7])
+    return out
+
+
+def summarise(draws: np.ndarray, probs=()) -> dict:
+    """draws: [chains, n, k] -> per-column rhat, bulk ESS, mean, mcse, and the rest of the summary row: mad, ess_tail, mcse_mean and -- with
+    probs -- `quantiles` [k, len(probs)] (type 7)."""
     c, n, k = draws.shape
-    out = dict(rhat=np.zeros(k), ess_bulk=np.zeros(k), ess_mean=np.zeros(k), mean=np.zeros(k), sd=np.zeros(k))
+    out = dict(rhat=np.zeros(k), ess_bulk=np.zeros(k), ess_mean=np.zeros(k), mean=np.zeros(k), sd=np.zeros(k), mad=np.zeros(k), ess_tail=np.zeros(k))
     for j in range(k):
         x = draws[:, :, j]
         out["rhat"][j] = rhat(x)
@@ -101,5 +159,10 @@ def summarise(draws: np.ndarray) -> dict:
         out["ess_mean"][j] = ess_mean(x)
         out["mean"][j] = x.mean()
         out["sd"][j] = x.std(ddof=1)
+        out["mad"][j] = mad(x)
+        out["ess_tail"][j] = ess_tail(x)
     out["mcse"] = out["sd"] / np.sqrt(out["ess_mean"])
+    out["mcse_mean"] = out["mcse"]
+    if len(probs):
+        out["quantiles"] = np.array([[quantile7(draws[:, :, j], p) for p in probs] for j in range(k)])
     return out

@@ -105,6 +105,10 @@ def load_library():
         L.potus_outcomes.argtypes = [ip, C.c_int, C.c_int, C.c_int, i32p, C.c_int, dp, llp, llp, llp, llp, llp]
         L.potus_outcomes_device.argtypes = [C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int, dp, i32p, C.c_int, dp, llp, llp, llp, llp, llp]
         L.potus_outcomes_timing.argtypes = [dp]
+    if hasattr(L, "potus_monitor"):                     # the posterior summary table (monitor.py)
+        L.potus_monitor.argtypes = [ip, C.c_int, C.c_int, C.c_int, dp, C.c_int, dp]
+        L.potus_monitor_device.argtypes = [C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int, dp, C.c_int, dp]
+        L.potus_R_monitor.argtypes = [ip, ip, ip, dp, ip, dp, ip]
     _LIB = L
     return L
 
@@ -119,9 +123,10 @@ EXPORTS = [
     "potus_set_datasets", "potus_simulate_prior", "potus_constrain", "potus_sbc_ranks",
     "potus_log_lik_device", "potus_loo_device", "potus_loo",
     "potus_outcomes", "potus_outcomes_device", "potus_outcomes_timing",
+    "potus_monitor", "potus_monitor_device",
     "potus_R_create", "potus_R_init", "potus_R_run", "potus_R_run_many", "potus_R_num_columns", "potus_R_saved_count",
     "potus_R_write_array", "potus_R_write_stan_csv", "potus_R_posterior_summary", "potus_R_diagnostics", "potus_R_check_convergence", "potus_R_backtest_scores", "potus_R_last_error", "potus_R_destroy",
-    "potus_R_set_datasets", "potus_R_simulate_prior", "potus_R_sbc_ranks", "potus_R_constrain", "potus_R_loo", "potus_R_outcomes",
+    "potus_R_set_datasets", "potus_R_simulate_prior", "potus_R_sbc_ranks", "potus_R_constrain", "potus_R_loo", "potus_R_outcomes", "potus_R_monitor",
 ]
 
 
@@ -399,6 +404,11 @@ class Handle:
         from .outcomes import outcomes
         return outcomes([self], ev, actual=actual, days=days, ev_to_win=ev_to_win)
 
+    def monitor(self, pars=None, cols=None, probs=(0.025, 0.25, 0.5, 0.75, 0.975)):
+        """The summary table of this handle's post-warm-up draws: mean, sd, mad, mcse, R-hat, ESS, quantiles (us_potus_model_amd.monitor)."""
+        from .monitor import monitor
+        return monitor([self], pars=pars, cols=cols, probs=probs)
+
     def write_stan_csv(self, directory, basename="poll_model_2020"):
         os.makedirs(directory, exist_ok=True)
         _check(self.L, self.L.potus_write_stan_csv(self.h, str(directory).encode(), basename.encode()))
@@ -577,6 +587,11 @@ class StanFit:
         """EV histogram, tipping point, joint win counts and p-values over every chain of the fit, on the device (us_potus_model_amd.outcomes)."""
         from .outcomes import outcomes
         return outcomes(self._hs, ev, actual=actual, days=days, ev_to_win=ev_to_win)
+
+    def monitor(self, pars=None, cols=None, probs=(0.025, 0.25, 0.5, 0.75, 0.975)):
+        """fit$summary() / print(stanfit) / rstan::monitor over every chain of the fit, on the device (us_potus_model_amd.monitor)."""
+        from .monitor import monitor
+        return monitor(self._hs, pars=pars, cols=cols, probs=probs)
 
     def extract(self, pars, permuted=False):
         """rstan::extract(out, pars=)[[1]]: array [draws, ...dims], chains merged.
