@@ -382,3 +382,46 @@ potus_tipping_point <- function(outcomes, states = NULL, day = nrow(outcomes$tip
   d <- d[cnt > 0, , drop = FALSE]
   d[order(-d$prop), , drop = FALSE]
 }
+
+# ---- conditional forecasts and the covariance of the state scores (us_potus_model_amd/scenario.py is the same in Python; DESIGN.md section 4h) ----
+# cor() of the election-day scores of the draws (final_2016.R:710-715) without the draws on the host, and the forecast GIVEN an event:
+# given = list(FL = "win", PA = "lose", national = c(0.48, 0.52)) -- names are state names (`states`, in state order), 1-based state indices
+# as strings ("3") or "national"; an interval is lo < x <= hi, "win" is (0.5, Inf], "lose" is (-Inf, 0.5].  day: the day the condition is
+# read on (1-based, default election day); days: c(first, last) of the outputs, 1-based, NULL = every day; ev: integer electoral votes or
+# NULL for the moments alone.  Returns n_kept, n_draws, probability, mean [days, S + 1], cov [days, S + 1, S + 1] (coordinate S + 1: the
+# national vote) and, with ev, potus_outcomes' ev_hist, tipping and joint of the kept draws (n_draws of that list = n_kept).
+potus_scenario <- function(fit, given = NULL, ev = NULL, day = NULL, days = NULL, ev_to_win = 270L, states = NULL) {
+  S <- as.integer(fit$data$S); nT <- as.integer(fit$data$T)
+  if (!is.null(ev) && any(ev != round(ev))) stop("potus_scenario: electoral votes must be integers")
+  if (is.null(days)) days <- c(1L, nT)
+  if (is.null(day)) day <- nT
+  lo <- rep(-Inf, S + 1L); hi <- rep(Inf, S + 1L)
+  for (nm in names(given)) {
+    k <- if (nm == "national") S + 1L else if (!is.null(states) && nm %in% states) match(nm, states) else suppressWarnings(as.integer(nm))
+    if (is.na(k) || k < 1L || k > S + 1L) stop("potus_scenario: '", nm, "' is no state name, state index or \"national\"")
+    g <- given[[nm]]
+    if (identical(g, "win")) lo[k] <- 0.5
+    else if (identical(g, "lose")) hi[k] <- 0.5
+    else if (is.numeric(g) && length(g) == 2L) { lo[k] <- g[1]; hi[k] <- g[2] }
+    else stop("potus_scenario: a condition is \"win\", \"lose\" or c(lo, hi)")
+  }
+  n <- as.integer(days[2] - days[1] + 1L); K <- if (is.null(ev)) 0L else as.integer(sum(ev)); m <- max(n, 1L)
+  r <- .C("potus_R_scenario", as.integer(fit$handles), length(fit$handles),
+          as.integer(c(day - 1L, days[1] - 1L, days[2], ev_to_win, length(given) > 0L, 1L, !is.null(ev))), as.double(lo), as.double(hi),
+          as.integer(if (is.null(ev)) rep(0L, S) else ev), n = double(2), mean = double(m * (S + 1L)), cov = double(m * (S + 1L)^2),
+          ev_hist = double(m * (K + 1L)), tipping = double(m * (S + 1L)), joint = double(m * (S + 2L)^2), status = integer(1))
+  .potus_check(r$status)
+  out <- list(n_kept = r$n[1], n_draws = r$n[2], probability = r$n[1] / r$n[2], mean = matrix(r$mean, n, S + 1L, byrow = TRUE),
+              cov = aperm(array(r$cov, c(S + 1L, S + 1L, n)), c(3, 2, 1)), days = days, day = day, given = given)
+  if (!is.null(ev))
+    out$outcomes <- list(ev_hist = matrix(r$ev_hist, n, K + 1L, byrow = TRUE), tipping = matrix(r$tipping, n, S + 1L, byrow = TRUE),
+                         joint = aperm(array(r$joint, c(S + 2L, S + 2L, n)), c(3, 2, 1)), n_draws = r$n[1], days = days, ev = ev, ev_to_win = ev_to_win)
+  out
+}
+
+# cov2cor of one day of a potus_scenario() result (default: its last day); NaN where a variance is zero
+potus_scenario_cor <- function(scenario, day = dim(scenario$cov)[1]) {
+  v <- scenario$cov[day, , ]
+  s <- ifelse(diag(v) > 0, 1 / sqrt(diag(v)), NaN)
+  v * outer(s, s)
+}

@@ -345,7 +345,7 @@ int potus_dense_check(int handle, int chain, int n_probe, double *out /*[2]*/);
  * Chain c fits data set c / (chains / n_datasets).  Needs chains % n_datasets == 0, one workgroup per chain (cus_per_chain = 1,
  * twin = 0) and the diagonal metric.  Per-chain calls (potus_get_draws, potus_write_array[_device], potus_chain_status,
  * potus_get_adaptation, potus_draws_device_ptr) work unchanged; calls that pool all chains (potus_posterior_summary[_many],
- * potus_diagnostics, potus_check_convergence, potus_extract_matrix, potus_write_stan_csv, potus_loo, potus_log_lik_device, potus_outcomes, potus_monitor) refuse with
+ * potus_diagnostics, potus_check_convergence, potus_extract_matrix, potus_write_stan_csv, potus_loo, potus_log_lik_device, potus_outcomes, potus_monitor, potus_scenario) refuse with
  * POTUS_ERR_STATE.  A chain
  * whose initialisation or step-size search fails does not fail potus_init / potus_run: potus_chain_status reports it, the
  * iteration and saved-draw counts are those of the other chains. */
@@ -420,6 +420,42 @@ int potus_outcomes_device(int device, const void *block, long long n_draws, int 
  * day range out of it (host clock), the counting kernel (HIP events). */
 int potus_outcomes_timing(double *ms /*[3]*/);
 
+/* ---- conditional forecasts and the covariance of the state scores ----
+ * final_2016.R:710-715 calls cor() on the election-day scores of the draws (the older run files cov(p[, election_day, ])); and the reader of a
+ * forecast asks for it GIVEN an event: the Democrat carries Florida, loses Pennsylvania, the national vote lands between 48 % and 52 %.
+ * For one draw and one day the S + 1 COORDINATES are x[s] = predicted_score[t, s] (s < S) and x[S] = nat = sum_s w[s] x[s], summed
+ * s = 0 .. S-1 in order with the handle's normalised weights.  The CONDITION reads nat exactly as potus_outcomes sums it (each step one fused
+ * multiply-add), so that `nat > 0.5` here and pop_win there can never disagree; coordinate S of mean and cov is the same in-order sum with every
+ * product and every sum rounded on its own -- what the loop gives in plain C on any host, so a host restatement holds it bit for bit.
+ *   Condition: given cond_day, lo[S+1] and hi[S+1], a draw is KEPT iff lo[k] < x_cond_day[k] <= hi[k] for every k.  -inf / +inf leave a
+ *     coordinate free; "wins s" is lo[s] = 0.5, "does not win s" is hi[s] = 0.5 (the strict rule of final_2016.R:817: complementary
+ *     conditions partition the draws); lo = hi = NULL keeps every draw.  A NaN bound or lo[k] >= hi[k] is refused (POTUS_ERR_ARG) before
+ *     the device is touched.
+ *   Outputs, per day of [day_begin, day_end) (0-based), over the kept draws only:
+ *     n_kept, n_draws                    P(condition) = n_kept / n_draws
+ *     mean    [days][S + 1]              sum / n_kept, one division
+ *     cov     [days][S + 1][S + 1]       two-pass: products of deviations from that mean, ddof 1; symmetric, both triangles written
+ *     ev_hist, tipping, joint            potus_outcomes' counts of the kept draws, same shapes and meaning
+ *   n_kept = 0: mean and cov NaN, counts zero, status OK.  n_kept = 1: mean is the draw, cov NaN.  Any output pointer may be NULL; ev may be
+ *   NULL when all three count outputs are.  The limits are potus_outcomes': S <= 63, sum(ev) <= 2047.
+ * The draws are taken in CANONICAL order -- chain after chain in the order the handles are listed, each chain's post-warm-up draws in iteration
+ * order: the row order of potus_extract_matrix -- and every floating-point sum runs in an order fixed by that sequence alone (chunks of 1024
+ * kept draws, chunk partials added in chunk order, no floating-point atomics): two handles of two chains give the bytes of one handle of
+ * four.  Warm-up rows of save_warmup = 1 are left out; handles with potus_set_datasets are refused (POTUS_ERR_STATE).  cond_day may lie
+ * outside [day_begin, day_end).  predicted_score never visits the host. */
+int potus_scenario(const int *handles, int n_handles, int cond_day, const double *lo /*[S+1] or NULL*/, const double *hi /*[S+1] or NULL*/,
+                   int day_begin, int day_end, const int32_t *ev, int ev_to_win,
+                   long long *n_kept, long long *n_draws, double *mean, double *cov,
+                   long long *ev_hist, long long *tipping, long long *joint);
+/* The same for a block [n_draws][n_days][S] of doubles in DEVICE memory of GPU `device`, its draws in the order they are to be summed in;
+ * w [S] as in potus_outcomes_device; cond_day indexes the block's days; the outputs cover all of them. */
+int potus_scenario_device(int device, const void *block /*[n_draws][n_days][S]*/, long long n_draws, int n_days, int S, const double *w,
+                          int cond_day, const double *lo, const double *hi, const int32_t *ev, int ev_to_win,
+                          long long *n_kept, double *mean, double *cov, long long *ev_hist, long long *tipping, long long *joint);
+/* Milliseconds of the calling thread's last potus_scenario[_device]: producing and gathering predicted_score (host clock), cutting the days
+ * out of it (host clock), keeping and compacting (host clock), the moments (HIP events), the counting kernel (HIP events). */
+int potus_scenario_timing(double *ms /*[5]*/);
+
 /* ---- .C()-callable wrappers (int* / double* / char** only) ---- */
 void potus_R_create(int *dims /*[8]: N_nat,N_state,T,S,P,M,Pop,variant*/,
                     int *state, int *day_state, int *day_national, int *poll_state,
@@ -460,6 +496,9 @@ void potus_R_loo(int *handles, int *n_handles, int *iopts /*[2]: integrate, r_ef
                  double *estimates_out /*[3][2]*/, int *status);
 void potus_R_outcomes(int *handles, int *n_handles, int *iopts /*[4]: day_begin, day_end, ev_to_win, actual given*/, int *ev, double *actual,
                       double *ev_hist, double *tipping, double *joint, double *below_actual, double *n_draws, int *status);
+/* counts as doubles, like potus_R_outcomes; n [2] = n_kept, n_draws; mean and cov are written when iopts[5], the counts when iopts[6] */
+void potus_R_scenario(int *handles, int *n_handles, int *iopts /*[7]: cond_day, day_begin, day_end, ev_to_win, bounds given, moments wanted, counts wanted*/,
+                      double *lo, double *hi, int *ev, double *n /*[2]*/, double *mean, double *cov, double *ev_hist, double *tipping, double *joint, int *status);
 
 #ifdef __cplusplus
 }

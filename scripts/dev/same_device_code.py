@@ -31,9 +31,11 @@ def functions(path):
             name, buf = m.group(1), []
         elif name:
             ins = re.sub(r"^\s*[0-9a-f]+:\s*", "", ln).split("//")[0].strip()
+            if ins in ("", "..."):            # the padding between functions, which moves with the sizes of the others
+                continue
             if re.match(r"s_c?branch\w*\s", ins):
                 ins = ins.split()[0] + " <rel>"
-            elif buf and re.match(r"s_add_u32 (s\d+), \1, 0x[0-9a-f]+$", ins) and (buf[-1].startswith("s_getpc_b64") or (len(buf) > 1 and buf[-2].startswith("s_getpc_b64"))):
+            elif buf and re.match(r"s_add_u32 (s\d+|vcc_lo), \1, 0x[0-9a-f]+$", ins) and (buf[-1].startswith("s_getpc_b64") or (len(buf) > 1 and buf[-2].startswith("s_getpc_b64"))):
                 ins = re.sub(r"0x[0-9a-f]+$", "<pcrel>", ins)
             buf.append(ins)
     if name:

@@ -2,7 +2,7 @@
 
 Layout: csrc/ (HIP kernels + the C ABI of include/potus_hmc.h), sampler.py (host mirror of the
 reference's `$sample()` / `rstan::extract()` surface), dataprep.py / synthetic.py (Stan data
-lists), diagnostics.py (R-hat / ESS), outcomes.py (joint election outcomes: EV histogram, tipping point), monitor.py (the posterior summary table), _abi.py (ctypes structs).
+lists), diagnostics.py (R-hat / ESS), outcomes.py (joint election outcomes: EV histogram, tipping point), monitor.py (the posterior summary table), scenario.py (conditional forecasts, covariance of the state scores), _abi.py (ctypes structs).
 """
 from . import _abi  # noqa: F401
 from .sampler import (Handle, PotusError, PotusModel, StanFit, backtest_scores, check_convergence, device_diagnostics, device_diagnostics_of_block,  # noqa: F401
@@ -13,3 +13,6 @@ from .outcomes import outcomes as joint_outcomes  # noqa: F401,E402
 from . import monitor  # noqa: F401,E402  (the module; its monitor() is also available as monitor_table)
 from .monitor import Monitor, monitor_of_block  # noqa: F401,E402
 from .monitor import monitor as monitor_table  # noqa: F401,E402
+from . import scenario  # noqa: F401,E402  (the module; its scenario() is also available as conditional_forecast)
+from .scenario import Scenario, scenario_of_block  # noqa: F401,E402
+from .scenario import scenario as conditional_forecast  # noqa: F401,E402

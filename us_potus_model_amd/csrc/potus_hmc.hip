@@ -18,6 +18,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <limits>
 #include <charconv>
 #include <chrono>
 #include <thread>
@@ -1114,6 +1115,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, c
 
 #include "potus_loo.hpp"   // per-poll log-likelihoods and PSIS-LOO (after wa_build_row, which it shares)
 #include "potus_outcomes.hpp"   // joint election outcomes: EV histogram, tipping point, joint win counts
+#include "potus_scenario.hpp"   // conditional forecasts and the covariance of the state scores
 
 // ======================================================================== host
 namespace {
@@ -3882,6 +3884,241 @@ int potus_outcomes_timing(double *ms) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------- conditional forecasts (potus_scenario.hpp)
+namespace {
+thread_local double g_sc_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};   // the last call of this thread (potus_scenario_timing)
+constexpr size_t SC_SCRATCH_BUDGET = (size_t)256 << 20;        // nat and the chunk partials of one block of days
+
+struct ScOut { long long *n_kept; double *mean, *cov; long long *ev_hist, *tipping, *joint; };
+
+// everything about the bounds, ev and ev_to_win: no device needed
+int sc_check(const char *what, int S, const double *lo, const double *hi, const int32_t *ev, int ev_to_win, const ScOut &o, int *ev_sum) {
+  if (S < 1 || S > OC_MAX_S) return fail(POTUS_ERR_UNSUPPORTED, "%s: S = %d (the kernels map the coordinates to the lanes of a wave: 1 .. %d)", what, S, OC_MAX_S);
+  if ((lo == nullptr) != (hi == nullptr)) return fail(POTUS_ERR_ARG, "%s: lo and hi are given together or not at all", what);
+  if (lo)
+    for (int k = 0; k <= S; k++) {
+      if (std::isnan(lo[k]) || std::isnan(hi[k])) return fail(POTUS_ERR_ARG, "%s: the bounds of coordinate %d hold a NaN", what, k);
+      if (lo[k] >= hi[k]) return fail(POTUS_ERR_ARG, "%s: lo[%d] = %g is not below hi[%d] = %g (the interval is empty)", what, k, lo[k], k, hi[k]);
+    }
+  *ev_sum = 0;
+  if (!ev) {
+    if (o.ev_hist || o.tipping || o.joint) return fail(POTUS_ERR_ARG, "%s: ev is null, but a count output is asked for", what);
+    return 0;
+  }
+  return oc_check(what, S, ev, ev_to_win, nullptr, ev_sum);
+}
+
+// items [nd][n_days][S] on the current device, in canonical order; the condition day's item of draw d at cond + d * cstride.
+// Everything the call returns, in the caller's host arrays (any of them may be null).
+int sc_compute(const char *what, hipStream_t st, const double *items, long long nd, int n_days, int S, const double *cond, long long cstride, const double *w,
+               const double *lo, const double *hi, const int32_t *ev, int ev_to_win, int ev_sum, const ScOut &o) {
+  const int C = S + 1;
+  const long long rowlen = (long long)n_days * S;
+  DevBufs tmp;
+  OcEvents e;
+  HIP_TRY(hipEventCreate(&e.a)); HIP_TRY(hipEventCreate(&e.b));
+  double *dw = nullptr;
+  if (const int rc_ = loo_alloc(tmp, &dw, (size_t)S * 8, what)) return rc_;
+  HIP_TRY(hipMemcpyAsync(dw, w, (size_t)S * 8, hipMemcpyHostToDevice, st));
+  // ---- keep + compact
+  const double t0 = dn_now();
+  const double *kept = items;
+  long long n = nd;
+  if (lo) {
+    const long long nblk = (nd + SC_KEEP_BLOCK - 1) / SC_KEEP_BLOCK;
+    double *dlh = nullptr;
+    unsigned char *flag = nullptr;
+    int *cnt = nullptr;
+    long long *first = nullptr;
+    if (const int rc_ = loo_alloc(tmp, &dlh, (size_t)2 * C * 8, what)) return rc_;
+    if (const int rc_ = loo_alloc(tmp, &flag, (size_t)nd, what)) return rc_;
+    if (const int rc_ = loo_alloc(tmp, &cnt, (size_t)nblk * 4, what)) return rc_;
+    if (const int rc_ = loo_alloc(tmp, &first, (size_t)(nblk + 1) * 8, what)) return rc_;
+    HIP_TRY(hipMemcpyAsync(dlh, lo, (size_t)C * 8, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dlh + C, hi, (size_t)C * 8, hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_sc_keep, dim3((unsigned)nblk), dim3(SC_THREADS), 0, st, cond, cstride, nd, S, (const double *)dw, (const double *)dlh, (const double *)(dlh + C), flag, cnt);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_sc_scan, dim3(1), dim3(64), 0, st, (const int *)cnt, nblk, first);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(&n, first + nblk, 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    if (n < 0 || n > nd) return fail(POTUS_ERR_DEVICE, "%s: the kept count %lld of %lld draws is out of range", what, n, nd);
+    if (n > 0 && n < nd) {
+      double *comp = nullptr;
+      if (const int rc_ = loo_alloc(tmp, &comp, (size_t)n * rowlen * 8, what)) return rc_;
+      const unsigned slices = (unsigned)std::min<long long>(std::max<long long>(1, rowlen / 512), 64);
+      hipLaunchKernelGGL(k_sc_compact, dim3((unsigned)nblk, slices), dim3(SC_THREADS), 0, st, items, nd, rowlen, (const unsigned char *)flag, (const long long *)first, comp);
+      HIP_TRY(hipGetLastError());
+      HIP_TRY(hipStreamSynchronize(st));
+      kept = comp;
+    }
+    g_sc_ms[2] = dn_now() - t0;
+  }
+  if (o.n_kept) *o.n_kept = n;
+  // ---- moments
+  const size_t n_mean = (size_t)n_days * C, n_cov = (size_t)n_days * C * C;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  const bool want_mean = o.mean && n >= 1, want_cov = o.cov && n >= 2;
+  if (o.mean && !want_mean) std::fill(o.mean, o.mean + n_mean, nan);
+  if (o.cov && !want_cov) std::fill(o.cov, o.cov + n_cov, nan);
+  if (want_mean || want_cov) {
+    if (n > 65535ll * SC_CHUNK) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld kept draws (the moments take at most %lld)", what, n, 65535ll * SC_CHUNK);
+    const int nchunks = (int)((n + SC_CHUNK - 1) / SC_CHUNK);
+    const size_t per_day = ((size_t)n + (size_t)nchunks * (C + (want_cov ? (size_t)C * C : 0))) * 8;
+    const int dblk = (int)std::min<size_t>((size_t)n_days, std::max<size_t>(1, SC_SCRATCH_BUDGET / per_day));
+    double *scratch = nullptr, *dmean = nullptr, *dcov = nullptr;
+    if (const int rc_ = loo_alloc(tmp, &scratch, per_day * dblk, what)) return rc_;
+    if (const int rc_ = loo_alloc(tmp, &dmean, n_mean * 8, what)) return rc_;
+    if (want_cov) if (const int rc_ = loo_alloc(tmp, &dcov, n_cov * 8, what)) return rc_;
+    ScParams P{kept, n, n_days, S, 0, nchunks, dw, scratch, scratch + (size_t)dblk * n, scratch + (size_t)dblk * n + (size_t)dblk * nchunks * C, dmean, dcov};
+    const int NT = (C + 15) / 16;
+    HIP_TRY(hipEventRecord(e.a, st));
+    for (int d0 = 0; d0 < n_days; d0 += dblk) {
+      P.day0 = d0;
+      const dim3 grid((unsigned)std::min(dblk, n_days - d0), (unsigned)nchunks);
+      hipLaunchKernelGGL(k_sc_nat, grid, dim3(SC_THREADS), 0, st, P);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_sc_sum, grid, dim3(SC_THREADS), 0, st, P);
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_sc_finish_mean, dim3(grid.x), dim3(64), 0, st, P);
+      HIP_TRY(hipGetLastError());
+      if (!want_cov) continue;
+      switch (NT) {
+        case 1: hipLaunchKernelGGL(k_sc_gram<1>, grid, dim3(SC_THREADS), 0, st, P); break;
+        case 2: hipLaunchKernelGGL(k_sc_gram<2>, grid, dim3(SC_THREADS), 0, st, P); break;
+        case 3: hipLaunchKernelGGL(k_sc_gram<3>, grid, dim3(SC_THREADS), 0, st, P); break;
+        default: hipLaunchKernelGGL(k_sc_gram<4>, grid, dim3(SC_THREADS), 0, st, P); break;
+      }
+      HIP_TRY(hipGetLastError());
+      hipLaunchKernelGGL(k_sc_finish_cov, dim3(grid.x), dim3(SC_THREADS), 0, st, P);
+      HIP_TRY(hipGetLastError());
+    }
+    HIP_TRY(hipEventRecord(e.b, st));
+    if (want_mean) HIP_TRY(hipMemcpyAsync(o.mean, dmean, n_mean * 8, hipMemcpyDeviceToHost, st));
+    if (want_cov) HIP_TRY(hipMemcpyAsync(o.cov, dcov, n_cov * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    float ms = 0.f;
+    if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) g_sc_ms[3] = ms;
+  }
+  // ---- counts: potus_outcomes' own counting of the kept draws
+  if (o.ev_hist || o.tipping || o.joint) {
+    if (n == 0) {
+      if (o.ev_hist) std::fill(o.ev_hist, o.ev_hist + (size_t)n_days * (ev_sum + 1), 0ll);
+      if (o.tipping) std::fill(o.tipping, o.tipping + (size_t)n_days * (S + 1), 0ll);
+      if (o.joint) std::fill(o.joint, o.joint + (size_t)n_days * (S + 2) * (S + 2), 0ll);
+    } else {
+      const double oc_ms = g_oc_ms[2];                               // (potus_outcomes_timing keeps speaking of the last potus_outcomes call)
+      const int rc = oc_count(st, kept, n, n_days, S, w, ev, ev_to_win, nullptr, ev_sum, OcOut{o.ev_hist, o.tipping, o.joint, nullptr, nullptr});
+      g_sc_ms[4] = g_oc_ms[2];
+      g_oc_ms[2] = oc_ms;
+      if (rc) return rc;
+    }
+  }
+  return 0;
+}
+} // namespace
+
+int potus_scenario_device(int device, const void *block, long long n_draws, int n_days, int S, const double *w, int cond_day, const double *lo, const double *hi,
+                          const int32_t *ev, int ev_to_win, long long *n_kept, double *mean, double *cov, long long *ev_hist, long long *tipping, long long *joint) {
+  const char *what = "potus_scenario_device";
+  if (!block || !w) return fail(POTUS_ERR_ARG, "%s: null block or weights", what);
+  if (n_draws < 1) return fail(POTUS_ERR_ARG, "%s: %lld draws (at least one)", what, n_draws);
+  if (n_draws > (1ll << 40)) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld draws (at most 2^40)", what, n_draws);
+  if (n_days < 1) return fail(POTUS_ERR_ARG, "%s: %d days (at least one)", what, n_days);
+  if (cond_day < 0 || cond_day >= n_days) return fail(POTUS_ERR_ARG, "%s: condition day %d of %d days", what, cond_day, n_days);
+  const ScOut o{n_kept, mean, cov, ev_hist, tipping, joint};
+  int ev_sum = 0;
+  if (const int rc_ = sc_check(what, S, lo, hi, ev, ev_to_win, o, &ev_sum)) return rc_;
+  for (int s = 0; s < S; s++) if (!std::isfinite(w[s])) return fail(POTUS_ERR_ARG, "%s: w[%d] is not finite", what, s);
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(POTUS_ERR_DEVICE, "%s: no HIP device %d", what, device);
+  DeviceGuard guard;
+  DeviceLocks lock(device);
+  HIP_TRY(hipSetDevice(device));
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, block) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
+    (void)hipGetLastError();
+    return fail(POTUS_ERR_ARG, "%s: the block is not device memory of GPU %d", what, device);
+  }
+  for (double &x : g_sc_ms) x = 0.0;
+  const double *items = (const double *)block;
+  return sc_compute(what, 0, items, n_draws, n_days, S, items + (size_t)cond_day * S, (long long)n_days * S, w, lo, hi, ev, ev_to_win, ev_sum, o);
+}
+
+// Pooled over the post-warm-up draws of every listed sampler, as potus_outcomes pools them, but in CANONICAL order: chain after chain in the
+// order the handles are listed, each chain's draws in iteration order (the row order of potus_extract_matrix) -- one k_oc_days launch per chain.
+int potus_scenario(const int *handles, int n_handles, int cond_day, const double *lo, const double *hi, int day_begin, int day_end, const int32_t *ev, int ev_to_win,
+                   long long *n_kept, long long *n_draws, double *mean, double *cov, long long *ev_hist, long long *tipping, long long *joint) {
+  const char *what = "potus_scenario";
+  if (!handles || n_handles < 1) return fail(POTUS_ERR_ARG, "%s: null handle list", what);
+  Pool P;
+  if (const int rc_ = P.resolve(handles, n_handles, what)) return rc_;
+  if (const int rc_ = P.same_posterior("a scenario pools the chains of one")) return rc_;
+  Sampler *s0 = P.s0;
+  const int S = s0->M.S, T = s0->M.T, TS = S * T;
+  if (day_begin < 0 || day_end > T || day_begin >= day_end) return fail(POTUS_ERR_ARG, "%s: days [%d, %d) of %d", what, day_begin, day_end, T);
+  if (cond_day < 0 || cond_day >= T) return fail(POTUS_ERR_ARG, "%s: condition day %d of %d days", what, cond_day, T);
+  const ScOut o{n_kept, mean, cov, ev_hist, tipping, joint};
+  int ev_sum = 0;
+  if (const int rc_ = sc_check(what, S, lo, hi, ev, ev_to_win, o, &ev_sum)) return rc_;
+  DeviceGuard guard;
+  DeviceLocks lock(P.devs);
+  if (const int rc_ = P.count()) return rc_;
+  std::vector<int> first(P.sps.size());
+  long long nd = 0;
+  for (size_t i = 0; i < P.sps.size(); i++) {
+    first[i] = warm_rows(P.sps[i], P.saved[i]);
+    nd += (long long)(P.saved[i] - first[i]) * P.sps[i]->R.chains;
+  }
+  if (nd < 1) return fail(POTUS_ERR_STATE, "%s needs at least one saved post-warm-up draw (%lld rows saved, all of them warm-up)", what, P.draws);
+  const int n_days = day_end - day_begin;
+  const bool cond_apart = lo && (cond_day < day_begin || cond_day >= day_end);   // the condition day as a one-day block of its own
+  const int col_end = s0->L.ncols, col_begin = col_end - TS;   // predicted_score = the generated-quantities block
+  HIP_TRY(hipSetDevice(s0->device));
+  DevBufs tmp;
+  double *items = nullptr, *citems = nullptr;
+  if (const int rc_ = loo_alloc(tmp, &items, (size_t)nd * n_days * S * 8, what)) return rc_;
+  if (cond_apart) if (const int rc_ = loo_alloc(tmp, &citems, (size_t)nd * S * 8, what)) return rc_;
+  for (double &x : g_sc_ms) x = 0.0;
+  long long row0 = 0;
+  for (size_t i = 0; i < P.sps.size(); i++) {
+    Sampler *sp = P.sps[i];
+    const int n_saved = P.saved[i], C = sp->R.chains;
+    const long long rows = n_saved - first[i];   // per chain
+    if (rows == 0) continue;
+    const size_t bytes = (size_t)n_saved * C * TS * 8;
+    DevBufs blkbuf;
+    double *blk = nullptr;
+    if (const int rc_ = loo_alloc(blkbuf, &blk, bytes, what)) return rc_;
+    const double t0 = dn_now();
+    if (const int rc = gather_block(s0, sp, bytes, blk, [&](double *out) { return write_array_range(sp, n_saved, col_begin, col_end, out, true, TS); })) return rc;
+    const double t1 = dn_now();
+    // chain c of the handle: its post-warm-up rows are C rows apart in the block
+    for (int c = 0; c < C; c++, row0 += rows) {
+      const double *src = blk + ((size_t)first[i] * C + c) * TS;
+      const unsigned gy = (unsigned)std::min<long long>(rows, 32768);
+      hipLaunchKernelGGL(k_oc_days, dim3((n_days + 63) / 64, gy), dim3(256), 0, s0->stream, src, (long long)C * TS, items + (size_t)row0 * n_days * S, rows, T, S, day_begin, day_end);
+      HIP_TRY(hipGetLastError());
+      if (cond_apart) {
+        hipLaunchKernelGGL(k_oc_days, dim3(1, gy), dim3(256), 0, s0->stream, src, (long long)C * TS, citems + (size_t)row0 * S, rows, T, S, cond_day, cond_day + 1);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+    HIP_TRY(hipStreamSynchronize(s0->stream));
+    g_sc_ms[0] += t1 - t0; g_sc_ms[1] += dn_now() - t1;
+  }
+  if (n_draws) *n_draws = nd;
+  const double *cond = cond_apart ? citems : items + (size_t)(cond_day - day_begin) * S;
+  return sc_compute(what, s0->stream, items, nd, n_days, S, lo ? cond : nullptr, cond_apart ? (long long)S : (long long)n_days * S, s0->h_w.data(), lo, hi, ev, ev_to_win,
+                    ev_sum, o);
+}
+
+int potus_scenario_timing(double *ms) {
+  if (!ms) return fail(POTUS_ERR_ARG, "potus_scenario_timing: null output");
+  for (int i = 0; i < 5; i++) ms[i] = g_sc_ms[i];
+  return 0;
+}
+
 // SURVEY 8(f4), "online R-hat-based early stop": the diagnostics of lp__ and mu_b[:, T] (the columns bench.py's ESS / s is defined on;
 // predicted_score[T, :] is their inverse logit) over the post-warm-up draws saved SO FAR by the pooled chains of the handles.  The host loop
 // that advances the sampler in chunks of `refresh` transitions may stop once *converged is set; nothing the sampler does depends on it (same
@@ -4531,6 +4768,29 @@ void potus_R_outcomes(int *handles, int *n_handles, int *iopts /*[4]: day_begin,
   for (size_t i = 0; i < j.size(); i++) joint[i] = (double)j[i];
   if (iopts[3]) for (size_t i = 0; i < b.size(); i++) below_actual[i] = (double)b[i];
   *n_draws = (double)n;
+}
+
+// counts come back as doubles; n[2] = n_kept, n_draws.  iopts[5], [6] say which outputs are wanted: the others are left alone
+void potus_R_scenario(int *handles, int *n_handles, int *iopts /*[7]: cond_day, day_begin, day_end, ev_to_win, bounds given, moments wanted, counts wanted*/,
+                      double *lo, double *hi, int *ev, double *n, double *mean, double *cov, double *ev_hist, double *tipping, double *joint, int *status) {
+  Sampler *sp = (handles && *n_handles >= 1) ? get(handles[0]) : nullptr;
+  if (!sp) { *status = fail(POTUS_ERR_STATE, "potus_R_scenario: bad handle"); return; }
+  const int S = sp->M.S;
+  const bool counts = iopts[6] != 0 && ev != nullptr;
+  if (iopts[6] && !ev) { *status = fail(POTUS_ERR_ARG, "potus_R_scenario: ev is null, but the counts are asked for"); return; }
+  const size_t days = iopts[2] > iopts[1] ? (size_t)(iopts[2] - iopts[1]) : 0;
+  long long sum = 0;
+  if (counts) for (int s = 0; s < S; s++) sum += ev[s] > 0 ? ev[s] : 0;
+  std::vector<long long> h, t, j;
+  if (counts) { h.resize(days * (size_t)(sum <= OC_EV_CAP ? sum + 1 : 0)); t.resize(days * (size_t)(S + 1)); j.resize(days * (size_t)(S + 2) * (S + 2)); }
+  long long nk = 0, nd = 0;
+  *status = potus_scenario(handles, *n_handles, iopts[0], iopts[4] ? lo : nullptr, iopts[4] ? hi : nullptr, iopts[1], iopts[2], counts ? ev : nullptr, iopts[3], &nk, &nd,
+                           iopts[5] ? mean : nullptr, iopts[5] ? cov : nullptr, counts ? h.data() : nullptr, counts ? t.data() : nullptr, counts ? j.data() : nullptr);
+  if (*status) return;
+  for (size_t i = 0; i < h.size(); i++) ev_hist[i] = (double)h[i];
+  for (size_t i = 0; i < t.size(); i++) tipping[i] = (double)t[i];
+  for (size_t i = 0; i < j.size(); i++) joint[i] = (double)j[i];
+  n[0] = (double)nk; n[1] = (double)nd;
 }
 
 } // extern "C"

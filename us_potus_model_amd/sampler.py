@@ -109,6 +109,12 @@ def load_library():
         L.potus_monitor.argtypes = [ip, C.c_int, C.c_int, C.c_int, dp, C.c_int, dp]
         L.potus_monitor_device.argtypes = [C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int, dp, C.c_int, dp]
         L.potus_R_monitor.argtypes = [ip, ip, ip, dp, ip, dp, ip]
+    if hasattr(L, "potus_scenario"):                    # conditional forecasts and the covariance of the state scores (scenario.py)
+        i32p, llp = C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
+        L.potus_scenario.argtypes = [ip, C.c_int, C.c_int, dp, dp, C.c_int, C.c_int, i32p, C.c_int, llp, llp, dp, dp, llp, llp, llp]
+        L.potus_scenario_device.argtypes = [C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int, dp, C.c_int, dp, dp, i32p, C.c_int, llp, dp, dp, llp, llp, llp]
+        L.potus_scenario_timing.argtypes = [dp]
+        L.potus_R_scenario.argtypes = [ip, ip, ip, dp, dp, ip, dp, dp, dp, dp, dp, dp, ip]
     _LIB = L
     return L
 
@@ -124,9 +130,10 @@ EXPORTS = [
     "potus_log_lik_device", "potus_loo_device", "potus_loo",
     "potus_outcomes", "potus_outcomes_device", "potus_outcomes_timing",
     "potus_monitor", "potus_monitor_device",
+    "potus_scenario", "potus_scenario_device", "potus_scenario_timing",
     "potus_R_create", "potus_R_init", "potus_R_run", "potus_R_run_many", "potus_R_num_columns", "potus_R_saved_count",
     "potus_R_write_array", "potus_R_write_stan_csv", "potus_R_posterior_summary", "potus_R_diagnostics", "potus_R_check_convergence", "potus_R_backtest_scores", "potus_R_last_error", "potus_R_destroy",
-    "potus_R_set_datasets", "potus_R_simulate_prior", "potus_R_sbc_ranks", "potus_R_constrain", "potus_R_loo", "potus_R_outcomes", "potus_R_monitor",
+    "potus_R_set_datasets", "potus_R_simulate_prior", "potus_R_sbc_ranks", "potus_R_constrain", "potus_R_loo", "potus_R_outcomes", "potus_R_monitor", "potus_R_scenario",
 ]
 
 
@@ -404,6 +411,11 @@ class Handle:
         from .outcomes import outcomes
         return outcomes([self], ev, actual=actual, days=days, ev_to_win=ev_to_win)
 
+    def scenario(self, ev=None, given=None, day=-1, days=None, ev_to_win=270, states=None):
+        """Mean, covariance and joint outcomes of this handle's post-warm-up draws that meet a condition (us_potus_model_amd.scenario)."""
+        from .scenario import scenario
+        return scenario([self], ev=ev, given=given, day=day, days=days, ev_to_win=ev_to_win, states=states)
+
     def monitor(self, pars=None, cols=None, probs=(0.025, 0.25, 0.5, 0.75, 0.975)):
         """The summary table of this handle's post-warm-up draws: mean, sd, mad, mcse, R-hat, ESS, quantiles (us_potus_model_amd.monitor)."""
         from .monitor import monitor
@@ -587,6 +599,11 @@ class StanFit:
         """EV histogram, tipping point, joint win counts and p-values over every chain of the fit, on the device (us_potus_model_amd.outcomes)."""
         from .outcomes import outcomes
         return outcomes(self._hs, ev, actual=actual, days=days, ev_to_win=ev_to_win)
+
+    def scenario(self, ev=None, given=None, day=-1, days=None, ev_to_win=270, states=None):
+        """The forecast given an event, and the covariance / correlation of the state scores, over every chain of the fit (us_potus_model_amd.scenario)."""
+        from .scenario import scenario
+        return scenario(self._hs, ev=ev, given=given, day=day, days=days, ev_to_win=ev_to_win, states=states)
 
     def monitor(self, pars=None, cols=None, probs=(0.025, 0.25, 0.5, 0.75, 0.975)):
         """fit$summary() / print(stanfit) / rstan::monitor over every chain of the fit, on the device (us_potus_model_amd.monitor)."""
