@@ -4,6 +4,7 @@ fixtures.  Floating point, so tolerances are stated: log density 1e-11 relative;
 
 Both device paths are covered: cus_per_chain = 1 (one workgroup per chain, potus_model.hpp /
 potus_nuts.hpp) and clusters of 8 and 16 workgroups per chain (potus_cluster.hpp)."""
+import functools
 from pathlib import Path
 
 import numpy as np
@@ -59,29 +60,49 @@ EDGE_SHAPES = {
 }
 
 
+EDGE_ROWS = 12
+
+
+@functools.lru_cache(maxsize=None)
+def _edge_reference(shape, variant):
+    """The oracle's side of test_edge_shapes_match_the_oracle, once per shape and variant for the three device paths: the data, three points with
+    their log density and gradient, the first EDGE_ROWS warm-up transitions of two chains.  On the oracle, transitions 2 to 4 of such designs are
+    one-leapfrog divergent rejections, so the rows compared must reach real trees: a non-divergent transition of depth >= 5 in each chain."""
+    from us_potus_model_amd import synthetic
+    data = synthetic.make(seed=3, variant=variant, **EDGE_SHAPES[shape])
+    m = OracleModel(data, variant)
+    q = np.random.default_rng(1).uniform(-2, 2, (3, m.D))
+    lpg = [m.log_prob_grad(qi) for qi in q]
+    o = m.default_opts(num_warmup=EDGE_ROWS, num_samples=0, save_warmup=1, seed=3, fast_grad=1)
+    chains = [m.sample_chain(c + 1, o)[0] for c in (0, 1)]
+    for c, ref in enumerate(chains):
+        assert ((ref[:, 3] >= 5) & (ref[:, 5] == 0)).any(), (shape, variant, c, ref[:, 3:6])
+    for a in (q, *chains, *(g for _, g in lpg)):
+        a.setflags(write=False)
+    return data, q, lpg, chains
+
+
 @pytest.mark.parametrize("cus", [1, 8, 16])
 @pytest.mark.parametrize("variant", ["full", "no_mode_adjustment"])
 @pytest.mark.parametrize("shape", list(EDGE_SHAPES))
 def test_edge_shapes_match_the_oracle(shape, variant, cus):
     """Empty and ragged inputs: no national / no state polls, a single state, two days (members without days),
-    a single pollster, campaigns where most days have no poll, the largest S a wave holds."""
-    from us_potus_model_amd import synthetic
-    data = synthetic.make(seed=3, variant=variant, **EDGE_SHAPES[shape])
-    h = Handle(data, variant, chains=2, num_warmup=10, num_samples=0, save_warmup=1, seed=3, cus_per_chain=cus)
-    m = OracleModel(data, variant)
-    q = np.random.default_rng(1).uniform(-2, 2, (3, h.D))
+    a single pollster, campaigns where most days have no poll, the largest S a wave holds.  Twelve transitions, so that trees of depth 5 and
+    more are compared (_edge_reference); a chain that leaves the oracle's on a 13th digit before row 12 is replayed transition by
+    transition from its own previous row instead (adaptation_replay.py), with the same tolerances."""
+    data, q, lpg, chains = _edge_reference(shape, variant)
+    h = Handle(data, variant, chains=2, num_warmup=EDGE_ROWS, num_samples=0, save_warmup=1, seed=3, cus_per_chain=cus)
     lp, g = h.log_prob_grad(q)
-    for i in range(3):
-        lpo, go = m.log_prob_grad(q[i])
+    for i, (lpo, go) in enumerate(lpg):
         assert abs(lp[i] - lpo) <= LP_RTOL * max(1.0, abs(lpo)), (i, lp[i], lpo)
         assert np.abs(g[i] - go).max() <= GRAD_RTOL * np.abs(go).max(), i
-    h.init(); h.run(4)
+    h.init(); h.run(EDGE_ROWS)
     d = h.draws()
-    o = m.default_opts(num_warmup=10, num_samples=0, save_warmup=1, seed=3, fast_grad=1)
-    for c in (0, 1):
-        ref = m.sample_chain(c + 1, o)[0][:4]
-        assert np.array_equal(d[c][:4, 3:6], ref[:, 3:6]), (c, d[c][:4, :7], ref[:, :7])
-        assert np.allclose(d[c][:4, 7:], ref[:, 7:], rtol=1e-6, atol=1e-7)
+    for c, ref in enumerate(chains):
+        if np.array_equal(d[c][:, 3:6], ref[:, 3:6]) and np.allclose(d[c][:, 7:], ref[:, 7:], rtol=1e-6, atol=1e-7):
+            continue
+        print(f"{shape} {variant} K={cus} chain {c + 1}: out of step with the oracle's chain; replaying every row from the device's previous one")
+        _adaptation_replayed_from_the_device_rows(data, variant, h, c, 3, [(0, EDGE_ROWS)])
     h.close()
 
 

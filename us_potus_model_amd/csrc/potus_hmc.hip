@@ -1600,7 +1600,24 @@ int build_cluster(Sampler *sp, const potus_data *d, int K) {
   // = 16 mod 32 doubles (the four rows a wave reads per MFMA step fall on disjoint LDS banks)
   // -- for poll-dense posteriors (more than 8 polls per day: the dense product then beats the walk over the polls, measured in
   // profiles/r03_cl_mfma_adjoint.txt; the reference's own posteriors have 4-6 and keep the walk); POTUS_CL_MFMA = 0 / 1 overrides
-  const bool mfma = DW == 4 && (getenv("POTUS_CL_MFMA") ? atoi(getenv("POTUS_CL_MFMA")) != 0 : Np > 8 * T);
+  // The choice by poll density is a matter of speed only: where a member is beyond what the adjoint scatter addresses (1023 polls, 63 polls
+  // of one state on one day, CL_CELLS_PER_THREAD x PT_THREADS polled cells) the walk runs the same data.  Forced on (POTUS_CL_MFMA = 1), such
+  // a member is refused below.
+  auto scatter_holds_every_member = [&]() {
+    for (int m = 0; m < K; m++) {
+      const int p0 = dp[cut[m]], np = dp[cut[m + 1]] - p0;
+      if (np >= 1024) return false;
+      int ncell = 0;
+      for (int il = 0; il < np;) {
+        int j = il + 1;
+        while (j < np && sp->h_pt[p0 + j] == sp->h_pt[p0 + il] && sp->h_ps[p0 + j] == sp->h_ps[p0 + il]) j++;
+        if (j - il > 63 || ++ncell > CL_CELLS_PER_THREAD * PT_THREADS) return false;
+        il = j;
+      }
+    }
+    return true;
+  };
+  const bool mfma = DW == 4 && (getenv("POTUS_CL_MFMA") ? atoi(getenv("POTUS_CL_MFMA")) != 0 : Np > 8 * T && scatter_holds_every_member());
   const int GS = 48, GROWS = 4 * ((M.SE + 3) / 4);
   if (mfma) sp->cl_dw = 12;
   std::vector<int> part((size_t)K * CP_N, 0), sched, perm;   // perm: internal index -> Stan index, -1 for padding
