@@ -710,10 +710,10 @@ def test_pooled_entry_points_accept_and_refuse_the_same_handle_lists(cases):
     (b on `second_device()`), `g` the other variant (another number of columns), `o` other poll counts (same columns), `short` the posterior of
     `a` with fewer saved draws, `few` fewer than four.  [a, b] is pooled; [a, a] is refused as listed twice, [a, g] and [a, o] as another
     posterior (potus_extract_matrix only looks at the number of columns, in its own words), [a, short] for its unequal counts except by the
-    summary, which pools whatever is saved; potus_check_convergence says "not yet" before it looks at the list while the first handle holds
+    summary, the outcomes and the scenario, which pool whatever is saved; potus_check_convergence says "not yet" before it looks at the list while the first handle holds
     fewer than four draws.  (PSIS-LOO's own refusals: tests/test_gpu_loo.py.)"""
     from conftest import second_device
-    from us_potus_model_amd import check_convergence, device_diagnostics, loo as loo_mod, synthetic
+    from us_potus_model_amd import check_convergence, device_diagnostics, loo as loo_mod, monitor as monitor_mod, outcomes as outcomes_mod, scenario as scenario_mod
     from us_potus_model_amd.sampler import PotusError
     data, variant = cases["small_full"]
     kw = dict(num_warmup=30, num_samples=20, seed=11, cus_per_chain=1, twin=0)
@@ -741,7 +741,8 @@ def test_pooled_entry_points_accept_and_refuse_the_same_handle_lists(cases):
         return out
 
     calls = {"extract": extract, "summary": lambda hs: posterior_summary(hs, np.ones(S)), "diagnostics": lambda hs: device_diagnostics(hs, 0, 3),
-             "check_convergence": check_convergence, "loo": loo_mod.loo}
+             "check_convergence": check_convergence, "loo": loo_mod.loo, "monitor": lambda hs: monitor_mod.monitor(hs, cols=(0, 3)),
+             "outcomes": lambda hs: outcomes_mod.outcomes(hs, np.ones(S)), "scenario": scenario_mod.scenario}
     for name, call in calls.items():
         call([a, b])
         with pytest.raises(PotusError, match="twice"):
@@ -753,7 +754,7 @@ def test_pooled_entry_points_accept_and_refuse_the_same_handle_lists(cases):
         else:
             with pytest.raises(PotusError, match="another posterior"):
                 call([a, o])
-        if name == "summary":
+        if name in ("summary", "outcomes", "scenario"):
             call([a, short])                                           # 2 x 20 + 2 x 10 draws
         else:
             with pytest.raises(PotusError, match="libpotus_hmc error 4.*saved"):
@@ -765,6 +766,50 @@ def test_pooled_entry_points_accept_and_refuse_the_same_handle_lists(cases):
         device_diagnostics([few], 0, 3)
     for h in (a, b, g, o, short, few):
         h.close()
+
+
+@pytest.mark.gpu
+def test_device_entry_points_refuse_what_is_not_their_device_memory():
+    """The *_device entry points that take a block of the caller's and a device number, with the smallest valid arguments and no sampler: a
+    block in device memory of the named GPU is taken; a host pointer (a NumPy array's), a device number past the last GPU and, where there
+    are two GPUs, a block of the other one are refused -- each before anything is launched, so no kernel ever sees such a pointer."""
+    import torch
+    from conftest import gpu_count
+    L = sampler.load_library()
+    LLP, I32P = C.POINTER(C.c_longlong), C.POINTER(C.c_int32)
+    rng = np.random.default_rng(5)
+    cols = rng.normal(size=(8, 2, 3))                                  # [draws, chains, columns]
+    ll = rng.normal(-3.0, 0.7, (3, 2, 8))                              # [polls, chains, draws]
+    items = rng.uniform(0.3, 0.7, (8, 1, 3))                           # [draws, days, states]
+    w, ev, probs = np.full(3, 1.0 / 3), np.array([3, 4, 5], dtype=np.int32), np.array([0.5])
+    out = np.zeros(64)
+    nk = C.c_longlong(0)
+    o, o2 = out[:32].ctypes.data_as(DP), out[32:].ctypes.data_as(DP)
+    calls = {
+        "potus_diagnostics_device": (cols, lambda dev, p: L.potus_diagnostics_device(dev, p, 8, 2, 3, o, o2)),
+        "potus_monitor_device": (cols, lambda dev, p: L.potus_monitor_device(dev, p, 8, 2, 3, probs.ctypes.data_as(DP), 1, o)),
+        "potus_loo_device": (ll, lambda dev, p: L.potus_loo_device(dev, p, 3, 2, 8, None, o, o2)),
+        "potus_outcomes_device": (items, lambda dev, p: L.potus_outcomes_device(dev, p, 8, 1, 3, w.ctypes.data_as(DP), ev.ctypes.data_as(I32P), 7, None,
+                                                                                 None, None, None, None, out.ctypes.data_as(LLP))),
+        "potus_scenario_device": (items, lambda dev, p: L.potus_scenario_device(dev, p, 8, 1, 3, w.ctypes.data_as(DP), 0, None, None, None, 7, C.byref(nk),
+                                                                                 o, None, None, None, None)),
+    }
+
+    def message():
+        buf = C.create_string_buffer(512)
+        L.potus_last_error(buf, 512)
+        return buf.value.decode()
+    for name, (host, call) in calls.items():
+        host = np.ascontiguousarray(host)
+        here = torch.tensor(host, device="cuda:0")
+        torch.cuda.synchronize()
+        assert call(0, C.c_void_p(here.data_ptr())) == 0, (name, message())
+        assert call(0, C.c_void_p(host.ctypes.data)) == 1 and "not device memory" in message() and name in message()
+        assert call(gpu_count(), C.c_void_p(here.data_ptr())) == 2 and "no HIP device" in message() and name in message()   # POTUS_ERR_DEVICE
+        if gpu_count() >= 2:
+            there = torch.tensor(host, device="cuda:1")
+            torch.cuda.synchronize()
+            assert call(0, C.c_void_p(there.data_ptr())) == 1 and "not device memory" in message()
 
 
 @pytest.mark.gpu

@@ -1295,18 +1295,39 @@ constexpr int POTUS_MAX_DEVICES = 64;
 std::mutex g_device_mu[POTUS_MAX_DEVICES];
 struct DeviceLocks {
   std::vector<std::unique_lock<std::mutex>> held;
-  explicit DeviceLocks(std::vector<int> devs) {
+  DeviceLocks() {}
+  explicit DeviceLocks(std::vector<int> devs) { take(std::move(devs)); }
+  explicit DeviceLocks(int dev) { take({dev}); }
+  void take(std::vector<int> devs) {
     std::sort(devs.begin(), devs.end());
     devs.erase(std::unique(devs.begin(), devs.end()), devs.end());
     for (int d : devs) held.emplace_back(g_device_mu[std::min(std::max(d, 0), POTUS_MAX_DEVICES - 1)]);
   }
-  explicit DeviceLocks(int dev) : DeviceLocks(std::vector<int>{dev}) {}
 };
 // the caller's HIP device is put back on every return path (the library works on the handles' devices)
 struct DeviceGuard {
   int prev = -1;
   DeviceGuard() { if (hipGetDevice(&prev) != hipSuccess) prev = -1; }
   ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
+};
+// What a *_device entry point works on: a block of the caller's in the memory of GPU `device`.  Declared on the entry point's stack once every check
+// that needs no device has passed; open() names the device, locks it, makes it current and refuses a pointer that is not that GPU's memory --
+// a kernel handed a host pointer, or another GPU's without peer access, is a memory fault.  The lock goes and the caller's device comes back with the object.
+struct DeviceBlock {
+  DeviceGuard guard;
+  DeviceLocks lock;
+  int open(const char *what, int device, const void *ptr, const char *ptr_name = "block") {
+    int ndev = 0;
+    if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(POTUS_ERR_DEVICE, "%s: no HIP device %d", what, device);
+    lock.take({device});
+    HIP_TRY(hipSetDevice(device));
+    hipPointerAttribute_t at;
+    if (hipPointerGetAttributes(&at, ptr) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
+      (void)hipGetLastError();
+      return fail(POTUS_ERR_ARG, "%s: the %s is not device memory of GPU %d", what, ptr_name, device);
+    }
+    return 0;
+  }
 };
 
 Sampler *get(int h) {
@@ -1333,6 +1354,12 @@ struct DevBufs {
     if (e == hipSuccess) v.push_back(q);
     *p = static_cast<T *>(q);
     return e;
+  }
+  // ... for the analysis calls: a refusal that names the caller and the size
+  template <class T> int get(T **p, size_t bytes, const char *what) {
+    if (alloc(p, bytes) == hipSuccess) return 0;
+    (void)hipGetLastError();
+    return fail(POTUS_ERR_DEVICE, "%s: hipMalloc of %zu bytes (%.1f MB) failed", what, bytes, bytes / 1048576.0);
   }
 };
 
@@ -2422,6 +2449,13 @@ int pool_transpose(Sampler *s0, const double *blk, double *cols, int n_post, int
   return 0;
 }
 
+// dynamic LDS of the kernels that sort a column of n items in runs (k_dg_column, k_mn_column, k_loo_psis): the keys and the indices of one run
+size_t sorted_run_lds(long long n) {
+  int npad = 1;
+  while (npad < n && npad < DG_RUN) npad <<= 1;
+  return (size_t)npad * 12;
+}
+
 } // namespace
 
 // ======================================================================== C ABI
@@ -3183,9 +3217,9 @@ static int write_array_range(Sampler *sp, int n_saved, int col_begin, int col_en
   const int grid = std::min(ndraw, 512);
   DevBufs tmp;
   double *scratch = nullptr, *dout = nullptr;
-  HIP_TRY(tmp.alloc(&scratch, (size_t)grid * sp->L.ncols * 8));
+  if (const int rc_ = tmp.get(&scratch, (size_t)grid * sp->L.ncols * 8, "potus_write_array")) return rc_;
   if (device_out) dout = out;
-  else HIP_TRY(tmp.alloc(&dout, (size_t)ndraw * nsel * 8));
+  else if (const int rc_ = tmp.get(&dout, (size_t)ndraw * nsel * 8, "potus_write_array")) return rc_;
   WAParams W{sp->R.draws, sp->R.chains, sp->R.n_save_max, n_saved, sp->R.row, sp->L.ncols, col_begin, col_end, scratch, dout, sp->sigma_ns, sp->sigma_nn, out_stride};
   hipLaunchKernelGGL(k_write_array, dim3(grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, W);
   HIP_TRY(hipGetLastError());
@@ -3254,9 +3288,9 @@ int potus_extract_matrix(const int *handles, int n_handles, int col_begin, int c
     HIP_TRY(hipSetDevice(sp->device));
     DevBufs tmp;
     double *rowsd = nullptr, *colsd = nullptr;
-    HIP_TRY(tmp.alloc(&rowsd, (size_t)nrow * nsel * 8)); HIP_TRY(tmp.alloc(&colsd, (size_t)nrow * nsel * 8));
-    const int rc = write_array_range(sp, saved[i], col_begin, col_end, rowsd, true);
-    if (rc) return rc;
+    int rc;
+    if ((rc = tmp.get(&rowsd, (size_t)nrow * nsel * 8, P.what)) || (rc = tmp.get(&colsd, (size_t)nrow * nsel * 8, P.what))) return rc;
+    if ((rc = write_array_range(sp, saved[i], col_begin, col_end, rowsd, true))) return rc;
     hipLaunchKernelGGL(k_rows_to_r_matrix, dim3((unsigned)((nrow + 31) / 32), (unsigned)((nsel + 31) / 32)), dim3(256), 0, sp->stream, rowsd, colsd, saved[i], sp->R.chains, nsel);
     HIP_TRY(hipGetLastError());
     // column k of this handle's block -> rows [off, off + nrow) of column k of the result
@@ -3273,13 +3307,8 @@ int potus_write_array_device(int handle, int col_begin, int col_end, void *out_d
   Sampler *sp = get(handle);
   if (!sp || !out_device) return fail(POTUS_ERR_STATE, "bad handle or null output");
   if (const int rc_ = check_cols(sp, col_begin, col_end)) return rc_;
-  DeviceLocks lock(sp->device);
-  HIP_TRY(hipSetDevice(sp->device));
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, out_device) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != sp->device) {
-    (void)hipGetLastError();
-    return fail(POTUS_ERR_ARG, "potus_write_array_device: the output is not device memory of GPU %d", sp->device);
-  }
+  DeviceBlock dev;
+  if (const int rc_ = dev.open("potus_write_array_device", sp->device, out_device, "output")) return rc_;
   int n_saved = 0, rc = saved_count(sp, &n_saved);
   if (rc) return rc;
   return write_array_range(sp, n_saved, col_begin, col_end, (double *)out_device, true);
@@ -3305,19 +3334,18 @@ int potus_posterior_summary_many(const int *handles, int n_handles, const double
   HIP_TRY(hipSetDevice(s0->device));
   DevBufs tmp;
   double *full = nullptr, *cols = nullptr, *dw = nullptr, *dev_ = nullptr, *dout = nullptr, *scr = nullptr;
-  HIP_TRY(tmp.alloc(&full, (size_t)nd * NC * 8));
-  HIP_TRY(tmp.alloc(&cols, (size_t)nd * NC * 8));
-  HIP_TRY(tmp.alloc(&dw, (size_t)S * 8)); HIP_TRY(tmp.alloc(&dev_, (size_t)S * 8));
-  HIP_TRY(tmp.alloc(&dout, ((size_t)TS * 4 + (size_t)T * 9) * 8));
+  int rc;
+  if ((rc = tmp.get(&full, (size_t)nd * NC * 8, P.what)) || (rc = tmp.get(&cols, (size_t)nd * NC * 8, P.what))) return rc;
+  if ((rc = tmp.get(&dw, (size_t)S * 8, P.what)) || (rc = tmp.get(&dev_, (size_t)S * 8, P.what))) return rc;
+  if ((rc = tmp.get(&dout, ((size_t)TS * 4 + (size_t)T * 9) * 8, P.what))) return rc;
   long long row0 = 0;
   for (int i = 0; i < n_handles; i++) {
     Sampler *sp = P.sps[i];
     const int n_saved = P.saved[i];
     const long long rows = (long long)n_saved * sp->R.chains;
     if (rows == 0) continue;
-    const int rc = gather_block(s0, sp, (size_t)rows * NC * 8, full + (size_t)row0 * NC,
-                                [&](double *out) { return write_array_range(sp, n_saved, col_begin, col_end, out, true, NC); });
-    if (rc) return rc;
+    if ((rc = gather_block(s0, sp, (size_t)rows * NC * 8, full + (size_t)row0 * NC,
+                           [&](double *out) { return write_array_range(sp, n_saved, col_begin, col_end, out, true, NC); }))) return rc;
     row0 += rows;
   }
   HIP_TRY(hipMemcpyAsync(dw, s0->h_w.data(), (size_t)S * 8, hipMemcpyHostToDevice, s0->stream));
@@ -3331,7 +3359,7 @@ int potus_posterior_summary_many(const int *handles, int n_handles, const double
   while (npad < nd && npad < PS_RUN) npad <<= 1;
   const size_t lds = (size_t)npad * 8;
   const int grid = std::min(NC, 1024);
-  if (nd > PS_RUN) HIP_TRY(tmp.alloc(&scr, (size_t)grid * (size_t)nd * 8));
+  if (nd > PS_RUN && (rc = tmp.get(&scr, (size_t)grid * (size_t)nd * 8, P.what))) return rc;
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_col_summary), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   double *o_state = dout, *o_natl = dout + (size_t)TS * 4, *o_ev = o_natl + (size_t)T * 4;
   hipLaunchKernelGGL(k_col_summary, dim3(grid), dim3(PS_THREADS), lds, s0->stream, (const double *)cols, scr, nd, T, S, o_state, o_natl, o_ev);
@@ -3351,7 +3379,8 @@ int potus_posterior_summary(int handle, const double *ev, double *state_out, dou
 namespace {
 // cols [NC][C][n] on the current device -> rhat / bulk ESS per column (host arrays)
 int diagnostics_of_columns(hipStream_t stream, const double *cols, long long n, int C, int NC, double *rhat_out, double *ess_out) {
-  if (2 * C > DG_MAXCH) return fail(POTUS_ERR_UNSUPPORTED, "potus_diagnostics: %d chains pooled (at most %d)", C, DG_MAXCH / 2);
+  const char *what = "potus_diagnostics";
+  if (2 * C > DG_MAXCH) return fail(POTUS_ERR_UNSUPPORTED, "%s: %d chains pooled (at most %d)", what, C, DG_MAXCH / 2);
   const long long N = 2ll * C * (n / 2);
   DevBufs tmp;
   double *zbuf = nullptr, *dout = nullptr;
@@ -3361,12 +3390,11 @@ int diagnostics_of_columns(hipStream_t stream, const double *cols, long long n, 
   // capped so that the scratch of a call stays within 768 MB whatever the number of pooled draws (a workgroup loops over columns)
   const long long per_wg = std::max<long long>(N, 1) * (16 + (N > DG_RUN ? 12 : 0));
   const int grid = (int)std::max<long long>(1, std::min<long long>(std::min(NC, 1024), (768ll << 20) / per_wg));
-  HIP_TRY(tmp.alloc(&zbuf, (size_t)grid * 2 * (size_t)std::max<long long>(N, 1) * 8));
-  if (N > DG_RUN) { HIP_TRY(tmp.alloc(&rkey, (size_t)grid * (size_t)N * 8)); HIP_TRY(tmp.alloc(&ridx, (size_t)grid * (size_t)N * 4)); }
-  HIP_TRY(tmp.alloc(&dout, (size_t)NC * 2 * 8));
-  int npad = 1;
-  while (npad < N && npad < DG_RUN) npad <<= 1;
-  const size_t lds = (size_t)npad * 12;                // keys + split indices
+  int rc;
+  if ((rc = tmp.get(&zbuf, (size_t)grid * 2 * (size_t)std::max<long long>(N, 1) * 8, what))) return rc;
+  if (N > DG_RUN && ((rc = tmp.get(&rkey, (size_t)grid * (size_t)N * 8, what)) || (rc = tmp.get(&ridx, (size_t)grid * (size_t)N * 4, what)))) return rc;
+  if ((rc = tmp.get(&dout, (size_t)NC * 2 * 8, what))) return rc;
+  const size_t lds = sorted_run_lds(N);                // keys + split indices
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dg_column), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   DgParams P{cols, zbuf, rkey, ridx, dout, dout + NC, n, C, NC};
   hipLaunchKernelGGL(k_dg_column, dim3(grid), dim3(DG_THREADS), lds, stream, P);
@@ -3381,14 +3409,11 @@ int diagnostics_of_columns(hipStream_t stream, const double *cols, long long n, 
 int potus_diagnostics_device(int device, const void *block, long long n_draws, int n_chains, int n_cols, double *rhat_out, double *ess_bulk_out) {
   if (!block || !rhat_out || !ess_bulk_out || n_draws < 1 || n_chains < 1 || n_cols < 1) return fail(POTUS_ERR_ARG, "potus_diagnostics_device: bad argument");
   if (2 * n_chains > DG_MAXCH) return fail(POTUS_ERR_UNSUPPORTED, "potus_diagnostics_device: %d chains pooled (at most %d)", n_chains, DG_MAXCH / 2);   // before anything is allocated
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(POTUS_ERR_DEVICE, "potus_diagnostics_device: no HIP device %d", device);
-  DeviceGuard guard;
-  DeviceLocks lock(device);
-  HIP_TRY(hipSetDevice(device));
+  DeviceBlock dev;
+  if (const int rc_ = dev.open("potus_diagnostics_device", device, block)) return rc_;
   DevBufs tmp;
   double *cols = nullptr;
-  HIP_TRY(tmp.alloc(&cols, (size_t)n_draws * n_chains * n_cols * 8));
+  if (const int rc_ = tmp.get(&cols, (size_t)n_draws * n_chains * n_cols * 8, "potus_diagnostics_device")) return rc_;
   if (const int rc_ = transpose_block(0, (const double *)block, cols, n_draws, n_chains, n_cols, n_chains, 0)) return rc_;
   return diagnostics_of_columns(0, cols, n_draws, n_chains, n_cols, rhat_out, ess_bulk_out);
 }
@@ -3405,10 +3430,67 @@ static int gather_columns(const Pool &P, int col_begin, int col_end, int n_warm_
     DevBufs blkbuf;
     double *blk = nullptr;
     int rc;
-    HIP_TRY(blkbuf.alloc(&blk, bytes));
+    if ((rc = blkbuf.get(&blk, bytes, P.what))) return rc;
     if ((rc = gather_block(s0, sp, bytes, blk, [&](double *out) { return write_array_range(sp, n_saved, col_begin, col_end, out, true, NC); }))) return rc;
     if ((rc = pool_transpose(s0, blk + (size_t)n_warm_rows * C * NC, cols, n_post, C, NC, Ctot, coff))) return rc;
     coff += C;
+  }
+  return 0;
+}
+
+// Days [day_begin, day_end) of predicted_score over the post-warm-up draws of a resolved pool of one posterior (Pool::same_posterior), counted here under
+// the caller's locks: gathered handle by handle and cut into items [nd][n_days][S] on the first handle's GPU (its device current on return).  The handles may
+// have saved different numbers of draws: every one of them is pooled.  Row order: as the handles saved them (row = saved draw x chain), one k_oc_days launch
+// per handle; or (by_chain) CANONICAL, chain after chain in the order the handles are listed, each chain's draws in iteration order (the row order of
+// potus_extract_matrix) -- one launch per chain.  extra_day >= 0: that day too, as a one-day block extra [nd][1][S] in the same order.
+struct DayItems {
+  DevBufs bufs;
+  double *items = nullptr, *extra = nullptr;
+  long long nd = 0;
+  double gather_ms = 0.0, reshape_ms = 0.0;   // gather + produce, day-range reshape: summed over the handles
+};
+static int gather_days(Pool &P, int day_begin, int day_end, bool by_chain, int extra_day, DayItems &g) {
+  Sampler *s0 = P.s0;
+  const int S = s0->M.S, T = s0->M.T, TS = S * T, n_days = day_end - day_begin;
+  if (day_begin < 0 || day_end > T || day_begin >= day_end) return fail(POTUS_ERR_ARG, "%s: days [%d, %d) of %d", P.what, day_begin, day_end, T);
+  int rc;
+  if ((rc = P.count())) return rc;
+  std::vector<int> first(P.sps.size());
+  for (size_t i = 0; i < P.sps.size(); i++) {
+    first[i] = warm_rows(P.sps[i], P.saved[i]);
+    g.nd += (long long)(P.saved[i] - first[i]) * P.sps[i]->R.chains;
+  }
+  if (g.nd < 1) return fail(POTUS_ERR_STATE, "%s needs at least one saved post-warm-up draw (%lld rows saved, all of them warm-up)", P.what, P.draws);
+  const int col_end = s0->L.ncols, col_begin = col_end - TS;   // predicted_score = the generated-quantities block
+  HIP_TRY(hipSetDevice(s0->device));
+  if ((rc = g.bufs.get(&g.items, (size_t)g.nd * n_days * S * 8, P.what))) return rc;
+  if (extra_day >= 0 && (rc = g.bufs.get(&g.extra, (size_t)g.nd * S * 8, P.what))) return rc;
+  long long row0 = 0;
+  for (size_t i = 0; i < P.sps.size(); i++) {
+    Sampler *sp = P.sps[i];
+    const int n_saved = P.saved[i], C = sp->R.chains, nsplit = by_chain ? C : 1;
+    const long long rows = (long long)(n_saved - first[i]) * C / nsplit;   // per launch
+    if (rows == 0) continue;
+    const size_t bytes = (size_t)n_saved * C * TS * 8;
+    DevBufs blkbuf;
+    double *blk = nullptr;
+    if ((rc = blkbuf.get(&blk, bytes, P.what))) return rc;
+    const double t0 = dn_now();
+    if ((rc = gather_block(s0, sp, bytes, blk, [&](double *out) { return write_array_range(sp, n_saved, col_begin, col_end, out, true, TS); }))) return rc;
+    const double t1 = dn_now();
+    // launch c: the handle's post-warm-up rows (row = saved draw x chain) from row c on, nsplit rows apart -- all of them, or those of chain c
+    for (int c = 0; c < nsplit; c++, row0 += rows) {
+      const double *src = blk + ((size_t)first[i] * C + c) * TS;
+      const unsigned gy = (unsigned)std::min<long long>(rows, 32768);
+      hipLaunchKernelGGL(k_oc_days, dim3((n_days + 63) / 64, gy), dim3(256), 0, s0->stream, src, (long long)nsplit * TS, g.items + (size_t)row0 * n_days * S, rows, T, S, day_begin, day_end);
+      HIP_TRY(hipGetLastError());
+      if (g.extra) {
+        hipLaunchKernelGGL(k_oc_days, dim3(1, gy), dim3(256), 0, s0->stream, src, (long long)nsplit * TS, g.extra + (size_t)row0 * S, rows, T, S, extra_day, extra_day + 1);
+        HIP_TRY(hipGetLastError());
+      }
+    }
+    HIP_TRY(hipStreamSynchronize(s0->stream));
+    g.gather_ms += t1 - t0; g.reshape_ms += dn_now() - t1;
   }
   return 0;
 }
@@ -3423,7 +3505,7 @@ static int diagnostics_pooled(const Pool &P, int col_begin, int col_end, double 
   HIP_TRY(hipSetDevice(s0->device));
   DevBufs tmp;
   double *cols = nullptr;
-  HIP_TRY(tmp.alloc(&cols, (size_t)n_post * Ctot * NC * 8));
+  if (const int rc_ = tmp.get(&cols, (size_t)n_post * Ctot * NC * 8, P.what)) return rc_;
   if (const int rc_ = gather_columns(P, col_begin, col_end, n_warm_rows, n_post, cols)) return rc_;
   return diagnostics_of_columns(s0->stream, cols, n_post, Ctot, NC, rhat_out, ess_bulk_out);
 }
@@ -3442,18 +3524,9 @@ int potus_diagnostics(const int *handles, int n_handles, int col_begin, int col_
 }
 
 // ---------------------------------------------------------------------------------------------- PSIS-LOO (potus_loo.hpp)
-extern "C++" {   // (the helpers are templates)
 namespace {
 constexpr size_t LOO_BLOCK_BUDGET = 256ull << 20;   // a call's log-likelihood blocks (half) and PSIS scratch (half)
 constexpr size_t LOO_ROW_BUDGET = 64ull << 20;      // k_loo_loglik's rebuilt output rows, per handle
-
-template <class T> int loo_alloc(DevBufs &b, T **p, size_t bytes, const char *what) {
-  if (b.alloc(p, bytes) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(POTUS_ERR_DEVICE, "%s: hipMalloc of %zu bytes (%.1f MB) failed", what, bytes, bytes / 1048576.0);
-  }
-  return 0;
-}
 
 // per handle: log C(n, y) of its polls in the model's order, and the row scratch of k_loo_loglik
 struct LooRows { double *lc = nullptr, *scratch = nullptr; int grid = 1; };
@@ -3467,10 +3540,10 @@ int loo_rows_setup(Sampler *sp, long long ndraw, DevBufs &keep, LooRows &r, cons
     lc[i] = (double)(lgammal(n + 1) - lgammal(y + 1) - lgammal(n - y + 1));
   }
   int rc;
-  if ((rc = loo_alloc(keep, &r.lc, lc.size() * 8, what))) return rc;
+  if ((rc = keep.get(&r.lc, lc.size() * 8, what))) return rc;
   HIP_TRY(hipMemcpy(r.lc, lc.data(), lc.size() * 8, hipMemcpyHostToDevice));
   r.grid = (int)std::max<long long>(1, std::min<long long>(std::min<long long>(ndraw, 512), (long long)(LOO_ROW_BUDGET / ((size_t)sp->L.ncols * 8))));
-  return loo_alloc(keep, &r.scratch, (size_t)r.grid * sp->L.ncols * 8, what);
+  return keep.get(&r.scratch, (size_t)r.grid * sp->L.ncols * 8, what);
 }
 
 // log-likelihoods of polls [b0, b1) of the handle's post-warm-up draws -> out [n_post][chains][b1 - b0], on the handle's device and stream
@@ -3499,17 +3572,15 @@ int loo_psis(hipStream_t st, const double *ll, int NP, int C, long long n, const
   unsigned long long *rkey = nullptr;
   unsigned *ridx = nullptr;
   int rc;
-  if ((rc = loo_alloc(tmp, &wsd, (size_t)grid * wsd_n * 8, what)) || (rc = loo_alloc(tmp, &wsi, (size_t)grid * S * 4, what)) ||
-      (rc = loo_alloc(tmp, &dout, (size_t)NP * LOO_NPW * 8, what)))
+  if ((rc = tmp.get(&wsd, (size_t)grid * wsd_n * 8, what)) || (rc = tmp.get(&wsi, (size_t)grid * S * 4, what)) ||
+      (rc = tmp.get(&dout, (size_t)NP * LOO_NPW * 8, what)))
     return rc;
-  if (S > DG_RUN && ((rc = loo_alloc(tmp, &rkey, (size_t)grid * S * 8, what)) || (rc = loo_alloc(tmp, &ridx, (size_t)grid * S * 4, what)))) return rc;
+  if (S > DG_RUN && ((rc = tmp.get(&rkey, (size_t)grid * S * 8, what)) || (rc = tmp.get(&ridx, (size_t)grid * S * 4, what)))) return rc;
   if (r_eff) {
-    if ((rc = loo_alloc(tmp, &dre, (size_t)NP * 8, what))) return rc;
+    if ((rc = tmp.get(&dre, (size_t)NP * 8, what))) return rc;
     HIP_TRY(hipMemcpyAsync(dre, r_eff, (size_t)NP * 8, hipMemcpyHostToDevice, st));
   }
-  int npad = 1;
-  while (npad < S && npad < DG_RUN) npad <<= 1;
-  const size_t lds = (size_t)npad * 12;                // keys + indices of one sorted run
+  const size_t lds = sorted_run_lds(S);                // keys + indices of one sorted run
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_loo_psis), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   PsisParams P{ll, dre, wsd, wsi, rkey, ridx, dout, n, C, NP, mmax};
   hipLaunchKernelGGL(k_loo_psis, dim3(grid), dim3(DG_THREADS), lds, st, P);
@@ -3537,7 +3608,6 @@ int loo_check_r_eff(const double *r_eff, int n, const char *what) {
   return 0;
 }
 } // namespace
-} // extern "C++"
 
 int potus_log_lik_device(int handle, int poll_begin, int poll_end, int integrate, void *out_device) {
   Sampler *sp = get(handle);
@@ -3546,14 +3616,8 @@ int potus_log_lik_device(int handle, int poll_begin, int poll_end, int integrate
   if (integrate != 0 && integrate != 1) return fail(POTUS_ERR_ARG, "potus_log_lik_device: integrate = %d (0: plain, 1: noise coordinate integrated out)", integrate);
   const int Np = sp->M.Npoll;
   if (poll_begin < 0 || poll_end > Np || poll_begin >= poll_end) return fail(POTUS_ERR_ARG, "potus_log_lik_device: polls [%d, %d) of %d", poll_begin, poll_end, Np);
-  DeviceGuard guard;
-  DeviceLocks lock(sp->device);
-  HIP_TRY(hipSetDevice(sp->device));
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, out_device) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != sp->device) {
-    (void)hipGetLastError();
-    return fail(POTUS_ERR_ARG, "potus_log_lik_device: the output is not device memory of GPU %d", sp->device);
-  }
+  DeviceBlock dev;
+  if (const int rc_ = dev.open("potus_log_lik_device", sp->device, out_device, "output")) return rc_;
   int n_saved = 0, rc = saved_count(sp, &n_saved);
   if (rc) return rc;
   const int first = warm_rows(sp, n_saved), n_post = n_saved - first, C = sp->R.chains;
@@ -3563,7 +3627,7 @@ int potus_log_lik_device(int handle, int poll_begin, int poll_end, int integrate
   if ((rc = loo_rows_setup(sp, (long long)n_post * C, keep, r, "potus_log_lik_device"))) return rc;
   const int nb = loo_block_polls((size_t)n_post * C * 8, poll_end - poll_begin);
   double *blk = nullptr, *out = (double *)out_device;
-  if ((rc = loo_alloc(keep, &blk, (size_t)n_post * C * nb * 8, "potus_log_lik_device"))) return rc;
+  if ((rc = keep.get(&blk, (size_t)n_post * C * nb * 8, "potus_log_lik_device"))) return rc;
   for (int b0 = poll_begin; b0 < poll_end; b0 += nb) {
     const int b1 = std::min(b0 + nb, poll_end);
     if ((rc = loo_loglik(sp, r, first, n_post, b0, b1, integrate, blk))) return rc;
@@ -3580,16 +3644,8 @@ int potus_loo_device(int device, const void *log_lik, int n_polls, int n_chains,
   if (2 * n_chains > DG_MAXCH) return fail(POTUS_ERR_UNSUPPORTED, "potus_loo_device: %d chains pooled (at most %d)", n_chains, DG_MAXCH / 2);
   if ((long long)n_chains * n_draws > 0x7fffffffll) return fail(POTUS_ERR_UNSUPPORTED, "potus_loo_device: %lld draws per poll (at most 2^31 - 1)", (long long)n_chains * n_draws);
   if (const int rc_ = loo_check_r_eff(r_eff, n_polls, "potus_loo_device")) return rc_;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(POTUS_ERR_DEVICE, "potus_loo_device: no HIP device %d", device);
-  DeviceGuard guard;
-  DeviceLocks lock(device);
-  HIP_TRY(hipSetDevice(device));
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, log_lik) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
-    (void)hipGetLastError();
-    return fail(POTUS_ERR_ARG, "potus_loo_device: the block is not device memory of GPU %d", device);
-  }
+  DeviceBlock dev;
+  if (const int rc_ = dev.open("potus_loo_device", device, log_lik)) return rc_;
   const int rc = loo_psis(0, (const double *)log_lik, n_polls, n_chains, n_draws, r_eff, pointwise_out, "potus_loo_device");
   if (rc) return rc;
   loo_estimates(pointwise_out, n_polls, estimates_out);
@@ -3624,7 +3680,7 @@ int potus_loo(const int *handles, int n_handles, int integrate, const double *r_
   const int nb = loo_block_polls((size_t)S * 16, Np);    // the pooled block, and one handle's block before its transpose
   HIP_TRY(hipSetDevice(s0->device));
   double *cols = nullptr;
-  if ((rc = loo_alloc(keep, &cols, (size_t)S * nb * 8, "potus_loo"))) return rc;
+  if ((rc = keep.get(&cols, (size_t)S * nb * 8, "potus_loo"))) return rc;
   for (int b0 = 0; b0 < Np; b0 += nb) {
     const int b1 = std::min(b0 + nb, Np), nbk = b1 - b0;
     int coff = 0;
@@ -3634,7 +3690,7 @@ int potus_loo(const int *handles, int n_handles, int integrate, const double *r_
       const size_t bytes = (size_t)n_post * C * nbk * 8;
       DevBufs blkbuf;
       double *blk = nullptr;
-      if ((rc = loo_alloc(blkbuf, &blk, bytes, "potus_loo"))) return rc;
+      if ((rc = blkbuf.get(&blk, bytes, "potus_loo"))) return rc;
       if ((rc = gather_block(s0, sp, bytes, blk, [&](double *out) { return loo_loglik(sp, rows[i], first, n_post, b0, b1, integrate, out); }))) return rc;
       if ((rc = pool_transpose(s0, blk, cols, n_post, C, nbk, Ctot, coff))) return rc;
       coff += C;
@@ -3671,15 +3727,13 @@ int monitor_of_columns(hipStream_t stream, const double *cols, long long n, int 
   // k_dg_column's scratch per workgroup (its runs hold the C middle draws too when n is odd) and its cap on the grid
   const long long per_wg = N * 16 + (M > DG_RUN ? M * 12 : 0);
   const int grid = (int)std::max<long long>(1, std::min<long long>(std::min(NC, 1024), (768ll << 20) / per_wg));
-  if ((rc = loo_alloc(tmp, &P.zbuf, (size_t)grid * 2 * (size_t)N * 8, what))) return rc;
+  if ((rc = tmp.get(&P.zbuf, (size_t)grid * 2 * (size_t)N * 8, what))) return rc;
   if (M > DG_RUN) {
-    if ((rc = loo_alloc(tmp, &P.rkey, (size_t)grid * (size_t)M * 8, what))) return rc;
-    if ((rc = loo_alloc(tmp, &P.ridx, (size_t)grid * (size_t)M * 4, what))) return rc;
+    if ((rc = tmp.get(&P.rkey, (size_t)grid * (size_t)M * 8, what))) return rc;
+    if ((rc = tmp.get(&P.ridx, (size_t)grid * (size_t)M * 4, what))) return rc;
   }
-  if ((rc = loo_alloc(tmp, &P.out, (size_t)NC * W * 8, what))) return rc;
-  int npad = 1;
-  while (npad < M && npad < DG_RUN) npad <<= 1;
-  const size_t lds = (size_t)npad * 12;                // keys + indices
+  if ((rc = tmp.get(&P.out, (size_t)NC * W * 8, what))) return rc;
+  const size_t lds = sorted_run_lds(M);                // keys + indices
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mn_column), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   P.cols = cols; P.n = n; P.C = C; P.NC = NC; P.n_probs = n_probs;
   for (int i = 0; i < n_probs; i++) P.probs[i] = probs[i];
@@ -3694,14 +3748,11 @@ int monitor_of_columns(hipStream_t stream, const double *cols, long long n, int 
 int potus_monitor_device(int device, const void *block, long long n_draws, int n_chains, int n_cols, const double *probs, int n_probs, double *out) {
   if (!block || n_draws < 1 || n_chains < 1 || n_cols < 1) return fail(POTUS_ERR_ARG, "potus_monitor_device: bad argument");
   if (const int rc_ = monitor_check("potus_monitor_device", probs, n_probs, out, n_draws, n_chains)) return rc_;   // before anything is allocated
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(POTUS_ERR_DEVICE, "potus_monitor_device: no HIP device %d", device);
-  DeviceGuard guard;
-  DeviceLocks lock(device);
-  HIP_TRY(hipSetDevice(device));
+  DeviceBlock dev;
+  if (const int rc_ = dev.open("potus_monitor_device", device, block)) return rc_;
   DevBufs tmp;
   double *cols = nullptr;
-  if (const int rc_ = loo_alloc(tmp, &cols, (size_t)n_draws * n_chains * n_cols * 8, "potus_monitor_device")) return rc_;
+  if (const int rc_ = tmp.get(&cols, (size_t)n_draws * n_chains * n_cols * 8, "potus_monitor_device")) return rc_;
   if (const int rc_ = transpose_block(0, (const double *)block, cols, n_draws, n_chains, n_cols, n_chains, 0)) return rc_;
   return monitor_of_columns(0, cols, n_draws, n_chains, n_cols, probs, n_probs, out, "potus_monitor_device");
 }
@@ -3733,7 +3784,7 @@ int potus_monitor(const int *handles, int n_handles, int col_begin, int col_end,
   const int W = MN_NSTATS + n_probs;
   DevBufs tmp;
   double *cols = nullptr;
-  if (const int rc_ = loo_alloc(tmp, &cols, (size_t)n_post * Ctot * nb * 8, "potus_monitor")) return rc_;
+  if (const int rc_ = tmp.get(&cols, (size_t)n_post * Ctot * nb * 8, "potus_monitor")) return rc_;
   for (int b0 = col_begin; b0 < col_end; b0 += nb) {
     const int b1 = std::min(b0 + nb, col_end);
     if (const int rc_ = gather_columns(P, b0, b1, n_warm_rows, n_post, cols)) return rc_;
@@ -3771,20 +3822,21 @@ int oc_check(const char *what, int S, const int32_t *ev, int ev_to_win, const do
   return 0;
 }
 
-// items [nd][n_days][S] on the current device -> the counts, in the caller's host arrays (any of them may be null)
-int oc_count(hipStream_t st, const double *items, long long nd, int n_days, int S, const double *w, const int32_t *ev, int ev_to_win, const double *actual,
-             int ev_sum, const OcOut &o) {
+// items [nd][n_days][S] on the current device -> the counts, in the caller's host arrays (any of them may be null); *kernel_ms = the counting kernel's time
+int oc_count(const char *what, hipStream_t st, const double *items, long long nd, int n_days, int S, const double *w, const int32_t *ev, int ev_to_win,
+             const double *actual, int ev_sum, const OcOut &o, double *kernel_ms) {
   const size_t n_hist = (size_t)n_days * (ev_sum + 1), n_tip = (size_t)n_days * (S + 1), n_joint = (size_t)n_days * (S + 2) * (S + 2),
                n_below = (size_t)n_days * S;
   DevBufs tmp;
   double *dw = nullptr, *dact = nullptr;
   int32_t *dev_ = nullptr;
   unsigned long long *dout = nullptr;
-  HIP_TRY(tmp.alloc(&dw, (size_t)S * 8)); HIP_TRY(tmp.alloc(&dev_, (size_t)S * 4));
-  HIP_TRY(tmp.alloc(&dout, (n_hist + n_tip + n_joint + n_below) * 8));
+  int rc;
+  if ((rc = tmp.get(&dw, (size_t)S * 8, what)) || (rc = tmp.get(&dev_, (size_t)S * 4, what))) return rc;
+  if ((rc = tmp.get(&dout, (n_hist + n_tip + n_joint + n_below) * 8, what))) return rc;
   HIP_TRY(hipMemcpyAsync(dw, w, (size_t)S * 8, hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(dev_, ev, (size_t)S * 4, hipMemcpyHostToDevice, st));
-  if (actual) { HIP_TRY(tmp.alloc(&dact, (size_t)S * 8)); HIP_TRY(hipMemcpyAsync(dact, actual, (size_t)S * 8, hipMemcpyHostToDevice, st)); }
+  if (actual) { if ((rc = tmp.get(&dact, (size_t)S * 8, what))) return rc; HIP_TRY(hipMemcpyAsync(dact, actual, (size_t)S * 8, hipMemcpyHostToDevice, st)); }
   HIP_TRY(hipMemsetAsync(dout, 0, (n_hist + n_tip + n_joint + n_below) * 8, st));
   // about 2048 workgroups over days x chunks of draws; a workgroup's own counters have 32 bits
   long long chunks = std::min<long long>(std::max(1, 2048 / n_days), (nd + 63) / 64);
@@ -3804,7 +3856,7 @@ int oc_count(hipStream_t st, const double *items, long long nd, int n_days, int 
   if (o.below_actual && actual) HIP_TRY(hipMemcpyAsync(o.below_actual, P.below, n_below * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
   float ms = 0.f;
-  if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) g_oc_ms[2] = ms;
+  if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) *kernel_ms = ms;
   if (o.n_draws) *o.n_draws = nd;
   return 0;
 }
@@ -3820,18 +3872,10 @@ int potus_outcomes_device(int device, const void *block, long long n_draws, int 
   int ev_sum = 0;
   if (const int rc_ = oc_check(what, S, ev, ev_to_win, actual, &ev_sum)) return rc_;
   for (int s = 0; s < S; s++) if (!std::isfinite(w[s])) return fail(POTUS_ERR_ARG, "%s: w[%d] is not finite", what, s);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(POTUS_ERR_DEVICE, "%s: no HIP device %d", what, device);
-  DeviceGuard guard;
-  DeviceLocks lock(device);
-  HIP_TRY(hipSetDevice(device));
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, block) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
-    (void)hipGetLastError();
-    return fail(POTUS_ERR_ARG, "%s: the block is not device memory of GPU %d", what, device);
-  }
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, device, block)) return rc_;
   g_oc_ms[0] = g_oc_ms[1] = g_oc_ms[2] = 0.0;
-  return oc_count(0, (const double *)block, n_draws, n_days, S, w, ev, ev_to_win, actual, ev_sum, OcOut{ev_hist, tipping, joint, below_actual, n_draws_out});
+  return oc_count(what, 0, (const double *)block, n_draws, n_days, S, w, ev, ev_to_win, actual, ev_sum, OcOut{ev_hist, tipping, joint, below_actual, n_draws_out}, &g_oc_ms[2]);
 }
 
 // Pooled over the post-warm-up draws of every listed sampler (the rules of potus_posterior_summary_many for what may be pooled, of potus_loo for
@@ -3844,55 +3888,16 @@ int potus_outcomes(const int *handles, int n_handles, int day_begin, int day_end
   if (const int rc_ = P.resolve(handles, n_handles, what)) return rc_;
   if (const int rc_ = P.same_posterior("joint outcomes pool the chains of one")) return rc_;
   Sampler *s0 = P.s0;
-  const int S = s0->M.S, T = s0->M.T, TS = S * T;
-  if (day_begin < 0 || day_end > T || day_begin >= day_end) return fail(POTUS_ERR_ARG, "%s: days [%d, %d) of %d", what, day_begin, day_end, T);
+  const int S = s0->M.S;
   int ev_sum = 0;
   if (const int rc_ = oc_check(what, S, ev, ev_to_win, actual, &ev_sum)) return rc_;
   DeviceGuard guard;
   DeviceLocks lock(P.devs);
-  if (const int rc_ = P.count()) return rc_;
-  std::vector<int> first(P.sps.size());
-  long long nd = 0;
-  for (size_t i = 0; i < P.sps.size(); i++) {
-    first[i] = warm_rows(P.sps[i], P.saved[i]);
-    nd += (long long)(P.saved[i] - first[i]) * P.sps[i]->R.chains;
-  }
-  if (nd < 1) return fail(POTUS_ERR_STATE, "%s needs at least one saved post-warm-up draw (%lld rows saved, all of them warm-up)", what, P.draws);
-  const int n_days = day_end - day_begin;
-  const int col_end = s0->L.ncols, col_begin = col_end - TS;   // predicted_score = the generated-quantities block
-  HIP_TRY(hipSetDevice(s0->device));
-  DevBufs tmp;
-  double *items = nullptr;
-  if (tmp.alloc(&items, (size_t)nd * n_days * S * 8) != hipSuccess) {
-    (void)hipGetLastError();
-    return fail(POTUS_ERR_DEVICE, "%s: no device memory for %lld draws x %d days x %d states", what, nd, n_days, S);
-  }
-  g_oc_ms[0] = g_oc_ms[1] = g_oc_ms[2] = 0.0;
-  long long row0 = 0;
-  for (size_t i = 0; i < P.sps.size(); i++) {
-    Sampler *sp = P.sps[i];
-    const int n_saved = P.saved[i], C = sp->R.chains;
-    const long long rows = (long long)(n_saved - first[i]) * C;
-    if (rows == 0) continue;
-    const size_t bytes = (size_t)n_saved * C * TS * 8;
-    DevBufs blkbuf;
-    double *blk = nullptr;
-    if (blkbuf.alloc(&blk, bytes) != hipSuccess) {
-      (void)hipGetLastError();
-      return fail(POTUS_ERR_DEVICE, "%s: no device memory for the predicted_score block of handle %d (%zu bytes)", what, handles[i], bytes);
-    }
-    const double t0 = dn_now();
-    if (const int rc = gather_block(s0, sp, bytes, blk, [&](double *out) { return write_array_range(sp, n_saved, col_begin, col_end, out, true, TS); })) return rc;
-    const double t1 = dn_now();
-    // the handle's post-warm-up rows (row = saved draw x chain), the days asked for, [draw][day][S]
-    hipLaunchKernelGGL(k_oc_days, dim3((n_days + 63) / 64, (unsigned)std::min<long long>(rows, 32768)), dim3(256), 0, s0->stream,
-                       (const double *)(blk + (size_t)first[i] * C * TS), (long long)TS, items + (size_t)row0 * n_days * S, rows, T, S, day_begin, day_end);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipStreamSynchronize(s0->stream));
-    g_oc_ms[0] += t1 - t0; g_oc_ms[1] += dn_now() - t1;
-    row0 += rows;
-  }
-  return oc_count(s0->stream, items, nd, n_days, S, s0->h_w.data(), ev, ev_to_win, actual, ev_sum, OcOut{ev_hist, tipping, joint, below_actual, n_draws_out});
+  DayItems g;
+  if (const int rc_ = gather_days(P, day_begin, day_end, false, -1, g)) return rc_;
+  g_oc_ms[0] = g.gather_ms; g_oc_ms[1] = g.reshape_ms; g_oc_ms[2] = 0.0;
+  return oc_count(what, s0->stream, g.items, g.nd, day_end - day_begin, S, s0->h_w.data(), ev, ev_to_win, actual, ev_sum,
+                  OcOut{ev_hist, tipping, joint, below_actual, n_draws_out}, &g_oc_ms[2]);
 }
 
 int potus_outcomes_timing(double *ms) {
@@ -3935,7 +3940,7 @@ int sc_compute(const char *what, hipStream_t st, const double *items, long long 
   OcEvents e;
   HIP_TRY(hipEventCreate(&e.a)); HIP_TRY(hipEventCreate(&e.b));
   double *dw = nullptr;
-  if (const int rc_ = loo_alloc(tmp, &dw, (size_t)S * 8, what)) return rc_;
+  if (const int rc_ = tmp.get(&dw, (size_t)S * 8, what)) return rc_;
   HIP_TRY(hipMemcpyAsync(dw, w, (size_t)S * 8, hipMemcpyHostToDevice, st));
   // ---- keep + compact
   const double t0 = dn_now();
@@ -3947,10 +3952,10 @@ int sc_compute(const char *what, hipStream_t st, const double *items, long long 
     unsigned char *flag = nullptr;
     int *cnt = nullptr;
     long long *first = nullptr;
-    if (const int rc_ = loo_alloc(tmp, &dlh, (size_t)2 * C * 8, what)) return rc_;
-    if (const int rc_ = loo_alloc(tmp, &flag, (size_t)nd, what)) return rc_;
-    if (const int rc_ = loo_alloc(tmp, &cnt, (size_t)nblk * 4, what)) return rc_;
-    if (const int rc_ = loo_alloc(tmp, &first, (size_t)(nblk + 1) * 8, what)) return rc_;
+    if (const int rc_ = tmp.get(&dlh, (size_t)2 * C * 8, what)) return rc_;
+    if (const int rc_ = tmp.get(&flag, (size_t)nd, what)) return rc_;
+    if (const int rc_ = tmp.get(&cnt, (size_t)nblk * 4, what)) return rc_;
+    if (const int rc_ = tmp.get(&first, (size_t)(nblk + 1) * 8, what)) return rc_;
     HIP_TRY(hipMemcpyAsync(dlh, lo, (size_t)C * 8, hipMemcpyHostToDevice, st));
     HIP_TRY(hipMemcpyAsync(dlh + C, hi, (size_t)C * 8, hipMemcpyHostToDevice, st));
     hipLaunchKernelGGL(k_sc_keep, dim3((unsigned)nblk), dim3(SC_THREADS), 0, st, cond, cstride, nd, S, (const double *)dw, (const double *)dlh, (const double *)(dlh + C), flag, cnt);
@@ -3962,7 +3967,7 @@ int sc_compute(const char *what, hipStream_t st, const double *items, long long 
     if (n < 0 || n > nd) return fail(POTUS_ERR_DEVICE, "%s: the kept count %lld of %lld draws is out of range", what, n, nd);
     if (n > 0 && n < nd) {
       double *comp = nullptr;
-      if (const int rc_ = loo_alloc(tmp, &comp, (size_t)n * rowlen * 8, what)) return rc_;
+      if (const int rc_ = tmp.get(&comp, (size_t)n * rowlen * 8, what)) return rc_;
       const unsigned slices = (unsigned)std::min<long long>(std::max<long long>(1, rowlen / 512), 64);
       hipLaunchKernelGGL(k_sc_compact, dim3((unsigned)nblk, slices), dim3(SC_THREADS), 0, st, items, nd, rowlen, (const unsigned char *)flag, (const long long *)first, comp);
       HIP_TRY(hipGetLastError());
@@ -3984,9 +3989,9 @@ int sc_compute(const char *what, hipStream_t st, const double *items, long long 
     const size_t per_day = ((size_t)n + (size_t)nchunks * (C + (want_cov ? (size_t)C * C : 0))) * 8;
     const int dblk = (int)std::min<size_t>((size_t)n_days, std::max<size_t>(1, SC_SCRATCH_BUDGET / per_day));
     double *scratch = nullptr, *dmean = nullptr, *dcov = nullptr;
-    if (const int rc_ = loo_alloc(tmp, &scratch, per_day * dblk, what)) return rc_;
-    if (const int rc_ = loo_alloc(tmp, &dmean, n_mean * 8, what)) return rc_;
-    if (want_cov) if (const int rc_ = loo_alloc(tmp, &dcov, n_cov * 8, what)) return rc_;
+    if (const int rc_ = tmp.get(&scratch, per_day * dblk, what)) return rc_;
+    if (const int rc_ = tmp.get(&dmean, n_mean * 8, what)) return rc_;
+    if (want_cov) if (const int rc_ = tmp.get(&dcov, n_cov * 8, what)) return rc_;
     ScParams P{kept, n, n_days, S, 0, nchunks, dw, scratch, scratch + (size_t)dblk * n, scratch + (size_t)dblk * n + (size_t)dblk * nchunks * C, dmean, dcov};
     const int NT = (C + 15) / 16;
     HIP_TRY(hipEventRecord(e.a, st));
@@ -4024,11 +4029,8 @@ int sc_compute(const char *what, hipStream_t st, const double *items, long long 
       if (o.tipping) std::fill(o.tipping, o.tipping + (size_t)n_days * (S + 1), 0ll);
       if (o.joint) std::fill(o.joint, o.joint + (size_t)n_days * (S + 2) * (S + 2), 0ll);
     } else {
-      const double oc_ms = g_oc_ms[2];                               // (potus_outcomes_timing keeps speaking of the last potus_outcomes call)
-      const int rc = oc_count(st, kept, n, n_days, S, w, ev, ev_to_win, nullptr, ev_sum, OcOut{o.ev_hist, o.tipping, o.joint, nullptr, nullptr});
-      g_sc_ms[4] = g_oc_ms[2];
-      g_oc_ms[2] = oc_ms;
-      if (rc) return rc;
+      // (its time is the scenario's: potus_outcomes_timing keeps speaking of the last potus_outcomes call)
+      return oc_count(what, st, kept, n, n_days, S, w, ev, ev_to_win, nullptr, ev_sum, OcOut{o.ev_hist, o.tipping, o.joint, nullptr, nullptr}, &g_sc_ms[4]);
     }
   }
   return 0;
@@ -4047,16 +4049,8 @@ int potus_scenario_device(int device, const void *block, long long n_draws, int 
   int ev_sum = 0;
   if (const int rc_ = sc_check(what, S, lo, hi, ev, ev_to_win, o, &ev_sum)) return rc_;
   for (int s = 0; s < S; s++) if (!std::isfinite(w[s])) return fail(POTUS_ERR_ARG, "%s: w[%d] is not finite", what, s);
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || device < 0 || device >= ndev) return fail(POTUS_ERR_DEVICE, "%s: no HIP device %d", what, device);
-  DeviceGuard guard;
-  DeviceLocks lock(device);
-  HIP_TRY(hipSetDevice(device));
-  hipPointerAttribute_t at;
-  if (hipPointerGetAttributes(&at, block) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
-    (void)hipGetLastError();
-    return fail(POTUS_ERR_ARG, "%s: the block is not device memory of GPU %d", what, device);
-  }
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, device, block)) return rc_;
   for (double &x : g_sc_ms) x = 0.0;
   const double *items = (const double *)block;
   return sc_compute(what, 0, items, n_draws, n_days, S, items + (size_t)cond_day * S, (long long)n_days * S, w, lo, hi, ev, ev_to_win, ev_sum, o);
@@ -4072,62 +4066,23 @@ int potus_scenario(const int *handles, int n_handles, int cond_day, const double
   if (const int rc_ = P.resolve(handles, n_handles, what)) return rc_;
   if (const int rc_ = P.same_posterior("a scenario pools the chains of one")) return rc_;
   Sampler *s0 = P.s0;
-  const int S = s0->M.S, T = s0->M.T, TS = S * T;
-  if (day_begin < 0 || day_end > T || day_begin >= day_end) return fail(POTUS_ERR_ARG, "%s: days [%d, %d) of %d", what, day_begin, day_end, T);
+  const int S = s0->M.S, T = s0->M.T;
   if (cond_day < 0 || cond_day >= T) return fail(POTUS_ERR_ARG, "%s: condition day %d of %d days", what, cond_day, T);
   const ScOut o{n_kept, mean, cov, ev_hist, tipping, joint};
   int ev_sum = 0;
   if (const int rc_ = sc_check(what, S, lo, hi, ev, ev_to_win, o, &ev_sum)) return rc_;
   DeviceGuard guard;
   DeviceLocks lock(P.devs);
-  if (const int rc_ = P.count()) return rc_;
-  std::vector<int> first(P.sps.size());
-  long long nd = 0;
-  for (size_t i = 0; i < P.sps.size(); i++) {
-    first[i] = warm_rows(P.sps[i], P.saved[i]);
-    nd += (long long)(P.saved[i] - first[i]) * P.sps[i]->R.chains;
-  }
-  if (nd < 1) return fail(POTUS_ERR_STATE, "%s needs at least one saved post-warm-up draw (%lld rows saved, all of them warm-up)", what, P.draws);
-  const int n_days = day_end - day_begin;
   const bool cond_apart = lo && (cond_day < day_begin || cond_day >= day_end);   // the condition day as a one-day block of its own
-  const int col_end = s0->L.ncols, col_begin = col_end - TS;   // predicted_score = the generated-quantities block
-  HIP_TRY(hipSetDevice(s0->device));
-  DevBufs tmp;
-  double *items = nullptr, *citems = nullptr;
-  if (const int rc_ = loo_alloc(tmp, &items, (size_t)nd * n_days * S * 8, what)) return rc_;
-  if (cond_apart) if (const int rc_ = loo_alloc(tmp, &citems, (size_t)nd * S * 8, what)) return rc_;
+  const int n_days = day_end - day_begin;
+  DayItems g;
+  if (const int rc_ = gather_days(P, day_begin, day_end, true, cond_apart ? cond_day : -1, g)) return rc_;
   for (double &x : g_sc_ms) x = 0.0;
-  long long row0 = 0;
-  for (size_t i = 0; i < P.sps.size(); i++) {
-    Sampler *sp = P.sps[i];
-    const int n_saved = P.saved[i], C = sp->R.chains;
-    const long long rows = n_saved - first[i];   // per chain
-    if (rows == 0) continue;
-    const size_t bytes = (size_t)n_saved * C * TS * 8;
-    DevBufs blkbuf;
-    double *blk = nullptr;
-    if (const int rc_ = loo_alloc(blkbuf, &blk, bytes, what)) return rc_;
-    const double t0 = dn_now();
-    if (const int rc = gather_block(s0, sp, bytes, blk, [&](double *out) { return write_array_range(sp, n_saved, col_begin, col_end, out, true, TS); })) return rc;
-    const double t1 = dn_now();
-    // chain c of the handle: its post-warm-up rows are C rows apart in the block
-    for (int c = 0; c < C; c++, row0 += rows) {
-      const double *src = blk + ((size_t)first[i] * C + c) * TS;
-      const unsigned gy = (unsigned)std::min<long long>(rows, 32768);
-      hipLaunchKernelGGL(k_oc_days, dim3((n_days + 63) / 64, gy), dim3(256), 0, s0->stream, src, (long long)C * TS, items + (size_t)row0 * n_days * S, rows, T, S, day_begin, day_end);
-      HIP_TRY(hipGetLastError());
-      if (cond_apart) {
-        hipLaunchKernelGGL(k_oc_days, dim3(1, gy), dim3(256), 0, s0->stream, src, (long long)C * TS, citems + (size_t)row0 * S, rows, T, S, cond_day, cond_day + 1);
-        HIP_TRY(hipGetLastError());
-      }
-    }
-    HIP_TRY(hipStreamSynchronize(s0->stream));
-    g_sc_ms[0] += t1 - t0; g_sc_ms[1] += dn_now() - t1;
-  }
-  if (n_draws) *n_draws = nd;
-  const double *cond = cond_apart ? citems : items + (size_t)(cond_day - day_begin) * S;
-  return sc_compute(what, s0->stream, items, nd, n_days, S, lo ? cond : nullptr, cond_apart ? (long long)S : (long long)n_days * S, s0->h_w.data(), lo, hi, ev, ev_to_win,
-                    ev_sum, o);
+  g_sc_ms[0] = g.gather_ms; g_sc_ms[1] = g.reshape_ms;
+  if (n_draws) *n_draws = g.nd;
+  const double *cond = cond_apart ? g.extra : g.items + (size_t)(cond_day - day_begin) * S;
+  return sc_compute(what, s0->stream, g.items, g.nd, n_days, S, lo ? cond : nullptr, cond_apart ? (long long)S : (long long)n_days * S, s0->h_w.data(), lo, hi, ev,
+                    ev_to_win, ev_sum, o);
 }
 
 int potus_scenario_timing(double *ms) {

@@ -15,7 +15,7 @@ import ctypes as C
 
 import numpy as np
 
-from .sampler import _check, _dp, load_library
+from .sampler import _check, _device_block, _dp, _handle_ids, load_library
 
 POINTWISE = ("elpd_loo", "p_loo", "looic", "pareto_k", "r_eff")
 ESTIMATES = ("elpd_loo", "p_loo", "looic")
@@ -81,12 +81,11 @@ class Loo:
 def loo(handles, integrate=True, r_eff=None, name=None):
     """potus_loo over the pooled post-warm-up draws of the listed handles (one posterior, one GPU or several).  r_eff: [N polls], or None
     (computed per poll as loo::relative_eff)."""
-    hs = list(handles) if isinstance(handles, (list, tuple)) else [handles]
+    hs, ids = _handle_ids(handles)
     h0 = hs[0]
     N = h0.n_polls
     pw, est = np.zeros((N, 5)), np.zeros((3, 2))
     re = None if r_eff is None else np.ascontiguousarray(r_eff, dtype=np.float64).reshape(N)
-    ids = (C.c_int * len(hs))(*[h.h for h in hs])
     _check(h0.L, h0.L.potus_loo(ids, len(hs), int(bool(integrate)), None if re is None else _dp(re), _dp(pw), _dp(est)))
     y, n = poll_vectors(h0.data)
     S = h0.post_warmup_saved() * sum(h.opts.chains for h in hs)
@@ -95,14 +94,11 @@ def loo(handles, integrate=True, r_eff=None, name=None):
 
 def loo_of_block(block, r_eff=None, name=None, y=None, n=None):
     """potus_loo_device on a torch tensor [polls, chains, draws] (float64, contiguous, on a GPU) of log-likelihoods."""
-    import torch
-    if not (block.is_cuda and block.dtype == torch.float64 and block.is_contiguous() and block.dim() == 3):
-        raise TypeError("loo_of_block needs a contiguous float64 [polls, chains, draws] tensor on the GPU")
+    _device_block(block, "loo_of_block", ("polls", "chains", "draws"))
     L = load_library()
     N, ch, nd = (int(x) for x in block.shape)
     pw, est = np.zeros((N, 5)), np.zeros((3, 2))
     re = None if r_eff is None else np.ascontiguousarray(r_eff, dtype=np.float64).reshape(N)
-    torch.cuda.current_stream(block.device).synchronize()
     _check(L, L.potus_loo_device(int(block.device.index or 0), C.c_void_p(block.data_ptr()), N, ch, nd, None if re is None else _dp(re),
                                  _dp(pw), _dp(est)))
     return Loo(pw, est, ch * nd, name, y, n)

@@ -17,7 +17,7 @@ import numpy as np
 
 from . import _abi
 from .diagnostics import MONITOR_STATS
-from .sampler import _check, _dp, load_library
+from .sampler import _check, _device_block, _dp, _handle_ids, load_library
 
 N_STATS = len(MONITOR_STATS)
 MAX_PROBS = 16
@@ -130,10 +130,9 @@ def _ranges(h, pars, cols):
 def monitor(handles, pars=None, cols=None, probs=DEFAULT_PROBS):
     """potus_monitor over the pooled post-warm-up draws of the listed handles (one posterior, one GPU or several).  pars: parameter names of
     Handle.layout or sampler columns ("mu_c", "polling_bias", "lp__", ...); cols: a (begin, end) column range instead; neither: the whole row."""
-    hs = list(handles) if isinstance(handles, (list, tuple)) else [handles]
+    hs, ids = _handle_ids(handles)
     h0 = hs[0]
     p = _probs(probs)
-    ids = (C.c_int * len(hs))(*[h.h for h in hs])
     parts, names, blocks, row = [], [], {}, 0
     for name, a, b, dims in _ranges(h0, pars, cols):
         t = np.zeros((b - a, N_STATS + p.size))
@@ -161,12 +160,9 @@ def monitor_of_block(block, probs=DEFAULT_PROBS, names=None, n_draws=None, n_cha
             raise TypeError("monitor_of_block: a device pointer needs n_draws, n_chains and n_cols")
         ptr, nd, nc, ncol, dev = (block if isinstance(block, C.c_void_p) else C.c_void_p(block)), int(n_draws), int(n_chains), int(n_cols), int(device)
     else:
-        import torch
-        if not (block.is_cuda and block.dtype == torch.float64 and block.is_contiguous() and block.dim() == 3):
-            raise TypeError("monitor_of_block needs a contiguous float64 [draws, chains, columns] tensor on the GPU")
+        _device_block(block, "monitor_of_block", ("draws", "chains", "columns"))
         nd, nc, ncol = (int(x) for x in block.shape)
         ptr, dev = C.c_void_p(block.data_ptr()), int(block.device.index or 0)
-        torch.cuda.current_stream(block.device).synchronize()
     t = np.zeros((ncol, N_STATS + p.size))
     _check(L, L.potus_monitor_device(dev, ptr, nd, nc, ncol, _dp(p) if p.size else None, int(p.size), _dp(t)))
     return Monitor(t, names if names is not None else [f"V{k + 1}" for k in range(ncol)], p, None, nc, nd)

@@ -15,7 +15,7 @@ import ctypes as C
 
 import numpy as np
 
-from .sampler import _check, _dp, load_library
+from .sampler import _check, _device_block, _dp, _handle_ids, load_library
 
 EV_CAP = 2047          # the kernel's histogram: sum(ev) at most this
 _LLP = C.POINTER(C.c_longlong)
@@ -49,6 +49,18 @@ def _actual(actual, S):
     if not ((a >= 0) & (a <= 1)).all():
         raise ValueError("outcomes: actual must lie in [0, 1]")
     return a
+
+
+def _national_weights(w, S):
+    """The weights of the national vote, normalised to sum to one: summed in index order as Python floats, so that every caller divides by
+    the same bits."""
+    w = np.asarray(w, dtype=np.float64)
+    if w.shape != (S,):
+        raise ValueError(f"w has shape {w.shape}, ({S},) expected")
+    sw = 0.0
+    for x in w:
+        sw += float(x)
+    return np.ascontiguousarray(w / sw)
 
 
 class Outcomes:
@@ -152,7 +164,7 @@ class Outcomes:
 def outcomes(handles, ev, actual=None, days=None, ev_to_win=270, states=None):
     """potus_outcomes over the pooled post-warm-up draws of the listed handles (one posterior, one GPU or several).  ev: integer electoral
     votes per state; actual: certified two-party share per state, or None; days: (begin, end) 0-based, None = all days."""
-    hs = list(handles) if isinstance(handles, (list, tuple)) else [handles]
+    hs, ids = _handle_ids(handles)
     h0 = hs[0]
     S, T = int(h0.data["S"]), int(h0.data["T"])
     e = _integer_ev(ev, S)
@@ -166,7 +178,6 @@ def outcomes(handles, ev, actual=None, days=None, ev_to_win=270, states=None):
     hist, tip, joint = np.zeros((n, K + 1), np.int64), np.zeros((n, S + 1), np.int64), np.zeros((n, S + 2, S + 2), np.int64)
     below = None if a is None else np.zeros((n, S), np.int64)
     nd = C.c_longlong(0)
-    ids = (C.c_int * len(hs))(*[h.h for h in hs])
     _check(h0.L, h0.L.potus_outcomes(ids, len(hs), d0, d1, e.ctypes.data_as(_I32P), int(ev_to_win), None if a is None else _dp(a),
                                      _llp(hist), _llp(tip), _llp(joint), None if below is None else _llp(below), C.byref(nd)))
     return Outcomes(hist, tip, joint, below, nd.value, e, ev_to_win, (d0, d1), a, states)
@@ -175,25 +186,16 @@ def outcomes(handles, ev, actual=None, days=None, ev_to_win=270, states=None):
 def outcomes_of_block(block, w, ev, actual=None, ev_to_win=270, states=None):
     """potus_outcomes_device on a torch tensor [draws, days, S] (float64, contiguous, on a GPU) of predicted scores -- e.g. the all-gathered
     blocks of a multi-rank job.  w: the weights of the national vote (normalised here to sum to one, in index order)."""
-    import torch
-    if not (block.is_cuda and block.dtype == torch.float64 and block.is_contiguous() and block.dim() == 3):
-        raise TypeError("outcomes_of_block needs a contiguous float64 [draws, days, S] tensor on the GPU")
+    _device_block(block, "outcomes_of_block", ("draws", "days", "S"))
     L = load_library()
     nd_, n, S = (int(x) for x in block.shape)
     e = _integer_ev(ev, S)
     a = _actual(actual, S)
-    w = np.asarray(w, dtype=np.float64)
-    if w.shape != (S,):
-        raise ValueError(f"w has shape {w.shape}, ({S},) expected")
-    sw = 0.0
-    for x in w:
-        sw += float(x)
-    w = np.ascontiguousarray(w / sw)
+    w = _national_weights(w, S)
     K = int(e.sum())
     hist, tip, joint = np.zeros((n, K + 1), np.int64), np.zeros((n, S + 1), np.int64), np.zeros((n, S + 2, S + 2), np.int64)
     below = None if a is None else np.zeros((n, S), np.int64)
     nd = C.c_longlong(0)
-    torch.cuda.current_stream(block.device).synchronize()
     _check(L, L.potus_outcomes_device(int(block.device.index or 0), C.c_void_p(block.data_ptr()), nd_, n, S, _dp(w), e.ctypes.data_as(_I32P),
                                       int(ev_to_win), None if a is None else _dp(a), _llp(hist), _llp(tip), _llp(joint),
                                       None if below is None else _llp(below), C.byref(nd)))

@@ -262,14 +262,11 @@ class Handle:
     def write_array_device(self, col_begin, col_end, out_tensor):
         """write_array straight into a torch tensor on this handle's GPU ([n_saved, chains, col_end - col_begin],
         float64, contiguous): the buffer an RCCL all-gather sends, no trip through the host."""
-        import torch
-        if not (out_tensor.is_cuda and out_tensor.dtype == torch.float64 and out_tensor.is_contiguous()):
-            raise TypeError("write_array_device needs a contiguous float64 tensor on the GPU")
+        _device_block(out_tensor, "write_array_device")                # (the library writes on its own stream)
         n = C.c_int()
         _check(self.L, self.L.potus_get_draws(self.h, None, C.byref(n)))
         if out_tensor.numel() != n.value * self.opts.chains * (col_end - col_begin):
             raise ValueError(f"tensor has {out_tensor.numel()} elements, {n.value} x {self.opts.chains} x {col_end - col_begin} expected")
-        torch.cuda.current_stream(out_tensor.device).synchronize()      # the library writes on its own stream
         _check(self.L, self.L.potus_write_array_device(self.h, col_begin, col_end, C.c_void_p(out_tensor.data_ptr())))
         return out_tensor
 
@@ -396,13 +393,10 @@ class Handle:
     def log_lik_device(self, poll_begin, poll_end, out, integrate=True):
         """potus_log_lik_device: per-poll log-likelihoods of the post-warm-up draws into a torch tensor on this handle's GPU
         ([poll_end - poll_begin, chains, draws], float64, contiguous).  integrate: each poll's own noise coordinate integrated out."""
-        import torch
-        if not (out.is_cuda and out.dtype == torch.float64 and out.is_contiguous()):
-            raise TypeError("log_lik_device needs a contiguous float64 tensor on the GPU")
+        _device_block(out, "log_lik_device")
         want = (int(poll_end) - int(poll_begin)) * self.opts.chains * self.post_warmup_saved()
         if out.numel() != want:
             raise ValueError(f"tensor has {out.numel()} elements, {want} expected")
-        torch.cuda.current_stream(out.device).synchronize()
         _check(self.L, self.L.potus_log_lik_device(self.h, int(poll_begin), int(poll_end), int(bool(integrate)), C.c_void_p(out.data_ptr())))
         return out
 
@@ -428,15 +422,30 @@ class Handle:
         return [str(Path(directory) / f"{basename}-{off + c + 1}.csv") for c in range(self.opts.chains)]
 
 
+def _handle_ids(handles):
+    """(the handles as a list, their ids as the C int array a pooled entry point takes): one handle or a list / tuple of them."""
+    hs = list(handles) if isinstance(handles, (list, tuple)) else [handles]
+    return hs, (C.c_int * len(hs))(*[h.h for h in hs])
+
+
+def _device_block(block, who, axes=None):
+    """What a *_device entry point may be handed: a contiguous float64 torch tensor on a GPU, with the axes named (any shape when None).
+    The library works on its own stream, so the tensor's current stream is synchronised here."""
+    import torch
+    if not (block.is_cuda and block.dtype == torch.float64 and block.is_contiguous() and (axes is None or block.dim() == len(axes))):
+        raise TypeError(f"{who} needs a contiguous float64 {'' if axes is None else '[' + ', '.join(axes) + '] '}tensor on the GPU")
+    torch.cuda.current_stream(block.device).synchronize()
+
+
 def posterior_summary(handles, ev):
     """potus_posterior_summary_many: the summaries of final_2016.R:708-762, 799-823 over the pooled draws of every
     listed handle (the chains of one posterior, on one GPU or several)."""
-    h0 = handles[0]
+    hs, ids = _handle_ids(handles)
+    h0 = hs[0]
     S, T = int(h0.data["S"]), int(h0.data["T"])
     ev = np.ascontiguousarray(ev, dtype=np.float64).reshape(S)
     st, na, eo = np.zeros((S, T, 4)), np.zeros((T, 4)), np.zeros((T, 5))
-    ids = (C.c_int * len(handles))(*[h.h for h in handles])
-    _check(h0.L, h0.L.potus_posterior_summary_many(ids, len(handles), _dp(ev), _dp(st), _dp(na), _dp(eo)))
+    _check(h0.L, h0.L.potus_posterior_summary_many(ids, len(hs), _dp(ev), _dp(st), _dp(na), _dp(eo)))
     return dict(state=np.ascontiguousarray(st.transpose(1, 0, 2)), national=na, electoral_votes=eo)
 
 
@@ -481,11 +490,11 @@ def run_pooled(handles, n_iter, coll_device=None):
 def device_diagnostics(handles, col_begin, col_end):
     """potus_diagnostics: rank-normalised split R-hat and bulk ESS of columns [col_begin, col_end) of the output row over the pooled
     chains of the listed handles (one posterior), computed on the first handle's GPU.  Returns (rhat, ess_bulk), each [col_end - col_begin]."""
-    h0 = handles[0]
+    hs, ids = _handle_ids(handles)
+    h0 = hs[0]
     n = int(col_end) - int(col_begin)
     rhat, ess = np.zeros(n), np.zeros(n)
-    ids = (C.c_int * len(handles))(*[h.h for h in handles])
-    _check(h0.L, h0.L.potus_diagnostics(ids, len(handles), int(col_begin), int(col_end), _dp(rhat), _dp(ess)))
+    _check(h0.L, h0.L.potus_diagnostics(ids, len(hs), int(col_begin), int(col_end), _dp(rhat), _dp(ess)))
     return rhat, ess
 
 
@@ -499,24 +508,21 @@ def _need_check_convergence(L):
 def check_convergence(handles, rhat_below=1.01, ess_at_least=400.0):
     """potus_check_convergence: (converged, rhat_max, ess_bulk_min) of lp__ and mu_b[:, T] over the post-warm-up draws the pooled chains of
     the handles have saved so far (the online early-stop check of SURVEY 8(f4); a deviation from Stan when acted upon)."""
-    h0 = handles[0]
+    hs, ids = _handle_ids(handles)
+    h0 = hs[0]
     _need_check_convergence(h0.L)
-    ids = (C.c_int * len(handles))(*[h.h for h in handles])
     conv, r, e = C.c_int(0), C.c_double(), C.c_double()
-    _check(h0.L, h0.L.potus_check_convergence(ids, len(handles), C.c_double(rhat_below), C.c_double(ess_at_least), C.byref(conv), C.byref(r), C.byref(e)))
+    _check(h0.L, h0.L.potus_check_convergence(ids, len(hs), C.c_double(rhat_below), C.c_double(ess_at_least), C.byref(conv), C.byref(r), C.byref(e)))
     return bool(conv.value), r.value, e.value
 
 
 def device_diagnostics_of_block(block):
     """potus_diagnostics_device on a torch tensor [draws, chains, columns] (float64, contiguous, on a GPU) -- e.g. the result of the
     all-gather of potus_write_array_device blocks.  Returns (rhat, ess_bulk) as numpy arrays [columns]."""
-    import torch
-    if not (block.is_cuda and block.dtype == torch.float64 and block.is_contiguous() and block.dim() == 3):
-        raise TypeError("device_diagnostics_of_block needs a contiguous float64 [draws, chains, columns] tensor on the GPU")
+    _device_block(block, "device_diagnostics_of_block", ("draws", "chains", "columns"))
     L = load_library()
     nd, nc, ncol = (int(x) for x in block.shape)
     rhat, ess = np.zeros(ncol), np.zeros(ncol)
-    torch.cuda.current_stream(block.device).synchronize()
     _check(L, L.potus_diagnostics_device(int(block.device.index or 0), C.c_void_p(block.data_ptr()), nd, nc, ncol, _dp(rhat), _dp(ess)))
     return rhat, ess
 
@@ -552,9 +558,8 @@ def run_many(handles, n_iter):
     """potus_run_many: advance several handles (other posteriors, other GPUs) concurrently from one host thread."""
     if not handles:
         return
-    L = handles[0].L
-    ids = (C.c_int * len(handles))(*[h.h for h in handles])
-    _check(L, L.potus_run_many(ids, len(handles), int(n_iter)))
+    hs, ids = _handle_ids(handles)
+    _check(hs[0].L, hs[0].L.potus_run_many(ids, len(hs), int(n_iter)))
 
 
 class StanFit:

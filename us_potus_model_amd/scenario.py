@@ -15,8 +15,8 @@ import ctypes as C
 
 import numpy as np
 
-from .outcomes import Outcomes, _I32P, _integer_ev, _llp
-from .sampler import _check, _dp, load_library
+from .outcomes import Outcomes, _I32P, _integer_ev, _llp, _national_weights
+from .sampler import _check, _device_block, _dp, _handle_ids, load_library
 
 
 def parse_given(given, S, states=None):
@@ -131,7 +131,7 @@ def scenario(handles, ev=None, given=None, day=-1, days=None, ev_to_win=270, sta
     """potus_scenario over the pooled post-warm-up draws of the listed handles (one posterior, one GPU or several), taken chain after chain.
     ev: integer electoral votes per state, or None for the moments alone; given: see parse_given; day: the condition day, 0-based, -1 =
     election day; days: (begin, end) of the outputs, 0-based, None = all days."""
-    hs = list(handles) if isinstance(handles, (list, tuple)) else [handles]
+    hs, ids = _handle_ids(handles)
     h0 = hs[0]
     S, T = int(h0.data["S"]), int(h0.data["T"])
     e = None if ev is None else _integer_ev(ev, S)
@@ -148,7 +148,6 @@ def scenario(handles, ev=None, given=None, day=-1, days=None, ev_to_win=270, sta
     mean, cov = np.zeros((n, S + 1)), np.zeros((n, S + 1, S + 1))
     hist, tip, joint = _counts(n, S, e)
     nk, nd = C.c_longlong(0), C.c_longlong(0)
-    ids = (C.c_int * len(hs))(*[h.h for h in hs])
     _check(h0.L, h0.L.potus_scenario(ids, len(hs), cd, None if lo is None else _dp(lo), None if hi is None else _dp(hi), d0, d1,
                                      None if e is None else e.ctypes.data_as(_I32P), int(ev_to_win), C.byref(nk), C.byref(nd), _dp(mean), _dp(cov),
                                      _llp_or_none(hist), _llp_or_none(tip), _llp_or_none(joint)))
@@ -159,19 +158,11 @@ def scenario(handles, ev=None, given=None, day=-1, days=None, ev_to_win=270, sta
 def scenario_of_block(block, w, ev=None, given=None, day=-1, ev_to_win=270, states=None):
     """potus_scenario_device on a torch tensor [draws, days, S] (float64, contiguous, on a GPU) of predicted scores, its draws in the order
     they are to be summed in.  w: the weights of the national vote (normalised here, in index order); day indexes the block's days."""
-    import torch
-    if not (block.is_cuda and block.dtype == torch.float64 and block.is_contiguous() and block.dim() == 3):
-        raise TypeError("scenario_of_block needs a contiguous float64 [draws, days, S] tensor on the GPU")
+    _device_block(block, "scenario_of_block", ("draws", "days", "S"))
     L = load_library()
     nd_, n, S = (int(x) for x in block.shape)
     e = None if ev is None else _integer_ev(ev, S)
-    w = np.asarray(w, dtype=np.float64)
-    if w.shape != (S,):
-        raise ValueError(f"w has shape {w.shape}, ({S},) expected")
-    sw = 0.0
-    for x in w:
-        sw += float(x)
-    w = np.ascontiguousarray(w / sw)
+    w = _national_weights(w, S)
     cd = n + int(day) if int(day) < 0 else int(day)
     if not 0 <= cd < n:
         raise ValueError(f"scenario_of_block: condition day {day} of {n}")
@@ -179,7 +170,6 @@ def scenario_of_block(block, w, ev=None, given=None, day=-1, ev_to_win=270, stat
     mean, cov = np.zeros((n, S + 1)), np.zeros((n, S + 1, S + 1))
     hist, tip, joint = _counts(n, S, e)
     nk = C.c_longlong(0)
-    torch.cuda.current_stream(block.device).synchronize()
     _check(L, L.potus_scenario_device(int(block.device.index or 0), C.c_void_p(block.data_ptr()), nd_, n, S, _dp(w), cd,
                                       None if lo is None else _dp(lo), None if hi is None else _dp(hi), None if e is None else e.ctypes.data_as(_I32P),
                                       int(ev_to_win), C.byref(nk), _dp(mean), _dp(cov), _llp_or_none(hist), _llp_or_none(tip), _llp_or_none(joint)))
