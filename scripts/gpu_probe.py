@@ -73,7 +73,7 @@ for chains in chain_counts:
                 for mm in (0, KCL // 2, KCL - 1):
                     print(f"  phase F, thread 0 of member {mm} (cycles per leaf since its X2 wait ended): own slots done {out[mm][52]/leaves:.0f}, barrier {out[mm][53]/leaves:.0f}, "
                           f"day block stored {out[mm][54]/leaves:.0f}, totals of the next position summed {out[mm][55]/leaves:.0f}")
-            PK = os.environ.get("POTUS_PROF_KIND", "")          # which optional counters the build carries in slots 56-61: "fetch" or "c"
+            PK = os.environ.get("POTUS_PROF_KIND", "")          # which optional counters the build carries in slots 56-61: "fetch", "fetch2" or "c"
             if KCL > 1 and PK == "fetch":
                 for mm in (0, KCL - 1):
                     print(f"  previous leaf's totals, member {mm}: first fetch of 16 words {out[mm][56]/leaves:.0f} cycles, needed a re-fetch in {100*out[mm][57]/leaves:.0f} % of the leaves, "
@@ -82,6 +82,11 @@ for chains in chain_counts:
                 for mm in (0, 1, KCL // 2, KCL - 1):
                     print(f"  X1 fetch (phase B, wave 0), member {mm}: first fetch {out[mm][56]/leaves:.0f} cycles, had to wait in {100*out[mm][57]/leaves:.0f} % of the leaves, "
                           f"{out[mm][58]/leaves:.2f} re-fetch rounds per leaf;  X2 prefix fetch (phase F, wave 0): first fetch {out[mm][59]/leaves:.0f} cycles, waited in "
+                          f"{100*out[mm][60]/leaves:.0f} %, {out[mm][61]/leaves:.2f} re-fetch rounds per leaf")
+            if KCL > 1 and PK == "fetch2":                      # -DPOTUS_PROF_FETCH=2: the other two sixteen-load rounds
+                for mm in (0, 1, KCL - 4, KCL - 1):
+                    print(f"  previous leaf's totals (phase B, wave 2), member {mm}: first fetch {out[mm][56]/leaves:.0f} cycles, had to wait in {100*out[mm][57]/leaves:.0f} % of the leaves, "
+                          f"{out[mm][58]/leaves:.2f} re-fetch rounds per leaf;  slot partials (phase F, wave 2): first fetch {out[mm][59]/leaves:.0f} cycles, waited in "
                           f"{100*out[mm][60]/leaves:.0f} %, {out[mm][61]/leaves:.2f} re-fetch rounds per leaf")
             passes = leaves + 1e-9
             for mm in ((0, KCL // 2, KCL - 1) if KCL > 1 and PK == "c" else ()):

@@ -170,6 +170,18 @@ template <class P> __device__ __forceinline__ P launder_s(P p) { // keep address
 #define PROFPTR nullptr
 #define CPROFPTR(c) nullptr
 #endif
+// -DPOTUS_PROF -DPOTUS_PROF_FETCH counts two of the sixteen-load rounds of a leaf in slots 56-58 and 59-61 (xld): by default X1 in phase B and the X2 prefix totals in
+// phase F (XPROF_A); with -DPOTUS_PROF_FETCH=2 the previous leaf's totals in phase B and the slot partials in phase F, wave 2 (XPROF_B)
+#if defined(POTUS_PROF_FETCH) && (POTUS_PROF_FETCH + 0) == 2
+#define XPROF_A(p) nullptr
+#define XPROF_B(p) (p)
+#elif defined(POTUS_PROF_FETCH)
+#define XPROF_A(p) (p)
+#define XPROF_B(p) nullptr
+#else
+#define XPROF_A(p) nullptr
+#define XPROF_B(p) nullptr
+#endif
 // ---------------------------------------------------------------- exchanges
 // Every payload word travels as 16 bytes {value, tag}: tag = (launch id, exchange number).  A reader
 // simply re-loads until the tag is the one it expects, so publishing is a fire-and-forget store and
@@ -254,8 +266,16 @@ __device__ __forceinline__ bool xld(const Xch &x_in, const unsigned (&vo)[NB], c
 #endif
   u32x4 w[NB];
   bool done[NB];                                   // wave-uniform
+  // The whole round is issued before anything waits for a word of it.  VMEM returns in order, so a tag compare that the scheduler sinks between
+  // two loads brings an s_waitcnt that holds the remaining loads back for a full L2 round trip -- which is what it did in four of the five
+  // sixteen-load rounds of the pass until round 7 (profiles/r07_cl_fetch_issue.txt): uniform offsets first, then nothing but loads between the fences.
+  unsigned ss[NB];
 #pragma unroll
-  for (int u = 0; u < NB; u++) w[u] = __builtin_amdgcn_raw_buffer_load_b128(x.xb, vo[u], __builtin_amdgcn_readfirstlane(so[u]), CL_AUX_SC1);
+  for (int u = 0; u < NB; u++) ss[u] = __builtin_amdgcn_readfirstlane(so[u]);
+  ISSUE_FENCE();
+#pragma unroll
+  for (int u = 0; u < NB; u++) w[u] = __builtin_amdgcn_raw_buffer_load_b128(x.xb, vo[u], ss[u], CL_AUX_SC1);
+  ISSUE_FENCE();
   bool all = true;
 #pragma unroll
   for (int u = 0; u < NB; u++) {
@@ -889,7 +909,7 @@ __device__ __forceinline__ double cl_pass_partial(CMp M_in, CCp CL_in, cip part_
   // (Round 5 built the obvious merger -- the totals in the lanes the X1 fetch leaves idle, one round of sixteen loads for both, three leaves in four -- and
   //  measured it 9 % slower, 14.55 against 13.29 us per leapfrog: the totals arrive late, and wave 0 then holds the suffix carry back with them; docs/HISTORY.md.)
   if (w == 2 && pend.n >= 0) {
-    cl_wide_consume(x, pend.tag, pend.nv, wout);
+    cl_wide_consume(x, pend.tag, pend.nv, wout, XPROF_B(prof));
   }
   // mu_b[:, t] = prior + L_T z_T + L_W C[:, t] and polling_bias = L_B z_b (stan:77,85-86) enter a poll's predictor only as
   // prior[s] + L_W[s, :] . (aT z_T + aB z_b + C[:, t]): the three factors are one matrix times three scalars (stan:42-55).  So
@@ -910,11 +930,7 @@ __device__ __forceinline__ double cl_pass_partial(CMp M_in, CCp CL_in, cip part_
         vo[u] = (mm < K && lane < S) ? 16u * (unsigned)lane : PT_OOB;
         so[u] = xch_eslot(x, x1tag, mm < K ? mm : 0);
       }
-#ifdef POTUS_PROF_FETCH
-      xld(x, vo, so, t16, x1tag, prof);   // slots 56-58
-#else
-      xld(x, vo, so, t16, x1tag, nullptr);
-#endif
+      xld(x, vo, so, t16, x1tag, XPROF_A(prof));   // slots 56-58
 #pragma unroll
       for (int u = 0; u < 16; u++) carry_m += t16[u];
     }
@@ -1356,11 +1372,7 @@ __device__ __forceinline__ double cl_pass_partial(CMp M_in, CCp CL_in, cip part_
         vo[u] = (mm < m && lane < S) ? 16u * (unsigned)(XP_PRE + lane) : PT_OOB;
         so[u] = xch_rslot(x, mm < m ? mm : 0);
       }
-#ifdef POTUS_PROF_FETCH
-      xld(x, vo, so, t16, 0u, prof + 3);   // slots 59-61: cycles of the first fetch, leaves that had to wait, re-fetch rounds
-#else
-      xld(x, vo, so, t16, 0u, nullptr);
-#endif
+      xld(x, vo, so, t16, 0u, XPROF_A(prof + 3));   // slots 59-61: cycles of the first fetch, leaves that had to wait, re-fetch rounds
 #pragma unroll
       for (int u = 0; u < 16; u++) carry_m += t16[u];
     }
@@ -1399,7 +1411,7 @@ __device__ __forceinline__ double cl_pass_partial(CMp M_in, CCp CL_in, cip part_
       unsigned vo[16], so[16];
 #pragma unroll
       for (int u = 0; u < 16; u++) { const int mm = mm0 + u; vo[u] = mm < K ? v1 : PT_OOB; so[u] = xch_rslot(x, mm < K ? mm : 0); }
-      xld(x, vo, so, t16);
+      xld(x, vo, so, t16, 0u, XPROF_B(w == 2 ? prof + 3 : nullptr));
 #pragma unroll
       for (int u = 0; u < 16; u++) sum += t16[u];
     }
