@@ -306,6 +306,38 @@ potus_sbc <- function(data, variant = c("full", "no_mode_adjustment"), columns, 
   list(ranks = less + floor(runif(length(less)) * (equal + 1)), L = rk$L, failed = failed)
 }
 
+# ---- the forecast timeline (us_potus_model_amd/timeline.py is the same in Python; DESIGN.md section 4i) ----
+# Every run date of a campaign fitted as chains of ONE handle and summarised per date on the device.  `data`: the data list of the LAST run date;
+# keep_state [n, N_state_polls] / keep_national [n, N_national_polls]: logical, the polls each run date has seen (the others get n_two_share = 0);
+# mu_b_prior [n, S] and mu_b_T_scale [n]: per run date, or NULL for the data list's.  days: c(first, last), 1-based, default election day alone.
+# Returns list(state = [n, days, S, 4] (low, high, mean, prob), national = [n, days, 4], electoral_votes = [n, days, 5] (mean, median, high, low,
+# P(>= ev_to_win)), n_draws = [n]; a run date with a failed chain has n_draws = 0 and NaN).
+potus_timeline <- function(data, keep_state, keep_national, ev, mu_b_prior = NULL, mu_b_T_scale = NULL, variant = c("full", "no_mode_adjustment"),
+                           chains_per_date = 4, iter_warmup = 1000, iter_sampling = 1000, days = NULL, ev_to_win = 270L, seed = 1843, device = 0) {
+  variant <- match.arg(variant)
+  keep_state <- matrix(as.logical(keep_state), ncol = as.integer(data$N_state_polls)); n <- nrow(keep_state)
+  keep_national <- matrix(as.logical(keep_national), nrow = n)
+  S <- as.integer(data$S); T <- as.integer(data$T)
+  days <- if (is.null(days)) c(T, T) else as.integer(days)
+  nd <- days[2] - days[1] + 1L
+  counts <- function(v, keep) as.integer(t(keep * matrix(as.integer(v), n, length(v), byrow = TRUE)))   # [n][polls], row-major
+  res <- .potus_create(data, variant, c(n * chains_per_date, 0L, iter_warmup, iter_sampling, 10L, as.integer(device), 0L, 1L, 0L, 0L, 0L, 0L),
+                       c(0.8, 0.05, 0.75, 10, 1, 2, seed))
+  .potus_check(res$status)
+  on.exit(.C("potus_R_destroy", res$handle, status = integer(1)))
+  .potus_check(.C("potus_R_set_datasets_ex", res$handle, n, counts(data$n_democrat_state, keep_state), counts(data$n_democrat_national, keep_national),
+                  counts(data$n_two_share_state, keep_state), counts(data$n_two_share_national, keep_national),
+                  as.integer(!is.null(mu_b_prior)), if (is.null(mu_b_prior)) double(1) else as.double(t(matrix(mu_b_prior, n, S))),
+                  as.integer(!is.null(mu_b_T_scale)), if (is.null(mu_b_T_scale)) double(1) else as.double(mu_b_T_scale), status = integer(1))$status)
+  .potus_check(.C("potus_R_init", res$handle, status = integer(1))$status)
+  .potus_check(.C("potus_R_run", res$handle, as.integer(iter_warmup + iter_sampling), status = integer(1))$status)
+  r <- .C("potus_R_timeline", res$handle, days[1] - 1L, days[2], as.double(ev), as.integer(ev_to_win), state = double(n * nd * S * 4),
+          national = double(n * nd * 4), ev = double(n * nd * 5), n_draws = integer(n), status = integer(1))
+  .potus_check(r$status)
+  list(state = aperm(array(r$state, c(4, S, nd, n)), 4:1), national = aperm(array(r$national, c(4, nd, n)), 3:1),
+       electoral_votes = aperm(array(r$ev, c(5, nd, n)), 3:1), n_draws = r$n_draws)
+}
+
 # ---- PSIS-LOO (us_potus_model_amd/loo.py is the same in Python; DESIGN.md section 4e) ----
 # What fit$loo() gives a cmdstanr user with a log_lik generated quantity, computed on the device over every chain of the fit (post-warm-up
 # draws).  integrate = TRUE integrates each poll's own noise coordinate out of its likelihood (plain PSIS-LOO meets high Pareto k there, since

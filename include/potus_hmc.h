@@ -341,7 +341,9 @@ int potus_dense_check(int handle, int chain, int n_probe, double *out /*[2]*/);
 
 /* ---- simulation-based calibration (Talts et al. 2018; DESIGN.md "Simulation-based calibration") ----
  * Many data sets in one handle: after potus_create and before potus_init, give n_datasets outcome vectors of the handle's polls
- * ([n][N_state_polls] and [n][N_national_polls], caller's order, 0 <= y <= n_two_share); everything else in the data is shared.
+ * ([n][N_state_polls] and [n][N_national_polls], caller's order, 0 <= y <= n_two_share); everything else in the data is shared
+ * (the data sets' models differ only in `pd` -- except on the handles of potus_set_datasets_ex below, whose data sets may also
+ * have poll sizes, a mu_b_prior and a mu_b_T_scale of their own).
  * Chain c fits data set c / (chains / n_datasets).  Needs chains % n_datasets == 0, one workgroup per chain (cus_per_chain = 1,
  * twin = 0) and the diagonal metric.  Per-chain calls (potus_get_draws, potus_write_array[_device], potus_chain_status,
  * potus_get_adaptation, potus_draws_device_ptr) work unchanged; calls that pool all chains (potus_posterior_summary[_many],
@@ -350,6 +352,37 @@ int potus_dense_check(int handle, int chain, int n_probe, double *out /*[2]*/);
  * whose initialisation or step-size search fails does not fail potus_init / potus_run: potus_chain_status reports it, the
  * iteration and saved-draw counts are those of the other chains. */
 int potus_set_datasets(int handle, int n_datasets, const int32_t *n_democrat_state, const int32_t *n_democrat_national);
+/* ---- the forecast timeline: the run dates of a campaign as the data sets of one handle ----
+ * potus_set_datasets with more that may differ between the data sets: the poll outcomes AND sizes ([n][N_state_polls], [n][N_national_polls];
+ * a NULL array = the handle's own values for every data set; n_two_share = 0 = this data set has not seen the poll: it adds 0 to the log
+ * density, its noise coordinate keeps its N(0,1) prior), mu_b_prior [n][S] and mu_b_T_scale [n] (> 0), each or both NULL = the handle's.
+ * Preconditions and refusals are potus_set_datasets': between potus_create and potus_init, one workgroup per chain, diagonal metric,
+ * chains % n_datasets == 0, 0 <= n_democrat <= n_two_share per data set.  Every data set gets a model of its own; with a prior or a scale
+ * given also its own transformed data, built by the code potus_create uses: chain c of the handle holds the bytes of a stand-alone handle on
+ * that data set's data with chain_id_offset = c.  potus_write_array[_device] build every row with the chain's own model.
+ * potus_sbc_ranks, potus_constrain and potus_simulate_prior work with the handle's one model and return POTUS_ERR_UNSUPPORTED on such a
+ * handle; the pooled calls refuse it as they refuse potus_set_datasets'. */
+int potus_set_datasets_ex(int handle, int n_datasets, const int32_t *n_democrat_state, const int32_t *n_democrat_national,
+                          const int32_t *n_two_share_state, const int32_t *n_two_share_national,
+                          const double *mu_b_prior /*[n][S] or NULL*/, const double *mu_b_T_scale /*[n] or NULL*/);
+/* Per data set of a handle (of potus_set_datasets or potus_set_datasets_ex; a handle without either is one data set) and per day of
+ * [day_begin, day_end) (0-based), over the data set's post-warm-up draws (warm-up rows of save_warmup = 1 are left out):
+ *   state_out [n][days][S][4]   low 2.5 %, high 97.5 %, mean, P(> 0.5) of predicted_score; quantiles are R's type 7
+ *   natl_out  [n][days][4]      the same for the state_weights-weighted national vote
+ *   ev_out    [n][days][5]      Democratic electoral votes sum_s ev[s] 1[score > 0.5]: mean, median, high, low, P(>= ev_to_win)
+ *   n_draws_out [n]             the draws summarised (chains per data set x post-warm-up draws)
+ * A data set with a chain whose potus_chain_status is non-zero gets n_draws_out = 0 and NaN everywhere; the others are unaffected.  Sums run
+ * in the canonical order of the draws (the data set's chains one after another, iterations within).  At most 16 384 post-warm-up draws per
+ * data set (chains per data set x num_samples; more is refused with POTUS_ERR_UNSUPPORTED before the device is touched).  No output row
+ * is built: election day costs prior + L_T z_T per draw, earlier days a suffix sum of the walk innovations on top. */
+int potus_timeline(int handle, int day_begin, int day_end, const double *ev /*[S]*/, int ev_to_win,
+                   double *state_out, double *natl_out, double *ev_out, int32_t *n_draws_out);
+/* predicted_score of those days into DEVICE memory of the handle's GPU: [n][draws per data set][days][S], a data set's draws in canonical
+ * order -- the slice of data set d is the `block` potus_outcomes_device and potus_scenario_device take.  The values are bit-equal to the
+ * predicted_score columns of potus_write_array.  The scores of a data set with a failed chain are NaN. */
+int potus_timeline_scores_device(int handle, int day_begin, int day_end, void *out_device);
+/* Milliseconds (HIP events) of the calling thread's last potus_timeline: the scores kernel, the summary kernel. */
+int potus_timeline_timing(double *ms /*[2]*/);
 /* Prior predictive simulation: n_sims draws theta ~ prior (poll_model_2020.stan:116-128) on the unconstrained scale (q_out [n_sims][D];
  * rho_e_bias ~ normal(0.7, 0.1) restricted to (0, 1), stored as logit(rho)) and y ~ binomial(n_two_share, inv_logit(logit_pi(theta)))
  * (stan:85-113; exact sampler: inversion when n min(p, 1 - p) < 10, BTRS above) in the caller's poll order.  Any output may be null.
@@ -488,6 +521,10 @@ void potus_R_backtest_scores(double *state_out, int *dims /*[3]: T, S, day*/, do
 void potus_R_last_error(char **buf, int *len);
 void potus_R_destroy(int *handle, int *status);
 void potus_R_set_datasets(int *handle, int *n_datasets, int *n_democrat_state, int *n_democrat_national, int *status);
+void potus_R_set_datasets_ex(int *handle, int *n_datasets, int *n_democrat_state, int *n_democrat_national, int *n_two_share_state, int *n_two_share_national,
+                             int *has_prior, double *mu_b_prior, int *has_scale, double *mu_b_T_scale, int *status);
+void potus_R_timeline(int *handle, int *day_begin, int *day_end, double *ev, int *ev_to_win, double *state_out, double *natl_out, double *ev_out,
+                      int *n_draws_out, int *status);
 void potus_R_simulate_prior(int *handle, double *seed, int *dims /*[2]: n_sims, sim_offset*/, double *q_out, int *n_democrat_state_out,
                             int *n_democrat_national_out, int *status);
 void potus_R_sbc_ranks(int *handle, double *truth, int *cols /*[3]: col_begin, col_end, thin*/, int *less, int *equal, int *L, int *status);

@@ -1116,6 +1116,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, c
 #include "potus_loo.hpp"   // per-poll log-likelihoods and PSIS-LOO (after wa_build_row, which it shares)
 #include "potus_outcomes.hpp"   // joint election outcomes: EV histogram, tipping point, joint win counts
 #include "potus_scenario.hpp"   // conditional forecasts and the covariance of the state scores
+#include "potus_timeline.hpp"   // run dates as the data sets of one handle: their rows, scores and summaries
 
 // ======================================================================== host
 namespace {
@@ -1280,8 +1281,12 @@ struct Sampler {
   double we_cov_ms = 0, we_chol_ms = 0, we_eps_ms = 0;   // window ends: covariance, factorisation, init_stepsize (host clock around synchronised sections)
   int we_count = 0;
   // potus_set_datasets: n_ds models that differ only in the poll outcomes (0: one data set, dM)
+  // potus_set_datasets_ex (ds_ex): ... in the poll outcomes and sizes, and with ds_own_prior in mu_b_prior / mu_b_T_scale (own mat, own aT)
   int n_ds = 0;
   DevModel *dMs = nullptr;
+  bool ds_ex = false, ds_own_prior = false;
+  std::vector<double> h_mat, h_cov, h_w_raw;   // host copies for the per-data-set models: the packed mat, state_covariance_0, state_weights as given
+  double h_nsd = 0, h_rw_scale = 0, h_T_scale = 0;   // sqrt(w' cov w), random_walk_scale, mu_b_T_scale
   int chains_per_ds() const { return n_ds ? R.chains / n_ds : R.chains; }
 };
 
@@ -1344,6 +1349,13 @@ int refuse_many_datasets(const Sampler *sp, const char *what) {
               sp->chains_per_ds(), sp->chains_per_ds());
 }
 
+// Calls that build rows with the handle's one model: the data sets of potus_set_datasets_ex have models of their own
+int refuse_own_models(const Sampler *sp, const char *what) {
+  if (!sp->ds_ex) return 0;
+  return fail(POTUS_ERR_UNSUPPORTED, "%s builds its rows with the handle's own model; the %d data sets of this handle (potus_set_datasets_ex) have "
+                                     "models of their own (poll sizes, mu_b_prior, mu_b_T_scale): use potus_write_array or a stand-alone handle", what, sp->n_ds);
+}
+
 // One owner for every temporary device buffer of a call: freed on every return path.
 struct DevBufs {
   std::vector<void *> v;
@@ -1374,6 +1386,27 @@ int upload(Sampler *s, const std::vector<T> &v, const T **dst) {
   return 0;
 }
 
+// chol((scale / nsd)^2 cov), column-major (stan:50-54)
+bool scaled_chol(const std::vector<double> &cov, double nsd, double scale, int S, std::vector<double> &Lout) {
+  std::vector<double> A(cov);
+  const double f = (scale / nsd) * (scale / nsd);
+  for (auto &x : A) x *= f;
+  return chol(A, Lout, S);
+}
+// What mu_b_prior and mu_b_T_scale put into DevModel::mat: LT_t [k][s], LT [s][k], prior [S], prior_ext [S + 2] (prior, its weighted average, 0).
+// build_model packs them; potus_set_datasets_ex rebuilds them per data set with the same code, so that the bytes are those of a stand-alone handle.
+struct PriorBlocks { std::vector<double> LT, LT_t, LTr, prior, px; };
+bool prior_blocks(const std::vector<double> &cov, double nsd, const std::vector<double> &w, int S, const double *mu_b_prior, double mu_b_T_scale, PriorBlocks &B) {
+  if (!scaled_chol(cov, nsd, mu_b_T_scale, S, B.LT)) return false;
+  B.LT_t.resize((size_t)S * S); B.LTr.resize((size_t)S * S);
+  for (int s = 0; s < S; s++) for (int k = 0; k < S; k++) { B.LT_t[(size_t)k * S + s] = B.LT[s + (size_t)k * S]; B.LTr[(size_t)s * S + k] = B.LT[s + (size_t)k * S]; }
+  B.prior.assign(mu_b_prior, mu_b_prior + S);
+  B.px = B.prior;
+  double nat = 0; for (int s = 0; s < S; s++) nat += w[s] * B.px[s];   // stan:87 applied to the prior part of mu_b
+  B.px.push_back(nat); B.px.push_back(0.0);
+  return true;
+}
+
 int build_model(Sampler *sp, const potus_data *d) {
   const bool full = d->variant == POTUS_VARIANT_FULL;
   const int S = d->S, T = d->T, Ns = d->N_state_polls, Nn = d->N_national_polls;
@@ -1396,20 +1429,16 @@ int build_model(Sampler *sp, const potus_data *d) {
   double nsd2 = 0;
   for (int i = 0; i < S; i++) for (int j = 0; j < S; j++) nsd2 += w[i] * cov[i + (size_t)j * S] * w[j];
   const double nsd = std::sqrt(nsd2);
-  auto scaled_chol = [&](double scale, std::vector<double> &Lout) {
-    std::vector<double> A(cov);
-    const double f = (scale / nsd) * (scale / nsd);
-    for (auto &x : A) x *= f;
-    return chol(A, Lout, S);
-  };
-  if (!scaled_chol(d->polling_bias_scale, sp->LB) || !scaled_chol(d->mu_b_T_scale, sp->LT) || !scaled_chol(d->random_walk_scale, sp->LW))
+  PriorBlocks pb;
+  if (!scaled_chol(cov, nsd, d->polling_bias_scale, S, sp->LB) || !prior_blocks(cov, nsd, w, S, d->mu_b_prior, d->mu_b_T_scale, pb) || !scaled_chol(cov, nsd, d->random_walk_scale, S, sp->LW))
     return fail(POTUS_ERR_ARG, "state_covariance_0 is not positive definite");
+  sp->LT = pb.LT;
+  sp->h_cov = cov; sp->h_w_raw = w; sp->h_nsd = nsd; sp->h_rw_scale = d->random_walk_scale; sp->h_T_scale = d->mu_b_T_scale;
   auto at = [&](const std::vector<double> &Lm, int i, int j) { return Lm[i + (size_t)j * S]; };
 
-  std::vector<double> Lw_ext((size_t)M.SE * M.SP, 0.0), LT_t((size_t)S * S), LB_t((size_t)S * S), LTr((size_t)S * S), LBr((size_t)S * S);
+  std::vector<double> Lw_ext((size_t)M.SE * M.SP, 0.0), LB_t((size_t)S * S), LBr((size_t)S * S);
   for (int s = 0; s < S; s++) for (int k = 0; k < S; k++) {
     Lw_ext[(size_t)s * M.SP + k] = at(sp->LW, s, k);
-    LT_t[(size_t)k * S + s] = at(sp->LT, s, k); LTr[(size_t)s * S + k] = at(sp->LT, s, k);
     LB_t[(size_t)k * S + s] = at(sp->LB, s, k); LBr[(size_t)s * S + k] = at(sp->LB, s, k);
   }
   for (int k = 0; k < S; k++) { double v = 0; for (int s = k; s < S; s++) v += at(sp->LW, s, k) * w[s]; Lw_ext[(size_t)S * M.SP + k] = v; }
@@ -1519,14 +1548,10 @@ int build_model(Sampler *sp, const potus_data *d) {
   // pack: mat = Lw_ext | LT_t | LB_t | LT | LB | prior | w
   std::vector<double> mat(Lw_ext);
   auto app = [&](const std::vector<double> &v) { const int off = (int)mat.size(); mat.insert(mat.end(), v.begin(), v.end()); return off; };
-  M.m_LTt = app(LT_t); M.m_LBt = app(LB_t); M.m_LT = app(LTr); M.m_LB = app(LBr);
-  M.m_prior = app(std::vector<double>(d->mu_b_prior, d->mu_b_prior + S)); M.m_w = app(w);
-  {
-    std::vector<double> px(d->mu_b_prior, d->mu_b_prior + S);
-    double nat = 0; for (int s = 0; s < S; s++) nat += w[s] * px[s];   // stan:87 applied to the prior part of mu_b
-    px.push_back(nat); px.push_back(0.0);
-    M.m_priorx = app(px);
-  }
+  M.m_LTt = app(pb.LT_t); M.m_LBt = app(LB_t); M.m_LT = app(pb.LTr); M.m_LB = app(LBr);
+  M.m_prior = app(pb.prior); M.m_w = app(w);
+  M.m_priorx = app(pb.px);
+  sp->h_mat = mat;
   // (stan:50-52 uses square(scale): the sign of a scale does not reach the factors, chol(c^2 A) = |c| chol(A))
   M.aT = std::fabs(d->mu_b_T_scale / d->random_walk_scale); M.aB = std::fabs(d->polling_bias_scale / d->random_walk_scale);
   M.Npad = (Np + 15) & ~15;
@@ -3221,7 +3246,8 @@ static int write_array_range(Sampler *sp, int n_saved, int col_begin, int col_en
   if (device_out) dout = out;
   else if (const int rc_ = tmp.get(&dout, (size_t)ndraw * nsel * 8, "potus_write_array")) return rc_;
   WAParams W{sp->R.draws, sp->R.chains, sp->R.n_save_max, n_saved, sp->R.row, sp->L.ncols, col_begin, col_end, scratch, dout, sp->sigma_ns, sp->sigma_nn, out_stride};
-  hipLaunchKernelGGL(k_write_array, dim3(grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, W);
+  if (sp->ds_ex) hipLaunchKernelGGL(k_write_array_ds, dim3(grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dMs, W, sp->chains_per_ds());   // the chain's own model
+  else hipLaunchKernelGGL(k_write_array, dim3(grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, W);
   HIP_TRY(hipGetLastError());
   if (!device_out) HIP_TRY(hipMemcpyAsync(out, dout, (size_t)ndraw * nsel * 8, hipMemcpyDeviceToHost, sp->stream));
   HIP_TRY(hipStreamSynchronize(sp->stream));
@@ -4308,9 +4334,184 @@ int potus_set_datasets(int handle, int n_datasets, const int32_t *n_democrat_sta
   return 0;
 }
 
+// Run dates as data sets: every data set may have its own poll sizes (0 = it has not seen the poll), prior and scale.
+int potus_set_datasets_ex(int handle, int n_datasets, const int32_t *n_democrat_state, const int32_t *n_democrat_national,
+                          const int32_t *n_two_share_state, const int32_t *n_two_share_national, const double *mu_b_prior, const double *mu_b_T_scale) {
+  const char *what = "potus_set_datasets_ex";
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  const int Ns = sp->M.Ns, Nn = sp->M.Nn, Np = Ns + Nn, Npad = sp->M.Npad, S = sp->M.S;
+  if (n_datasets < 1) return fail(POTUS_ERR_ARG, "%s: n_datasets = %d, at least 1", what, n_datasets);
+  if (sp->inited) return fail(POTUS_ERR_STATE, "%s: the handle is already initialised (call it between potus_create and potus_init)", what);
+  if (sp->n_ds) return fail(POTUS_ERR_STATE, "%s: the handle already holds %d data sets", what, sp->n_ds);
+  if (sp->dense) return fail(POTUS_ERR_UNSUPPORTED, "%s: the dense metric is not supported (metric = POTUS_METRIC_DIAG only)", what);
+  if (sp->K != 1 || sp->twin) return fail(POTUS_ERR_UNSUPPORTED, "%s: needs one workgroup per chain (cus_per_chain = 1, twin = 0); this handle runs %d x %d", what, sp->K, sp->sides());
+  if (sp->R.chains % n_datasets) return fail(POTUS_ERR_ARG, "%s: chains = %d is not a multiple of n_datasets = %d", what, sp->R.chains, n_datasets);
+  if (mu_b_prior) for (size_t i = 0; i < (size_t)n_datasets * S; i++) if (!std::isfinite(mu_b_prior[i])) return fail(POTUS_ERR_ARG, "%s: data set %d: mu_b_prior is not finite", what, (int)(i / S) + 1);
+  if (mu_b_T_scale) for (int k = 0; k < n_datasets; k++) if (!(mu_b_T_scale[k] > 0) || !std::isfinite(mu_b_T_scale[k])) return fail(POTUS_ERR_ARG, "%s: data set %d: mu_b_T_scale = %g, must be positive and finite", what, k + 1, mu_b_T_scale[k]);
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  std::vector<double> base((size_t)4 * Npad);
+  HIP_TRY(hipMemcpy(base.data(), sp->M.pd, base.size() * 8, hipMemcpyDeviceToHost));
+  std::vector<double> pd((size_t)n_datasets * 4 * Npad);
+  for (int k = 0; k < n_datasets; k++) {
+    double *blk = pd.data() + (size_t)k * 4 * Npad;
+    std::copy(base.begin(), base.end(), blk);
+    for (int i = 0; i < Np; i++) {   // day-sorted poll i is state poll qidx - o_ns or national poll qidx - o_nn (build_model)
+      const int qi = sp->h_pq[i];
+      const bool nat = sp->h_ps[i] == S;
+      const int j = nat ? qi - sp->M.o_nn : qi - sp->M.o_ns;
+      const int32_t *ya = nat ? n_democrat_national : n_democrat_state, *na = nat ? n_two_share_national : n_two_share_state;
+      const size_t at = (size_t)k * (nat ? Nn : Ns) + j;
+      const double n = na ? (double)na[at] : base[(size_t)Npad + i], y = ya ? (double)ya[at] : base[i];
+      if (n < 0) return fail(POTUS_ERR_ARG, "%s: data set %d: n_two_share_%s[%d] = %d is negative", what, k + 1, nat ? "national" : "state", j + 1, (int)n);
+      if (y < 0 || y > n) return fail(POTUS_ERR_ARG, "%s: data set %d: n_democrat_%s[%d] = %d outside [0,%d]", what, k + 1, nat ? "national" : "state", j + 1, (int)y, (int)n);
+      blk[i] = y; blk[(size_t)Npad + i] = n;
+    }
+  }
+  const double *dpd = nullptr;
+  if (const int rc = upload(sp, pd, &dpd)) return rc;
+  std::vector<DevModel> ms(n_datasets, sp->M);
+  for (int k = 0; k < n_datasets; k++) ms[k].pd = dpd + (size_t)k * 4 * Npad;
+  if (mu_b_prior || mu_b_T_scale) {   // own mat and aT: the blocks build_model derives from the prior and the scale, by its code
+    const size_t nm = sp->h_mat.size();
+    std::vector<double> mats((size_t)n_datasets * nm);
+    for (int k = 0; k < n_datasets; k++) {
+      double *m = mats.data() + (size_t)k * nm;
+      std::copy(sp->h_mat.begin(), sp->h_mat.end(), m);
+      PriorBlocks pb;
+      const double scale = mu_b_T_scale ? mu_b_T_scale[k] : sp->h_T_scale;
+      const double *prior = mu_b_prior ? mu_b_prior + (size_t)k * S : sp->h_mat.data() + sp->M.m_prior;
+      if (!prior_blocks(sp->h_cov, sp->h_nsd, sp->h_w_raw, S, prior, scale, pb)) return fail(POTUS_ERR_ARG, "%s: data set %d: the covariance scaled by mu_b_T_scale = %g is not positive definite", what, k + 1, scale);
+      std::copy(pb.LT_t.begin(), pb.LT_t.end(), m + sp->M.m_LTt);
+      std::copy(pb.LTr.begin(), pb.LTr.end(), m + sp->M.m_LT);
+      ms[k].aT = std::fabs(scale / sp->h_rw_scale);
+      std::copy(pb.prior.begin(), pb.prior.end(), m + sp->M.m_prior);
+      std::copy(pb.px.begin(), pb.px.end(), m + sp->M.m_priorx);
+    }
+    const double *dmat = nullptr;
+    if (const int rc = upload(sp, mats, &dmat)) return rc;
+    for (int k = 0; k < n_datasets; k++) ms[k].mat = dmat + (size_t)k * nm;
+    sp->ds_own_prior = true;
+  }
+  const DevModel *dms = nullptr;
+  if (const int rc = upload(sp, ms, &dms)) return rc;
+  sp->dMs = const_cast<DevModel *>(dms);
+  sp->n_ds = n_datasets;
+  sp->ds_ex = true;
+  return 0;
+}
+
+namespace {
+thread_local double g_tl_ms[2] = {0.0, 0.0};   // the last call of this thread: k_tl_scores, k_tl_summary (HIP events)
+
+struct TlPlan { int n_ds, cpd, first, n_post, nd; std::vector<int> skip; const DevModel *Mg; };
+// everything potus_timeline[_scores_device] checks before a kernel runs; the argument tests come before the first HIP call
+int tl_check_args(const char *what, Sampler *sp, int day_begin, int day_end, TlPlan &pl) {
+  pl.n_ds = std::max(sp->n_ds, 1); pl.cpd = sp->chains_per_ds(); pl.nd = day_end - day_begin;
+  if (day_begin < 0 || day_end > sp->M.T || day_begin >= day_end) return fail(POTUS_ERR_ARG, "%s: bad day range [%d,%d) of %d days", what, day_begin, day_end, sp->M.T);
+  if ((long long)pl.cpd * sp->R.num_samples > TL_MAX_DRAWS)
+    return fail(POTUS_ERR_UNSUPPORTED, "%s: %d chains x %d draws per data set: a data set's draws are sorted in LDS, at most %d", what, pl.cpd, sp->R.num_samples, TL_MAX_DRAWS);
+  if (sp->K != 1 || sp->twin || sp->dense) return fail(POTUS_ERR_UNSUPPORTED, "%s: needs one workgroup per chain and the diagonal metric (the handles potus_set_datasets[_ex] take)", what);
+  return 0;
+}
+int tl_plan(const char *what, Sampler *sp, TlPlan &pl) {   // under the device lock
+  std::vector<ChainScalars> sc;
+  if (const int rc = read_scalars(sp, sc)) return rc;
+  int n_saved = 0;
+  if (const int rc = saved_count(sp, &n_saved)) return rc;
+  pl.first = warm_rows(sp, n_saved); pl.n_post = n_saved - pl.first;
+  if (pl.n_post < 1) return fail(POTUS_ERR_STATE, "%s: no post-warm-up draws saved yet (%d saved, %d of them warm-up)", what, n_saved, pl.first);
+  pl.skip.assign(pl.n_ds, 0);
+  for (int c = 0; c < sp->R.chains; c++) if (sc[c].status != 0) pl.skip[c / pl.cpd] = 1;
+  pl.Mg = sp->n_ds ? sp->dMs : sp->dM;
+  return 0;
+}
+int tl_scores(Sampler *sp, const TlPlan &pl, int day_begin, int day_end, const int *dskip, double *out) {
+  const long long items = (long long)sp->R.chains * pl.n_post;
+  TlScoreParams P{sp->R.draws, sp->R.chains, sp->R.n_save_max, sp->R.row, pl.first, pl.n_post, pl.cpd, day_begin, day_end, dskip, out};
+  hipLaunchKernelGGL(k_tl_scores, dim3((unsigned)std::min<long long>((items + 3) / 4, 65535)), dim3(256), 0, sp->stream, pl.Mg, P);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+} // namespace
+
+int potus_timeline_scores_device(int handle, int day_begin, int day_end, void *out_device) {
+  const char *what = "potus_timeline_scores_device";
+  Sampler *sp = get(handle);
+  if (!sp || !out_device) return fail(POTUS_ERR_STATE, "bad handle or null output");
+  TlPlan pl;
+  if (const int rc_ = tl_check_args(what, sp, day_begin, day_end, pl)) return rc_;
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, sp->device, out_device, "output")) return rc_;
+  if (const int rc_ = tl_plan(what, sp, pl)) return rc_;
+  DevBufs tmp;
+  int *dskip = nullptr;
+  if (const int rc_ = tmp.get(&dskip, (size_t)pl.n_ds * 4, what)) return rc_;
+  HIP_TRY(hipMemcpyAsync(dskip, pl.skip.data(), (size_t)pl.n_ds * 4, hipMemcpyHostToDevice, sp->stream));
+  if (const int rc_ = tl_scores(sp, pl, day_begin, day_end, dskip, (double *)out_device)) return rc_;
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  return 0;
+}
+
+int potus_timeline(int handle, int day_begin, int day_end, const double *ev, int ev_to_win, double *state_out, double *natl_out, double *ev_out, int32_t *n_draws_out) {
+  const char *what = "potus_timeline";
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  if (!ev || !state_out || !natl_out || !ev_out || !n_draws_out) return fail(POTUS_ERR_ARG, "%s: null argument", what);
+  TlPlan pl;
+  if (const int rc_ = tl_check_args(what, sp, day_begin, day_end, pl)) return rc_;
+  DeviceGuard guard;
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  if (const int rc_ = tl_plan(what, sp, pl)) return rc_;
+  const int S = sp->M.S, nd = pl.nd, n = pl.cpd * pl.n_post, n_ds = pl.n_ds;
+  DevBufs tmp;
+  OcEvents e0, e1;
+  HIP_TRY(hipEventCreate(&e0.a)); HIP_TRY(hipEventCreate(&e0.b)); HIP_TRY(hipEventCreate(&e1.a)); HIP_TRY(hipEventCreate(&e1.b));
+  double *x = nullptr, *dw = nullptr, *dev_ = nullptr, *dout = nullptr;
+  int *dskip = nullptr;
+  int rc;
+  const size_t n_out = (size_t)n_ds * nd * ((size_t)S * 4 + 9);
+  if ((rc = tmp.get(&x, (size_t)n_ds * n * nd * S * 8, what)) || (rc = tmp.get(&dw, (size_t)S * 8, what)) || (rc = tmp.get(&dev_, (size_t)S * 8, what)) ||
+      (rc = tmp.get(&dout, n_out * 8, what)) || (rc = tmp.get(&dskip, (size_t)n_ds * 4, what))) return rc;
+  HIP_TRY(hipMemcpyAsync(dskip, pl.skip.data(), (size_t)n_ds * 4, hipMemcpyHostToDevice, sp->stream));
+  HIP_TRY(hipMemcpyAsync(dw, sp->h_w.data(), (size_t)S * 8, hipMemcpyHostToDevice, sp->stream));
+  HIP_TRY(hipMemcpyAsync(dev_, ev, (size_t)S * 8, hipMemcpyHostToDevice, sp->stream));
+  HIP_TRY(hipEventRecord(e0.a, sp->stream));
+  if ((rc = tl_scores(sp, pl, day_begin, day_end, dskip, x))) return rc;
+  HIP_TRY(hipEventRecord(e0.b, sp->stream));
+  int npad = 1;
+  while (npad < n) npad <<= 1;
+  const size_t lds = (size_t)npad * 8;
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_tl_summary), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  double *o_state = dout, *o_natl = o_state + (size_t)n_ds * nd * S * 4, *o_ev = o_natl + (size_t)n_ds * nd * 4;
+  TlSumParams Q{x, n_ds, n, nd, S, dw, dev_, (double)ev_to_win, dskip, o_state, o_natl, o_ev};
+  HIP_TRY(hipEventRecord(e1.a, sp->stream));
+  hipLaunchKernelGGL(k_tl_summary, dim3((unsigned)std::min<long long>((long long)n_ds * nd * (S + 2), 65535)), dim3(TL_THREADS), lds, sp->stream, Q);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(e1.b, sp->stream));
+  HIP_TRY(hipMemcpyAsync(state_out, o_state, (size_t)n_ds * nd * S * 4 * 8, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipMemcpyAsync(natl_out, o_natl, (size_t)n_ds * nd * 4 * 8, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipMemcpyAsync(ev_out, o_ev, (size_t)n_ds * nd * 5 * 8, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  float ms0 = 0, ms1 = 0;
+  HIP_TRY(hipEventElapsedTime(&ms0, e0.a, e0.b)); HIP_TRY(hipEventElapsedTime(&ms1, e1.a, e1.b));
+  g_tl_ms[0] = ms0; g_tl_ms[1] = ms1;
+  for (int k = 0; k < n_ds; k++) n_draws_out[k] = pl.skip[k] ? 0 : n;
+  return 0;
+}
+
+int potus_timeline_timing(double *ms) {
+  if (!ms) return fail(POTUS_ERR_ARG, "potus_timeline_timing: null output");
+  ms[0] = g_tl_ms[0]; ms[1] = g_tl_ms[1];
+  return 0;
+}
+
 int potus_simulate_prior(int handle, uint64_t seed, int n_sims, int sim_offset, double *q_out, int32_t *n_democrat_state_out, int32_t *n_democrat_national_out) {
   Sampler *sp = get(handle);
   if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  if (const int rc_ = refuse_own_models(sp, "potus_simulate_prior")) return rc_;
   if (n_sims < 0 || sim_offset < 0 || (long long)sim_offset + n_sims >= 0xFFFFFFFFll) return fail(POTUS_ERR_ARG, "potus_simulate_prior: n_sims = %d, sim_offset = %d", n_sims, sim_offset);
   if (n_sims == 0) return 0;
   DeviceLocks lock(sp->device);
@@ -4341,6 +4542,7 @@ int potus_simulate_prior(int handle, uint64_t seed, int n_sims, int sim_offset, 
 int potus_constrain(int handle, const double *q, int n, int col_begin, int col_end, double *out) {
   Sampler *sp = get(handle);
   if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  if (const int rc_ = refuse_own_models(sp, "potus_constrain")) return rc_;
   if (n < 0 || (n > 0 && (!q || !out))) return fail(POTUS_ERR_ARG, "potus_constrain: null argument");
   if (const int rc_ = check_cols(sp, col_begin, col_end)) return rc_;
   if (n == 0) return 0;
@@ -4365,6 +4567,7 @@ int potus_constrain(int handle, const double *q, int n, int col_begin, int col_e
 int potus_sbc_ranks(int handle, const double *truth, int col_begin, int col_end, int thin, int32_t *less, int32_t *equal, int *L) {
   Sampler *sp = get(handle);
   if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  if (const int rc_ = refuse_own_models(sp, "potus_sbc_ranks")) return rc_;
   if (!truth || !less || !equal || !L) return fail(POTUS_ERR_ARG, "potus_sbc_ranks: null argument");
   if (col_begin < POTUS_N_SAMPLER_COLS || col_end > sp->L.ncols || col_begin >= col_end)
     return fail(POTUS_ERR_ARG, "potus_sbc_ranks: bad column range [%d,%d) (columns %d .. %d)", col_begin, col_end, POTUS_N_SAMPLER_COLS, sp->L.ncols);
@@ -4700,6 +4903,14 @@ void potus_R_backtest_scores(double *state_out, int *dims /*[3]: T, S, day*/, do
 void potus_R_saved_count(int *handle, int *n_saved, int *status) { *status = potus_get_draws(*handle, nullptr, n_saved); }
 void potus_R_last_error(char **buf, int *len) { potus_last_error(buf[0], *len); }
 void potus_R_destroy(int *handle, int *status) { *status = potus_destroy(*handle); }
+void potus_R_set_datasets_ex(int *handle, int *n_datasets, int *n_democrat_state, int *n_democrat_national, int *n_two_share_state, int *n_two_share_national,
+                             int *has_prior, double *mu_b_prior, int *has_scale, double *mu_b_T_scale, int *status) {
+  *status = potus_set_datasets_ex(*handle, *n_datasets, n_democrat_state, n_democrat_national, n_two_share_state, n_two_share_national,
+                                  *has_prior ? mu_b_prior : nullptr, *has_scale ? mu_b_T_scale : nullptr);
+}
+void potus_R_timeline(int *handle, int *day_begin, int *day_end, double *ev, int *ev_to_win, double *state_out, double *natl_out, double *ev_out, int *n_draws_out, int *status) {
+  *status = potus_timeline(*handle, *day_begin, *day_end, ev, *ev_to_win, state_out, natl_out, ev_out, n_draws_out);
+}
 void potus_R_set_datasets(int *handle, int *n_datasets, int *n_democrat_state, int *n_democrat_national, int *status) {
   *status = potus_set_datasets(*handle, *n_datasets, n_democrat_state, n_democrat_national);
 }

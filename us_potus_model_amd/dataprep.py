@@ -117,8 +117,9 @@ def state_correlation(data_dir: Path, dem_year: int = 2016) -> np.ndarray:
     return make_positive_definite(new_C)
 
 
-def build_2016(data_dir: str | Path, run_date: str = "2016-11-08") -> dict:
-    """The full `data` list for the 2016 backtest (final_2016.R:66-514)."""
+def build_2016(data_dir: str | Path, run_date: str = "2016-11-08", _levels: bool = False) -> dict:
+    """The full `data` list for the 2016 backtest (final_2016.R:66-514).  _levels: also return the names behind the mode and
+    population indices (build_timeline compares polls across run dates by name)."""
     data_dir = Path(data_dir)
     RUN_DATE = pd.Timestamp(run_date)
     election_day = pd.Timestamp("2016-11-08")
@@ -217,6 +218,8 @@ def build_2016(data_dir: str | Path, run_date: str = "2016-11-08") -> dict:
     )
     meta = dict(states=states, pollsters=pollsters, ev_state=st.ev.to_numpy(),
                 first_day=str(first_day.date()), election_day=str(election_day.date()))
+    if _levels:
+        return dict(data=data, meta=meta, levels=dict(mode=sorted(df["mode"].astype(str).unique()), pop=sorted(df.polltype.astype(str).unique())))
     return dict(data=data, meta=meta)
 
 
@@ -344,6 +347,67 @@ def build_2012(data_dir, run_date=None):
 
 def build_2008(data_dir, run_date=None):
     return build_backtest(data_dir, 2008, run_date)
+
+
+def _poll_keys(built: dict, kind: str):
+    """One tuple per poll of a built data list that names the poll independently of the run date's index levels:
+    (state, day, pollster name, mode name, population name, n_two_share, n_democrat, unadjusted)."""
+    d, names = built["data"], built["meta"]["pollsters"]
+    lv = built.get("levels")
+    n = int(d[f"N_{kind}_polls"])
+    st = np.asarray(d["state"]) if kind == "state" else np.full(n, 52)
+    mode = [lv["mode"][i - 1] for i in d[f"poll_mode_{kind}"]] if lv else [""] * n
+    pop = [lv["pop"][i - 1] for i in d[f"poll_pop_{kind}"]] if lv else [""] * n
+    return [(int(st[i]), int(d[f"day_{kind}"][i]), str(names[int(d[f"poll_{kind}"][i]) - 1]), mode[i], pop[i], int(d[f"n_two_share_{kind}"][i]),
+             int(d[f"n_democrat_{kind}"][i]), float(d[f"unadjusted_{kind}"][i])) for i in range(n)]
+
+
+def build_timeline(data_dir: str | Path, year: int, run_dates) -> dict:
+    """The run dates of a campaign on ONE design (us_potus_model_amd.timeline): the data list of the LAST run date, exactly what build_2016 /
+    build_backtest return for it, plus per run date the polls it has seen (keep_state [n, N_state_polls], keep_national [n, N_national_polls]),
+    its mu_b_prior [n, S] and its mu_b_T_scale [n].  Every date is checked against build_*(run_date = that date): the kept polls are the same
+    multiset of (state, day, pollster name, mode, population, n_two_share, n_democrat, unadjusted); T, state_weights and state_covariance_0 are
+    equal; prior and scale are that build's, bit for bit.  A date for which the last date's design does not serve -- so early that the first
+    day moves, or one at which the de-duplication keeps another poll -- raises ValueError naming the date and what differed."""
+    from collections import Counter
+    data_dir = Path(data_dir)
+    run_dates = [str(pd.Timestamp(r).date()) for r in run_dates]
+    if not run_dates or sorted(run_dates) != run_dates:
+        raise ValueError("build_timeline: run_dates must be given in ascending order")
+
+    def build(r):
+        return build_2016(data_dir, r, _levels=True) if int(year) == 2016 else build_backtest(data_dir, int(year), r)
+    last = build(run_dates[-1])
+    D = last["data"]
+    S = int(D["S"])
+    keys_last = {k: _poll_keys(last, k) for k in ("state", "national")}
+    keep = {k: np.zeros((len(run_dates), len(keys_last[k])), bool) for k in keys_last}
+    prior, scale = np.zeros((len(run_dates), S)), np.zeros(len(run_dates))
+    for j, r in enumerate(run_dates):
+        try:
+            b = last if j == len(run_dates) - 1 else build(r)
+        except (ValueError, AssertionError, KeyError) as e:     # e.g. a date before the first poll, or before every state has a prior
+            raise ValueError(f"build_timeline: run date {r}: the data list of that date cannot be built ({type(e).__name__}: {e})") from e
+        d = b["data"]
+        if int(d["T"]) != int(D["T"]) or b["meta"]["first_day"] != last["meta"]["first_day"]:
+            raise ValueError(f"build_timeline: run date {r}: the first day moves (T = {d['T']} from {b['meta']['first_day']}, the last run date has "
+                             f"T = {D['T']} from {last['meta']['first_day']})")
+        for name in ("state_weights", "state_covariance_0"):
+            if np.asarray(d[name]).tobytes() != np.asarray(D[name]).tobytes():
+                raise ValueError(f"build_timeline: run date {r}: {name} differs from the last run date's")
+        for k in ("state", "national"):
+            want = Counter(_poll_keys(b, k))
+            for i, key in enumerate(keys_last[k]):
+                if want[key] > 0:
+                    want[key] -= 1
+                    keep[k][j, i] = True
+            left = +want
+            if left:
+                raise ValueError(f"build_timeline: run date {r}: {sum(left.values())} {k} poll(s) of that date are not in the last run date's design "
+                                 f"(another day origin, or the de-duplication keeps another poll), e.g. {next(iter(left))}")
+        prior[j], scale[j] = np.asarray(d["mu_b_prior"], dtype=np.float64), float(d["mu_b_T_scale"])
+    built = dict(data=D, meta=last["meta"])
+    return dict(built, keep_state=keep["state"], keep_national=keep["national"], mu_b_prior=prior, mu_b_T_scale=scale, run_dates=run_dates)
 
 
 def save_npz(path: str | Path, built: dict) -> None:

@@ -115,6 +115,12 @@ def load_library():
         L.potus_scenario_device.argtypes = [C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int, dp, C.c_int, dp, dp, i32p, C.c_int, llp, dp, dp, llp, llp, llp]
         L.potus_scenario_timing.argtypes = [dp]
         L.potus_R_scenario.argtypes = [ip, ip, ip, dp, dp, ip, dp, dp, dp, dp, dp, dp, ip]
+    if hasattr(L, "potus_timeline"):                    # run dates as the data sets of one handle (timeline.py)
+        i32p = C.POINTER(C.c_int32)
+        L.potus_set_datasets_ex.argtypes = [C.c_int, C.c_int, i32p, i32p, i32p, i32p, dp, dp]
+        L.potus_timeline.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, dp, dp, i32p]
+        L.potus_timeline_scores_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.potus_timeline_timing.argtypes = [dp]
     _LIB = L
     return L
 
@@ -127,6 +133,7 @@ EXPORTS = [
     "potus_last_run_timing", "potus_posterior_summary", "potus_posterior_summary_many", "potus_backtest_scores",
     "potus_diagnostics", "potus_diagnostics_device", "potus_check_convergence",
     "potus_set_datasets", "potus_simulate_prior", "potus_constrain", "potus_sbc_ranks",
+    "potus_set_datasets_ex", "potus_timeline", "potus_timeline_scores_device", "potus_timeline_timing",
     "potus_log_lik_device", "potus_loo_device", "potus_loo",
     "potus_outcomes", "potus_outcomes_device", "potus_outcomes_timing",
     "potus_monitor", "potus_monitor_device",
@@ -134,6 +141,7 @@ EXPORTS = [
     "potus_R_create", "potus_R_init", "potus_R_run", "potus_R_run_many", "potus_R_num_columns", "potus_R_saved_count",
     "potus_R_write_array", "potus_R_write_stan_csv", "potus_R_posterior_summary", "potus_R_diagnostics", "potus_R_check_convergence", "potus_R_backtest_scores", "potus_R_last_error", "potus_R_destroy",
     "potus_R_set_datasets", "potus_R_simulate_prior", "potus_R_sbc_ranks", "potus_R_constrain", "potus_R_loo", "potus_R_outcomes", "potus_R_monitor", "potus_R_scenario",
+    "potus_R_set_datasets_ex", "potus_R_timeline",
 ]
 
 
@@ -353,6 +361,63 @@ class Handle:
             raise ValueError(f"{ys.shape[0]} state and {yn.shape[0]} national outcome vectors")
         _check(self.L, self.L.potus_set_datasets(self.h, n, _ip(ys), _ip(yn)))
         self.n_datasets = n
+
+    def set_datasets_ex(self, n_democrat_state=None, n_democrat_national=None, n_two_share_state=None, n_two_share_national=None,
+                        mu_b_prior=None, mu_b_T_scale=None, n=None):
+        """potus_set_datasets_ex: data sets that may differ in the poll outcomes and sizes ([n, N_state_polls], [n, N_national_polls];
+        n_two_share = 0: the data set has not seen the poll), mu_b_prior [n, S] and mu_b_T_scale [n].  None = the handle's own for every data set."""
+        Ns, Nn, S = int(self.data["N_state_polls"]), int(self.data["N_national_polls"]), int(self.data["S"])
+        given = [(a, w) for a, w in ((n_democrat_state, Ns), (n_two_share_state, Ns), (n_democrat_national, Nn), (n_two_share_national, Nn),
+                                     (mu_b_prior, S), (mu_b_T_scale, 1)) if a is not None and w]
+        counts = {np.asarray(a).reshape(-1, w).shape[0] for a, w in given} | ({int(n)} if n is not None else set())
+        if len(counts) != 1:
+            raise ValueError(f"set_datasets_ex: the arrays give {sorted(counts)} data sets (pass n when every array is None)")
+        n = counts.pop()
+        keep = []
+
+        def ints(a, w):
+            if a is None or not w:
+                return None
+            keep.append(np.ascontiguousarray(np.asarray(a, dtype=np.int32).reshape(n, w)))
+            return _ip(keep[-1])
+
+        def dbls(a, w):
+            if a is None:
+                return None
+            keep.append(np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(n, w)))
+            return _dp(keep[-1])
+        _check(self.L, self.L.potus_set_datasets_ex(self.h, n, ints(n_democrat_state, Ns), ints(n_democrat_national, Nn), ints(n_two_share_state, Ns),
+                                                    ints(n_two_share_national, Nn), dbls(mu_b_prior, S), dbls(mu_b_T_scale, 1)))
+        self.n_datasets = n
+
+    def timeline(self, ev, days=None, ev_to_win=270):
+        """potus_timeline: per data set of this handle and per day of `days` = (begin, end) (0-based, default: election day only) the summaries of
+        posterior_summary over the data set's post-warm-up draws.  dict(state [n, days, S, 4], national [n, days, 4], electoral_votes [n, days, 5],
+        n_draws [n]); a data set with a failed chain has n_draws = 0 and NaN."""
+        S, T = int(self.data["S"]), int(self.data["T"])
+        t0, t1 = (T - 1, T) if days is None else (int(days[0]), int(days[1]))
+        n, nd = int(getattr(self, "n_datasets", 1)), max(t1 - t0, 0)
+        ev = np.ascontiguousarray(ev, dtype=np.float64).reshape(S)
+        st, na, eo, cnt = np.zeros((n, nd, S, 4)), np.zeros((n, nd, 4)), np.zeros((n, nd, 5)), np.zeros(n, np.int32)
+        _check(self.L, self.L.potus_timeline(self.h, t0, t1, _dp(ev), int(ev_to_win), _dp(st), _dp(na), _dp(eo), _ip(cnt)))
+        return dict(state=st, national=na, electoral_votes=eo, n_draws=cnt)
+
+    def timeline_scores_device(self, days=None):
+        """potus_timeline_scores_device: predicted_score of the days (begin, end) as a torch tensor [n_datasets, draws per data set, days, S] on this handle's GPU."""
+        import torch
+        T, S = int(self.data["T"]), int(self.data["S"])
+        t0, t1 = (T - 1, T) if days is None else (int(days[0]), int(days[1]))
+        n = int(getattr(self, "n_datasets", 1))
+        per = (self.opts.chains // n) * self.post_warmup_saved()
+        out = torch.empty((n, per, max(t1 - t0, 1), S), dtype=torch.float64, device=f"cuda:{self.opts.device}")
+        torch.cuda.current_stream(out.device).synchronize()
+        _check(self.L, self.L.potus_timeline_scores_device(self.h, t0, t1, C.c_void_p(out.data_ptr())))
+        return out
+
+    def timeline_timing(self):
+        ms = np.zeros(2)
+        _check(self.L, self.L.potus_timeline_timing(_dp(ms)))
+        return dict(scores_ms=float(ms[0]), summary_ms=float(ms[1]))
 
     def simulate_prior(self, seed, n_sims, sim_offset=0):
         """potus_simulate_prior: (q [n_sims, D], n_democrat_state [n_sims, Ns], n_democrat_national [n_sims, Nn]) drawn from the prior
