@@ -378,6 +378,46 @@ potus_loo_compare <- function(...) {
   out
 }
 
+# ---- exact K-fold cross-validation (us_potus_model_amd/crossval.py is the same in Python; DESIGN.md section 4j) ----
+# Every fold refitted, all folds as the chains of ONE launch: fold k is a data set in which the polls with fold == k keep their place in the design with
+# n_two_share = 0, and potus_cv_lpd evaluates each of them under the draws of the fold that did not see it (real y and n; integrate = TRUE: the poll's
+# noise coordinate integrated over its N(0,1) prior, the exact predictive density).  fold: one number in 1..K per poll, state polls then national
+# polls (e.g. sample(rep_len(1:K, N)), or one number per pollster for leave-pollster-out).
+# Returns list(pointwise = [N, 2] (elpd, mcse: delta method, draws taken as independent), elpd_kfold, se = sqrt(N) sd(elpd), fold, n_draws [K]);
+# a fold with a failed chain is an error.
+potus_kfold <- function(data, fold, variant = c("full", "no_mode_adjustment"), chains_per_fold = 4, iter_warmup = 1000, iter_sampling = 1000,
+                        integrate = TRUE, seed = 1843, device = 0) {
+  variant <- match.arg(variant)
+  Ns <- as.integer(data$N_state_polls); Nn <- as.integer(data$N_national_polls); N <- Ns + Nn
+  fold <- as.integer(fold); K <- max(fold)
+  if (length(fold) != N || min(fold) < 1L) stop("potus_kfold: fold must hold one number in 1..K per poll (state polls, then national polls)")
+  held <- outer(seq_len(K), fold, "==")                                                    # [K, N]
+  counts <- function(v, keep) as.integer(t(keep * matrix(as.integer(v), K, length(v), byrow = TRUE)))   # [K][polls], row-major
+  res <- .potus_create(data, variant, c(K * chains_per_fold, 0L, iter_warmup, iter_sampling, 10L, as.integer(device), 0L, 1L, 0L, 0L, 0L, 0L),
+                       c(0.8, 0.05, 0.75, 10, 1, 2, seed))
+  .potus_check(res$status)
+  on.exit(.C("potus_R_destroy", res$handle, status = integer(1)))
+  ks <- !held[, seq_len(Ns), drop = FALSE]; kn <- !held[, Ns + seq_len(Nn), drop = FALSE]
+  .potus_check(.C("potus_R_set_datasets_ex", res$handle, K, counts(data$n_democrat_state, ks), counts(data$n_democrat_national, kn),
+                  counts(data$n_two_share_state, ks), counts(data$n_two_share_national, kn), 0L, double(1), 0L, double(1), status = integer(1))$status)
+  .potus_check(.C("potus_R_init", res$handle, status = integer(1))$status)
+  .potus_check(.C("potus_R_run", res$handle, as.integer(iter_warmup + iter_sampling), status = integer(1))$status)
+  if (is.loaded("potus_call_cv_lpd")) {
+    v <- .Call("potus_call_cv_lpd", res$handle, as.integer(t(!ks)), as.integer(t(!kn)), K, as.integer(isTRUE(integrate)))
+    r <- list(lpd = v[seq_len(K * N * 2)], n_draws = as.integer(v[K * N * 2 + seq_len(K)]))
+  } else {
+    r <- .C("potus_R_cv_lpd", res$handle, as.integer(t(!ks)), as.integer(t(!kn)), as.integer(isTRUE(integrate)), lpd = double(K * N * 2),
+            n_draws = integer(K), status = integer(1))
+    .potus_check(r$status)
+  }
+  if (any(r$n_draws == 0L)) stop(sprintf("potus_kfold: fold %d: a chain of its fit failed", which(r$n_draws == 0L)[1]))
+  lpd <- aperm(array(r$lpd, c(2, N, K)), 3:1)                                              # [K, N, 2]
+  at <- cbind(fold, seq_len(N))
+  elpd <- lpd[, , 1][at]
+  mcse <- sqrt(pmax(expm1(lpd[, , 2][at] - 2 * elpd), 0) / r$n_draws[fold])
+  list(pointwise = cbind(elpd = elpd, mcse = mcse), elpd_kfold = sum(elpd), se = sqrt(N) * sd(elpd), fold = fold, n_draws = r$n_draws)
+}
+
 # ---- joint election outcomes (us_potus_model_amd/outcomes.py is the same in Python; DESIGN.md section 4f) ----
 # What the run scripts compute from the JOINT outcome of a draw, counted on the device over the post-warm-up draws of every chain of the fit:
 # the distribution of Democratic electoral votes (final_2016.R:904-920), the tipping-point state (final_2012.R:809-843), how often states i and j

@@ -60,3 +60,21 @@ SEXP potus_call_sampler_params(SEXP handles) {
   UNPROTECT(2);
   return out;
 }
+
+/* potus_cv_lpd (exact cross-validation; potus_kfold() of the shim prefers it when loaded): held_state / held_national are integer vectors
+ * [n_datasets x polls], data set after data set.  One numeric vector comes back, allocated once: [n_datasets][polls][2] (log mean p, log mean p^2;
+ * NaN where the pair was not asked for), then the n_datasets draw counts (0 = a chain of the data set failed). */
+SEXP potus_call_cv_lpd(SEXP handle, SEXP held_state, SEXP held_national, SEXP n_datasets, SEXP integrate) {
+  if (!Rf_isInteger(handle) || LENGTH(handle) != 1) Rf_error("potus_call_cv_lpd: handle must be one integer");
+  if (!Rf_isInteger(held_state) || !Rf_isInteger(held_national)) Rf_error("potus_call_cv_lpd: the masks must be integer vectors");
+  const int n = Rf_asInteger(n_datasets);
+  if (n < 1 || LENGTH(held_state) % n || LENGTH(held_national) % n) Rf_error("potus_call_cv_lpd: the masks do not hold n_datasets rows");
+  const R_xlen_t cells = (R_xlen_t)2 * (LENGTH(held_state) + LENGTH(held_national));
+  SEXP out = PROTECT(Rf_allocVector(REALSXP, cells + n));
+  SEXP cnt = PROTECT(Rf_allocVector(INTSXP, n));
+  const int status = potus_cv_lpd(INTEGER(handle)[0], INTEGER(held_state), INTEGER(held_national), Rf_asInteger(integrate), REAL(out), INTEGER(cnt));
+  for (int k = 0; k < n && !status; k++) REAL(out)[cells + k] = (double)INTEGER(cnt)[k];
+  UNPROTECT(2);
+  if (status) potus_call_fail(status);
+  return out;
+}

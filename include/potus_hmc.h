@@ -383,6 +383,30 @@ int potus_timeline(int handle, int day_begin, int day_end, const double *ev /*[S
 int potus_timeline_scores_device(int handle, int day_begin, int day_end, void *out_device);
 /* Milliseconds (HIP events) of the calling thread's last potus_timeline: the scores kernel, the summary kernel. */
 int potus_timeline_timing(double *ms /*[2]*/);
+/* ---- exact cross-validation: held-out polls under the draws of the data set that did not see them ----
+ * A fold of K-fold cross-validation, or a run date of leave-future-out, is a data set of potus_set_datasets_ex whose held-out polls have
+ * n_two_share = 0.  For every (data set, poll) pair the masks name, the calls evaluate log p(y | n, draw) on the data set's post-warm-up draws
+ * (warm-up rows of save_warmup = 1 are left out) with the data set's own model -- its prior and scale -- and the y, n and sigma of the data
+ * given to potus_create.  integrate = 1: the poll's noise coordinate integrated over its N(0,1) prior, the exact predictive density of a poll
+ * the data set has not seen; integrate = 0: at the draw's own noise coordinate.  Handles of potus_set_datasets[_ex], and a plain handle,
+ * which counts as one data set (in-sample values: those of potus_log_lik_device, byte for byte).  Refused before any kernel runs: a NULL mask or
+ * output (POTUS_ERR_ARG; out_device = NULL is the exception below), a handle that is not initialised or has no post-warm-up draw saved
+ * (POTUS_ERR_STATE), the dense metric (POTUS_ERR_UNSUPPORTED).  All-zero masks are no error: n_pairs = 0 and every output cell is NaN.
+ * The same handle and masks give the same bytes on every call.
+ * held_state [n_datasets][N_state_polls], held_national [n_datasets][N_national_polls]: nonzero = evaluate this poll under this
+ * data set's draws (caller's poll order).  out_device [n_pairs][draws per data set]; out_device = NULL: only *n_pairs.
+ * Pairs are ordered by data set, then state polls in data order, then national polls; a data set's draws in canonical order (its chains
+ * one after another, iterations within).  The pairs of a data set with a failed chain (potus_chain_status) are NaN. */
+int potus_cv_log_lik_device(int handle, const int32_t *held_state, const int32_t *held_national, int integrate,
+                            void *out_device, long long *n_pairs);
+/* lpd_out [n_datasets][N_state_polls + N_national_polls][2] = log mean p, log mean p^2 over the data set's post-warm-up draws;
+ * NaN where the pair was not asked for; n_draws_out [n_datasets] (0 for a data set with a failed chain).  The Monte-Carlo variance of the
+ * first slot is (exp(slot1 - 2 slot0) - 1) / n_draws by the delta method, with the draws taken as independent.  The pairs are worked in
+ * blocks whose log-likelihood buffer stays within 256 MB (environment variable POTUS_CV_BLOCK_BUDGET, bytes: tests); the results do not
+ * depend on the blocking. */
+int potus_cv_lpd(int handle, const int32_t *held_state, const int32_t *held_national, int integrate,
+                 double *lpd_out, int32_t *n_draws_out);
+int potus_cv_timing(double *ms /*[2]: k_cv_loglik, k_cv_reduce, HIP events, calling thread's last potus_cv_lpd*/);
 /* Prior predictive simulation: n_sims draws theta ~ prior (poll_model_2020.stan:116-128) on the unconstrained scale (q_out [n_sims][D];
  * rho_e_bias ~ normal(0.7, 0.1) restricted to (0, 1), stored as logit(rho)) and y ~ binomial(n_two_share, inv_logit(logit_pi(theta)))
  * (stan:85-113; exact sampler: inversion when n min(p, 1 - p) < 10, BTRS above) in the caller's poll order.  Any output may be null.
@@ -525,6 +549,7 @@ void potus_R_set_datasets_ex(int *handle, int *n_datasets, int *n_democrat_state
                              int *has_prior, double *mu_b_prior, int *has_scale, double *mu_b_T_scale, int *status);
 void potus_R_timeline(int *handle, int *day_begin, int *day_end, double *ev, int *ev_to_win, double *state_out, double *natl_out, double *ev_out,
                       int *n_draws_out, int *status);
+void potus_R_cv_lpd(int *handle, int *held_state, int *held_national, int *integrate, double *lpd_out, int *n_draws_out, int *status);
 void potus_R_simulate_prior(int *handle, double *seed, int *dims /*[2]: n_sims, sim_offset*/, double *q_out, int *n_democrat_state_out,
                             int *n_democrat_national_out, int *status);
 void potus_R_sbc_ranks(int *handle, double *truth, int *cols /*[3]: col_begin, col_end, thin*/, int *less, int *equal, int *L, int *status);

@@ -2,12 +2,14 @@
 """The forecast timeline of a campaign: N run dates fitted as chains of one launch and summarised on the device, next to the loop of
 stand-alone fits it replaces (us_potus_model_amd.timeline).
 
-  python scripts/timeline.py --design 2016 --dates 32 --chains 4 [--warmup 200 --samples 200] [--no-loop]
+  python scripts/timeline.py --design 2016 --dates 32 --chains 4 [--warmup 200 --samples 200] [--no-loop] [--lfo]
 
 Reads tests/golden/data_2016.npz and tests/golden/timeline_2016.npz (the masks, priors and scales of 32 run dates, every fourth day up to
 election day; scripts/make_timeline_fixture.py).  --design small: four data sets of the synthetic design instead.
 Prints the wall time of the one-launch fit, of the loop of stand-alone fits of the same dates (skipped with --no-loop), potus_timeline's
-kernel times next to the numpy restatement's, and the election-day forecast per run date."""
+kernel times next to the numpy restatement's, and the election-day forecast per run date.  --lfo adds leave-future-out (Timeline.lfo,
+DESIGN.md section 4j): per run date the exact log predictive density of the polls that arrived before the next run date, under the date's
+own draws, with no refit."""
 import argparse
 import sys
 import time
@@ -54,6 +56,7 @@ def main():
     ap.add_argument("--samples", type=int, default=200)
     ap.add_argument("--seed", type=int, default=1843)
     ap.add_argument("--no-loop", action="store_true", help="skip the loop of stand-alone fits")
+    ap.add_argument("--lfo", action="store_true", help="leave-future-out: score every run date on the polls that arrived before the next one")
     ap.add_argument("--loop-one-workgroup", action="store_true", help="the loop's fits with one workgroup per chain (the bytes of the one launch) "
                                                                       "instead of the layout the library picks for a 4-chain handle")
     a = ap.parse_args()
@@ -89,6 +92,18 @@ def main():
         na, e = s["national"][d, 0], s["electoral_votes"][d, 0]
         polls = int(design["keep_state"][d].sum() + design["keep_national"][d].sum())
         print(f"{str(design['run_dates'][d]):12s} {polls:5d}  {na[0]:.4f} {na[2]:.4f} {na[1]:.4f}            {e[0]:7.1f}  {e[4]:.3f}    {sd['rhat_max'][d]:.3f}   {sd['ess_bulk_min'][d]:.0f}")
+    if a.lfo:
+        t0 = time.perf_counter()
+        f = tl.lfo()
+        wall_lfo = time.perf_counter() - t0
+        ms = tl.handle.cv_timing()
+        print(f"leave-future-out: {wall_lfo * 1e3:8.2f} ms wall, one potus_cv_lpd call, {int(f['n_held'].sum())} (date, poll) pairs "
+              f"(kernels: k_cv_loglik {ms['loglik_ms']:.3f} ms, k_cv_reduce {ms['reduce_ms']:.3f} ms)")
+        print("run date     polls arriving before the next date   elpd (sum)   elpd per poll")
+        for d in range(n):
+            k = int(f["n_held"][d])
+            print(f"{str(design['run_dates'][d]):12s} {k:5d}                                 {f['elpd'][d]:10.2f}   {f['elpd'][d] / k if k else float('nan'):8.3f}")
+        print(f"total: {int(f['n_held'].sum())} polls, elpd_lfo {np.nansum(f['elpd']):.1f}")
     tl.close()
 
     if not a.no_loop:

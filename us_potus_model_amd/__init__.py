@@ -2,7 +2,7 @@
 
 Layout: csrc/ (HIP kernels + the C ABI of include/potus_hmc.h), sampler.py (host mirror of the
 reference's `$sample()` / `rstan::extract()` surface), dataprep.py / synthetic.py (Stan data
-lists), diagnostics.py (R-hat / ESS), outcomes.py (joint election outcomes: EV histogram, tipping point), monitor.py (the posterior summary table), scenario.py (conditional forecasts, covariance of the state scores), _abi.py (ctypes structs).
+lists), diagnostics.py (R-hat / ESS), outcomes.py (joint election outcomes: EV histogram, tipping point), monitor.py (the posterior summary table), scenario.py (conditional forecasts, covariance of the state scores), timeline.py (run dates as the data sets of one handle), crossval.py (exact K-fold and leave-future-out cross-validation), _abi.py (ctypes structs).
 """
 from . import _abi  # noqa: F401
 from .sampler import (Handle, PotusError, PotusModel, StanFit, backtest_scores, check_convergence, device_diagnostics, device_diagnostics_of_block,  # noqa: F401

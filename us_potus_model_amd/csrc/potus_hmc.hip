@@ -1117,6 +1117,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, c
 #include "potus_outcomes.hpp"   // joint election outcomes: EV histogram, tipping point, joint win counts
 #include "potus_scenario.hpp"   // conditional forecasts and the covariance of the state scores
 #include "potus_timeline.hpp"   // run dates as the data sets of one handle: their rows, scores and summaries
+#include "potus_crossval.hpp"   // exact cross-validation: held-out polls under the draws of the data set that did not see them
 
 // ======================================================================== host
 namespace {
@@ -2486,7 +2487,7 @@ size_t sorted_run_lds(long long n) {
 // ======================================================================== C ABI
 extern "C" {
 
-const char *potus_version(void) { return "potus_hmc 0.5 (gfx950)"; }   // 0.5: potus_opts.pooled_metric (round 6);   // 0.4: potus_opts.metric_storage (round 3), potus_diagnostics* (round 4)
+const char *potus_version(void) { return "potus_hmc 0.5 (gfx950)"; }   // 0.5: potus_opts.pooled_metric (round 6), and the entry points added since without a change to potus_opts (... potus_timeline*, potus_cv_*);   // 0.4: potus_opts.metric_storage (round 3), potus_diagnostics* (round 4)
 
 int potus_last_error(char *buf, int len) {
   if (buf && len > 0) { std::snprintf(buf, (size_t)len, "%s", g_err.c_str()); }
@@ -4508,6 +4509,160 @@ int potus_timeline_timing(double *ms) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------- exact cross-validation (potus_crossval.hpp)
+namespace {
+constexpr size_t CV_BLOCK_BUDGET = 256ull << 20;   // the ll block of one round of potus_cv_lpd (POTUS_CV_BLOCK_BUDGET, bytes: tests)
+thread_local double g_cv_ms[2] = {0.0, 0.0};       // the calling thread's last potus_cv_lpd: k_cv_loglik, k_cv_reduce (HIP events, summed over the blocks)
+
+struct CvPlan {
+  int n_ds = 1, cpd = 1, Np = 0, first = 0, n_post = 0;
+  std::vector<int> off, held, pair_ds, pair_k, skip;   // pairs by data set, then by poll number; held = the pair's poll in the model's order
+  const DevModel *Mg = nullptr;
+  long long n_pairs() const { return (long long)held.size(); }
+};
+// every refusal that needs no device, and the held lists in the model's poll order (the qi mapping k_loo_loglik inverts)
+int cv_check_args(const char *what, Sampler *sp, const int32_t *held_state, const int32_t *held_national, int integrate, CvPlan &pl) {
+  const int Ns = sp->M.Ns, Nn = sp->M.Nn, Np = Ns + Nn, S = sp->M.S;
+  if ((Ns && !held_state) || (Nn && !held_national)) return fail(POTUS_ERR_ARG, "%s: null mask", what);
+  if (integrate != 0 && integrate != 1) return fail(POTUS_ERR_ARG, "%s: integrate = %d (0: the draw's noise coordinate, 1: integrated out)", what, integrate);
+  if (sp->dense) return fail(POTUS_ERR_UNSUPPORTED, "%s: the dense metric is not supported (metric = POTUS_METRIC_DIAG only)", what);
+  if (!sp->inited) return fail(POTUS_ERR_STATE, "%s: the handle is not initialised (potus_init, then potus_run)", what);
+  pl.n_ds = std::max(sp->n_ds, 1); pl.cpd = sp->chains_per_ds(); pl.Np = Np;
+  std::vector<int> model_of(Np, -1);
+  for (int i = 0; i < Np; i++) {   // day-sorted poll i is state poll qidx - o_ns or national poll qidx - o_nn (build_model)
+    const int qi = sp->h_pq[i];
+    model_of[sp->h_ps[i] == S ? Ns + (qi - sp->M.o_nn) : qi - sp->M.o_ns] = i;
+  }
+  pl.off.assign(1, 0);
+  for (int d = 0; d < pl.n_ds; d++) {
+    for (int k = 0; k < Np; k++)
+      if (k < Ns ? held_state[(size_t)d * Ns + k] : held_national[(size_t)d * Nn + (k - Ns)]) { pl.held.push_back(model_of[k]); pl.pair_ds.push_back(d); pl.pair_k.push_back(k); }
+    pl.off.push_back((int)pl.held.size());
+  }
+  return 0;
+}
+int cv_plan(const char *what, Sampler *sp, CvPlan &pl) {   // under the device lock, before anything is allocated or launched
+  std::vector<ChainScalars> sc;
+  if (const int rc = read_scalars(sp, sc)) return rc;
+  int n_saved = 0;
+  if (const int rc = saved_count(sp, &n_saved)) return rc;
+  pl.first = warm_rows(sp, n_saved); pl.n_post = n_saved - pl.first;
+  if (pl.n_post < 1) return fail(POTUS_ERR_STATE, "%s: no post-warm-up draws saved yet (%d saved, %d of them warm-up)", what, n_saved, pl.first);
+  pl.skip.assign(pl.n_ds, 0);
+  for (int c = 0; c < sp->R.chains; c++) if (sc[c].status != 0) pl.skip[c / pl.cpd] = 1;
+  pl.Mg = sp->n_ds ? sp->dMs : sp->dM;
+  return 0;
+}
+struct CvDev { LooRows rows; int *off = nullptr, *held = nullptr, *pair_ds = nullptr, *skip = nullptr; };
+int cv_upload(const char *what, Sampler *sp, const CvPlan &pl, DevBufs &keep, CvDev &d) {
+  int rc;
+  if ((rc = loo_rows_setup(sp, (long long)pl.n_post * sp->R.chains, keep, d.rows, what))) return rc;
+  const size_t np = (size_t)pl.n_pairs();
+  if ((rc = keep.get(&d.off, pl.off.size() * 4, what)) || (rc = keep.get(&d.held, np * 4, what)) || (rc = keep.get(&d.pair_ds, np * 4, what)) ||
+      (rc = keep.get(&d.skip, (size_t)pl.n_ds * 4, what))) return rc;
+  HIP_TRY(hipMemcpyAsync(d.off, pl.off.data(), pl.off.size() * 4, hipMemcpyHostToDevice, sp->stream));
+  HIP_TRY(hipMemcpyAsync(d.held, pl.held.data(), np * 4, hipMemcpyHostToDevice, sp->stream));
+  HIP_TRY(hipMemcpyAsync(d.pair_ds, pl.pair_ds.data(), np * 4, hipMemcpyHostToDevice, sp->stream));
+  HIP_TRY(hipMemcpyAsync(d.skip, pl.skip.data(), (size_t)pl.n_ds * 4, hipMemcpyHostToDevice, sp->stream));
+  return 0;
+}
+// ll of pairs [p0, p1) -> out [p1 - p0][draws per data set], on the handle's stream
+int cv_loglik(Sampler *sp, const CvPlan &pl, const CvDev &d, int p0, int p1, int integrate, double *out) {
+  CvParams P{sp->R.draws, sp->R.chains, sp->R.n_save_max, sp->R.row, sp->L.ncols, pl.first, pl.n_post, pl.cpd, integrate,
+             sp->M.pd, d.rows.lc, d.off, d.held, d.skip, p0, p1, d.rows.scratch, out};
+  hipLaunchKernelGGL(k_cv_loglik, dim3(d.rows.grid), dim3(256), 0, sp->stream, pl.Mg, P);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+} // namespace
+
+int potus_cv_log_lik_device(int handle, const int32_t *held_state, const int32_t *held_national, int integrate, void *out_device, long long *n_pairs) {
+  const char *what = "potus_cv_log_lik_device";
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  if (!out_device && !n_pairs) return fail(POTUS_ERR_ARG, "%s: null output", what);
+  CvPlan pl;
+  if (const int rc_ = cv_check_args(what, sp, held_state, held_national, integrate, pl)) return rc_;
+  if (n_pairs) *n_pairs = pl.n_pairs();
+  if (!out_device) return 0;
+  if (pl.n_pairs() == 0) {   // nothing to write: only the state of the handle is left to check
+    DeviceGuard guard;
+    DeviceLocks lock(sp->device);
+    HIP_TRY(hipSetDevice(sp->device));
+    return cv_plan(what, sp, pl);
+  }
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, sp->device, out_device, "output")) return rc_;
+  if (const int rc_ = cv_plan(what, sp, pl)) return rc_;
+  DevBufs keep;
+  CvDev d;
+  if (const int rc_ = cv_upload(what, sp, pl, keep, d)) return rc_;
+  if (const int rc_ = cv_loglik(sp, pl, d, 0, (int)pl.n_pairs(), integrate, (double *)out_device)) return rc_;
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  return 0;
+}
+
+int potus_cv_lpd(int handle, const int32_t *held_state, const int32_t *held_national, int integrate, double *lpd_out, int32_t *n_draws_out) {
+  const char *what = "potus_cv_lpd";
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  if (!lpd_out || !n_draws_out) return fail(POTUS_ERR_ARG, "%s: null output", what);
+  CvPlan pl;
+  if (const int rc_ = cv_check_args(what, sp, held_state, held_national, integrate, pl)) return rc_;
+  DeviceGuard guard;
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  if (const int rc_ = cv_plan(what, sp, pl)) return rc_;
+  const long long nd = (long long)pl.cpd * pl.n_post;
+  const int np = (int)pl.n_pairs();
+  for (size_t i = 0; i < (size_t)pl.n_ds * pl.Np * 2; i++) lpd_out[i] = std::numeric_limits<double>::quiet_NaN();
+  for (int k = 0; k < pl.n_ds; k++) n_draws_out[k] = pl.skip[k] ? 0 : (int32_t)nd;
+  g_cv_ms[0] = g_cv_ms[1] = 0.0;
+  if (np == 0) return 0;
+  size_t budget = CV_BLOCK_BUDGET;
+  if (const char *e = getenv("POTUS_CV_BLOCK_BUDGET")) budget = std::max<size_t>(1, (size_t)atoll(e));
+  const int nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)np, budget / ((size_t)nd * 8)));   // pairs per block
+  DevBufs keep;
+  CvDev d;
+  int rc;
+  if ((rc = cv_upload(what, sp, pl, keep, d))) return rc;
+  double *blk = nullptr, *dout = nullptr;
+  if ((rc = keep.get(&blk, (size_t)nb * nd * 8, what)) || (rc = keep.get(&dout, (size_t)np * 2 * 8, what))) return rc;
+  const int n_blocks = (np + nb - 1) / nb;
+  std::vector<OcEvents> e0(n_blocks), e1(n_blocks);
+  for (int b = 0; b < n_blocks; b++) {
+    const int p0 = b * nb, p1 = std::min(p0 + nb, np);
+    HIP_TRY(hipEventCreate(&e0[b].a)); HIP_TRY(hipEventCreate(&e0[b].b)); HIP_TRY(hipEventCreate(&e1[b].a)); HIP_TRY(hipEventCreate(&e1[b].b));
+    HIP_TRY(hipEventRecord(e0[b].a, sp->stream));
+    if ((rc = cv_loglik(sp, pl, d, p0, p1, integrate, blk))) return rc;
+    HIP_TRY(hipEventRecord(e0[b].b, sp->stream));
+    CvReduceParams Q{blk, d.pair_ds + p0, d.skip, p1 - p0, (int)nd, dout + (size_t)p0 * 2};
+    HIP_TRY(hipEventRecord(e1[b].a, sp->stream));
+    hipLaunchKernelGGL(k_cv_reduce, dim3((unsigned)std::min((p1 - p0 + 3) / 4, 65535)), dim3(256), 0, sp->stream, Q);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipEventRecord(e1[b].b, sp->stream));
+  }
+  std::vector<double> h((size_t)np * 2);
+  HIP_TRY(hipMemcpyAsync(h.data(), dout, h.size() * 8, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  for (int b = 0; b < n_blocks; b++) {
+    float ms0 = 0, ms1 = 0;
+    HIP_TRY(hipEventElapsedTime(&ms0, e0[b].a, e0[b].b)); HIP_TRY(hipEventElapsedTime(&ms1, e1[b].a, e1[b].b));
+    g_cv_ms[0] += ms0; g_cv_ms[1] += ms1;
+  }
+  for (int p = 0; p < np; p++) {
+    double *o = lpd_out + ((size_t)pl.pair_ds[p] * pl.Np + pl.pair_k[p]) * 2;
+    o[0] = h[(size_t)p * 2]; o[1] = h[(size_t)p * 2 + 1];
+  }
+  return 0;
+}
+
+int potus_cv_timing(double *ms) {
+  if (!ms) return fail(POTUS_ERR_ARG, "potus_cv_timing: null output");
+  ms[0] = g_cv_ms[0]; ms[1] = g_cv_ms[1];
+  return 0;
+}
+
 int potus_simulate_prior(int handle, uint64_t seed, int n_sims, int sim_offset, double *q_out, int32_t *n_democrat_state_out, int32_t *n_democrat_national_out) {
   Sampler *sp = get(handle);
   if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
@@ -4910,6 +5065,9 @@ void potus_R_set_datasets_ex(int *handle, int *n_datasets, int *n_democrat_state
 }
 void potus_R_timeline(int *handle, int *day_begin, int *day_end, double *ev, int *ev_to_win, double *state_out, double *natl_out, double *ev_out, int *n_draws_out, int *status) {
   *status = potus_timeline(*handle, *day_begin, *day_end, ev, *ev_to_win, state_out, natl_out, ev_out, n_draws_out);
+}
+void potus_R_cv_lpd(int *handle, int *held_state, int *held_national, int *integrate, double *lpd_out, int *n_draws_out, int *status) {
+  *status = potus_cv_lpd(*handle, held_state, held_national, *integrate, lpd_out, n_draws_out);
 }
 void potus_R_set_datasets(int *handle, int *n_datasets, int *n_democrat_state, int *n_democrat_national, int *status) {
   *status = potus_set_datasets(*handle, *n_datasets, n_democrat_state, n_democrat_national);

@@ -121,6 +121,12 @@ def load_library():
         L.potus_timeline.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, dp, dp, i32p]
         L.potus_timeline_scores_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.potus_timeline_timing.argtypes = [dp]
+    if hasattr(L, "potus_cv_lpd"):                      # exact cross-validation (crossval.py)
+        i32p = C.POINTER(C.c_int32)
+        L.potus_cv_log_lik_device.argtypes = [C.c_int, i32p, i32p, C.c_int, C.c_void_p, C.POINTER(C.c_longlong)]
+        L.potus_cv_lpd.argtypes = [C.c_int, i32p, i32p, C.c_int, dp, i32p]
+        L.potus_cv_timing.argtypes = [dp]
+        L.potus_R_cv_lpd.argtypes = [ip, ip, ip, ip, dp, ip, ip]
     _LIB = L
     return L
 
@@ -135,13 +141,14 @@ EXPORTS = [
     "potus_set_datasets", "potus_simulate_prior", "potus_constrain", "potus_sbc_ranks",
     "potus_set_datasets_ex", "potus_timeline", "potus_timeline_scores_device", "potus_timeline_timing",
     "potus_log_lik_device", "potus_loo_device", "potus_loo",
+    "potus_cv_log_lik_device", "potus_cv_lpd", "potus_cv_timing",
     "potus_outcomes", "potus_outcomes_device", "potus_outcomes_timing",
     "potus_monitor", "potus_monitor_device",
     "potus_scenario", "potus_scenario_device", "potus_scenario_timing",
     "potus_R_create", "potus_R_init", "potus_R_run", "potus_R_run_many", "potus_R_num_columns", "potus_R_saved_count",
     "potus_R_write_array", "potus_R_write_stan_csv", "potus_R_posterior_summary", "potus_R_diagnostics", "potus_R_check_convergence", "potus_R_backtest_scores", "potus_R_last_error", "potus_R_destroy",
     "potus_R_set_datasets", "potus_R_simulate_prior", "potus_R_sbc_ranks", "potus_R_constrain", "potus_R_loo", "potus_R_outcomes", "potus_R_monitor", "potus_R_scenario",
-    "potus_R_set_datasets_ex", "potus_R_timeline",
+    "potus_R_set_datasets_ex", "potus_R_timeline", "potus_R_cv_lpd",
 ]
 
 
@@ -464,6 +471,46 @@ class Handle:
             raise ValueError(f"tensor has {out.numel()} elements, {want} expected")
         _check(self.L, self.L.potus_log_lik_device(self.h, int(poll_begin), int(poll_end), int(bool(integrate)), C.c_void_p(out.data_ptr())))
         return out
+
+    def _cv_masks(self, held_state, held_national):
+        """The two masks as contiguous int32 [n_datasets, polls] arrays (None where the data have no such polls)."""
+        n = int(getattr(self, "n_datasets", 1))
+        out = []
+        for m, key in ((held_state, "N_state_polls"), (held_national, "N_national_polls")):
+            w = int(self.data[key])
+            a = np.ascontiguousarray(np.asarray(m).reshape(-1, w) != 0, dtype=np.int32) if w else np.zeros((n, 0), np.int32)
+            if a.shape[0] != n:
+                raise ValueError(f"cross-validation mask for {a.shape[0]} data sets, the handle holds {n}")
+            out.append(a)
+        return n, out[0], out[1]
+
+    def cv_log_lik_device(self, held_state, held_national, integrate=True):
+        """potus_cv_log_lik_device: log p(y | n, draw) of every (data set, poll) pair the masks [n_datasets, polls] name, over the data set's
+        post-warm-up draws, as a torch tensor [pairs, draws per data set] on this handle's GPU; pairs by data set, then state polls, then
+        national polls."""
+        import torch
+        n, ms, mn = self._cv_masks(held_state, held_national)
+        np_ = C.c_longlong(0)
+        _check(self.L, self.L.potus_cv_log_lik_device(self.h, _ip(ms), _ip(mn), int(bool(integrate)), None, C.byref(np_)))
+        per = (self.opts.chains // n) * self.post_warmup_saved()
+        out = torch.empty((np_.value, per), dtype=torch.float64, device=f"cuda:{self.opts.device}")
+        if np_.value:                                      # (an empty tensor has no memory to point at)
+            torch.cuda.current_stream(out.device).synchronize()
+            _check(self.L, self.L.potus_cv_log_lik_device(self.h, _ip(ms), _ip(mn), int(bool(integrate)), C.c_void_p(out.data_ptr()), None))
+        return out
+
+    def cv_lpd(self, held_state, held_national, integrate=True):
+        """potus_cv_lpd: (lpd [n_datasets, polls, 2] = log mean p and log mean p^2 of every pair the masks name over the data set's post-warm-up
+        draws, NaN elsewhere; n_draws [n_datasets], 0 for a data set with a failed chain)."""
+        n, ms, mn = self._cv_masks(held_state, held_national)
+        lpd, cnt = np.zeros((n, self.n_polls, 2)), np.zeros(n, np.int32)
+        _check(self.L, self.L.potus_cv_lpd(self.h, _ip(ms), _ip(mn), int(bool(integrate)), _dp(lpd), _ip(cnt)))
+        return lpd, cnt
+
+    def cv_timing(self):
+        ms = np.zeros(2)
+        _check(self.L, self.L.potus_cv_timing(_dp(ms)))
+        return dict(loglik_ms=float(ms[0]), reduce_ms=float(ms[1]))
 
     def outcomes(self, ev, actual=None, days=None, ev_to_win=270):
         """Joint election outcomes of this handle's post-warm-up draws (us_potus_model_amd.outcomes)."""

@@ -76,6 +76,16 @@ def set_design(handle, design):
                            design.get("mu_b_prior"), design.get("mu_b_T_scale"), n=n)
 
 
+def lfo_masks(design):
+    """(held_state, held_national) of leave-future-out: date d is scored on the polls date d + 1 keeps and date d does not; the last date on none."""
+    out = []
+    for k in (design["keep_state"], design["keep_national"]):
+        h = np.zeros_like(k, dtype=bool)
+        h[:-1] = k[1:] & ~k[:-1]
+        out.append(h)
+    return out[0], out[1]
+
+
 class Timeline:
     """The fitted run dates of a design: `.handle` holds chains_per_date consecutive chains per date."""
 
@@ -97,21 +107,37 @@ class Timeline:
         out = h.timeline(ev, (t0, t1), ev_to_win)
         out["timing"] = h.timeline_timing()
         if diagnostics:
-            import torch
-            x = h.timeline_scores_device((t0, t1))                                    # [dates, draws, days, S]
-            w = torch.as_tensor(self._w / self._w.sum(), device=x.device)
-            rh, es = np.full(self.n_dates, np.nan), np.full(self.n_dates, np.nan)
-            per = x.shape[1] // self.chains_per_date
-            for d in range(self.n_dates):
-                if out["n_draws"][d] == 0 or per < 4:
-                    continue
-                cells = torch.cat([x[d], (x[d] * w).sum(-1, keepdim=True)], dim=-1)    # [draws, days, S + 1]
-                blk = cells.reshape(self.chains_per_date, per, -1).permute(1, 0, 2).contiguous()
-                r, e = device_diagnostics_of_block(blk)
-                rh[d], es[d] = float(np.nanmax(r)), float(np.nanmin(e))
-            out["rhat_max"], out["ess_bulk_min"] = rh, es
+            out["rhat_max"], out["ess_bulk_min"] = self.diagnostics((t0, t1), out["n_draws"])
         out["days"], out["run_dates"] = (t0, t1), list(self.design.get("run_dates", range(self.n_dates)))
         return out
+
+    def diagnostics(self, days=None, n_draws=None):
+        """(rhat_max, ess_bulk_min) per date over the state scores and the national vote of `days` (potus_diagnostics_device on the date's
+        slice); NaN for a date whose n_draws is 0 (a failed chain) or with fewer than 4 draws per chain."""
+        import torch
+        x = self.handle.timeline_scores_device(self._days(days))                      # [dates, draws, days, S]
+        w = torch.as_tensor(self._w / self._w.sum(), device=x.device)
+        rh, es = np.full(self.n_dates, np.nan), np.full(self.n_dates, np.nan)
+        per = x.shape[1] // self.chains_per_date
+        for d in range(self.n_dates):
+            if (n_draws is not None and n_draws[d] == 0) or per < 4:
+                continue
+            cells = torch.cat([x[d], (x[d] * w).sum(-1, keepdim=True)], dim=-1)        # [draws, days, S + 1]
+            blk = cells.reshape(self.chains_per_date, per, -1).permute(1, 0, 2).contiguous()
+            r, e = device_diagnostics_of_block(blk)
+            rh[d], es[d] = float(np.nanmax(r)), float(np.nanmin(e))
+        return rh, es
+
+    def lfo(self, integrate=True):
+        """Leave-future-out (Buerkner, Gabry, Vehtari 2020) on the fitted run dates, no refit: date d is scored on the polls that arrived
+        before date d + 1 (lfo_masks), under its own draws, by one potus_cv_lpd call.  dict(elpd [dates] the sum over the date's held-out
+        polls (0 where it holds none, NaN for a date with a failed chain), n_held [dates], lpd [dates, polls, 2] the pointwise log mean p
+        and log mean p^2, NaN where not held out; n_draws [dates])."""
+        hs, hn = lfo_masks(self.design)
+        lpd, cnt = self.handle.cv_lpd(hs, hn, integrate)
+        held = np.concatenate([hs, hn], axis=1)
+        elpd = np.array([lpd[d, held[d], 0].sum() for d in range(self.n_dates)])
+        return dict(elpd=elpd, n_held=held.sum(1), lpd=lpd, n_draws=cnt, run_dates=list(self.design.get("run_dates", range(self.n_dates))))
 
     def _block(self, d, days):
         if not 0 <= int(d) < self.n_dates:
