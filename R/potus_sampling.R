@@ -418,6 +418,39 @@ potus_kfold <- function(data, fold, variant = c("full", "no_mode_adjustment"), c
   list(pointwise = cbind(elpd = elpd, mcse = mcse), elpd_kfold = sum(elpd), se = sqrt(N) * sd(elpd), fold = fold, n_draws = r$n_draws)
 }
 
+# ---- the posterior mode (PotusModel.optimize is the same in Python; DESIGN.md section 4k) ----
+# cmdstanr's model$optimize(data, jacobian = FALSE, algorithm = "lbfgs"): batched L-BFGS on the device, `paths` starts in one launch.
+# init: the radius of the uniform starts, or a matrix [paths, D] of unconstrained starting points.  pars: 0-based output-row columns
+# c(begin, end) whose constrained values are wanted (NULL: none).  Returns list(q [paths, D], lp, grad_norm, return_code (1 ABSF, 2 RELF,
+# 3 ABSGRAD, 4 RELGRAD, 5 ABSX, 6 MAXIT, 7 LSFAIL, 8 INIT), iterations, grad_evals [paths], best, rows [paths, end - begin] or NULL).
+potus_optimize <- function(data, variant = c("full", "no_mode_adjustment"), jacobian = FALSE, init = 2, paths = 1, seed = 1843, iter = 2000,
+                           history_size = 5, init_alpha = 1e-3, tol_obj = 1e-12, tol_rel_obj = 1e4, tol_grad = 1e-8, tol_rel_grad = 1e7,
+                           tol_param = 1e-8, path_offset = 0, pars = NULL, device = 0) {
+  variant <- match.arg(variant)
+  own <- is.matrix(init)
+  if (own) paths <- nrow(init)
+  res <- .potus_create(data, variant, c(1L, 0L, 0L, 0L, 10L, as.integer(device), 0L, 1L, 0L, 0L, 0L, 0L),
+                       c(0.8, 0.05, 0.75, 10, 1, if (own) 2 else init, seed))
+  .potus_check(res$status)
+  on.exit(.C("potus_R_destroy", res$handle, status = integer(1)))
+  info <- .C("potus_R_num_columns", res$handle, D = integer(1), n_cols = integer(1), status = integer(1))
+  .potus_check(info$status)
+  D <- info$D
+  cols <- if (is.null(pars)) c(0L, 1L) else as.integer(pars)
+  nsel <- cols[2] - cols[1]
+  r <- .C("potus_R_optimize", res$handle, as.integer(c(isTRUE(jacobian), history_size, iter, path_offset, paths, own, !is.null(pars))),
+          as.double(c(init_alpha, tol_obj, tol_rel_obj, tol_grad, tol_rel_grad, tol_param)), if (own) as.double(t(init)) else double(1),
+          q = double(paths * D), lp = double(paths), grad_norm = double(paths), info = integer(3 * paths), cols,
+          rows = double(max(paths * nsel, 1)), status = integer(1))
+  .potus_check(r$status)
+  info3 <- matrix(r$info, paths, 3, byrow = TRUE)
+  ok <- info3[, 1] >= 1 & info3[, 1] <= 5
+  pool <- if (any(ok)) ok else is.finite(r$lp)
+  list(q = matrix(r$q, paths, D, byrow = TRUE), lp = r$lp, grad_norm = r$grad_norm, return_code = info3[, 1], iterations = info3[, 2],
+       grad_evals = info3[, 3], best = which(pool)[which.max(r$lp[pool])],
+       rows = if (is.null(pars)) NULL else matrix(r$rows[seq_len(paths * nsel)], paths, nsel, byrow = TRUE))
+}
+
 # ---- joint election outcomes (us_potus_model_amd/outcomes.py is the same in Python; DESIGN.md section 4f) ----
 # What the run scripts compute from the JOINT outcome of a draw, counted on the device over the post-warm-up draws of every chain of the fit:
 # the distribution of Democratic electoral votes (final_2016.R:904-920), the tipping-point state (final_2012.R:809-843), how often states i and j

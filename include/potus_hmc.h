@@ -407,6 +407,43 @@ int potus_cv_log_lik_device(int handle, const int32_t *held_state, const int32_t
 int potus_cv_lpd(int handle, const int32_t *held_state, const int32_t *held_national, int integrate,
                  double *lpd_out, int32_t *n_draws_out);
 int potus_cv_timing(double *ms /*[2]: k_cv_loglik, k_cv_reduce, HIP events, calling thread's last potus_cv_lpd*/);
+/* ---- the posterior mode: cmdstanr's $optimize(), batched -- one workgroup per path, every path in ONE launch ----
+ * L-BFGS (history_size pairs, two-loop recursion, initial scaling s'y / y'y; a pair with s'y <= 0 is skipped, a direction that is no ascent
+ * direction resets the history) with a strong-Wolfe line search (c1 = 1e-4, c2 = 0.9; first trial step of the first iteration init_alpha,
+ * afterwards 1; at most 20 evaluations per iteration, a non-finite trial shrinks the step) on log_prob<jacobian> of the unconstrained
+ * coordinates: jacobian = 1 is the mode of the density the sampler draws from, jacobian = 0 (CmdStan's default for optimisation) the
+ * penalised maximum-likelihood point.  The no-mode variant has no constrained parameter: both settings are the same computation there.
+ * Stopping rules are CmdStan 2.24's, tested after each accepted step with strict <, so a tolerance of 0 switches a rule off; eps = 2^-52:
+ *   1 ABSF     |f_k - f_{k-1}| < tol_obj                                    5 ABSX    ||x_k - x_{k-1}||_2 < tol_param
+ *   2 RELF     |f_k - f_{k-1}| / max(|f_k|, |f_{k-1}|, tol_obj) < tol_rel_obj eps     6 MAXIT   iter iterations done
+ *   3 ABSGRAD  ||g||_2 < tol_grad                                           7 LSFAIL  the line search failed; the last accepted point is returned
+ *   4 RELGRAD  g' H g / max(|f|, tol_obj) < tol_rel_grad eps                8 INIT    no finite start; q, lp and the gradient norm of the path are NaN
+ * (H the L-BFGS inverse-Hessian approximation).  A launch ends after at most 100 + 21 iter model passes per path whatever the data.
+ * Path p of a handle with data sets (potus_set_datasets[_ex]) uses the model of data set p / (n_paths / n_datasets), as the sampler picks a
+ * chain's; on a plain handle every path uses the handle's model.  Starts: q0 [n_paths][D] is tried once per path; q0 = NULL draws
+ * U(-init_radius, init_radius) starts, up to 100 attempts per path, from Philox4x32-10 as the sampler's (counter = {index, purpose | aux << 8,
+ * iter, chain}, key = the handle's seed) with the NEW purpose 7:
+ *   coordinate i of attempt a of path p   uniform of (index i, purpose 7, aux a, iter 0xFFFFFFFF, chain path_offset + p + 1)
+ * so the bytes of a path do not depend on how paths are batched, and no stream of the sampler is reused.  Every sum runs in a fixed order
+ * without atomics: the same (model, start, options) give the same bytes on every call and in every batch.
+ * Callable any time after potus_create, before or after potus_init / potus_run: the call reads the models, works in buffers of its own and
+ * touches no chain state -- a run continued afterwards gives the bytes of an uninterrupted run.  opts = NULL: the defaults.
+ * Refused before any kernel runs: cus_per_chain > 1 or the dense metric (POTUS_ERR_UNSUPPORTED); n_paths <= 0 or, on a handle with data sets,
+ * no multiple of their number; NULL q_out, lp_out or info_out; history_size outside 1..20; iter < 1; a negative or NaN tolerance; init_alpha
+ * not finite and > 0; jacobian not 0 or 1; row_out with a bad column range (POTUS_ERR_ARG).  A path that ends INIT or LSFAIL does not fail
+ * the call.  gnorm_out may be NULL.
+ * row_out [n_paths][col_end - col_begin] (or NULL): the CmdStan output row of q_out[p], built on the device with the PATH'S OWN model by
+ * the row builder of potus_write_array; column 0 (lp__) is lp_out[p], the sampler columns 1-6 are NaN as potus_constrain leaves them.  It is
+ * what gives the constrained point on potus_set_datasets_ex handles, which potus_constrain refuses. */
+typedef struct potus_optimize_opts {
+  int32_t jacobian, history_size, iter, path_offset;
+  double init_alpha, tol_obj, tol_rel_obj, tol_grad, tol_rel_grad, tol_param;
+} potus_optimize_opts;   /* 64 bytes */
+void potus_default_optimize_opts(potus_optimize_opts *o);   /* 0, 5, 2000, 0, 1e-3, 1e-12, 1e4, 1e-8, 1e7, 1e-8 */
+int potus_optimize(int handle, const potus_optimize_opts *o, const double *q0 /*[n_paths][D] or NULL*/, int n_paths, double *q_out /*[n_paths][D]*/,
+                   double *lp_out /*[n_paths]*/, double *gnorm_out /*[n_paths]*/, int32_t *info_out /*[n_paths][3]: code, iterations, gradient evaluations*/,
+                   int col_begin, int col_end, double *row_out /*[n_paths][col_end - col_begin] or NULL*/);
+int potus_optimize_timing(double *ms /*[1]: k_opt_lbfgs, HIP events, calling thread's last potus_optimize*/);
 /* Prior predictive simulation: n_sims draws theta ~ prior (poll_model_2020.stan:116-128) on the unconstrained scale (q_out [n_sims][D];
  * rho_e_bias ~ normal(0.7, 0.1) restricted to (0, 1), stored as logit(rho)) and y ~ binomial(n_two_share, inv_logit(logit_pi(theta)))
  * (stan:85-113; exact sampler: inversion when n min(p, 1 - p) < 10, BTRS above) in the caller's poll order.  Any output may be null.
@@ -550,6 +587,9 @@ void potus_R_set_datasets_ex(int *handle, int *n_datasets, int *n_democrat_state
 void potus_R_timeline(int *handle, int *day_begin, int *day_end, double *ev, int *ev_to_win, double *state_out, double *natl_out, double *ev_out,
                       int *n_draws_out, int *status);
 void potus_R_cv_lpd(int *handle, int *held_state, int *held_national, int *integrate, double *lpd_out, int *n_draws_out, int *status);
+void potus_R_optimize(int *handle, int *iopts /*[7]: jacobian, history_size, iter, path_offset, n_paths, q0 given, rows wanted*/,
+                      double *dopts /*[6]: init_alpha, tol_obj, tol_rel_obj, tol_grad, tol_rel_grad, tol_param*/, double *q0, double *q_out, double *lp_out,
+                      double *gnorm_out, int *info_out, int *cols /*[2]: col_begin, col_end*/, double *row_out, int *status);
 void potus_R_simulate_prior(int *handle, double *seed, int *dims /*[2]: n_sims, sim_offset*/, double *q_out, int *n_democrat_state_out,
                             int *n_democrat_national_out, int *status);
 void potus_R_sbc_ranks(int *handle, double *truth, int *cols /*[3]: col_begin, col_end, thin*/, int *less, int *equal, int *L, int *status);

@@ -5,7 +5,7 @@ reference's `$sample()` / `rstan::extract()` surface), dataprep.py / synthetic.p
 lists), diagnostics.py (R-hat / ESS), outcomes.py (joint election outcomes: EV histogram, tipping point), monitor.py (the posterior summary table), scenario.py (conditional forecasts, covariance of the state scores), timeline.py (run dates as the data sets of one handle), crossval.py (exact K-fold and leave-future-out cross-validation), _abi.py (ctypes structs).
 """
 from . import _abi  # noqa: F401
-from .sampler import (Handle, PotusError, PotusModel, StanFit, backtest_scores, check_convergence, device_diagnostics, device_diagnostics_of_block,  # noqa: F401
+from .sampler import (Handle, Optimum, PotusError, PotusModel, StanFit, backtest_scores, check_convergence, device_diagnostics, device_diagnostics_of_block,  # noqa: F401
                       load_library, posterior_summary, run_many, sampling)
 from . import outcomes  # noqa: F401,E402  (the module; its outcomes() is also available as joint_outcomes)
 from .outcomes import Outcomes, outcomes_of_block  # noqa: F401,E402

@@ -56,6 +56,18 @@ class PotusOpts(C.Structure):
     ]
 
 
+class PotusOptimizeOpts(C.Structure):
+    """potus_optimize_opts (64 bytes); start from potus_default_optimize_opts()."""
+    _fields_ = [
+        ("jacobian", C.c_int32), ("history_size", C.c_int32), ("iter", C.c_int32), ("path_offset", C.c_int32),
+        ("init_alpha", C.c_double), ("tol_obj", C.c_double), ("tol_rel_obj", C.c_double), ("tol_grad", C.c_double),
+        ("tol_rel_grad", C.c_double), ("tol_param", C.c_double),
+    ]
+
+
+OPTIMIZE_CODES = {1: "ABSF", 2: "RELF", 3: "ABSGRAD", 4: "RELGRAD", 5: "ABSX", 6: "MAXIT", 7: "LSFAIL", 8: "INIT"}
+
+
 def make_data(data: dict, variant: str | int = "full"):
     """Build a PotusData from the R-style named list. Returns (struct, keepalive).
 

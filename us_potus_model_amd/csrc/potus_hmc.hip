@@ -1118,6 +1118,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, c
 #include "potus_scenario.hpp"   // conditional forecasts and the covariance of the state scores
 #include "potus_timeline.hpp"   // run dates as the data sets of one handle: their rows, scores and summaries
 #include "potus_crossval.hpp"   // exact cross-validation: held-out polls under the draws of the data set that did not see them
+#include "potus_optimize.hpp"   // the posterior mode: batched L-BFGS, one workgroup per path
 
 // ======================================================================== host
 namespace {
@@ -4663,6 +4664,98 @@ int potus_cv_timing(double *ms) {
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------- the posterior mode (potus_optimize.hpp)
+namespace {
+thread_local double g_opt_ms = 0.0;   // the calling thread's last potus_optimize: k_opt_lbfgs (HIP events)
+}
+
+void potus_default_optimize_opts(potus_optimize_opts *o) {
+  if (!o) return;
+  o->jacobian = 0; o->history_size = 5; o->iter = 2000; o->path_offset = 0;
+  o->init_alpha = 1e-3; o->tol_obj = 1e-12; o->tol_rel_obj = 1e4; o->tol_grad = 1e-8; o->tol_rel_grad = 1e7; o->tol_param = 1e-8;
+}
+
+int potus_optimize(int handle, const potus_optimize_opts *opts, const double *q0, int n_paths, double *q_out, double *lp_out, double *gnorm_out,
+                   int32_t *info_out, int col_begin, int col_end, double *row_out) {
+  const char *what = "potus_optimize";
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  potus_optimize_opts o;
+  potus_default_optimize_opts(&o);
+  if (opts) o = *opts;
+  if (sp->K != 1) return fail(POTUS_ERR_UNSUPPORTED, "%s: needs one workgroup per chain (cus_per_chain = 1); this handle runs %d per chain", what, sp->K);
+  if (sp->dense) return fail(POTUS_ERR_UNSUPPORTED, "%s: the dense metric is not supported (metric = POTUS_METRIC_DIAG only)", what);
+  if (!sp->k1_unsupported.empty()) return fail(POTUS_ERR_UNSUPPORTED, "%s: %s", what, sp->k1_unsupported.c_str());
+  if (n_paths <= 0) return fail(POTUS_ERR_ARG, "%s: n_paths = %d, at least 1", what, n_paths);
+  if (sp->n_ds && n_paths % sp->n_ds) return fail(POTUS_ERR_ARG, "%s: n_paths = %d is not a multiple of the handle's %d data sets", what, n_paths, sp->n_ds);
+  if (!q_out || !lp_out || !info_out) return fail(POTUS_ERR_ARG, "%s: null output (q_out, lp_out and info_out are required)", what);
+  if (o.history_size < 1 || o.history_size > OPT_MAX_HISTORY) return fail(POTUS_ERR_ARG, "%s: history_size = %d outside 1..%d", what, o.history_size, OPT_MAX_HISTORY);
+  if (o.iter < 1) return fail(POTUS_ERR_ARG, "%s: iter = %d, at least 1", what, o.iter);
+  const double tols[5] = {o.tol_obj, o.tol_rel_obj, o.tol_grad, o.tol_rel_grad, o.tol_param};
+  static const char *const tol_names[5] = {"tol_obj", "tol_rel_obj", "tol_grad", "tol_rel_grad", "tol_param"};
+  for (int k = 0; k < 5; k++) if (!(tols[k] >= 0.0)) return fail(POTUS_ERR_ARG, "%s: %s = %g, must be >= 0 (0 switches the rule off)", what, tol_names[k], tols[k]);
+  if (!(o.init_alpha > 0.0) || !std::isfinite(o.init_alpha)) return fail(POTUS_ERR_ARG, "%s: init_alpha = %g, must be positive and finite", what, o.init_alpha);
+  if (o.jacobian != 0 && o.jacobian != 1) return fail(POTUS_ERR_ARG, "%s: jacobian = %d, 0 or 1", what, o.jacobian);
+  if (o.path_offset < 0 || (long long)o.path_offset + n_paths >= 0xFFFFFFFFll) return fail(POTUS_ERR_ARG, "%s: path_offset = %d with %d paths", what, o.path_offset, n_paths);
+  if (row_out) if (const int rc_ = check_cols(sp, col_begin, col_end)) return rc_;
+  const int D = sp->L.D, row = POTUS_N_SAMPLER_COLS + D, Dpad = (D + 7) & ~7, nvec = 2 * o.history_size + 5;
+  if ((unsigned long long)nvec * Dpad * 8ull >= 0x7fffffffull) return fail(POTUS_ERR_UNSUPPORTED, "%s: D = %d with history_size = %d: a path's working set must stay below 2 GB", what, D, o.history_size);
+  DeviceGuard guard;
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_opt_lbfgs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp->lds_bytes));
+  DevBufs tmp;   // the working set is the call's own: the sampler's chain state is not touched
+  double *dq0 = nullptr, *work = nullptr, *rows = nullptr, *dlp = nullptr, *dgn = nullptr;
+  int *dinfo = nullptr;
+  int rc;
+  if ((rc = tmp.get(&work, (size_t)n_paths * nvec * Dpad * 8, what)) || (rc = tmp.get(&rows, (size_t)n_paths * row * 8, what)) ||
+      (rc = tmp.get(&dlp, (size_t)n_paths * 8, what)) || (rc = tmp.get(&dgn, (size_t)n_paths * 8, what)) || (rc = tmp.get(&dinfo, (size_t)n_paths * 3 * 4, what))) return rc;
+  if (q0) {
+    if ((rc = tmp.get(&dq0, (size_t)n_paths * D * 8, what))) return rc;
+    HIP_TRY(hipMemcpyAsync(dq0, q0, (size_t)n_paths * D * 8, hipMemcpyHostToDevice, sp->stream));
+  }
+  OcEvents ev;
+  HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b));
+  const int per_ds = sp->n_ds ? n_paths / sp->n_ds : n_paths;
+  const DevModel *Mg = sp->n_ds ? sp->dMs : sp->dM;
+  OptParams P{dq0, work, rows, dlp, dgn, dinfo, per_ds, o.history_size, o.iter, o.jacobian, o.path_offset, Dpad,
+              o.init_alpha, o.tol_obj, o.tol_rel_obj, o.tol_grad, o.tol_rel_grad, o.tol_param, sp->R.init_radius, sp->R.seed_lo, sp->R.seed_hi};
+  OptParams *dP = nullptr;
+  if ((rc = tmp.get(&dP, sizeof(OptParams), what))) return rc;
+  HIP_TRY(hipMemcpyAsync(dP, &P, sizeof(OptParams), hipMemcpyHostToDevice, sp->stream));
+  HIP_TRY(hipEventRecord(ev.a, sp->stream));
+  hipLaunchKernelGGL(k_opt_lbfgs, dim3(n_paths), dim3(PT_THREADS), sp->lds_bytes, sp->stream, Mg, (const OptParams *)dP);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipEventRecord(ev.b, sp->stream));
+  std::vector<double> hrows((size_t)n_paths * row);
+  HIP_TRY(hipMemcpyAsync(hrows.data(), rows, hrows.size() * 8, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipMemcpyAsync(lp_out, dlp, (size_t)n_paths * 8, hipMemcpyDeviceToHost, sp->stream));
+  if (gnorm_out) HIP_TRY(hipMemcpyAsync(gnorm_out, dgn, (size_t)n_paths * 8, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipMemcpyAsync(info_out, dinfo, (size_t)n_paths * 3 * 4, hipMemcpyDeviceToHost, sp->stream));
+  if (row_out) {   // the CmdStan row of every path's point, built with the path's own model
+    const int nsel = col_end - col_begin, grid = std::min(n_paths, 512);
+    double *scratch = nullptr, *dout = nullptr;
+    if ((rc = tmp.get(&scratch, (size_t)grid * sp->L.ncols * 8, what)) || (rc = tmp.get(&dout, (size_t)n_paths * nsel * 8, what))) return rc;
+    WAParams W{rows, n_paths, 1, 1, row, sp->L.ncols, col_begin, col_end, scratch, dout, sp->sigma_ns, sp->sigma_nn, nsel};   // one saved draw of n_paths chains
+    if (sp->n_ds) hipLaunchKernelGGL(k_write_array_ds, dim3(grid), dim3(256), 0, sp->stream, Mg, W, per_ds);
+    else hipLaunchKernelGGL(k_write_array, dim3(grid), dim3(256), 0, sp->stream, Mg, W);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(hipMemcpyAsync(row_out, dout, (size_t)n_paths * nsel * 8, hipMemcpyDeviceToHost, sp->stream));
+  }
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  float ms = 0;
+  HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
+  g_opt_ms = ms;
+  for (int i = 0; i < n_paths; i++) std::copy(hrows.begin() + (size_t)i * row + POTUS_N_SAMPLER_COLS, hrows.begin() + (size_t)(i + 1) * row, q_out + (size_t)i * D);
+  return 0;
+}
+
+int potus_optimize_timing(double *ms) {
+  if (!ms) return fail(POTUS_ERR_ARG, "potus_optimize_timing: null output");
+  ms[0] = g_opt_ms;
+  return 0;
+}
+
 int potus_simulate_prior(int handle, uint64_t seed, int n_sims, int sim_offset, double *q_out, int32_t *n_democrat_state_out, int32_t *n_democrat_national_out) {
   Sampler *sp = get(handle);
   if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
@@ -5068,6 +5161,14 @@ void potus_R_timeline(int *handle, int *day_begin, int *day_end, double *ev, int
 }
 void potus_R_cv_lpd(int *handle, int *held_state, int *held_national, int *integrate, double *lpd_out, int *n_draws_out, int *status) {
   *status = potus_cv_lpd(*handle, held_state, held_national, *integrate, lpd_out, n_draws_out);
+}
+void potus_R_optimize(int *handle, int *iopts /*[7]: jacobian, history_size, iter, path_offset, n_paths, q0 given, rows wanted*/,
+                      double *dopts /*[6]: init_alpha, tol_obj, tol_rel_obj, tol_grad, tol_rel_grad, tol_param*/, double *q0, double *q_out, double *lp_out,
+                      double *gnorm_out, int *info_out, int *cols /*[2]: col_begin, col_end*/, double *row_out, int *status) {
+  potus_optimize_opts o;
+  o.jacobian = iopts[0]; o.history_size = iopts[1]; o.iter = iopts[2]; o.path_offset = iopts[3];
+  o.init_alpha = dopts[0]; o.tol_obj = dopts[1]; o.tol_rel_obj = dopts[2]; o.tol_grad = dopts[3]; o.tol_rel_grad = dopts[4]; o.tol_param = dopts[5];
+  *status = potus_optimize(*handle, &o, iopts[5] ? q0 : nullptr, iopts[4], q_out, lp_out, gnorm_out, info_out, cols[0], cols[1], iopts[6] ? row_out : nullptr);
 }
 void potus_R_set_datasets(int *handle, int *n_datasets, int *n_democrat_state, int *n_democrat_national, int *status) {
   *status = potus_set_datasets(*handle, *n_datasets, n_democrat_state, n_democrat_national);

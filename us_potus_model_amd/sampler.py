@@ -127,6 +127,14 @@ def load_library():
         L.potus_cv_lpd.argtypes = [C.c_int, i32p, i32p, C.c_int, dp, i32p]
         L.potus_cv_timing.argtypes = [dp]
         L.potus_R_cv_lpd.argtypes = [ip, ip, ip, ip, dp, ip, ip]
+    if hasattr(L, "potus_optimize"):                    # the posterior mode (Handle.optimize, PotusModel.optimize)
+        i32p, oop = C.POINTER(C.c_int32), C.POINTER(_abi.PotusOptimizeOpts)
+        L.potus_default_optimize_opts.argtypes = [oop]
+        L.potus_default_optimize_opts.restype = None
+        L.potus_optimize.argtypes = [C.c_int, oop, dp, C.c_int, dp, dp, dp, i32p, C.c_int, C.c_int, dp]
+        L.potus_optimize_timing.argtypes = [dp]
+        L.potus_R_optimize.argtypes = [ip, ip, dp, dp, dp, dp, dp, ip, ip, dp, ip]
+        L.potus_R_optimize.restype = None
     _LIB = L
     return L
 
@@ -142,13 +150,14 @@ EXPORTS = [
     "potus_set_datasets_ex", "potus_timeline", "potus_timeline_scores_device", "potus_timeline_timing",
     "potus_log_lik_device", "potus_loo_device", "potus_loo",
     "potus_cv_log_lik_device", "potus_cv_lpd", "potus_cv_timing",
+    "potus_default_optimize_opts", "potus_optimize", "potus_optimize_timing",
     "potus_outcomes", "potus_outcomes_device", "potus_outcomes_timing",
     "potus_monitor", "potus_monitor_device",
     "potus_scenario", "potus_scenario_device", "potus_scenario_timing",
     "potus_R_create", "potus_R_init", "potus_R_run", "potus_R_run_many", "potus_R_num_columns", "potus_R_saved_count",
     "potus_R_write_array", "potus_R_write_stan_csv", "potus_R_posterior_summary", "potus_R_diagnostics", "potus_R_check_convergence", "potus_R_backtest_scores", "potus_R_last_error", "potus_R_destroy",
     "potus_R_set_datasets", "potus_R_simulate_prior", "potus_R_sbc_ranks", "potus_R_constrain", "potus_R_loo", "potus_R_outcomes", "potus_R_monitor", "potus_R_scenario",
-    "potus_R_set_datasets_ex", "potus_R_timeline", "potus_R_cv_lpd",
+    "potus_R_set_datasets_ex", "potus_R_timeline", "potus_R_cv_lpd", "potus_R_optimize",
 ]
 
 
@@ -425,6 +434,45 @@ class Handle:
         ms = np.zeros(2)
         _check(self.L, self.L.potus_timeline_timing(_dp(ms)))
         return dict(scores_ms=float(ms[0]), summary_ms=float(ms[1]))
+
+    def optimize_opts(self, **opts):
+        """potus_default_optimize_opts with the given fields replaced (jacobian, history_size, iter, path_offset, init_alpha, tol_*)."""
+        o = _abi.PotusOptimizeOpts()
+        self.L.potus_default_optimize_opts(C.byref(o))
+        for k, v in opts.items():
+            if not hasattr(o, k):
+                raise TypeError(f"unknown optimiser option {k!r}")
+            setattr(o, k, v)
+        return o
+
+    def optimize(self, q0=None, paths=None, cols=None, opts=None, **fields):
+        """potus_optimize: the mode of every path in one launch (batched L-BFGS, one workgroup per path).  q0 [paths, D] starts, or None for
+        `paths` library starts (U(-init_radius, init_radius), Philox purpose 7).  On a handle with data sets path p uses data set
+        p // (paths // n_datasets).  cols = (begin, end): also the CmdStan output row columns of every path's point, built with the path's
+        own model.  fields: those of potus_optimize_opts (or opts: a filled struct).  Returns dict(q [paths, D], lp, grad_norm, return_code, iterations,
+        grad_evals [paths] and, with cols, rows [paths, end - begin])."""
+        o = opts if opts is not None else self.optimize_opts(**fields)
+        p0 = None
+        if q0 is not None:
+            q0 = np.ascontiguousarray(np.atleast_2d(q0), dtype=np.float64)
+            if q0.shape[1] != self.D or (paths is not None and int(paths) != q0.shape[0]):
+                raise ValueError(f"optimize: q0 has shape {q0.shape}, [{paths if paths is not None else 'paths'}, {self.D}] expected")
+            paths, p0 = q0.shape[0], _dp(q0)
+        n = int(1 if paths is None else paths)
+        q, lp, gn, info = np.zeros((max(n, 0), self.D)), np.zeros(max(n, 0)), np.zeros(max(n, 0)), np.zeros((max(n, 0), 3), np.int32)
+        a, b = (0, 0) if cols is None else (int(cols[0]), int(cols[1]))
+        rows = None if cols is None else np.zeros((max(n, 0), max(b - a, 1)))
+        _check(self.L, self.L.potus_optimize(self.h, C.byref(o), p0, n, _dp(q), _dp(lp), _dp(gn), _ip(info), a, b, None if rows is None else _dp(rows)))
+        out = dict(q=q, lp=lp, grad_norm=gn, return_code=info[:, 0].copy(), iterations=info[:, 1].copy(), grad_evals=info[:, 2].copy())
+        if rows is not None:
+            out["rows"] = rows[:, :b - a]
+        return out
+
+    def optimize_timing(self):
+        """Milliseconds (HIP events) of k_opt_lbfgs in this thread's last optimize()."""
+        ms = np.zeros(1)
+        _check(self.L, self.L.potus_optimize_timing(_dp(ms)))
+        return float(ms[0])
 
     def simulate_prior(self, seed, n_sims, sim_offset=0):
         """potus_simulate_prior: (q [n_sims, D], n_democrat_state [n_sims, Ns], n_democrat_national [n_sims, Nn]) drawn from the prior
@@ -770,6 +818,48 @@ class StanFit:
         return files
 
 
+class Optimum:
+    """What cmdstanr's fit$optimize() returns, for `paths` starts at once: q [paths, D] (unconstrained), lp, grad_norm, return_code
+    (_abi.OPTIMIZE_CODES), iterations, grad_evals [paths]; `best` = the path with the highest lp among those that ended with a
+    convergence code (1-5), else among all that have a point.  The constrained values are built on first use (Handle.constrain)."""
+
+    def __init__(self, handle, res, jacobian):
+        self._h, self.jacobian = handle, bool(jacobian)
+        self.q, self.lp, self.grad_norm = res["q"], res["lp"], res["grad_norm"]
+        self.return_code, self.iterations, self.grad_evals = res["return_code"], res["iterations"], res["grad_evals"]
+        conv = (self.return_code >= 1) & (self.return_code <= 5)
+        pool = conv if conv.any() else np.isfinite(self.lp)
+        if not pool.any():
+            raise PotusError("optimize: no path found a finite starting point (return code INIT on every path)")
+        self.best = int(np.flatnonzero(pool)[np.argmax(self.lp[pool])])
+        self._row = None
+
+    @property
+    def codes(self):
+        return [_abi.OPTIMIZE_CODES.get(int(c), str(int(c))) for c in self.return_code]
+
+    def mle(self, par, path=None):
+        """fit$mle(par): the constrained values of one path (default: best), shaped as extract() shapes a single draw."""
+        if par == "lp__":
+            return float(self.lp[self.best if path is None else int(path)])
+        if par not in self._h.layout:
+            raise KeyError(f"unknown parameter {par!r}")
+        if self._row is None:
+            self._row = self._h.constrain(self.q, 0, self._h.n_cols)
+        a, b, dims = self._h.layout[par]
+        v = self._row[self.best if path is None else int(path), a:b]
+        if not dims:
+            return float(v[0])
+        return v.reshape(tuple(reversed(dims))).transpose(tuple(range(len(dims) - 1, -1, -1))).copy()    # column-major -> dims
+
+    def as_inits(self, chains):
+        """[chains, D]: the best path's point for every chain (Handle.init(q0) / PotusModel.sample(inits=))."""
+        return np.tile(self.q[self.best], (int(chains), 1))
+
+    def close(self):
+        self._h.close()
+
+
 class PotusModel:
     """cmdstanr::cmdstan_model() for the two poll models (final_2016.R:532, final_2012.R:558)."""
 
@@ -781,6 +871,24 @@ class PotusModel:
             raise ValueError(f"unknown model {stan_file_or_variant!r}")
         self.variant = v
         self.model_name = "poll_model_2020_model" if v == "full" else "poll_model_2020_no_mode_adjustment_model"
+
+    def optimize(self, data, jacobian=False, init=2.0, paths=1, seed=1843, iter=2000, history_size=5, init_alpha=1e-3,
+                 tol_obj=1e-12, tol_rel_obj=1e4, tol_grad=1e-8, tol_rel_grad=1e7, tol_param=1e-8, path_offset=0, device=0):
+        """cmdstanr's model$optimize(data, jacobian = FALSE, algorithm = "lbfgs"): the posterior mode on the device, `paths` starts in one
+        launch.  init: the radius of the uniform starts, or an array [paths, D] (or [D]) of unconstrained starting points.  path_offset: library start
+        p is that of path path_offset + p, whatever the batch (timeline.modes: run date d with one path per date is path d)."""
+        radius = 2.0 if not np.isscalar(init) else float(init)
+        h = Handle(data, self.variant, chains=1, num_warmup=0, num_samples=0, seed=int(seed), init_radius=radius, device=int(device),
+                   cus_per_chain=1, twin=0)                       # (a handle that will not sample: no draws array)
+        try:
+            q0 = None if np.isscalar(init) else np.atleast_2d(np.asarray(init, dtype=np.float64))
+            res = h.optimize(q0, None if q0 is not None else int(paths), jacobian=int(bool(jacobian)), iter=int(iter), history_size=int(history_size),
+                             init_alpha=float(init_alpha), tol_obj=float(tol_obj), tol_rel_obj=float(tol_rel_obj), tol_grad=float(tol_grad),
+                             tol_rel_grad=float(tol_rel_grad), tol_param=float(tol_param), path_offset=int(path_offset))
+            return Optimum(h, res, jacobian)
+        except Exception:
+            h.close()
+            raise
 
     def sample(self, data, seed=1843, chains=4, parallel_chains=None, iter_warmup=1000, iter_sampling=1000,
                refresh=100, adapt_delta=0.8, max_treedepth=10, init=2.0, save_warmup=False, device=0,

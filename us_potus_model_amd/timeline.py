@@ -187,6 +187,31 @@ def fit(design, variant="full", chains_per_date=4, **opts):
     return Timeline(h, design, chains_per_date, wall)
 
 
+def modes(design, variant="full", paths_per_date=1, device=0, seed=1843, init_radius=2.0, **opts):
+    """The posterior mode of every run date of a design in ONE launch (potus_optimize on a potus_set_datasets_ex handle: batched
+    L-BFGS, one workgroup per path), with the election-day predicted_score of every path from row_out -- built with the date's own
+    model.  opts: the fields of potus_optimize_opts (jacobian, iter, history_size, tol_*, ...).  dict(q [dates, paths, D], lp,
+    grad_norm, return_code, iterations, grad_evals [dates, paths], predicted_score [dates, paths, S], best [dates] the path with the
+    highest lp among the date's converged ones, ms the kernel's time)."""
+    n, k = int(design["keep_state"].shape[0]), int(paths_per_date)
+    h = Handle(design["data"], variant, chains=n, num_warmup=0, num_samples=0, seed=int(seed), init_radius=float(init_radius), device=int(device),
+               **_BATCHED)                                        # one chain per date carries the date's model; nothing is sampled
+    try:
+        set_design(h, design)
+        S, T = int(design["data"]["S"]), int(design["data"]["T"])
+        a = h.layout["predicted_score"][0]
+        res = h.optimize(None, n * k, cols=(a + T - 1, a + T * (S - 1) + T), **opts)       # predicted_score is T x S column-major: day T of every state
+        out = {key: res[key].reshape((n, k) + res[key].shape[1:]) for key in ("q", "lp", "grad_norm", "return_code", "iterations", "grad_evals")}
+        out["predicted_score"] = np.ascontiguousarray(res["rows"][:, ::T]).reshape(n, k, S)
+        ok = (out["return_code"] >= 1) & (out["return_code"] <= 5)
+        out["best"] = np.array([int(np.argmax(np.where(ok[d] if ok[d].any() else np.isfinite(out["lp"][d]), out["lp"][d], -np.inf))) for d in range(n)])
+        out["ms"] = h.optimize_timing()
+        out["run_dates"] = list(design.get("run_dates", range(n)))
+        return out
+    finally:
+        h.close()
+
+
 def save_fixture(path, design):
     """The per-date part of a design (masks, priors, scales, dates) as one .npz: data only."""
     np.savez_compressed(path, keep_state=np.packbits(design["keep_state"], axis=1), keep_national=np.packbits(design["keep_national"], axis=1),
