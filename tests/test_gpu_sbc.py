@@ -167,6 +167,27 @@ def test_many_datasets_equal_single_handles_byte_for_byte(many):
     assert d_many[0].tobytes() != d_many[2].tobytes()
 
 
+def test_set_datasets_and_set_datasets_ex_give_the_same_draws(cases):
+    """The plain call is the _ex call with only the outcomes given: the same models byte for byte, hence the same chains."""
+    data, variant = cases["small_full"]
+    ys, yn = np.asarray(data["n_democrat_state"], np.int32), np.asarray(data["n_democrat_national"], np.int32)
+    ys, yn = np.stack([ys, ys // 2]), np.stack([yn, yn // 2])
+    draws = []
+    for ex in (False, True):
+        g = Handle(data, variant, chains=4, num_warmup=20, num_samples=10, seed=1843, cus_per_chain=1, twin=0)
+        if ex:
+            g.set_datasets_ex(n_democrat_state=ys, n_democrat_national=yn)
+        else:
+            g.set_datasets(ys, yn)
+        g.init()
+        g.run(30)
+        draws.append(g.draws())
+        g.close()
+    assert draws[0].shape[1] == 10 and np.isfinite(draws[0]).all()
+    assert np.array_equal(draws[0], draws[1])
+    assert not np.array_equal(draws[0][0], draws[0][2])     # the two data sets differ, and so do their chains
+
+
 def test_many_datasets_refusals(many, cases, tmp_path):
     data, variant = cases["small_full"]
     ys, yn = np.asarray(data["n_democrat_state"])[None], np.asarray(data["n_democrat_national"])[None]
@@ -190,8 +211,10 @@ def test_many_datasets_refusals(many, cases, tmp_path):
     g = Handle(data, variant, chains=2, num_warmup=10, num_samples=10, cus_per_chain=1, twin=0)
     bad = np.repeat(ys, 2, 0).copy()
     bad[1, 3] = int(data["n_two_share_state"][3]) + 1
-    with pytest.raises(PotusError, match="data set 2: n_democrat_state\\[4\\]"):
+    with pytest.raises(PotusError, match=r"potus_set_datasets: data set 2: n_democrat_state\[4\]"):   # names the function that was called
         g.set_datasets(bad, np.repeat(yn, 2, 0))
+    g.set_datasets(np.repeat(ys, 2, 0), np.repeat(yn, 2, 0))                    # ... and the refusal left nothing behind
+    assert g.n_datasets == 2
     g.close()
     # calls that pool all chains of the handle refuse and point to per-data-set slicing
     from us_potus_model_amd import sampler

@@ -329,6 +329,21 @@ def test_saved_warmup_rows_are_left_out(cases):
     h.close()
 
 
+def test_event_timings_of_outcomes_and_scenario_are_positive(cases):
+    """The HIP-event slots of the two getters after one call each on two chains x ten draws: a span that was recorded and read is finite and > 0."""
+    data, variant = cases["small_full"]
+    h = _fit(data, variant, chains=2, nw=20, ns=10, seed=7)
+    ev = _ev_for(int(data["S"]))
+    h.outcomes(ev)
+    ms = oc.last_timing()
+    assert np.isfinite(ms[2]) and ms[2] > 0, ms             # the counting kernel
+    h.scenario(ev)
+    ms = sc.last_timing()
+    assert np.isfinite(ms[3]) and ms[3] > 0, ms             # the moments
+    assert np.isfinite(ms[4]) and ms[4] > 0, ms             # the counts
+    h.close()
+
+
 # 5. refusals: a status with a message, never a fault, and the handle stays usable
 def test_refusals(fitted, cases):
     import torch

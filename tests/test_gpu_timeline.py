@@ -210,7 +210,7 @@ def test_refusals(tl):
     g = Handle(data, "full", chains=N_DS, num_warmup=10, num_samples=10, cus_per_chain=1, twin=0)
     y = np.tile(np.asarray(data["n_democrat_state"], np.int32), (N_DS, 1))
     y[1, 3] = int(data["n_two_share_state"][3]) + 1
-    with pytest.raises(PotusError, match="data set 2: n_democrat_state\\[4\\]"):
+    with pytest.raises(PotusError, match=r"potus_set_datasets_ex: data set 2: n_democrat_state\[4\]"):   # names the function that was called
         g.set_datasets_ex(n_democrat_state=y)
     n0 = np.zeros((N_DS, int(data["N_state_polls"])), np.int32)                 # a poll the data set has not seen cannot have Democrats in it
     with pytest.raises(PotusError, match="data set 1: n_democrat_state"):

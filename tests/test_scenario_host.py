@@ -31,6 +31,15 @@ def test_new_names_are_declared_exported_and_wrapped():
     assert re.search(r"calls that pool all chains \([^)]*potus_scenario[^)]*\) refuse", hdr.replace("\n *", ""))
 
 
+def test_timing_getter_refuses_a_null_output_by_its_own_name():
+    import ctypes as C
+    L = sampler.load_library()
+    assert L.potus_scenario_timing(None) == 1              # POTUS_ERR_ARG: no device needed
+    buf = C.create_string_buffer(512)
+    L.potus_last_error(buf, 512)
+    assert buf.value.decode().startswith("potus_scenario_timing:")
+
+
 # ---- the restatement against brute force, exact
 def _brute(ps, w, cond_day, lo, hi):
     """Every number as a Fraction of the float64 inputs: keep mask, mean and covariance of the S + 1 coordinates, no rounding anywhere."""

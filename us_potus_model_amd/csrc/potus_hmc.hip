@@ -1377,6 +1377,31 @@ struct DevBufs {
   }
 };
 
+// One pair of events around a span of a stream's work, destroyed on every return path: HIP_TRY(t.made) once, start() and stop() around the span,
+// elapsed() once the stream has been synchronised.  A call that may ignore a failed reading tests elapsed(); one that may not returns elapsed_or_fail().
+struct EventTimer {
+  hipEvent_t a = nullptr, b = nullptr;
+  hipError_t made, err = hipSuccess;
+  EventTimer() { if ((made = hipEventCreate(&a)) == hipSuccess) made = hipEventCreate(&b); }
+  EventTimer(const EventTimer &) = delete;
+  ~EventTimer() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
+  hipError_t start(hipStream_t st) { return hipEventRecord(a, st); }
+  hipError_t stop(hipStream_t st) { return hipEventRecord(b, st); }
+  bool elapsed(double *ms) {   // *ms is left alone when the reading fails
+    float f = 0.f;
+    if ((err = hipEventElapsedTime(&f, a, b)) == hipSuccess) *ms = f;
+    return err == hipSuccess;
+  }
+  int elapsed_or_fail(double *ms) { return elapsed(ms) ? 0 : fail(POTUS_ERR_DEVICE, "hipEventElapsedTime failed: %s", hipGetErrorString(err)); }
+};
+
+// what every *_timing getter does: the calling thread's last figures, n of them
+int timing_out(const char *what, const double *src, int n, double *ms) {
+  if (!ms) return fail(POTUS_ERR_ARG, "%s: null output", what);
+  std::copy(src, src + n, ms);
+  return 0;
+}
+
 template <class T>
 int upload(Sampler *s, const std::vector<T> &v, const T **dst) {
   void *p = nullptr;
@@ -2371,6 +2396,27 @@ int saved_count(Sampler *sp, int *n_saved) {
 // warm-up rows among the first n_saved rows of a handle (save_warmup = 1): not draws from the posterior -- rstan::monitor and extract() drop them
 int warm_rows(const Sampler *sp, int n_saved) { return sp->opts.save_warmup ? std::min(n_saved, sp->R.num_warmup) : 0; }
 
+// The draws of ONE handle's data sets (one data set when potus_set_datasets[_ex] was not called): what every call that works on them per data set needs.
+// of() is the part that needs no device -- the data sets, their chains, their models; ds_plan() adds the post-warm-up window and who has failed.
+struct DsPlan {
+  int n_ds = 1, cpd = 1, first = 0, n_post = 0;   // data sets, chains of each; saved rows [first, first + n_post) are the draws
+  std::vector<int> failed, skip;                  // per chain: its status is not 0; per data set: one of its chains has failed
+  const DevModel *Mg = nullptr;                   // n_ds models on the device (the handle's one model when it holds one data set)
+  void of(const Sampler *sp) { n_ds = std::max(sp->n_ds, 1); cpd = sp->chains_per_ds(); Mg = sp->n_ds ? sp->dMs : sp->dM; }
+};
+int ds_plan(const char *what, Sampler *sp, DsPlan &pl) {   // under the device lock, before anything is allocated or launched
+  pl.of(sp);
+  std::vector<ChainScalars> sc;
+  if (const int rc = read_scalars(sp, sc)) return rc;
+  int n_saved = 0;
+  if (const int rc = saved_count(sp, &n_saved)) return rc;
+  pl.first = warm_rows(sp, n_saved); pl.n_post = n_saved - pl.first;
+  if (pl.n_post < 1) return fail(POTUS_ERR_STATE, "%s: no post-warm-up draws saved yet (%d saved, %d of them warm-up)", what, n_saved, pl.first);
+  pl.failed.assign(sp->R.chains, 0); pl.skip.assign(pl.n_ds, 0);
+  for (int c = 0; c < sp->R.chains; c++) if (sc[c].status != 0) pl.failed[c] = pl.skip[c / pl.cpd] = 1;
+  return 0;
+}
+
 int check_cols(const Sampler *sp, int col_begin, int col_end) {
   if (col_begin < 0 || col_end > sp->L.ncols || col_begin >= col_end) return fail(POTUS_ERR_ARG, "bad column range [%d,%d) of %d", col_begin, col_end, sp->L.ncols);
   return 0;
@@ -3235,23 +3281,37 @@ int potus_draws_device_ptr(int handle, void **dptr, long long *n_doubles) {
   return 0;
 }
 
+// One row-builder launch on the sampler's stream: the W.n_saved x W.chains rows of W.draws.  The CALLER chooses the kernel: per_ds = 0 builds every row
+// with the one model M (k_write_array), per_ds > 0 builds chain c's rows with M[c / per_ds] (k_write_array_ds).  The grid and W.scratch are owned here;
+// W.out is the caller's or, when null, comes from tmp too.  Allocations fail by the name `what` (DevBufs::get), or with what = null as HIP calls fail.
+static int launch_rows(Sampler *sp, DevBufs &tmp, const char *what, const DevModel *M, int per_ds, WAParams &W) {
+  const int n = W.n_saved * W.chains, nsel = W.col_end - W.col_begin, grid = std::min(n, 512);
+  double *scratch = nullptr, *dout = W.out;
+  if (what) {
+    if (const int rc_ = tmp.get(&scratch, (size_t)grid * sp->L.ncols * 8, what)) return rc_;
+    if (!dout) if (const int rc_ = tmp.get(&dout, (size_t)n * nsel * 8, what)) return rc_;
+  } else {
+    HIP_TRY(tmp.alloc(&scratch, (size_t)grid * sp->L.ncols * 8));
+    if (!dout) HIP_TRY(tmp.alloc(&dout, (size_t)n * nsel * 8));
+  }
+  W.scratch = scratch; W.out = dout;
+  if (per_ds) hipLaunchKernelGGL(k_write_array_ds, dim3(grid), dim3(256), 0, sp->stream, M, W, per_ds);
+  else hipLaunchKernelGGL(k_write_array, dim3(grid), dim3(256), 0, sp->stream, M, W);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
 // out: host buffer, or (device_out) a device buffer of the sampler's GPU that receives the rows directly
 static int write_array_range(Sampler *sp, int n_saved, int col_begin, int col_end, double *out, bool device_out = false, int out_stride = 0) {
   const int nsel = col_end - col_begin;
   if (out_stride <= 0) out_stride = nsel;
   const int ndraw = n_saved * sp->R.chains;
   if (ndraw == 0) return 0;
-  const int grid = std::min(ndraw, 512);
   DevBufs tmp;
-  double *scratch = nullptr, *dout = nullptr;
-  if (const int rc_ = tmp.get(&scratch, (size_t)grid * sp->L.ncols * 8, "potus_write_array")) return rc_;
-  if (device_out) dout = out;
-  else if (const int rc_ = tmp.get(&dout, (size_t)ndraw * nsel * 8, "potus_write_array")) return rc_;
-  WAParams W{sp->R.draws, sp->R.chains, sp->R.n_save_max, n_saved, sp->R.row, sp->L.ncols, col_begin, col_end, scratch, dout, sp->sigma_ns, sp->sigma_nn, out_stride};
-  if (sp->ds_ex) hipLaunchKernelGGL(k_write_array_ds, dim3(grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dMs, W, sp->chains_per_ds());   // the chain's own model
-  else hipLaunchKernelGGL(k_write_array, dim3(grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, W);
-  HIP_TRY(hipGetLastError());
-  if (!device_out) HIP_TRY(hipMemcpyAsync(out, dout, (size_t)ndraw * nsel * 8, hipMemcpyDeviceToHost, sp->stream));
+  WAParams W{sp->R.draws, sp->R.chains, sp->R.n_save_max, n_saved, sp->R.row, sp->L.ncols, col_begin, col_end, nullptr, device_out ? out : nullptr, sp->sigma_ns, sp->sigma_nn, out_stride};
+  if (const int rc_ = sp->ds_ex ? launch_rows(sp, tmp, "potus_write_array", sp->dMs, sp->chains_per_ds(), W)   // the chain's own model
+                                : launch_rows(sp, tmp, "potus_write_array", sp->dM, 0, W)) return rc_;
+  if (!device_out) HIP_TRY(hipMemcpyAsync(out, W.out, (size_t)ndraw * nsel * 8, hipMemcpyDeviceToHost, sp->stream));
   HIP_TRY(hipStreamSynchronize(sp->stream));
   return 0;
 }
@@ -3827,10 +3887,6 @@ thread_local double g_oc_ms[3] = {0.0, 0.0, 0.0};   // the last call of this thr
 static_assert(sizeof(long long) == sizeof(unsigned long long), "the counts are copied out as they are");
 
 struct OcOut { long long *ev_hist, *tipping, *joint, *below_actual, *n_draws; };
-struct OcEvents {
-  hipEvent_t a = nullptr, b = nullptr;
-  ~OcEvents() { if (a) (void)hipEventDestroy(a); if (b) (void)hipEventDestroy(b); }
-};
 
 // everything about ev, ev_to_win and actual: no device needed
 int oc_check(const char *what, int S, const int32_t *ev, int ev_to_win, const double *actual, int *ev_sum) {
@@ -3872,19 +3928,18 @@ int oc_count(const char *what, hipStream_t st, const double *items, long long nd
   const long long chunk = (nd + chunks - 1) / chunks;
   chunks = (nd + chunk - 1) / chunk;
   OcParams P{items, nd, chunk, n_days, S, ev_to_win, ev_sum, dw, dev_, dact, dout, dout + n_hist, dout + n_hist + n_tip, dout + n_hist + n_tip + n_joint};
-  OcEvents e;
-  HIP_TRY(hipEventCreate(&e.a)); HIP_TRY(hipEventCreate(&e.b));
-  HIP_TRY(hipEventRecord(e.a, st));
+  EventTimer e;
+  HIP_TRY(e.made);
+  HIP_TRY(e.start(st));
   hipLaunchKernelGGL(k_oc_count, dim3((unsigned)n_days, (unsigned)chunks), dim3(OC_THREADS), 0, st, P);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e.b, st));
+  HIP_TRY(e.stop(st));
   if (o.ev_hist) HIP_TRY(hipMemcpyAsync(o.ev_hist, P.ev_hist, n_hist * 8, hipMemcpyDeviceToHost, st));
   if (o.tipping) HIP_TRY(hipMemcpyAsync(o.tipping, P.tipping, n_tip * 8, hipMemcpyDeviceToHost, st));
   if (o.joint) HIP_TRY(hipMemcpyAsync(o.joint, P.joint, n_joint * 8, hipMemcpyDeviceToHost, st));
   if (o.below_actual && actual) HIP_TRY(hipMemcpyAsync(o.below_actual, P.below, n_below * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
-  float ms = 0.f;
-  if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) *kernel_ms = ms;
+  (void)e.elapsed(kernel_ms);
   if (o.n_draws) *o.n_draws = nd;
   return 0;
 }
@@ -3929,9 +3984,7 @@ int potus_outcomes(const int *handles, int n_handles, int day_begin, int day_end
 }
 
 int potus_outcomes_timing(double *ms) {
-  if (!ms) return fail(POTUS_ERR_ARG, "potus_outcomes_timing: null output");
-  for (int i = 0; i < 3; i++) ms[i] = g_oc_ms[i];
-  return 0;
+  return timing_out("potus_outcomes_timing", g_oc_ms, 3, ms);
 }
 
 // ---------------------------------------------------------------------------------------------- conditional forecasts (potus_scenario.hpp)
@@ -3965,8 +4018,8 @@ int sc_compute(const char *what, hipStream_t st, const double *items, long long 
   const int C = S + 1;
   const long long rowlen = (long long)n_days * S;
   DevBufs tmp;
-  OcEvents e;
-  HIP_TRY(hipEventCreate(&e.a)); HIP_TRY(hipEventCreate(&e.b));
+  EventTimer e;
+  HIP_TRY(e.made);
   double *dw = nullptr;
   if (const int rc_ = tmp.get(&dw, (size_t)S * 8, what)) return rc_;
   HIP_TRY(hipMemcpyAsync(dw, w, (size_t)S * 8, hipMemcpyHostToDevice, st));
@@ -4022,7 +4075,7 @@ int sc_compute(const char *what, hipStream_t st, const double *items, long long 
     if (want_cov) if (const int rc_ = tmp.get(&dcov, n_cov * 8, what)) return rc_;
     ScParams P{kept, n, n_days, S, 0, nchunks, dw, scratch, scratch + (size_t)dblk * n, scratch + (size_t)dblk * n + (size_t)dblk * nchunks * C, dmean, dcov};
     const int NT = (C + 15) / 16;
-    HIP_TRY(hipEventRecord(e.a, st));
+    HIP_TRY(e.start(st));
     for (int d0 = 0; d0 < n_days; d0 += dblk) {
       P.day0 = d0;
       const dim3 grid((unsigned)std::min(dblk, n_days - d0), (unsigned)nchunks);
@@ -4043,12 +4096,11 @@ int sc_compute(const char *what, hipStream_t st, const double *items, long long 
       hipLaunchKernelGGL(k_sc_finish_cov, dim3(grid.x), dim3(SC_THREADS), 0, st, P);
       HIP_TRY(hipGetLastError());
     }
-    HIP_TRY(hipEventRecord(e.b, st));
+    HIP_TRY(e.stop(st));
     if (want_mean) HIP_TRY(hipMemcpyAsync(o.mean, dmean, n_mean * 8, hipMemcpyDeviceToHost, st));
     if (want_cov) HIP_TRY(hipMemcpyAsync(o.cov, dcov, n_cov * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
-    float ms = 0.f;
-    if (hipEventElapsedTime(&ms, e.a, e.b) == hipSuccess) g_sc_ms[3] = ms;
+    (void)e.elapsed(&g_sc_ms[3]);
   }
   // ---- counts: potus_outcomes' own counting of the kept draws
   if (o.ev_hist || o.tipping || o.joint) {
@@ -4114,9 +4166,7 @@ int potus_scenario(const int *handles, int n_handles, int cond_day, const double
 }
 
 int potus_scenario_timing(double *ms) {
-  if (!ms) return fail(POTUS_ERR_ARG, "potus_scenario_timing: null output");
-  for (int i = 0; i < 5; i++) ms[i] = g_sc_ms[i];
-  return 0;
+  return timing_out("potus_scenario_timing", g_sc_ms, 5, ms);
 }
 
 // SURVEY 8(f4), "online R-hat-based early stop": the diagnostics of lp__ and mu_b[:, T] (the columns bench.py's ESS / s is defined on;
@@ -4293,57 +4343,14 @@ int potus_write_stan_csv(int handle, const char *dir, const char *basename) {
   return 0;
 }
 
-// Development aid (POTUS_PROF builds only; not part of include/potus_hmc.h): per-chain cycle
-// counters of the kernel phases.  Returns the number of slots written per chain, 0 otherwise.
 // ------------------------------------------------------------------------ simulation-based calibration (DESIGN.md "Simulation-based calibration")
-int potus_set_datasets(int handle, int n_datasets, const int32_t *n_democrat_state, const int32_t *n_democrat_national) {
-  Sampler *sp = get(handle);
-  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
-  const int Ns = sp->M.Ns, Nn = sp->M.Nn, Np = Ns + Nn, Npad = sp->M.Npad;
-  if (n_datasets < 1) return fail(POTUS_ERR_ARG, "potus_set_datasets: n_datasets = %d, at least 1", n_datasets);
-  if ((Ns && !n_democrat_state) || (Nn && !n_democrat_national)) return fail(POTUS_ERR_ARG, "potus_set_datasets: null outcome array");
-  if (sp->inited) return fail(POTUS_ERR_STATE, "potus_set_datasets: the handle is already initialised (call it between potus_create and potus_init)");
-  if (sp->n_ds) return fail(POTUS_ERR_STATE, "potus_set_datasets: the handle already holds %d data sets", sp->n_ds);
-  if (sp->dense) return fail(POTUS_ERR_UNSUPPORTED, "potus_set_datasets: the dense metric is not supported (metric = POTUS_METRIC_DIAG only)");
-  if (sp->K != 1 || sp->twin) return fail(POTUS_ERR_UNSUPPORTED, "potus_set_datasets: needs one workgroup per chain (cus_per_chain = 1, twin = 0); this handle runs %d x %d", sp->K, sp->sides());
-  if (sp->R.chains % n_datasets) return fail(POTUS_ERR_ARG, "potus_set_datasets: chains = %d is not a multiple of n_datasets = %d", sp->R.chains, n_datasets);
-  DeviceLocks lock(sp->device);
-  HIP_TRY(hipSetDevice(sp->device));
-  std::vector<double> base((size_t)4 * Npad);
-  HIP_TRY(hipMemcpy(base.data(), sp->M.pd, base.size() * 8, hipMemcpyDeviceToHost));
-  std::vector<double> pd((size_t)n_datasets * 4 * Npad);
-  for (int k = 0; k < n_datasets; k++) {
-    double *blk = pd.data() + (size_t)k * 4 * Npad;
-    std::copy(base.begin(), base.end(), blk);
-    for (int i = 0; i < Np; i++) {   // day-sorted poll i is state poll qidx - o_ns or national poll qidx - o_nn (build_model)
-      const int qi = sp->h_pq[i];
-      const bool nat = sp->h_ps[i] == sp->M.S;
-      const int j = nat ? qi - sp->M.o_nn : qi - sp->M.o_ns;
-      const int y = nat ? n_democrat_national[(size_t)k * Nn + j] : n_democrat_state[(size_t)k * Ns + j];
-      const double n = base[(size_t)Npad + i];
-      if (y < 0 || y > n) return fail(POTUS_ERR_ARG, "potus_set_datasets: data set %d: n_democrat_%s[%d] = %d outside [0,%d]", k + 1, nat ? "national" : "state", j + 1, y, (int)n);
-      blk[i] = (double)y;
-    }
-  }
-  const double *dpd = nullptr;
-  if (const int rc = upload(sp, pd, &dpd)) return rc;
-  std::vector<DevModel> ms(n_datasets, sp->M);
-  for (int k = 0; k < n_datasets; k++) ms[k].pd = dpd + (size_t)k * 4 * Npad;
-  const DevModel *dms = nullptr;
-  if (const int rc = upload(sp, ms, &dms)) return rc;
-  sp->dMs = const_cast<DevModel *>(dms);
-  sp->n_ds = n_datasets;
-  return 0;
-}
-
-// Run dates as data sets (DESIGN.md section 4i): every data set may have its own poll sizes (0 = it has not seen the poll), prior and scale.
-int potus_set_datasets_ex(int handle, int n_datasets, const int32_t *n_democrat_state, const int32_t *n_democrat_national,
-                          const int32_t *n_two_share_state, const int32_t *n_two_share_national, const double *mu_b_prior, const double *mu_b_T_scale) {
-  const char *what = "potus_set_datasets_ex";
-  Sampler *sp = get(handle);
+// potus_set_datasets and potus_set_datasets_ex (ex: the four arrays may be null, the poll sizes and the prior may differ per data set, ds_ex is set)
+static int set_datasets_impl(const char *what, Sampler *sp, int n_datasets, const int32_t *y_state, const int32_t *y_national, const int32_t *n_state,
+                             const int32_t *n_national, const double *mu_b_prior, const double *mu_b_T_scale, bool ex) {
   if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
   const int Ns = sp->M.Ns, Nn = sp->M.Nn, Np = Ns + Nn, Npad = sp->M.Npad, S = sp->M.S;
   if (n_datasets < 1) return fail(POTUS_ERR_ARG, "%s: n_datasets = %d, at least 1", what, n_datasets);
+  if (!ex && ((Ns && !y_state) || (Nn && !y_national))) return fail(POTUS_ERR_ARG, "%s: null outcome array", what);
   if (sp->inited) return fail(POTUS_ERR_STATE, "%s: the handle is already initialised (call it between potus_create and potus_init)", what);
   if (sp->n_ds) return fail(POTUS_ERR_STATE, "%s: the handle already holds %d data sets", what, sp->n_ds);
   if (sp->dense) return fail(POTUS_ERR_UNSUPPORTED, "%s: the dense metric is not supported (metric = POTUS_METRIC_DIAG only)", what);
@@ -4363,10 +4370,10 @@ int potus_set_datasets_ex(int handle, int n_datasets, const int32_t *n_democrat_
       const int qi = sp->h_pq[i];
       const bool nat = sp->h_ps[i] == S;
       const int j = nat ? qi - sp->M.o_nn : qi - sp->M.o_ns;
-      const int32_t *ya = nat ? n_democrat_national : n_democrat_state, *na = nat ? n_two_share_national : n_two_share_state;
+      const int32_t *ya = nat ? y_national : y_state, *na = nat ? n_national : n_state;
       const size_t at = (size_t)k * (nat ? Nn : Ns) + j;
       const double n = na ? (double)na[at] : base[(size_t)Npad + i], y = ya ? (double)ya[at] : base[i];
-      if (n < 0) return fail(POTUS_ERR_ARG, "%s: data set %d: n_two_share_%s[%d] = %d is negative", what, k + 1, nat ? "national" : "state", j + 1, (int)n);
+      if (ex && n < 0) return fail(POTUS_ERR_ARG, "%s: data set %d: n_two_share_%s[%d] = %d is negative", what, k + 1, nat ? "national" : "state", j + 1, (int)n);
       if (y < 0 || y > n) return fail(POTUS_ERR_ARG, "%s: data set %d: n_democrat_%s[%d] = %d outside [0,%d]", what, k + 1, nat ? "national" : "state", j + 1, (int)y, (int)n);
       blk[i] = y; blk[(size_t)Npad + i] = n;
     }
@@ -4400,33 +4407,32 @@ int potus_set_datasets_ex(int handle, int n_datasets, const int32_t *n_democrat_
   if (const int rc = upload(sp, ms, &dms)) return rc;
   sp->dMs = const_cast<DevModel *>(dms);
   sp->n_ds = n_datasets;
-  sp->ds_ex = true;
+  if (ex) sp->ds_ex = true;
   return 0;
+}
+
+int potus_set_datasets(int handle, int n_datasets, const int32_t *n_democrat_state, const int32_t *n_democrat_national) {
+  return set_datasets_impl("potus_set_datasets", get(handle), n_datasets, n_democrat_state, n_democrat_national, nullptr, nullptr, nullptr, nullptr, false);
+}
+
+// Run dates as data sets (DESIGN.md section 4i): every data set may have its own poll sizes (0 = it has not seen the poll), prior and scale.
+int potus_set_datasets_ex(int handle, int n_datasets, const int32_t *n_democrat_state, const int32_t *n_democrat_national,
+                          const int32_t *n_two_share_state, const int32_t *n_two_share_national, const double *mu_b_prior, const double *mu_b_T_scale) {
+  return set_datasets_impl("potus_set_datasets_ex", get(handle), n_datasets, n_democrat_state, n_democrat_national, n_two_share_state, n_two_share_national,
+                           mu_b_prior, mu_b_T_scale, true);
 }
 
 namespace {
 thread_local double g_tl_ms[2] = {0.0, 0.0};   // the last call of this thread: k_tl_scores, k_tl_summary (HIP events)
 
-struct TlPlan { int n_ds, cpd, first, n_post, nd; std::vector<int> skip; const DevModel *Mg; };
+struct TlPlan : DsPlan { int nd = 0; };
 // everything potus_timeline[_scores_device] checks before a kernel runs; the argument tests come before the first HIP call
 int tl_check_args(const char *what, Sampler *sp, int day_begin, int day_end, TlPlan &pl) {
-  pl.n_ds = std::max(sp->n_ds, 1); pl.cpd = sp->chains_per_ds(); pl.nd = day_end - day_begin;
+  pl.of(sp); pl.nd = day_end - day_begin;
   if (day_begin < 0 || day_end > sp->M.T || day_begin >= day_end) return fail(POTUS_ERR_ARG, "%s: bad day range [%d,%d) of %d days", what, day_begin, day_end, sp->M.T);
   if ((long long)pl.cpd * sp->R.num_samples > TL_MAX_DRAWS)
     return fail(POTUS_ERR_UNSUPPORTED, "%s: %d chains x %d draws per data set: a data set's draws are sorted in LDS, at most %d", what, pl.cpd, sp->R.num_samples, TL_MAX_DRAWS);
   if (sp->K != 1 || sp->twin || sp->dense) return fail(POTUS_ERR_UNSUPPORTED, "%s: needs one workgroup per chain and the diagonal metric (the handles potus_set_datasets[_ex] take)", what);
-  return 0;
-}
-int tl_plan(const char *what, Sampler *sp, TlPlan &pl) {   // under the device lock
-  std::vector<ChainScalars> sc;
-  if (const int rc = read_scalars(sp, sc)) return rc;
-  int n_saved = 0;
-  if (const int rc = saved_count(sp, &n_saved)) return rc;
-  pl.first = warm_rows(sp, n_saved); pl.n_post = n_saved - pl.first;
-  if (pl.n_post < 1) return fail(POTUS_ERR_STATE, "%s: no post-warm-up draws saved yet (%d saved, %d of them warm-up)", what, n_saved, pl.first);
-  pl.skip.assign(pl.n_ds, 0);
-  for (int c = 0; c < sp->R.chains; c++) if (sc[c].status != 0) pl.skip[c / pl.cpd] = 1;
-  pl.Mg = sp->n_ds ? sp->dMs : sp->dM;
   return 0;
 }
 int tl_scores(Sampler *sp, const TlPlan &pl, int day_begin, int day_end, const int *dskip, double *out) {
@@ -4446,7 +4452,7 @@ int potus_timeline_scores_device(int handle, int day_begin, int day_end, void *o
   if (const int rc_ = tl_check_args(what, sp, day_begin, day_end, pl)) return rc_;
   DeviceBlock dev;
   if (const int rc_ = dev.open(what, sp->device, out_device, "output")) return rc_;
-  if (const int rc_ = tl_plan(what, sp, pl)) return rc_;
+  if (const int rc_ = ds_plan(what, sp, pl)) return rc_;
   DevBufs tmp;
   int *dskip = nullptr;
   if (const int rc_ = tmp.get(&dskip, (size_t)pl.n_ds * 4, what)) return rc_;
@@ -4466,11 +4472,11 @@ int potus_timeline(int handle, int day_begin, int day_end, const double *ev, int
   DeviceGuard guard;
   DeviceLocks lock(sp->device);
   HIP_TRY(hipSetDevice(sp->device));
-  if (const int rc_ = tl_plan(what, sp, pl)) return rc_;
+  if (const int rc_ = ds_plan(what, sp, pl)) return rc_;
   const int S = sp->M.S, nd = pl.nd, n = pl.cpd * pl.n_post, n_ds = pl.n_ds;
   DevBufs tmp;
-  OcEvents e0, e1;
-  HIP_TRY(hipEventCreate(&e0.a)); HIP_TRY(hipEventCreate(&e0.b)); HIP_TRY(hipEventCreate(&e1.a)); HIP_TRY(hipEventCreate(&e1.b));
+  EventTimer e0, e1;
+  HIP_TRY(e0.made); HIP_TRY(e1.made);
   double *x = nullptr, *dw = nullptr, *dev_ = nullptr, *dout = nullptr;
   int *dskip = nullptr;
   int rc;
@@ -4480,34 +4486,32 @@ int potus_timeline(int handle, int day_begin, int day_end, const double *ev, int
   HIP_TRY(hipMemcpyAsync(dskip, pl.skip.data(), (size_t)n_ds * 4, hipMemcpyHostToDevice, sp->stream));
   HIP_TRY(hipMemcpyAsync(dw, sp->h_w.data(), (size_t)S * 8, hipMemcpyHostToDevice, sp->stream));
   HIP_TRY(hipMemcpyAsync(dev_, ev, (size_t)S * 8, hipMemcpyHostToDevice, sp->stream));
-  HIP_TRY(hipEventRecord(e0.a, sp->stream));
+  HIP_TRY(e0.start(sp->stream));
   if ((rc = tl_scores(sp, pl, day_begin, day_end, dskip, x))) return rc;
-  HIP_TRY(hipEventRecord(e0.b, sp->stream));
+  HIP_TRY(e0.stop(sp->stream));
   int npad = 1;
   while (npad < n) npad <<= 1;
   const size_t lds = (size_t)npad * 8;
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_tl_summary), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   double *o_state = dout, *o_natl = o_state + (size_t)n_ds * nd * S * 4, *o_ev = o_natl + (size_t)n_ds * nd * 4;
   TlSumParams Q{x, n_ds, n, nd, S, dw, dev_, (double)ev_to_win, dskip, o_state, o_natl, o_ev};
-  HIP_TRY(hipEventRecord(e1.a, sp->stream));
+  HIP_TRY(e1.start(sp->stream));
   hipLaunchKernelGGL(k_tl_summary, dim3((unsigned)std::min<long long>((long long)n_ds * nd * (S + 2), 65535)), dim3(TL_THREADS), lds, sp->stream, Q);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(e1.b, sp->stream));
+  HIP_TRY(e1.stop(sp->stream));
   HIP_TRY(hipMemcpyAsync(state_out, o_state, (size_t)n_ds * nd * S * 4 * 8, hipMemcpyDeviceToHost, sp->stream));
   HIP_TRY(hipMemcpyAsync(natl_out, o_natl, (size_t)n_ds * nd * 4 * 8, hipMemcpyDeviceToHost, sp->stream));
   HIP_TRY(hipMemcpyAsync(ev_out, o_ev, (size_t)n_ds * nd * 5 * 8, hipMemcpyDeviceToHost, sp->stream));
   HIP_TRY(hipStreamSynchronize(sp->stream));
-  float ms0 = 0, ms1 = 0;
-  HIP_TRY(hipEventElapsedTime(&ms0, e0.a, e0.b)); HIP_TRY(hipEventElapsedTime(&ms1, e1.a, e1.b));
+  double ms0 = 0, ms1 = 0;
+  if ((rc = e0.elapsed_or_fail(&ms0)) || (rc = e1.elapsed_or_fail(&ms1))) return rc;
   g_tl_ms[0] = ms0; g_tl_ms[1] = ms1;
   for (int k = 0; k < n_ds; k++) n_draws_out[k] = pl.skip[k] ? 0 : n;
   return 0;
 }
 
 int potus_timeline_timing(double *ms) {
-  if (!ms) return fail(POTUS_ERR_ARG, "potus_timeline_timing: null output");
-  ms[0] = g_tl_ms[0]; ms[1] = g_tl_ms[1];
-  return 0;
+  return timing_out("potus_timeline_timing", g_tl_ms, 2, ms);
 }
 
 // ---------------------------------------------------------------------------------------------- exact cross-validation (potus_crossval.hpp)
@@ -4515,10 +4519,9 @@ namespace {
 constexpr size_t CV_BLOCK_BUDGET = 256ull << 20;   // the ll block of one round of potus_cv_lpd (POTUS_CV_BLOCK_BUDGET, bytes: tests)
 thread_local double g_cv_ms[2] = {0.0, 0.0};       // the calling thread's last potus_cv_lpd: k_cv_loglik, k_cv_reduce (HIP events, summed over the blocks)
 
-struct CvPlan {
-  int n_ds = 1, cpd = 1, Np = 0, first = 0, n_post = 0;
-  std::vector<int> off, held, pair_ds, pair_k, skip;   // pairs by data set, then by poll number; held = the pair's poll in the model's order
-  const DevModel *Mg = nullptr;
+struct CvPlan : DsPlan {
+  int Np = 0;
+  std::vector<int> off, held, pair_ds, pair_k;   // pairs by data set, then by poll number; held = the pair's poll in the model's order
   long long n_pairs() const { return (long long)held.size(); }
 };
 // every refusal that needs no device, and the held lists in the model's poll order (the qi mapping k_loo_loglik inverts)
@@ -4528,7 +4531,7 @@ int cv_check_args(const char *what, Sampler *sp, const int32_t *held_state, cons
   if (integrate != 0 && integrate != 1) return fail(POTUS_ERR_ARG, "%s: integrate = %d (0: the draw's noise coordinate, 1: integrated out)", what, integrate);
   if (sp->dense) return fail(POTUS_ERR_UNSUPPORTED, "%s: the dense metric is not supported (metric = POTUS_METRIC_DIAG only)", what);
   if (!sp->inited) return fail(POTUS_ERR_STATE, "%s: the handle is not initialised (potus_init, then potus_run)", what);
-  pl.n_ds = std::max(sp->n_ds, 1); pl.cpd = sp->chains_per_ds(); pl.Np = Np;
+  pl.of(sp); pl.Np = Np;
   std::vector<int> model_of(Np, -1);
   for (int i = 0; i < Np; i++) {   // day-sorted poll i is state poll qidx - o_ns or national poll qidx - o_nn (build_model)
     const int qi = sp->h_pq[i];
@@ -4540,18 +4543,6 @@ int cv_check_args(const char *what, Sampler *sp, const int32_t *held_state, cons
       if (k < Ns ? held_state[(size_t)d * Ns + k] : held_national[(size_t)d * Nn + (k - Ns)]) { pl.held.push_back(model_of[k]); pl.pair_ds.push_back(d); pl.pair_k.push_back(k); }
     pl.off.push_back((int)pl.held.size());
   }
-  return 0;
-}
-int cv_plan(const char *what, Sampler *sp, CvPlan &pl) {   // under the device lock, before anything is allocated or launched
-  std::vector<ChainScalars> sc;
-  if (const int rc = read_scalars(sp, sc)) return rc;
-  int n_saved = 0;
-  if (const int rc = saved_count(sp, &n_saved)) return rc;
-  pl.first = warm_rows(sp, n_saved); pl.n_post = n_saved - pl.first;
-  if (pl.n_post < 1) return fail(POTUS_ERR_STATE, "%s: no post-warm-up draws saved yet (%d saved, %d of them warm-up)", what, n_saved, pl.first);
-  pl.skip.assign(pl.n_ds, 0);
-  for (int c = 0; c < sp->R.chains; c++) if (sc[c].status != 0) pl.skip[c / pl.cpd] = 1;
-  pl.Mg = sp->n_ds ? sp->dMs : sp->dM;
   return 0;
 }
 struct CvDev { LooRows rows; int *off = nullptr, *held = nullptr, *pair_ds = nullptr, *skip = nullptr; };
@@ -4590,11 +4581,11 @@ int potus_cv_log_lik_device(int handle, const int32_t *held_state, const int32_t
     DeviceGuard guard;
     DeviceLocks lock(sp->device);
     HIP_TRY(hipSetDevice(sp->device));
-    return cv_plan(what, sp, pl);
+    return ds_plan(what, sp, pl);
   }
   DeviceBlock dev;
   if (const int rc_ = dev.open(what, sp->device, out_device, "output")) return rc_;
-  if (const int rc_ = cv_plan(what, sp, pl)) return rc_;
+  if (const int rc_ = ds_plan(what, sp, pl)) return rc_;
   DevBufs keep;
   CvDev d;
   if (const int rc_ = cv_upload(what, sp, pl, keep, d)) return rc_;
@@ -4613,7 +4604,7 @@ int potus_cv_lpd(int handle, const int32_t *held_state, const int32_t *held_nati
   DeviceGuard guard;
   DeviceLocks lock(sp->device);
   HIP_TRY(hipSetDevice(sp->device));
-  if (const int rc_ = cv_plan(what, sp, pl)) return rc_;
+  if (const int rc_ = ds_plan(what, sp, pl)) return rc_;
   const long long nd = (long long)pl.cpd * pl.n_post;
   const int np = (int)pl.n_pairs();
   for (size_t i = 0; i < (size_t)pl.n_ds * pl.Np * 2; i++) lpd_out[i] = std::numeric_limits<double>::quiet_NaN();
@@ -4630,25 +4621,25 @@ int potus_cv_lpd(int handle, const int32_t *held_state, const int32_t *held_nati
   double *blk = nullptr, *dout = nullptr;
   if ((rc = keep.get(&blk, (size_t)nb * nd * 8, what)) || (rc = keep.get(&dout, (size_t)np * 2 * 8, what))) return rc;
   const int n_blocks = (np + nb - 1) / nb;
-  std::vector<OcEvents> e0(n_blocks), e1(n_blocks);
+  std::vector<EventTimer> e0(n_blocks), e1(n_blocks);
   for (int b = 0; b < n_blocks; b++) {
     const int p0 = b * nb, p1 = std::min(p0 + nb, np);
-    HIP_TRY(hipEventCreate(&e0[b].a)); HIP_TRY(hipEventCreate(&e0[b].b)); HIP_TRY(hipEventCreate(&e1[b].a)); HIP_TRY(hipEventCreate(&e1[b].b));
-    HIP_TRY(hipEventRecord(e0[b].a, sp->stream));
+    HIP_TRY(e0[b].made); HIP_TRY(e1[b].made);
+    HIP_TRY(e0[b].start(sp->stream));
     if ((rc = cv_loglik(sp, pl, d, p0, p1, integrate, blk))) return rc;
-    HIP_TRY(hipEventRecord(e0[b].b, sp->stream));
+    HIP_TRY(e0[b].stop(sp->stream));
     CvReduceParams Q{blk, d.pair_ds + p0, d.skip, p1 - p0, (int)nd, dout + (size_t)p0 * 2};
-    HIP_TRY(hipEventRecord(e1[b].a, sp->stream));
+    HIP_TRY(e1[b].start(sp->stream));
     hipLaunchKernelGGL(k_cv_reduce, dim3((unsigned)std::min((p1 - p0 + 3) / 4, 65535)), dim3(256), 0, sp->stream, Q);
     HIP_TRY(hipGetLastError());
-    HIP_TRY(hipEventRecord(e1[b].b, sp->stream));
+    HIP_TRY(e1[b].stop(sp->stream));
   }
   std::vector<double> h((size_t)np * 2);
   HIP_TRY(hipMemcpyAsync(h.data(), dout, h.size() * 8, hipMemcpyDeviceToHost, sp->stream));
   HIP_TRY(hipStreamSynchronize(sp->stream));
   for (int b = 0; b < n_blocks; b++) {
-    float ms0 = 0, ms1 = 0;
-    HIP_TRY(hipEventElapsedTime(&ms0, e0[b].a, e0[b].b)); HIP_TRY(hipEventElapsedTime(&ms1, e1[b].a, e1[b].b));
+    double ms0 = 0, ms1 = 0;
+    if ((rc = e0[b].elapsed_or_fail(&ms0)) || (rc = e1[b].elapsed_or_fail(&ms1))) return rc;
     g_cv_ms[0] += ms0; g_cv_ms[1] += ms1;
   }
   for (int p = 0; p < np; p++) {
@@ -4659,9 +4650,7 @@ int potus_cv_lpd(int handle, const int32_t *held_state, const int32_t *held_nati
 }
 
 int potus_cv_timing(double *ms) {
-  if (!ms) return fail(POTUS_ERR_ARG, "potus_cv_timing: null output");
-  ms[0] = g_cv_ms[0]; ms[1] = g_cv_ms[1];
-  return 0;
+  return timing_out("potus_cv_timing", g_cv_ms, 2, ms);
 }
 
 // ---------------------------------------------------------------------------------------------- the posterior mode (potus_optimize.hpp)
@@ -4714,46 +4703,40 @@ int potus_optimize(int handle, const potus_optimize_opts *opts, const double *q0
     if ((rc = tmp.get(&dq0, (size_t)n_paths * D * 8, what))) return rc;
     HIP_TRY(hipMemcpyAsync(dq0, q0, (size_t)n_paths * D * 8, hipMemcpyHostToDevice, sp->stream));
   }
-  OcEvents ev;
-  HIP_TRY(hipEventCreate(&ev.a)); HIP_TRY(hipEventCreate(&ev.b));
-  const int per_ds = sp->n_ds ? n_paths / sp->n_ds : n_paths;
-  const DevModel *Mg = sp->n_ds ? sp->dMs : sp->dM;
+  EventTimer ev;
+  HIP_TRY(ev.made);
+  DsPlan pl;   // the models of the handle's data sets; the paths are dealt to them as chains are
+  pl.of(sp);
+  const int per_ds = n_paths / pl.n_ds;
+  const DevModel *Mg = pl.Mg;
   OptParams P{dq0, work, rows, dlp, dgn, dinfo, per_ds, o.history_size, o.iter, o.jacobian, o.path_offset, Dpad,
               o.init_alpha, o.tol_obj, o.tol_rel_obj, o.tol_grad, o.tol_rel_grad, o.tol_param, sp->R.init_radius, sp->R.seed_lo, sp->R.seed_hi};
   OptParams *dP = nullptr;
   if ((rc = tmp.get(&dP, sizeof(OptParams), what))) return rc;
   HIP_TRY(hipMemcpyAsync(dP, &P, sizeof(OptParams), hipMemcpyHostToDevice, sp->stream));
-  HIP_TRY(hipEventRecord(ev.a, sp->stream));
+  HIP_TRY(ev.start(sp->stream));
   hipLaunchKernelGGL(k_opt_lbfgs, dim3(n_paths), dim3(PT_THREADS), sp->lds_bytes, sp->stream, Mg, (const OptParams *)dP);
   HIP_TRY(hipGetLastError());
-  HIP_TRY(hipEventRecord(ev.b, sp->stream));
+  HIP_TRY(ev.stop(sp->stream));
   std::vector<double> hrows((size_t)n_paths * row);
   HIP_TRY(hipMemcpyAsync(hrows.data(), rows, hrows.size() * 8, hipMemcpyDeviceToHost, sp->stream));
   HIP_TRY(hipMemcpyAsync(lp_out, dlp, (size_t)n_paths * 8, hipMemcpyDeviceToHost, sp->stream));
   if (gnorm_out) HIP_TRY(hipMemcpyAsync(gnorm_out, dgn, (size_t)n_paths * 8, hipMemcpyDeviceToHost, sp->stream));
   HIP_TRY(hipMemcpyAsync(info_out, dinfo, (size_t)n_paths * 3 * 4, hipMemcpyDeviceToHost, sp->stream));
   if (row_out) {   // the CmdStan row of every path's point, built with the path's own model
-    const int nsel = col_end - col_begin, grid = std::min(n_paths, 512);
-    double *scratch = nullptr, *dout = nullptr;
-    if ((rc = tmp.get(&scratch, (size_t)grid * sp->L.ncols * 8, what)) || (rc = tmp.get(&dout, (size_t)n_paths * nsel * 8, what))) return rc;
-    WAParams W{rows, n_paths, 1, 1, row, sp->L.ncols, col_begin, col_end, scratch, dout, sp->sigma_ns, sp->sigma_nn, nsel};   // one saved draw of n_paths chains
-    if (sp->n_ds) hipLaunchKernelGGL(k_write_array_ds, dim3(grid), dim3(256), 0, sp->stream, Mg, W, per_ds);
-    else hipLaunchKernelGGL(k_write_array, dim3(grid), dim3(256), 0, sp->stream, Mg, W);
-    HIP_TRY(hipGetLastError());
-    HIP_TRY(hipMemcpyAsync(row_out, dout, (size_t)n_paths * nsel * 8, hipMemcpyDeviceToHost, sp->stream));
+    const int nsel = col_end - col_begin;
+    WAParams W{rows, n_paths, 1, 1, row, sp->L.ncols, col_begin, col_end, nullptr, nullptr, sp->sigma_ns, sp->sigma_nn, nsel};   // one saved draw of n_paths chains
+    if ((rc = launch_rows(sp, tmp, what, Mg, sp->n_ds ? per_ds : 0, W))) return rc;
+    HIP_TRY(hipMemcpyAsync(row_out, W.out, (size_t)n_paths * nsel * 8, hipMemcpyDeviceToHost, sp->stream));
   }
   HIP_TRY(hipStreamSynchronize(sp->stream));
-  float ms = 0;
-  HIP_TRY(hipEventElapsedTime(&ms, ev.a, ev.b));
-  g_opt_ms = ms;
+  if ((rc = ev.elapsed_or_fail(&g_opt_ms))) return rc;
   for (int i = 0; i < n_paths; i++) std::copy(hrows.begin() + (size_t)i * row + POTUS_N_SAMPLER_COLS, hrows.begin() + (size_t)(i + 1) * row, q_out + (size_t)i * D);
   return 0;
 }
 
 int potus_optimize_timing(double *ms) {
-  if (!ms) return fail(POTUS_ERR_ARG, "potus_optimize_timing: null output");
-  ms[0] = g_opt_ms;
-  return 0;
+  return timing_out("potus_optimize_timing", &g_opt_ms, 1, ms);
 }
 
 int potus_simulate_prior(int handle, uint64_t seed, int n_sims, int sim_offset, double *q_out, int32_t *n_democrat_state_out, int32_t *n_democrat_national_out) {
@@ -4799,15 +4782,13 @@ int potus_constrain(int handle, const double *q, int n, int col_begin, int col_e
   const int D = sp->L.D, row = POTUS_N_SAMPLER_COLS + D, nsel = col_end - col_begin;
   std::vector<double> blk((size_t)n * row, NAN);   // the sampler columns of these rows are NaN
   for (int i = 0; i < n; i++) std::copy(q + (size_t)i * D, q + (size_t)(i + 1) * D, blk.begin() + (size_t)i * row + POTUS_N_SAMPLER_COLS);
-  const int grid = std::min(n, 512);
   DevBufs tmp;
-  double *dblk = nullptr, *scratch = nullptr, *dout = nullptr;
-  HIP_TRY(tmp.alloc(&dblk, blk.size() * 8)); HIP_TRY(tmp.alloc(&scratch, (size_t)grid * sp->L.ncols * 8)); HIP_TRY(tmp.alloc(&dout, (size_t)n * nsel * 8));
+  double *dblk = nullptr;
+  HIP_TRY(tmp.alloc(&dblk, blk.size() * 8));
   HIP_TRY(hipMemcpyAsync(dblk, blk.data(), blk.size() * 8, hipMemcpyHostToDevice, sp->stream));
-  WAParams W{dblk, 1, n, n, row, sp->L.ncols, col_begin, col_end, scratch, dout, sp->sigma_ns, sp->sigma_nn, nsel};   // n draws of one chain
-  hipLaunchKernelGGL(k_write_array, dim3(grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, W);
-  HIP_TRY(hipGetLastError());
-  HIP_TRY(hipMemcpyAsync(out, dout, (size_t)n * nsel * 8, hipMemcpyDeviceToHost, sp->stream));
+  WAParams W{dblk, 1, n, n, row, sp->L.ncols, col_begin, col_end, nullptr, nullptr, sp->sigma_ns, sp->sigma_nn, nsel};   // n draws of one chain
+  if (const int rc_ = launch_rows(sp, tmp, nullptr, sp->dM, 0, W)) return rc_;
+  HIP_TRY(hipMemcpyAsync(out, W.out, (size_t)n * nsel * 8, hipMemcpyDeviceToHost, sp->stream));
   HIP_TRY(hipStreamSynchronize(sp->stream));
   return 0;
 }
@@ -4822,15 +4803,9 @@ int potus_sbc_ranks(int handle, const double *truth, int col_begin, int col_end,
   if (thin < 1) return fail(POTUS_ERR_ARG, "potus_sbc_ranks: thin = %d, at least 1", thin);
   DeviceLocks lock(sp->device);
   HIP_TRY(hipSetDevice(sp->device));
-  std::vector<ChainScalars> sc;
-  if (const int rc = read_scalars(sp, sc)) return rc;
-  int n_saved = 0;
-  if (const int rc = saved_count(sp, &n_saved)) return rc;
-  const int first = sp->R.save_warmup ? sp->R.num_warmup : 0, n_post = n_saved - first;
-  if (n_post < 1) return fail(POTUS_ERR_STATE, "potus_sbc_ranks: no post-warm-up draws saved yet (%d saved, %d of them warm-up)", n_saved, std::min(n_saved, first));
-  const int nL = (n_post + thin - 1) / thin, chains = sp->R.chains, n_ds = std::max(sp->n_ds, 1), cpd = sp->chains_per_ds(), nsel = col_end - col_begin;
-  std::vector<int> skip(chains);
-  for (int c = 0; c < chains; c++) skip[c] = sc[c].status != 0;
+  DsPlan pl;
+  if (const int rc = ds_plan("potus_sbc_ranks", sp, pl)) return rc;
+  const int nL = (pl.n_post + thin - 1) / thin, chains = sp->R.chains, n_ds = pl.n_ds, cpd = pl.cpd, nsel = col_end - col_begin;
   const int grid = std::min(chains, 1024);
   DevBufs tmp;
   double *dtruth = nullptr, *scratch = nullptr;
@@ -4839,8 +4814,8 @@ int potus_sbc_ranks(int handle, const double *truth, int col_begin, int col_end,
   HIP_TRY(tmp.alloc(&cl, (size_t)chains * nsel * 4)); HIP_TRY(tmp.alloc(&ce, (size_t)chains * nsel * 4));
   HIP_TRY(tmp.alloc(&dl, (size_t)n_ds * nsel * 4)); HIP_TRY(tmp.alloc(&de, (size_t)n_ds * nsel * 4));
   HIP_TRY(hipMemcpyAsync(dtruth, truth, (size_t)n_ds * nsel * 8, hipMemcpyHostToDevice, sp->stream));
-  HIP_TRY(hipMemcpyAsync(dskip, skip.data(), (size_t)chains * 4, hipMemcpyHostToDevice, sp->stream));
-  RankParams P{sp->R.draws, chains, sp->R.n_save_max, sp->R.row, sp->L.ncols, col_begin, col_end, first, thin, nL, cpd, dtruth, dskip, scratch, cl, ce};
+  HIP_TRY(hipMemcpyAsync(dskip, pl.failed.data(), (size_t)chains * 4, hipMemcpyHostToDevice, sp->stream));   // per chain: what k_sbc_ranks takes
+  RankParams P{sp->R.draws, chains, sp->R.n_save_max, sp->R.row, sp->L.ncols, col_begin, col_end, pl.first, thin, nL, cpd, dtruth, dskip, scratch, cl, ce};
   hipLaunchKernelGGL(k_sbc_ranks, dim3(grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, P);
   HIP_TRY(hipGetLastError());
   const int rgrid = (int)std::min<long long>(((long long)n_ds * nsel + 255) / 256, 1024);
@@ -4853,6 +4828,8 @@ int potus_sbc_ranks(int handle, const double *truth, int col_begin, int col_end,
   return 0;
 }
 
+// Development aid (POTUS_PROF builds only; not part of include/potus_hmc.h): per-chain cycle
+// counters of the kernel phases.  Returns the number of slots written per chain, 0 otherwise.
 int potus_debug_profile(int handle, double *out) {
   Sampler *sp = get(handle);
   if (!sp || !sp->R.prof || !out) return 0;
@@ -4973,20 +4950,19 @@ static int dense_matvec_probe_impl(bool pooled, int device, int chains, int D, i
       HIP_TRY(hipMemcpy(P.state + ((size_t)c * DV_COUNT + DV_POOLP + k) * P.LD, x_host + ((size_t)c * nrhs + k) * D, (size_t)D * 8, hipMemcpyHostToDevice));
   }
   if ((rc = pr.set_rounds(rds))) return rc;
-  hipEvent_t e0 = nullptr, e1 = nullptr;
-  HIP_TRY(hipEventCreate(&e0)); HIP_TRY(hipEventCreate(&e1));
+  EventTimer e;
+  HIP_TRY(e.made);
   DnActive act;
   act.n = 0;
   if (n_act < chains && chains <= DN_ACT_MAX && !getenv("POTUS_PROBE_NO_COMPACTION")) for (int c = 0; c < chains; c++) if (act_flag[c]) act.idx[act.n++] = c;
   dense_symv_launch(0, P, act, nrhs);   // warm-up
-  (void)hipEventRecord(e0, 0);
+  (void)e.start(0);
   for (int r = 0; r < reps; r++) dense_symv_launch(0, P, act, nrhs);
-  (void)hipEventRecord(e1, 0);
+  (void)e.stop(0);
   const bool ok = hipDeviceSynchronize() == hipSuccess && hipGetLastError() == hipSuccess;
-  float t = 0; (void)hipEventElapsedTime(&t, e0, e1);
-  (void)hipEventDestroy(e0); (void)hipEventDestroy(e1);
+  double t = 0; (void)e.elapsed(&t);
   if (!ok) return fail(POTUS_ERR_DEVICE, "k_dn_symv failed");
-  if (ms) *ms = (double)t / reps;
+  if (ms) *ms = t / reps;
   if (pass_bytes) *pass_bytes = pooled ? (long long)D * P.LD * (P.f32 ? 4 : 8) * ((n_act * nrhs + DNP_RMAX - 1) / DNP_RMAX)
                                        : dense_pass_bytes(D, P.LD, P.rb) * (nrhs == 3 ? 2 : 1) / (P.f32 ? 2 : 1);
   for (int c = 0; c < chains; c++) {

@@ -183,6 +183,7 @@ class Handle:
         self.L = load_library()
         self.data = data
         self.variant = variant
+        self.n_datasets = 1                        # until set_datasets[_ex]
         self._d, self._keep = _abi.make_data(data, variant)
         o = _abi.PotusOpts()
         self.L.potus_default_opts(C.byref(o))
@@ -316,11 +317,6 @@ class Handle:
         _check(L, L.potus_dense_adapt_timing(self.h, C.byref(a), C.byref(b), C.byref(c), C.byref(n)))
         return dict(cov_ms=a.value, chol_ms=b.value, init_stepsize_ms=c.value, window_ends=n.value)
 
-    def iterations_done(self):
-        n = C.c_int()
-        _check(self.L, self.L.potus_iterations_done(self.h, C.byref(n)))
-        return n.value
-
     def pool_window(self):
         """pooled_metric = 2: (pending, count, mean, m2) of a window end that waits for the host -- mean [D] and m2 [D, LD] are torch tensors ON the handle's
         GPU that alias the library's buffers (zero copy; m2[:, :D] is the matrix of centred outer products, both triangles)."""
@@ -406,13 +402,18 @@ class Handle:
                                                     ints(n_two_share_national, Nn), dbls(mu_b_prior, S), dbls(mu_b_T_scale, 1)))
         self.n_datasets = n
 
+    def _day_range(self, days):
+        """days = (begin, end), 0-based; None: election day only."""
+        T = int(self.data["T"])
+        return (T - 1, T) if days is None else (int(days[0]), int(days[1]))
+
     def timeline(self, ev, days=None, ev_to_win=270):
         """potus_timeline: per data set of this handle and per day of `days` = (begin, end) (0-based, default: election day only) the summaries of
         posterior_summary over the data set's post-warm-up draws.  dict(state [n, days, S, 4], national [n, days, 4], electoral_votes [n, days, 5],
         n_draws [n]); a data set with a failed chain has n_draws = 0 and NaN."""
-        S, T = int(self.data["S"]), int(self.data["T"])
-        t0, t1 = (T - 1, T) if days is None else (int(days[0]), int(days[1]))
-        n, nd = int(getattr(self, "n_datasets", 1)), max(t1 - t0, 0)
+        S = int(self.data["S"])
+        t0, t1 = self._day_range(days)
+        n, nd = self.n_datasets, max(t1 - t0, 0)
         ev = np.ascontiguousarray(ev, dtype=np.float64).reshape(S)
         st, na, eo, cnt = np.zeros((n, nd, S, 4)), np.zeros((n, nd, 4)), np.zeros((n, nd, 5)), np.zeros(n, np.int32)
         _check(self.L, self.L.potus_timeline(self.h, t0, t1, _dp(ev), int(ev_to_win), _dp(st), _dp(na), _dp(eo), _ip(cnt)))
@@ -421,9 +422,9 @@ class Handle:
     def timeline_scores_device(self, days=None):
         """potus_timeline_scores_device: predicted_score of the days (begin, end) as a torch tensor [n_datasets, draws per data set, days, S] on this handle's GPU."""
         import torch
-        T, S = int(self.data["T"]), int(self.data["S"])
-        t0, t1 = (T - 1, T) if days is None else (int(days[0]), int(days[1]))
-        n = int(getattr(self, "n_datasets", 1))
+        S = int(self.data["S"])
+        t0, t1 = self._day_range(days)
+        n = self.n_datasets
         per = (self.opts.chains // n) * self.post_warmup_saved()
         out = torch.empty((n, per, max(t1 - t0, 1), S), dtype=torch.float64, device=f"cuda:{self.opts.device}")
         torch.cuda.current_stream(out.device).synchronize()
@@ -522,7 +523,7 @@ class Handle:
 
     def _cv_masks(self, held_state, held_national):
         """The two masks as contiguous int32 [n_datasets, polls] arrays (None where the data have no such polls)."""
-        n = int(getattr(self, "n_datasets", 1))
+        n = self.n_datasets
         out = []
         for m, key in ((held_state, "N_state_polls"), (held_national, "N_national_polls")):
             w = int(self.data[key])
