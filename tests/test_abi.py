@@ -54,6 +54,37 @@ def test_num_params_and_columns(cases, name, D, ncols):
     assert n2 == ncols
 
 
+def _tiny(variant, Ns, Nn):
+    """S = 2, T = 2, P = 1, M = Pop = 1: every optional block of the output row is empty or one column wide."""
+    S, i32 = 2, lambda k, v=1: np.full(k, v, np.int32)
+    d = dict(S=S, T=2, P=1, M=1, Pop=1, N_state_polls=Ns, N_national_polls=Nn, mu_b_prior=np.zeros(S), state_weights=np.full(S, 0.5),
+             state_covariance_0=np.eye(S), sigma_c=0.06, sigma_m=0.04, sigma_pop=0.04, sigma_measure_noise_national=0.04, sigma_measure_noise_state=0.04,
+             sigma_e_bias=0.02, random_walk_scale=0.02, mu_b_T_scale=0.3, polling_bias_scale=0.03)
+    for kind, k in (("state", Ns), ("national", Nn)):
+        d.update({f"day_{kind}": i32(k), f"poll_{kind}": i32(k), f"poll_mode_{kind}": i32(k), f"poll_pop_{kind}": i32(k), f"unadjusted_{kind}": np.zeros(k),
+                  f"n_democrat_{kind}": i32(k, 5), f"n_two_share_{kind}": i32(k, 10)})
+    d["state"] = i32(Ns)
+    return d
+
+
+@pytest.mark.parametrize("variant", ["full", "no_mode_adjustment"])
+@pytest.mark.parametrize("Ns,Nn", [(0, 0), (0, 3), (3, 0), (1, 1)])
+def test_num_columns_with_empty_and_one_column_blocks(variant, Ns, Nn):
+    """potus_num_columns takes its count from the row's block table (RowCols); _abi.column_layout and potus_column_name keep tables of their own."""
+    data = _tiny(variant, Ns, Nn)
+    L = sampler.load_library()
+    d, keep = _abi.make_data(data, variant)
+    a, b = C.c_int(), C.c_int()
+    layout, ncols = _abi.column_layout(data, variant)
+    assert L.potus_num_params(C.byref(d), C.byref(a)) == 0 and a.value == _abi.num_params(data, variant)
+    assert L.potus_num_columns(C.byref(d), C.byref(b)) == 0 and b.value == ncols == layout["predicted_score"][1]
+    buf = C.create_string_buffer(96)
+    for name, (c0, c1, _) in layout.items():                                 # the first column of every block that is not empty carries its name
+        if c1 > c0:
+            assert L.potus_column_name(C.byref(d), c0, buf, 96) == 0 and buf.value.decode().split(".")[0] == name, (name, buf.value)
+    assert L.potus_column_name(C.byref(d), ncols, buf, 96) != 0
+
+
 def test_column_names_follow_cmdstan(cases):
     data, variant = cases["2016"]
     L = sampler.load_library()

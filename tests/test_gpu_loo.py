@@ -70,13 +70,26 @@ def _close(a, b, tol=1e-8):
     assert err.max() <= tol, float(err.max())
 
 
+@pytest.mark.parametrize("via", ["log_lik", "cv_log_lik"])
 @pytest.mark.parametrize("variant", VARIANTS)
-def test_plain_log_lik_equals_scipy_on_the_logit_pi_columns(fits, variant):
+def test_plain_log_lik_equals_scipy_on_the_logit_pi_columns(fits, variant, via):
+    """The three users of the row's poll predictor agree on the row's column blocks: the logit_pi columns are wa_build_row's, the
+    log-likelihoods k_loo_loglik's (via = log_lik) or k_cv_loglik's (cv_log_lik: the plain handle as one data set that holds every poll out).
+    On the host the noise term comes out of logit_pi and goes back in: eta = logit_pi - raw_measure_noise sigma, x = eta + sigma z."""
     h = fits[variant]
-    y, n, _ = _polls(h.data)
-    lp = _columns(h, "logit_pi_democrat_state", "logit_pi_democrat_national")
-    ref = stats.binom.logpmf(y[:, None, None], n[:, None, None], 1.0 / (1.0 + np.exp(-lp)))
-    assert np.abs(_log_lik(h, False) - ref).max() < 1e-9
+    y, n, sig = _polls(h.data)
+    Ns, Nn = int(h.data["N_state_polls"]), int(h.data["N_national_polls"])
+    assert Ns > 0 and Nn > 0 and len(y) == Ns + Nn                       # state polls and national polls are both compared
+    z = _columns(h, "raw_measure_noise_state", "raw_measure_noise_national")
+    eta = _columns(h, "logit_pi_democrat_state", "logit_pi_democrat_national") - sig[:, None, None] * z
+    ref = stats.binom.logpmf(y[:, None, None], n[:, None, None], 1.0 / (1.0 + np.exp(-(eta + sig[:, None, None] * z))))
+    if via == "log_lik":
+        ll = _log_lik(h, False)
+    else:
+        ll = h.cv_log_lik_device(np.ones((1, Ns)), np.ones((1, Nn)), integrate=False).cpu().numpy().reshape(ref.shape)
+    err = np.abs(ll - ref)
+    print(f"{variant} {via}: largest |device - scipy| state polls {err[:Ns].max():.2e}, national polls {err[Ns:].max():.2e}")
+    assert err[:Ns].max() < 1e-9 and err[Ns:].max() < 1e-9
 
 
 @pytest.mark.parametrize("variant", VARIANTS)

@@ -95,6 +95,31 @@ def test_chains_equal_stand_alone_handles_byte_for_byte(tl):
     assert d_many[0].tobytes() != d_many[2].tobytes() and d_many[0].tobytes() != d_many[6].tobytes()
 
 
+@pytest.mark.parametrize("variant", ["full", "no_mode_adjustment"])
+def test_data_sets_that_are_the_handles_own_give_the_rows_of_a_plain_handle(variant):
+    """One row loop serves both kinds of handle: with chains_per_ds = 2 (k_write_array_ds; two data sets that are the handle's own data, prior
+    and scale) and with chains_per_ds = 0 (k_write_array, the plain handle) it must pick the same model for every chain.  4 x 130 = 520 rows:
+    the 512 workgroups wrap."""
+    data = synthetic.small(variant)
+    Ns, Nn, nw, ns = int(data["N_state_polls"]), int(data["N_national_polls"]), 20, 130
+    design = timeline.design_of(data, np.ones((2, Ns), bool), np.ones((2, Nn), bool), np.tile(np.asarray(data["mu_b_prior"], dtype=np.float64), (2, 1)),
+                                np.full(2, float(data["mu_b_T_scale"])))
+    _, ncols = _abi.column_layout(data, variant)
+    rows = []
+    for many in (True, False):
+        h = Handle(data, variant, chains=4, num_warmup=nw, num_samples=ns, **OPTS)
+        if many:
+            timeline.set_design(h, design)
+        h.init()
+        h.run(nw + ns)
+        assert h.chain_status()[0] == [0] * 4
+        rows.append((h.draws(), h.write_array(0, ncols, ns)))
+        h.close()
+    assert rows[0][1].shape == (ns, 4, ncols) and ns * 4 > 512
+    assert rows[0][0].tobytes() == rows[1][0].tobytes()
+    assert rows[0][1].tobytes() == rows[1][1].tobytes()
+
+
 @pytest.mark.parametrize("days", ["first", "last", "all", "middle"])
 def test_scores_equal_write_array(tl, days):
     T = tl["T"]

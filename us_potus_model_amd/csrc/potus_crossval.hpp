@@ -28,9 +28,8 @@
 #include "potus_loo.hpp"
 
 struct CvParams {
-  const double *draws;   // [chains][n_save_max][row]
-  int chains, n_save_max, row, ncols;
-  int first, n_post, chains_per_ds, integrate;   // post-warm-up rows first .. first + n_post - 1 of every chain
+  RowSrc src;
+  int ncols, n_post, chains_per_ds, integrate;   // post-warm-up rows src.first .. src.first + n_post - 1 of every chain
   const double *pd0;     // [4][Npad] y, n, unadjusted, sigma of the data given to potus_create, in the model's poll order
   const double *lc;      // [Npoll] log C(n, y) of that data, same order
   const int *off;        // [n_datasets + 1] offsets of the data sets' held lists
@@ -41,9 +40,9 @@ struct CvParams {
   double *out;           // [p1 - p0][chains_per_ds * n_post]
 };
 __global__ __launch_bounds__(256) void k_cv_loglik(const DevModel *Mg, CvParams P) {
-  __shared__ double s_bT[64], s_pb[64], s_misc[4];
+  __shared__ RowLds lds;
   const int tid = threadIdx.x;
-  const long long n_items = (long long)P.chains * P.n_post, nd = (long long)P.chains_per_ds * P.n_post;
+  const long long n_items = (long long)P.src.chains * P.n_post, nd = (long long)P.chains_per_ds * P.n_post;
   double *row = P.scratch + (size_t)blockIdx.x * P.ncols;
   for (long long d = blockIdx.x; d < n_items; d += gridDim.x) {          // workgroup-uniform
     const int chain = (int)(d / P.n_post), iter = (int)(d % P.n_post), ds = chain / P.chains_per_ds;
@@ -55,20 +54,15 @@ __global__ __launch_bounds__(256) void k_cv_loglik(const DevModel *Mg, CvParams 
       continue;
     }
     const DevModel M = Mg[ds];
-    const int S = M.S, T = M.T, Np = M.Npad;
-    // wa_build_row's column blocks
-    const int o_mub = POTUS_N_SAMPLER_COLS + M.D, o_muc = o_mub + S * T, o_mum = o_muc + M.P, o_mupop = o_mum + (M.full ? M.M : 0);
-    const int o_eb = o_mupop + (M.full ? M.Pop : 0), o_pb = o_eb + (M.full ? T : 0), o_nat = o_pb + S, o_natpb = o_nat + T;
-    const double *src = P.draws + ((size_t)chain * P.n_save_max + P.first + iter) * P.row;
-    wa_build_row(M, src, row, s_bT, s_pb, s_misc);
-    const double *q = src + POTUS_N_SAMPLER_COLS;
+    const int Np = M.Npad;
+    const RowCols c = row_cols(M);
+    const double *src = P.src.at(chain, iter), *q = src + POTUS_N_SAMPLER_COLS;
+    wa_build_row(M, src, row, lds);
     for (int j = j0 + tid; j < j1; j += 256) {
       const int i = P.held[j];
-      const int s = M.pi[i], t = M.pi[Np + i], qi = M.pi[5 * Np + i];
-      const bool nat = s == S;
-      double eta = (nat ? row[o_nat + t] : row[o_mub + s + S * t]) + row[o_muc + M.pi[2 * Np + i]];
-      if (M.full) eta += row[o_mum + M.pi[3 * Np + i]] + row[o_mupop + M.pi[4 * Np + i]] + P.pd0[2 * Np + i] * row[o_eb + t];
-      eta += nat ? row[o_natpb] : row[o_pb + s];
+      const int s = M.pi[i], qi = M.pi[5 * Np + i];
+      double eta = row_poll_eta(M, c, row, P.pd0 + 2 * Np, i);
+      eta += s == M.S ? row[c.nat_polling_bias] : row[c.polling_bias + s];
       P.out[(size_t)(j - P.p0) * nd + at] = P.lc[i] + loo_poll_ll(P.pd0[i], P.pd0[Np + i], eta, P.pd0[3 * Np + i], q[qi], P.integrate);
     }
     __syncthreads();

@@ -825,233 +825,7 @@ __global__ void k_dn_import_q(const RunParams *Rg, const DnParams P, const int *
   }
 }
 
-// write_array (stan:70-113 transformed parameters, stan:134-140 generated quantities) for saved
-// draws; one 256-thread workgroup per draw builds the full CmdStan row in scratch and copies
-// the requested column range.  out layout: [iter][chain][col_end - col_begin].
-struct WAParams {
-  const double *draws; // [chains][n_save_max][row]
-  int chains, n_save_max, n_saved, row, ncols, col_begin, col_end;
-  double *scratch;     // [gridDim.x][ncols]
-  double *out;         // [n_saved * chains][out_stride], the first col_end - col_begin entries of a row are written
-  double sigma_ns, sigma_nn;
-  int out_stride;
-};
-// One full CmdStan output row (ncols doubles) from a draw's sampler columns and unconstrained point src[0 .. 7 + D); src must not
-// alias row.  Called by every thread of a 256-thread workgroup; s_bT / s_pb hold 64 doubles, s_misc 4 (LDS).  Shared by
-// k_write_array, k_simulate_prior and k_sbc_ranks.
-__device__ __forceinline__ void wa_build_row(const DevModel &M, const double *src, double *row, double *s_bT, double *s_pb, double *s_misc) {
-  const int tid = threadIdx.x, S = M.S, T = M.T, D = M.D;
-  const int o_par = POTUS_N_SAMPLER_COLS;
-  const int o_mub = o_par + D, o_muc = o_mub + S * T;
-  const int o_mum = o_muc + M.P, o_mupop = o_mum + (M.full ? M.M : 0), o_eb = o_mupop + (M.full ? M.Pop : 0);
-  const int o_pb = o_eb + (M.full ? T : 0), o_nat = o_pb + S, o_natpb = o_nat + T, o_srho = o_natpb + 1;
-  const int o_etas = o_srho + (M.full ? 1 : 0), o_etan = o_etas + M.Ns, o_gq = o_etan + M.Nn;
-  const double *q = src + POTUS_N_SAMPLER_COLS;
-  for (int i = tid; i < POTUS_N_SAMPLER_COLS + D; i += 256) row[i] = src[i];
-  __syncthreads();
-  double *Ct = row + o_gq; // suffix sums, staged where predicted_score will go
-  if (tid < S) {
-    double run = 0.0;
-    Ct[tid + S * (T - 1)] = 0.0;
-    for (int t = T - 2; t >= 0; t--) { run += q[M.o_Z + tid + S * t]; Ct[tid + S * t] = run; }
-    double bT = M.mat[M.m_prior + tid], pb = 0.0;
-    for (int k = 0; k <= tid; k++) { bT += M.mat[M.m_LT + tid * S + k] * q[M.o_zT + k]; pb += M.mat[M.m_LB + tid * S + k] * q[M.o_zb + k]; }
-    s_bT[tid] = bT; s_pb[tid] = pb; row[o_pb + tid] = pb;
-  }
-  if (tid == 64 && M.full) {
-    const double mue = 0.02 * q[M.o_mue], rho = d_inv_logit(q[M.o_rho]), srho = sqrt(1.0 - rho * rho) * M.sigma_e;
-    row[o_par + M.o_mue] = mue; row[o_par + M.o_rho] = rho; row[o_srho] = srho;
-    double e = q[M.o_ze] * M.sigma_e;
-    row[o_eb] = e;
-    for (int t = 1; t < T; t++) { e = mue + rho * (e - mue) + q[M.o_ze + t] * srho; row[o_eb + t] = e; }
-  }
-  for (int i = tid; i < M.P; i += 256) row[o_muc + i] = q[M.o_c + i] * M.sigma_c;
-  if (M.full) {
-    for (int i = tid; i < M.M; i += 256) row[o_mum + i] = q[M.o_m + i] * M.sigma_m;
-    for (int i = tid; i < M.Pop; i += 256) row[o_mupop + i] = q[M.o_pop + i] * M.sigma_pop;
-  }
-  __syncthreads();
-  for (int idx = tid; idx < S * T; idx += 256) {
-    const int s = idx % S, t = idx / S;
-    double a = s_bT[s];
-    const double *Lrow = M.mat + s * M.SP, *Cc = Ct + S * t;
-    for (int k = 0; k <= s; k++) a += Lrow[k] * Cc[k];
-    row[o_mub + idx] = a;
-  }
-  if (tid == 0) { double a = 0.0; for (int s = 0; s < S; s++) a += s_pb[s] * M.mat[M.m_w + s]; s_misc[0] = a; row[o_natpb] = a; }
-  __syncthreads();
-  for (int t = tid; t < T; t += 256) {
-    double a = 0.0;
-    for (int s = 0; s < S; s++) a += row[o_mub + s + S * t] * M.mat[M.m_w + s];
-    row[o_nat + t] = a;
-  }
-  __syncthreads();
-  for (int i = tid; i < M.Npoll; i += 256) {
-    const int s = M.pi[i], t = M.pi[M.Npad + i], qi = M.pi[5 * M.Npad + i];
-    const bool nat = s == S;
-    double eta = (nat ? row[o_nat + t] : row[o_mub + s + S * t]) + row[o_muc + M.pi[2 * M.Npad + i]];
-    if (M.full) eta += row[o_mum + M.pi[3 * M.Npad + i]] + row[o_mupop + M.pi[4 * M.Npad + i]] + M.pd[2 * M.Npad + i] * row[o_eb + t];
-    eta += q[qi] * M.pd[3 * M.Npad + i] + (nat ? s_misc[0] : s_pb[s]);
-    if (nat) row[o_etan + (qi - M.o_nn)] = eta; else row[o_etas + (qi - M.o_ns)] = eta;
-  }
-  __syncthreads();
-  for (int idx = tid; idx < S * T; idx += 256) { // predicted_score[t,s] = inv_logit(mu_b[s,t]) (stan:135-139)
-    const int t = idx % T, s = idx / T;
-    row[o_gq + idx] = d_inv_logit(row[o_mub + s + S * t]);
-  }
-  __syncthreads();
-}
-
-__global__ __launch_bounds__(256) void k_write_array(const DevModel *Mg, WAParams W) {
-  const DevModel M = *Mg;
-  __shared__ double s_bT[64], s_pb[64], s_misc[4];
-  const int tid = threadIdx.x;
-  double *row = W.scratch + (size_t)blockIdx.x * W.ncols;
-  for (int d = blockIdx.x; d < W.n_saved * W.chains; d += gridDim.x) {
-    const int iter = d / W.chains, chain = d % W.chains;
-    const double *src = W.draws + ((size_t)chain * W.n_save_max + iter) * W.row;
-    wa_build_row(M, src, row, s_bT, s_pb, s_misc);
-    const int nsel = W.col_end - W.col_begin;
-    double *dst = W.out + (size_t)d * W.out_stride;
-    for (int i = tid; i < nsel; i += 256) dst[i] = row[W.col_begin + i];
-    __syncthreads();
-  }
-}
-
-// ------------------------------------------------------------------------ prior predictive simulation and SBC ranks
-// Offsets of the two logit_pi blocks in an output row (wa_build_row's layout).
-__device__ __forceinline__ int wa_o_etas(const DevModel &M) {
-  return POTUS_N_SAMPLER_COLS + M.D + M.S * M.T + M.P + (M.full ? M.M + M.Pop + M.T : 0) + M.S + M.T + 1 + (M.full ? 1 : 0);
-}
-
-// y ~ binomial(n, p) with p = inv_logit(eta), exactly: inversion (sequential search from 0) when n min(p, 1 - p) < 10, else BTRS (Hoermann
-// 1993, "The generation of binomial random variates", with the exact log-ratio lgamma form of its acceptance bound).  Uniforms of attempt a
-// come from Philox counter (iter a, RNG_PRIOR, aux 2 / 3, index idx).
-__device__ int binomial_logit_draw(const RngKey &key, uint32_t idx, int n, double eta) {
-  if (n <= 0) return 0;
-  const double e = exp(-fabs(eta));
-  const double p = e / (1.0 + e), q = 1.0 / (1.0 + e);          // p = min(pi, 1 - pi), computed without cancellation
-  const bool flip = eta > 0;
-  int k = 0;
-  if ((double)n * p < 10.0) {
-    const double s = p / q, a = (n + 1) * s, r0 = pow(q, (double)n);
-    for (uint32_t att = 0; att < 64; att++) {
-      double u = rng_uniform(key, att, RNG_PRIOR, 2, idx), r = r0;
-      int x = 0;
-      while (u > r && x <= n) { u -= r; x++; r *= a / x - s; }
-      k = x;
-      if (x <= n) break;                                            // (x > n: the rounding of the cumulative sum ran out; draw again)
-    }
-    k = min(k, n);
-  } else {
-    const double spq = sqrt(n * p * q), b = 1.15 + 2.53 * spq, a = -0.0873 + 0.0248 * b + 0.01 * p, c = n * p + 0.5;
-    const double vr = 0.92 - 4.2 / b, alpha = (2.83 + 5.1 / b) * spq, lpq = log(p / q), m = floor((n + 1) * p);
-    const double h = lgamma(m + 1.0) + lgamma(n - m + 1.0);
-    for (uint32_t att = 0; att < 4096; att++) {
-      const double u = rng_uniform(key, att, RNG_PRIOR, 2, idx) - 0.5, v0 = rng_uniform(key, att, RNG_PRIOR, 3, idx);
-      const double us = 0.5 - fabs(u), kk = floor((2.0 * a / us + b) * u + c);
-      if (kk < 0.0 || kk > (double)n) continue;
-      k = (int)kk;
-      if (us >= 0.07 && v0 <= vr) break;
-      const double v = log(v0 * alpha / (a / (us * us) + b));
-      if (v <= h - lgamma(kk + 1.0) - lgamma(n - kk + 1.0) + (kk - m) * lpq) break;
-    }
-  }
-  return flip ? n - k : k;
-}
-
-struct SimParams {
-  double *qrow;        // [n][7 + D]: sampler columns zero, then the drawn unconstrained point
-  double *scratch;     // [gridDim.x][ncols]
-  int *y;              // [n][Ns + Nn]: state polls, then national polls, in the caller's order
-  int n, ncols, sim_offset;
-  unsigned seed_lo, seed_hi;
-};
-// One workgroup per simulation: theta ~ prior (stan:116-128 on the unconstrained scale), logit_pi by the row builder, y ~ binomial.
-// Counters (key chain field = sim_offset + sim + 1, so a simulation's bytes do not depend on the batching) are listed in potus_hmc.h.
-__global__ __launch_bounds__(256) void k_simulate_prior(const DevModel *Mg, SimParams P) {
-  const DevModel M = *Mg;
-  __shared__ double s_bT[64], s_pb[64], s_misc[4];
-  const int tid = threadIdx.x, D = M.D, Ns = M.Ns;
-  const int o_etas = wa_o_etas(M), o_etan = o_etas + Ns;
-  double *row = P.scratch + (size_t)blockIdx.x * P.ncols;
-  for (int sim = blockIdx.x; sim < P.n; sim += gridDim.x) {
-    const RngKey key{P.seed_lo, P.seed_hi, (uint32_t)(P.sim_offset + sim + 1)};
-    double *src = P.qrow + (size_t)sim * (POTUS_N_SAMPLER_COLS + D);
-    double *q = src + POTUS_N_SAMPLER_COLS;
-    if (tid < POTUS_N_SAMPLER_COLS) src[tid] = 0.0;
-    for (int j = tid; 2 * j < D; j += 256) {
-      double z0, z1;
-      rng_normal_pair(key, 0, RNG_PRIOR, 0, (uint32_t)j, z0, z1);
-      q[2 * j] = z0;
-      if (2 * j + 1 < D) q[2 * j + 1] = z1;
-    }
-    __syncthreads();
-    if (M.full && tid == 0) {   // rho_e_bias ~ normal(0.7, 0.1) restricted to (0, 1): rejection; P(reject) = 1.3e-3
-      double rho = 0.7;
-      for (uint32_t att = 0; att < 256; att++) {
-        double z0, z1;
-        rng_normal_pair(key, 0, RNG_PRIOR, 1, att, z0, z1);
-        const double r = 0.7 + 0.1 * z0;
-        if (r > 0.0 && r < 1.0) { rho = r; break; }
-      }
-      q[M.o_rho] = log(rho / (1.0 - rho));
-    }
-    __syncthreads();
-    wa_build_row(M, src, row, s_bT, s_pb, s_misc);
-    for (int i = tid; i < M.Npoll; i += 256) {
-      const int qi = M.pi[5 * M.Npad + i];
-      const bool nat = M.pi[i] == M.S;
-      const int j = nat ? qi - M.o_nn : qi - M.o_ns;
-      const uint32_t idx = (uint32_t)(nat ? Ns + j : j);
-      P.y[(size_t)sim * M.Npoll + idx] = binomial_logit_draw(key, idx, (int)M.pd[M.Npad + i], row[nat ? o_etan + j : o_etas + j]);
-    }
-    __syncthreads();
-  }
-}
-
-struct RankParams {
-  const double *draws; // [chains][n_save_max][row]
-  int chains, n_save_max, row, ncols, col_begin, col_end;
-  int first, thin, L, chains_per_ds;   // saved draws first, first + thin, ... (L of them) of every chain
-  const double *truth; // [n_datasets][col_end - col_begin]
-  const int *skip;     // [chains]: nonzero = the chain failed, its counts stay zero
-  double *scratch;     // [gridDim.x][ncols]
-  int *less, *equal;   // [chains][col_end - col_begin]
-};
-// One workgroup per chain: each compared draw's output row is rebuilt (wa_build_row) and compared with the truth of the chain's data
-// set; a thread owns the same columns for the whole launch, so its counts are plain loads and stores.
-__global__ __launch_bounds__(256) void k_sbc_ranks(const DevModel *Mg, RankParams P) {
-  const DevModel M = *Mg;
-  __shared__ double s_bT[64], s_pb[64], s_misc[4];
-  const int tid = threadIdx.x, nsel = P.col_end - P.col_begin;
-  double *row = P.scratch + (size_t)blockIdx.x * P.ncols;
-  for (int chain = blockIdx.x; chain < P.chains; chain += gridDim.x) {
-    const double *tr = P.truth + (size_t)(chain / P.chains_per_ds) * nsel;
-    int *ls = P.less + (size_t)chain * nsel, *eq = P.equal + (size_t)chain * nsel;
-    for (int i = tid; i < nsel; i += 256) { ls[i] = 0; eq[i] = 0; }
-    if (P.skip[chain]) continue;
-    for (int j = 0; j < P.L; j++) {
-      const double *src = P.draws + ((size_t)chain * P.n_save_max + P.first + (size_t)j * P.thin) * P.row;
-      wa_build_row(M, src, row, s_bT, s_pb, s_misc);
-      for (int i = tid; i < nsel; i += 256) {
-        const double v = row[P.col_begin + i], t = tr[i];
-        ls[i] += v < t ? 1 : 0;
-        eq[i] += v == t ? 1 : 0;
-      }
-      __syncthreads();
-    }
-  }
-}
-// Counts per data set: [n_datasets][nsel] = sum over the data set's chains.
-__global__ __launch_bounds__(256) void k_sbc_reduce(const int *less, const int *equal, int n_ds, int chains_per_ds, int nsel, int *less_out, int *equal_out) {
-  for (long long k = (long long)blockIdx.x * 256 + threadIdx.x; k < (long long)n_ds * nsel; k += (long long)gridDim.x * 256) {
-    const int ds = (int)(k / nsel), i = (int)(k % nsel);
-    int a = 0, b = 0;
-    for (int c = ds * chains_per_ds; c < (ds + 1) * chains_per_ds; c++) { a += less[(size_t)c * nsel + i]; b += equal[(size_t)c * nsel + i]; }
-    less_out[k] = a; equal_out[k] = b;
-  }
-}
+#include "potus_rows.hpp"   // the output row of a draw: its column blocks, its builder and the kernels around it
 
 // Many data sets in one handle (potus_set_datasets): Mg = [n_datasets] models that differ only in the poll outcomes (pd), chain c
 // uses data set c / chains_per_ds.  One workgroup per chain, diagonal metric.  The bodies are those of k_init / k_run line for line
@@ -1113,7 +887,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, c
   }
 }
 
-#include "potus_loo.hpp"   // per-poll log-likelihoods and PSIS-LOO (after wa_build_row, which it shares)
+#include "potus_loo.hpp"   // per-poll log-likelihoods and PSIS-LOO (after potus_rows.hpp, whose row builder it shares)
 #include "potus_outcomes.hpp"   // joint election outcomes: EV histogram, tipping point, joint win counts
 #include "potus_scenario.hpp"   // conditional forecasts and the covariance of the state scores
 #include "potus_timeline.hpp"   // run dates as the data sets of one handle: their rows, scores and summaries
@@ -1149,9 +923,7 @@ Layout make_layout(const potus_data *d) {
   L.o_ns = o; o += d->N_state_polls;
   L.o_zb = o; o += d->S;
   L.D = o;
-  const int tp = d->S * d->T + d->P + (full ? d->M + d->Pop + d->T : 0) + d->S + d->T + 1 + (full ? 1 : 0)
-                 + d->N_state_polls + d->N_national_polls;
-  L.ncols = POTUS_N_SAMPLER_COLS + L.D + tp + d->T * d->S;
+  L.ncols = row_cols(d, L.D).ncols;
   return L;
 }
 
@@ -1244,7 +1016,6 @@ struct Sampler {
   RunParams R{};
   potus_opts opts{};
   Layout L{};
-  double sigma_ns = 0, sigma_nn = 0;
   std::vector<void *> allocs;
   size_t lds_bytes = 0;
   std::string k1_unsupported;   // why the one-workgroup kernels cannot run this model (empty: they can); cluster mode may still
@@ -1448,7 +1219,6 @@ int build_model(Sampler *sp, const potus_data *d) {
   M.o_zT = L.o_zT; M.o_Z = L.o_Z; M.o_c = L.o_c; M.o_m = L.o_m; M.o_pop = L.o_pop; M.o_mue = L.o_mue; M.o_rho = L.o_rho;
   M.o_ze = L.o_ze; M.o_nn = L.o_nn; M.o_ns = L.o_ns; M.o_zb = L.o_zb; M.nmid = L.o_nn - L.o_c;
   M.sigma_c = d->sigma_c; M.sigma_m = d->sigma_m; M.sigma_pop = d->sigma_pop; M.sigma_e = d->sigma_e_bias;
-  sp->sigma_ns = d->sigma_measure_noise_state; sp->sigma_nn = d->sigma_measure_noise_national;
   M.sigma_ns = d->sigma_measure_noise_state; M.sigma_nn = d->sigma_measure_noise_national;
 
   // transformed data (stan:42-55)
@@ -2566,23 +2336,23 @@ int potus_column_name(const potus_data *d, int col, char *buf, int len) {
   if (col < 0) return fail(POTUS_ERR_ARG, "negative column");
   if (col < POTUS_N_SAMPLER_COLS) { std::snprintf(buf, (size_t)len, "%s", samp[col]); return 0; }
   const bool full = d->variant == POTUS_VARIANT_FULL;
-  struct Blk { const char *name; int r, c; }; // r x c column-major; c = 0: vector, r = 0: scalar
+  struct Blk { const char *name; int r, c; }; // r x c column-major; c = 0: vector of r (which may be empty), c < 0: scalar
   std::vector<Blk> b = {{"raw_mu_b_T", d->S, 0}, {"raw_mu_b", d->S, d->T}, {"raw_mu_c", d->P, 0}};
-  if (full) { b.push_back({"raw_mu_m", d->M, 0}); b.push_back({"raw_mu_pop", d->Pop, 0}); b.push_back({"mu_e_bias", 0, 0});
-              b.push_back({"rho_e_bias", 0, 0}); b.push_back({"raw_e_bias", d->T, 0}); }
+  if (full) { b.push_back({"raw_mu_m", d->M, 0}); b.push_back({"raw_mu_pop", d->Pop, 0}); b.push_back({"mu_e_bias", 1, -1});
+              b.push_back({"rho_e_bias", 1, -1}); b.push_back({"raw_e_bias", d->T, 0}); }
   b.push_back({"raw_measure_noise_national", d->N_national_polls, 0}); b.push_back({"raw_measure_noise_state", d->N_state_polls, 0});
   b.push_back({"raw_polling_bias", d->S, 0});
   b.push_back({"mu_b", d->S, d->T}); b.push_back({"mu_c", d->P, 0});
   if (full) { b.push_back({"mu_m", d->M, 0}); b.push_back({"mu_pop", d->Pop, 0}); b.push_back({"e_bias", d->T, 0}); }
-  b.push_back({"polling_bias", d->S, 0}); b.push_back({"national_mu_b_average", d->T, 0}); b.push_back({"national_polling_bias_average", 0, 0});
-  if (full) b.push_back({"sigma_rho", 0, 0});
+  b.push_back({"polling_bias", d->S, 0}); b.push_back({"national_mu_b_average", d->T, 0}); b.push_back({"national_polling_bias_average", 1, -1});
+  if (full) b.push_back({"sigma_rho", 1, -1});
   b.push_back({"logit_pi_democrat_state", d->N_state_polls, 0}); b.push_back({"logit_pi_democrat_national", d->N_national_polls, 0});
   b.push_back({"predicted_score", d->T, d->S});
   int c = col - POTUS_N_SAMPLER_COLS;
   for (const Blk &k : b) {
-    const int n = k.r == 0 ? 1 : (k.c == 0 ? k.r : k.r * k.c);
+    const int n = k.c <= 0 ? k.r : k.r * k.c;
     if (c < n) {
-      if (k.r == 0) std::snprintf(buf, (size_t)len, "%s", k.name);
+      if (k.c < 0) std::snprintf(buf, (size_t)len, "%s", k.name);
       else if (k.c == 0) std::snprintf(buf, (size_t)len, "%s.%d", k.name, c + 1);
       else std::snprintf(buf, (size_t)len, "%s.%d.%d", k.name, c % k.r + 1, c / k.r + 1);
       return 0;
@@ -3281,11 +3051,12 @@ int potus_draws_device_ptr(int handle, void **dptr, long long *n_doubles) {
   return 0;
 }
 
-// One row-builder launch on the sampler's stream: the W.n_saved x W.chains rows of W.draws.  The CALLER chooses the kernel: per_ds = 0 builds every row
+static RowSrc row_src(const Sampler *sp, int first) { return RowSrc{sp->R.draws, sp->R.chains, sp->R.n_save_max, sp->R.row, first}; }   // a handle's saved draws
+// One row-builder launch on the sampler's stream: the W.n_saved x W.src.chains rows of W.src.  The CALLER chooses the kernel: per_ds = 0 builds every row
 // with the one model M (k_write_array), per_ds > 0 builds chain c's rows with M[c / per_ds] (k_write_array_ds).  The grid and W.scratch are owned here;
 // W.out is the caller's or, when null, comes from tmp too.  Allocations fail by the name `what` (DevBufs::get), or with what = null as HIP calls fail.
 static int launch_rows(Sampler *sp, DevBufs &tmp, const char *what, const DevModel *M, int per_ds, WAParams &W) {
-  const int n = W.n_saved * W.chains, nsel = W.col_end - W.col_begin, grid = std::min(n, 512);
+  const int n = W.n_saved * W.src.chains, nsel = W.col_end - W.col_begin, grid = std::min(n, 512);
   double *scratch = nullptr, *dout = W.out;
   if (what) {
     if (const int rc_ = tmp.get(&scratch, (size_t)grid * sp->L.ncols * 8, what)) return rc_;
@@ -3308,9 +3079,8 @@ static int write_array_range(Sampler *sp, int n_saved, int col_begin, int col_en
   const int ndraw = n_saved * sp->R.chains;
   if (ndraw == 0) return 0;
   DevBufs tmp;
-  WAParams W{sp->R.draws, sp->R.chains, sp->R.n_save_max, n_saved, sp->R.row, sp->L.ncols, col_begin, col_end, nullptr, device_out ? out : nullptr, sp->sigma_ns, sp->sigma_nn, out_stride};
-  if (const int rc_ = sp->ds_ex ? launch_rows(sp, tmp, "potus_write_array", sp->dMs, sp->chains_per_ds(), W)   // the chain's own model
-                                : launch_rows(sp, tmp, "potus_write_array", sp->dM, 0, W)) return rc_;
+  WAParams W{row_src(sp, 0), n_saved, sp->L.ncols, col_begin, col_end, nullptr, device_out ? out : nullptr, out_stride};
+  if (const int rc_ = launch_rows(sp, tmp, "potus_write_array", sp->ds_ex ? sp->dMs : sp->dM, sp->ds_ex ? sp->chains_per_ds() : 0, W)) return rc_;   // ds_ex: the chain's own model
   if (!device_out) HIP_TRY(hipMemcpyAsync(out, W.out, (size_t)ndraw * nsel * 8, hipMemcpyDeviceToHost, sp->stream));
   HIP_TRY(hipStreamSynchronize(sp->stream));
   return 0;
@@ -3418,7 +3188,7 @@ int potus_posterior_summary_many(const int *handles, int n_handles, const double
   const long long nd = P.draws;
   const int S = s0->M.S, T = s0->M.T, TS = S * T, NC = TS + 2 * T;
   if (nd < 2) return fail(POTUS_ERR_STATE, "posterior summaries need at least two saved draws");
-  const int col_end = s0->L.ncols, col_begin = col_end - TS;   // predicted_score = the generated-quantities block
+  const int col_end = s0->L.ncols, col_begin = row_cols(s0->M).predicted_score;   // the generated-quantities block
   HIP_TRY(hipSetDevice(s0->device));
   DevBufs tmp;
   double *full = nullptr, *cols = nullptr, *dw = nullptr, *dev_ = nullptr, *dout = nullptr, *scr = nullptr;
@@ -3549,7 +3319,7 @@ static int gather_days(Pool &P, int day_begin, int day_end, bool by_chain, int e
     g.nd += (long long)(P.saved[i] - first[i]) * P.sps[i]->R.chains;
   }
   if (g.nd < 1) return fail(POTUS_ERR_STATE, "%s needs at least one saved post-warm-up draw (%lld rows saved, all of them warm-up)", P.what, P.draws);
-  const int col_end = s0->L.ncols, col_begin = col_end - TS;   // predicted_score = the generated-quantities block
+  const int col_end = s0->L.ncols, col_begin = row_cols(s0->M).predicted_score;   // the generated-quantities block
   HIP_TRY(hipSetDevice(s0->device));
   if ((rc = g.bufs.get(&g.items, (size_t)g.nd * n_days * S * 8, P.what))) return rc;
   if (extra_day >= 0 && (rc = g.bufs.get(&g.extra, (size_t)g.nd * S * 8, P.what))) return rc;
@@ -3636,7 +3406,7 @@ int loo_rows_setup(Sampler *sp, long long ndraw, DevBufs &keep, LooRows &r, cons
 
 // log-likelihoods of polls [b0, b1) of the handle's post-warm-up draws -> out [n_post][chains][b1 - b0], on the handle's device and stream
 int loo_loglik(Sampler *sp, const LooRows &r, int first, int n_post, int b0, int b1, int integrate, double *out) {
-  LlParams P{sp->R.draws, sp->R.chains, sp->R.n_save_max, sp->R.row, sp->L.ncols, first, n_post, b0, b1, integrate, r.lc, r.scratch, out};
+  LlParams P{row_src(sp, first), sp->L.ncols, n_post, b0, b1, integrate, r.lc, r.scratch, out};
   hipLaunchKernelGGL(k_loo_loglik, dim3(r.grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, P);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -4437,7 +4207,7 @@ int tl_check_args(const char *what, Sampler *sp, int day_begin, int day_end, TlP
 }
 int tl_scores(Sampler *sp, const TlPlan &pl, int day_begin, int day_end, const int *dskip, double *out) {
   const long long items = (long long)sp->R.chains * pl.n_post;
-  TlScoreParams P{sp->R.draws, sp->R.chains, sp->R.n_save_max, sp->R.row, pl.first, pl.n_post, pl.cpd, day_begin, day_end, dskip, out};
+  TlScoreParams P{row_src(sp, pl.first), pl.n_post, pl.cpd, day_begin, day_end, dskip, out};
   hipLaunchKernelGGL(k_tl_scores, dim3((unsigned)std::min<long long>((items + 3) / 4, 65535)), dim3(256), 0, sp->stream, pl.Mg, P);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -4560,7 +4330,7 @@ int cv_upload(const char *what, Sampler *sp, const CvPlan &pl, DevBufs &keep, Cv
 }
 // ll of pairs [p0, p1) -> out [p1 - p0][draws per data set], on the handle's stream
 int cv_loglik(Sampler *sp, const CvPlan &pl, const CvDev &d, int p0, int p1, int integrate, double *out) {
-  CvParams P{sp->R.draws, sp->R.chains, sp->R.n_save_max, sp->R.row, sp->L.ncols, pl.first, pl.n_post, pl.cpd, integrate,
+  CvParams P{row_src(sp, pl.first), sp->L.ncols, pl.n_post, pl.cpd, integrate,
              sp->M.pd, d.rows.lc, d.off, d.held, d.skip, p0, p1, d.rows.scratch, out};
   hipLaunchKernelGGL(k_cv_loglik, dim3(d.rows.grid), dim3(256), 0, sp->stream, pl.Mg, P);
   HIP_TRY(hipGetLastError());
@@ -4725,7 +4495,7 @@ int potus_optimize(int handle, const potus_optimize_opts *opts, const double *q0
   HIP_TRY(hipMemcpyAsync(info_out, dinfo, (size_t)n_paths * 3 * 4, hipMemcpyDeviceToHost, sp->stream));
   if (row_out) {   // the CmdStan row of every path's point, built with the path's own model
     const int nsel = col_end - col_begin;
-    WAParams W{rows, n_paths, 1, 1, row, sp->L.ncols, col_begin, col_end, nullptr, nullptr, sp->sigma_ns, sp->sigma_nn, nsel};   // one saved draw of n_paths chains
+    WAParams W{RowSrc{rows, n_paths, 1, row, 0}, 1, sp->L.ncols, col_begin, col_end, nullptr, nullptr, nsel};   // one saved draw of n_paths chains
     if ((rc = launch_rows(sp, tmp, what, Mg, sp->n_ds ? per_ds : 0, W))) return rc;
     HIP_TRY(hipMemcpyAsync(row_out, W.out, (size_t)n_paths * nsel * 8, hipMemcpyDeviceToHost, sp->stream));
   }
@@ -4786,7 +4556,7 @@ int potus_constrain(int handle, const double *q, int n, int col_begin, int col_e
   double *dblk = nullptr;
   HIP_TRY(tmp.alloc(&dblk, blk.size() * 8));
   HIP_TRY(hipMemcpyAsync(dblk, blk.data(), blk.size() * 8, hipMemcpyHostToDevice, sp->stream));
-  WAParams W{dblk, 1, n, n, row, sp->L.ncols, col_begin, col_end, nullptr, nullptr, sp->sigma_ns, sp->sigma_nn, nsel};   // n draws of one chain
+  WAParams W{RowSrc{dblk, 1, n, row, 0}, n, sp->L.ncols, col_begin, col_end, nullptr, nullptr, nsel};   // n draws of one chain
   if (const int rc_ = launch_rows(sp, tmp, nullptr, sp->dM, 0, W)) return rc_;
   HIP_TRY(hipMemcpyAsync(out, W.out, (size_t)n * nsel * 8, hipMemcpyDeviceToHost, sp->stream));
   HIP_TRY(hipStreamSynchronize(sp->stream));
@@ -4815,7 +4585,7 @@ int potus_sbc_ranks(int handle, const double *truth, int col_begin, int col_end,
   HIP_TRY(tmp.alloc(&dl, (size_t)n_ds * nsel * 4)); HIP_TRY(tmp.alloc(&de, (size_t)n_ds * nsel * 4));
   HIP_TRY(hipMemcpyAsync(dtruth, truth, (size_t)n_ds * nsel * 8, hipMemcpyHostToDevice, sp->stream));
   HIP_TRY(hipMemcpyAsync(dskip, pl.failed.data(), (size_t)chains * 4, hipMemcpyHostToDevice, sp->stream));   // per chain: what k_sbc_ranks takes
-  RankParams P{sp->R.draws, chains, sp->R.n_save_max, sp->R.row, sp->L.ncols, col_begin, col_end, pl.first, thin, nL, cpd, dtruth, dskip, scratch, cl, ce};
+  RankParams P{row_src(sp, pl.first), sp->L.ncols, col_begin, col_end, thin, nL, cpd, dtruth, dskip, scratch, cl, ce};
   hipLaunchKernelGGL(k_sbc_ranks, dim3(grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, P);
   HIP_TRY(hipGetLastError());
   const int rgrid = (int)std::min<long long>(((long long)n_ds * nsel + 255) / 256, 1024);

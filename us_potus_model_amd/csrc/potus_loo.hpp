@@ -65,9 +65,8 @@ __device__ double loo_poll_ll(double y, double n, double eta, double sig, double
 }
 
 struct LlParams {
-  const double *draws;  // [chains][n_save_max][row]
-  int chains, n_save_max, row, ncols;
-  int first, n_post;    // saved draws first .. first + n_post - 1 of every chain (the post-warm-up ones)
+  RowSrc src;
+  int ncols, n_post;    // saved draws src.first .. src.first + n_post - 1 of every chain (the post-warm-up ones)
   int p0, p1, integrate;
   const double *lc;     // [Npoll] log C(n, y) in the model's (day-sorted) poll order
   double *scratch;      // [gridDim.x][ncols]
@@ -75,26 +74,22 @@ struct LlParams {
 };
 __global__ __launch_bounds__(256) void k_loo_loglik(const DevModel *Mg, LlParams P) {
   const DevModel M = *Mg;
-  __shared__ double s_bT[64], s_pb[64], s_misc[4];
-  const int tid = threadIdx.x, S = M.S, T = M.T, nb = P.p1 - P.p0, Np = M.Npad;
-  // wa_build_row's column blocks
-  const int o_mub = POTUS_N_SAMPLER_COLS + M.D, o_muc = o_mub + S * T, o_mum = o_muc + M.P, o_mupop = o_mum + (M.full ? M.M : 0);
-  const int o_eb = o_mupop + (M.full ? M.Pop : 0), o_pb = o_eb + (M.full ? T : 0), o_nat = o_pb + S, o_natpb = o_nat + T;
+  __shared__ RowLds lds;
+  const int tid = threadIdx.x, nb = P.p1 - P.p0, Np = M.Npad;
+  const RowCols c = row_cols(M);
   double *row = P.scratch + (size_t)blockIdx.x * P.ncols;
-  for (long long d = blockIdx.x; d < (long long)P.n_post * P.chains; d += gridDim.x) {
-    const int iter = (int)(d / P.chains), chain = (int)(d % P.chains);
-    const double *src = P.draws + ((size_t)chain * P.n_save_max + P.first + iter) * P.row;
-    wa_build_row(M, src, row, s_bT, s_pb, s_misc);
-    const double *q = src + POTUS_N_SAMPLER_COLS;
+  for (long long d = blockIdx.x; d < (long long)P.n_post * P.src.chains; d += gridDim.x) {
+    const int iter = (int)(d / P.src.chains), chain = (int)(d % P.src.chains);
+    const double *src = P.src.at(chain, iter), *q = src + POTUS_N_SAMPLER_COLS;
+    wa_build_row(M, src, row, lds);
     double *dst = P.out + (size_t)d * nb;
     for (int i = tid; i < M.Npoll; i += 256) {
-      const int s = M.pi[i], t = M.pi[Np + i], qi = M.pi[5 * Np + i];
-      const bool nat = s == S;
+      const int s = M.pi[i], qi = M.pi[5 * Np + i];
+      const bool nat = s == M.S;
       const int k = nat ? M.Ns + (qi - M.o_nn) : qi - M.o_ns;
       if (k < P.p0 || k >= P.p1) continue;
-      double eta = (nat ? row[o_nat + t] : row[o_mub + s + S * t]) + row[o_muc + M.pi[2 * Np + i]];
-      if (M.full) eta += row[o_mum + M.pi[3 * Np + i]] + row[o_mupop + M.pi[4 * Np + i]] + M.pd[2 * Np + i] * row[o_eb + t];
-      eta += nat ? row[o_natpb] : row[o_pb + s];
+      double eta = row_poll_eta(M, c, row, M.pd + 2 * Np, i);
+      eta += nat ? row[c.nat_polling_bias] : row[c.polling_bias + s];
       dst[k - P.p0] = P.lc[i] + loo_poll_ll(M.pd[i], M.pd[Np + i], eta, M.pd[3 * Np + i], q[qi], P.integrate);
     }
     __syncthreads();

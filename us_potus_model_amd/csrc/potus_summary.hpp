@@ -5,7 +5,7 @@
 // Any number of pooled draws (BASELINE configs[2]: 64 chains x 1000 = 64 000) and any number of samplers
 // (the chains of one posterior spread over several handles / GPUs):
 //
-//   1. k_write_array (potus_hmc.hip) produces predicted_score of every saved draw, [draw][T*S], cell = t + T*s;
+//   1. k_write_array (potus_rows.hpp) produces predicted_score of every saved draw, [draw][T*S], cell = t + T*s;
 //   2. k_ps_derived adds the two per-draw series the scripts build -- the state_weights-weighted national vote and the
 //      Democratic electoral votes -- and k_ps_transpose turns everything into COLUMNS, [column][draw], so that
 //      the draws of a cell are contiguous;

@@ -3,10 +3,9 @@
 //
 // What a forecaster shows from the refits of a campaign is how predicted_score of a few days -- election day above all -- moved
 // from one run date to the next (final_2016.R:66-67 RUN_DATE, :708-762 intervals, :799-823 electoral votes).  Neither kernel
-// builds the output row of a draw (43 360 columns for the 2016 design):
+// builds the output row of a draw (43 360 columns for the 2016 design); potus_write_array[_device] of such a handle does, with the
+// CHAIN'S model (k_write_array_ds, potus_rows.hpp):
 //
-//   k_write_array_ds  potus_write_array[_device] of a handle made by potus_set_datasets_ex: k_write_array with the CHAIN'S model
-//                     (mu_b, predicted_score and logit_pi depend on the data set's prior).  wa_build_row is shared.
 //   k_tl_scores       predicted_score of the days [t0, t1) of every post-warm-up draw, straight from the saved unconstrained draw
 //                     and the chain's model:  mu_b[:, t] = prior + L_T z_T + L_W (sum of the walk innovations after t).
 //                     One WAVE per draw, lane = state.  Election day needs no suffix sum and no L_W product.
@@ -33,33 +32,16 @@
 #define TL_MAX_DRAWS PS_RUN
 #define TL_THREADS PS_THREADS
 
-// potus_set_datasets_ex handles: Mg = [n_datasets] models, chain c uses Mg[c / chains_per_ds].  The body is k_write_array's.
-__global__ __launch_bounds__(256) void k_write_array_ds(const DevModel *Mg, WAParams W, int chains_per_ds) {
-  __shared__ double s_bT[64], s_pb[64], s_misc[4];
-  const int tid = threadIdx.x;
-  double *row = W.scratch + (size_t)blockIdx.x * W.ncols;
-  for (int d = blockIdx.x; d < W.n_saved * W.chains; d += gridDim.x) {
-    const int iter = d / W.chains, chain = d % W.chains;
-    const DevModel M = Mg[chain / chains_per_ds];
-    const double *src = W.draws + ((size_t)chain * W.n_save_max + iter) * W.row;
-    wa_build_row(M, src, row, s_bT, s_pb, s_misc);
-    const int nsel = W.col_end - W.col_begin;
-    double *dst = W.out + (size_t)d * W.out_stride;
-    for (int i = tid; i < nsel; i += 256) dst[i] = row[W.col_begin + i];
-    __syncthreads();
-  }
-}
-
 struct TlScoreParams {
-  const double *draws;   // [chains][n_save_max][row]
-  int chains, n_save_max, row, first, n_post, chains_per_ds;   // post-warm-up rows first .. first + n_post - 1 of every chain
+  RowSrc src;
+  int n_post, chains_per_ds;   // post-warm-up rows src.first .. src.first + n_post - 1 of every chain
   int t0, t1;            // days [t0, t1), 0-based
   const int *skip;       // [n_datasets]: nonzero = a chain of the data set failed, its scores are NaN
   double *out;           // [chains * n_post][t1 - t0][S]  (= [n_datasets][chains_per_ds * n_post][t1 - t0][S])
 };
 __global__ __launch_bounds__(256) void k_tl_scores(const DevModel *Mg, TlScoreParams P) {
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6, nd = P.t1 - P.t0;
-  const long long n_items = (long long)P.chains * P.n_post;
+  const long long n_items = (long long)P.src.chains * P.n_post;
   for (long long item = (long long)blockIdx.x * 4 + wave; item < n_items; item += (long long)gridDim.x * 4) {   // wave-uniform
     const int chain = (int)(item / P.n_post), it = (int)(item % P.n_post), ds = chain / P.chains_per_ds;
     const DevModel &M = Mg[ds];
@@ -70,7 +52,7 @@ __global__ __launch_bounds__(256) void k_tl_scores(const DevModel *Mg, TlScorePa
       for (int i = lane; i < nd * S; i += 64) dst[i] = NAN;
       continue;
     }
-    const double *q = P.draws + ((size_t)chain * P.n_save_max + P.first + it) * P.row + POTUS_N_SAMPLER_COLS;
+    const double *q = P.src.at(chain, it) + POTUS_N_SAMPLER_COLS;
     double bT = 0.0;
     if (act) {
       bT = M.mat[M.m_prior + s];
