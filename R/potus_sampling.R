@@ -451,6 +451,32 @@ potus_optimize <- function(data, variant = c("full", "no_mode_adjustment"), jaco
        rows = if (is.null(pars)) NULL else matrix(r$rows[seq_len(paths * nsel)], paths, nsel, byrow = TRUE))
 }
 
+# ---- the Laplace approximation (Handle.laplace is the same in Python; DESIGN.md section 4n) ----
+# cmdstanr's model$laplace(data, mode =, draws =, jacobian = TRUE): minus the Hessian of log_prob<jacobian> at `mode` (a vector of D unconstrained
+# coordinates, or a matrix [modes, D]; e.g. potus_optimize(..., jacobian = TRUE)$q) by central differences on the device, its Cholesky factor, and
+# `draws` draws mode + L^-T u.  u: NULL for the library's normals (Philox, purpose 8) or an array [D, draws, modes] (column-major: u[, n, m] is draw n).
+# Returns list(q [modes * draws, D], lp, lp_approx, log_ratio = lp - lp_approx up to lp(mode), return_code (0 ok, 1 NOT_PD, 2 mode not finite),
+# log_det, grad_norm, min_pivot [modes], precision [D, D, modes] or NULL).
+potus_laplace <- function(data, mode, variant = c("full", "no_mode_adjustment"), draws = 1000, jacobian = TRUE, seed = 1843, h = 1e-4, u = NULL,
+                          draw_offset = 0, precision = FALSE, device = 0) {
+  variant <- match.arg(variant)
+  if (!is.matrix(mode)) mode <- matrix(mode, 1)
+  modes <- nrow(mode)
+  res <- .potus_create(data, variant, c(1L, 0L, 0L, 0L, 10L, as.integer(device), 0L, 1L, 0L, 0L, 0L, 0L), c(0.8, 0.05, 0.75, 10, 1, 2, seed))
+  .potus_check(res$status)
+  on.exit(.C("potus_R_destroy", res$handle, status = integer(1)))
+  D <- ncol(mode)
+  n <- modes * draws
+  r <- .C("potus_R_laplace", res$handle, as.integer(c(isTRUE(jacobian), draw_offset, modes, draws, !is.null(u), isTRUE(precision))), as.double(h),
+          as.double(t(mode)), if (is.null(u)) double(1) else as.double(u), q = double(max(n * D, 1)), lp = double(max(n, 1)), lp_approx = double(max(n, 1)),
+          info = double(4 * modes), precision = double(if (isTRUE(precision)) modes * D * D else 1), status = integer(1))
+  .potus_check(r$status)
+  info4 <- matrix(r$info, modes, 4, byrow = TRUE)
+  list(q = matrix(r$q[seq_len(n * D)], n, D, byrow = TRUE), lp = r$lp[seq_len(n)], lp_approx = r$lp_approx[seq_len(n)],
+       log_ratio = r$lp[seq_len(n)] - r$lp_approx[seq_len(n)], return_code = info4[, 1], log_det = info4[, 2], grad_norm = info4[, 3],
+       min_pivot = info4[, 4], precision = if (isTRUE(precision)) array(r$precision, c(D, D, modes)) else NULL)
+}
+
 # ---- joint election outcomes (us_potus_model_amd/outcomes.py is the same in Python; DESIGN.md section 4f) ----
 # What the run scripts compute from the JOINT outcome of a draw, counted on the device over the post-warm-up draws of every chain of the fit:
 # the distribution of Democratic electoral votes (final_2016.R:904-920), the tipping-point state (final_2012.R:809-843), how often states i and j

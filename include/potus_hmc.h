@@ -444,6 +444,35 @@ int potus_optimize(int handle, const potus_optimize_opts *o, const double *q0 /*
                    double *lp_out /*[n_paths]*/, double *gnorm_out /*[n_paths]*/, int32_t *info_out /*[n_paths][3]: code, iterations, gradient evaluations*/,
                    int col_begin, int col_end, double *row_out /*[n_paths][col_end - col_begin] or NULL*/);
 int potus_optimize_timing(double *ms /*[1]: k_opt_lbfgs, HIP events, calling thread's last potus_optimize*/);
+/* ---- the Laplace approximation: cmdstanr's $laplace(mode =, draws =, jacobian =) ----
+ * For each of n_modes points: P = minus the Hessian of log_prob<jacobian> by central differences of the device gradient (step
+ * h_j = h max(1, |mode_j|)), symmetrised; its Cholesky factor P = L L' on the matrix cores; n_draws draws x = mode + L^-T u with u standard
+ * normal -- the caller's u, or Philox4x32-10 with purpose 8: coordinates 2 i and 2 i + 1 of draw n are the Box-Muller pair of counter
+ * {i, 8, 0, draw_offset + n + 1}, key = the handle's seed.  A draw's bytes depend on (matrix, u of that draw) alone: not on n_draws, not on
+ * draw_offset, not on the other modes of the call, not on the memory budget (POTUS_LAPLACE_MATRIX_BUDGET, bytes; default 16 GiB of D x D
+ * matrices in flight).  lp_out is log_prob<jacobian = true> of the draw with the bytes of potus_log_prob_grad; lp_approx_out = -1/2 |u|^2, so
+ * lp - lp(mode) - lp_approx is the draw's log importance ratio up to a constant.
+ * Modes per handle as paths in potus_optimize: on a handle with data sets n_modes is a multiple of their number and mode m uses data set
+ * m / (n_modes / n_datasets).  info_out [n_modes][4]: code (0 ok; 1 NOT_PD: a non-positive pivot, the mode's draws, log det and pivot are NaN;
+ * 2: the mode is not finite, everything of it is NaN), log det P, |g|_2 at the mode (of log_prob<jacobian>), the smallest pivot min L_ii^2.
+ * A mode that fails does not fail the call.  n_draws = 0 with precision_out is the Hessian alone.  The call needs cus_per_chain = 1 and the
+ * diagonal metric, is possible any time after potus_create and touches no chain state.  The rows [lp__, six NaN, x] of the last call stay
+ * on the handle for the three accessors below (replaced by the next call, freed by potus_destroy):
+ *   potus_laplace_write_array_device  [n_modes * n_draws][col_end - col_begin] CmdStan columns of every draw, built with the mode's model
+ *   potus_laplace_scores_device       [n_modes][n_draws][days][S] predicted_score: a mode's block is what potus_outcomes_device takes
+ *   potus_laplace_summary             potus_timeline's outputs with a mode in the place of a data set (at most 16 384 draws per mode);
+ *                                     a mode whose code is not 0 gives NaN and n_draws_out = 0 */
+typedef struct potus_laplace_opts { int32_t jacobian, draw_offset, pad0, pad1; double h; } potus_laplace_opts;   /* 24 bytes */
+void potus_default_laplace_opts(potus_laplace_opts *o);   /* 1, 0, 0, 0, 1e-4 (h: the best step on the 2016 design, profiles/laplace_2016.txt) */
+int potus_laplace(int handle, const potus_laplace_opts *o, const double *mode /*[n_modes][D]*/, int n_modes,
+                  const double *u /*[n_modes][n_draws][D] or NULL*/, int n_draws,
+                  double *q_out /*[n_modes][n_draws][D] or NULL*/, double *lp_out, double *lp_approx_out /*[n_modes][n_draws] or NULL*/,
+                  double *info_out /*[n_modes][4]*/, double *precision_out /*[n_modes][D][D] or NULL*/);
+int potus_laplace_write_array_device(int handle, int col_begin, int col_end, void *out_device);
+int potus_laplace_scores_device(int handle, int day_begin, int day_end, void *out_device);
+int potus_laplace_summary(int handle, int day_begin, int day_end, const double *ev, int ev_to_win,
+                          double *state_out, double *natl_out, double *ev_out, int32_t *n_draws_out);
+int potus_laplace_timing(double *ms /*[4]: Hessian, factor, solve, lp__; HIP events, calling thread's last potus_laplace*/);
 /* Prior predictive simulation: n_sims draws theta ~ prior (poll_model_2020.stan:116-128) on the unconstrained scale (q_out [n_sims][D];
  * rho_e_bias ~ normal(0.7, 0.1) restricted to (0, 1), stored as logit(rho)) and y ~ binomial(n_two_share, inv_logit(logit_pi(theta)))
  * (stan:85-113; exact sampler: inversion when n min(p, 1 - p) < 10, BTRS above) in the caller's poll order.  Any output may be null.
@@ -590,6 +619,8 @@ void potus_R_cv_lpd(int *handle, int *held_state, int *held_national, int *integ
 void potus_R_optimize(int *handle, int *iopts /*[7]: jacobian, history_size, iter, path_offset, n_paths, q0 given, rows wanted*/,
                       double *dopts /*[6]: init_alpha, tol_obj, tol_rel_obj, tol_grad, tol_rel_grad, tol_param*/, double *q0, double *q_out, double *lp_out,
                       double *gnorm_out, int *info_out, int *cols /*[2]: col_begin, col_end*/, double *row_out, int *status);
+void potus_R_laplace(int *handle, int *iopts /*[6]: jacobian, draw_offset, n_modes, n_draws, u given, precision wanted*/, double *h, double *mode, double *u,
+                     double *q_out, double *lp_out, double *lp_approx_out, double *info_out, double *precision_out, int *status);
 void potus_R_simulate_prior(int *handle, double *seed, int *dims /*[2]: n_sims, sim_offset*/, double *q_out, int *n_democrat_state_out,
                             int *n_democrat_national_out, int *status);
 void potus_R_sbc_ranks(int *handle, double *truth, int *cols /*[3]: col_begin, col_end, thin*/, int *less, int *equal, int *L, int *status);

@@ -65,6 +65,14 @@ class PotusOptimizeOpts(C.Structure):
     ]
 
 
+class PotusLaplaceOpts(C.Structure):
+    """potus_laplace_opts (24 bytes); start from potus_default_laplace_opts()."""
+    _fields_ = [
+        ("jacobian", C.c_int32), ("draw_offset", C.c_int32), ("pad0", C.c_int32), ("pad1", C.c_int32), ("h", C.c_double),
+    ]
+
+
+LAPLACE_CODES = {0: "OK", 1: "NOT_PD", 2: "NOT_FINITE"}
 OPTIMIZE_CODES = {1: "ABSF", 2: "RELF", 3: "ABSGRAD", 4: "RELGRAD", 5: "ABSX", 6: "MAXIT", 7: "LSFAIL", 8: "INIT"}
 
 

@@ -19,6 +19,7 @@
 #include <cstdlib>
 #include <cstring>
 #include <limits>
+#include <memory>
 #include <charconv>
 #include <chrono>
 #include <thread>
@@ -893,6 +894,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, c
 #include "potus_timeline.hpp"   // run dates as the data sets of one handle: their rows, scores and summaries
 #include "potus_crossval.hpp"   // exact cross-validation: held-out polls under the draws of the data set that did not see them
 #include "potus_optimize.hpp"   // the posterior mode: batched L-BFGS, one workgroup per path
+#include "potus_laplace.hpp"    // the Laplace approximation at a mode: Hessian, factor, draws
 
 // ======================================================================== host
 namespace {
@@ -1061,6 +1063,10 @@ struct Sampler {
   std::vector<double> h_mat, h_cov, h_w_raw;   // host copies for the per-data-set models: the packed mat, state_covariance_0, state_weights as given
   double h_nsd = 0, h_rw_scale = 0, h_T_scale = 0;   // sqrt(w' cov w), random_walk_scale, mu_b_T_scale
   int chains_per_ds() const { return n_ds ? R.chains / n_ds : R.chains; }
+  // potus_laplace: the rows [lp__, six NaN, x] of the last call's draws, [lap_modes][lap_draws][7 + D]; apart from chain state
+  double *lap_rows = nullptr;
+  int lap_modes = 0, lap_draws = 0;
+  std::vector<int> lap_code;   // per mode: 0 = its rows are draws
 };
 
 std::mutex g_mu;
@@ -2587,6 +2593,7 @@ int potus_destroy(int handle) {
   (void)hipSetDevice(sp->device);
   (void)hipStreamSynchronize(sp->stream);
   for (void *p : sp->allocs) (void)hipFree(p);
+  if (sp->lap_rows) (void)hipFree(sp->lap_rows);
   (void)hipEventDestroy(sp->ev0); (void)hipEventDestroy(sp->ev1); (void)hipStreamDestroy(sp->stream);
   if (sp->mv0) (void)hipEventDestroy(sp->mv0);
   if (sp->mv1) (void)hipEventDestroy(sp->mv1);
@@ -4509,6 +4516,310 @@ int potus_optimize_timing(double *ms) {
   return timing_out("potus_optimize_timing", &g_opt_ms, 1, ms);
 }
 
+// ---------------------------------------------------------------------------------------------- the Laplace approximation (potus_laplace.hpp)
+namespace {
+constexpr size_t LAP_MATRIX_BUDGET = 16ull << 30;   // D x LD matrices in flight (POTUS_LAPLACE_MATRIX_BUDGET, bytes: tests)
+thread_local double g_lap_ms[4] = {0.0, 0.0, 0.0, 0.0};   // the calling thread's last potus_laplace: Hessian, factor, solve, lp__ (HIP events, summed)
+
+// the timed spans of one stage of a call: as many event pairs as the stage has spans, summed once the stream is synchronised
+struct LapSpans {
+  std::vector<std::unique_ptr<EventTimer>> v;
+  int begin(hipStream_t st) {
+    v.emplace_back(new EventTimer());
+    HIP_TRY(v.back()->made);
+    HIP_TRY(v.back()->start(st));
+    return 0;
+  }
+  int end(hipStream_t st) { HIP_TRY(v.back()->stop(st)); return 0; }
+  int sum(double *ms) {
+    *ms = 0.0;
+    for (auto &e : v) { double x = 0; if (const int rc = e->elapsed_or_fail(&x)) return rc; *ms += x; }
+    return 0;
+  }
+};
+
+// what the three accessors check first: a successful potus_laplace with draws on this handle
+int lap_have_rows(const char *what, const Sampler *sp) {
+  if (!sp->lap_rows || sp->lap_draws < 1) return fail(POTUS_ERR_STATE, "%s: no Laplace draws on this handle (potus_laplace with n_draws >= 1 first)", what);
+  return 0;
+}
+int lap_per_ds(const Sampler *sp) { return sp->lap_modes / std::max(sp->n_ds, 1) * sp->lap_draws; }   // rows per data set, mode-major
+} // namespace
+
+void potus_default_laplace_opts(potus_laplace_opts *o) {
+  if (!o) return;
+  o->jacobian = 1; o->draw_offset = 0; o->pad0 = 0; o->pad1 = 0; o->h = 1e-4;
+}
+
+int potus_laplace(int handle, const potus_laplace_opts *opts, const double *mode, int n_modes, const double *u, int n_draws,
+                  double *q_out, double *lp_out, double *lp_approx_out, double *info_out, double *precision_out) {
+  const char *what = "potus_laplace";
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  potus_laplace_opts o;
+  potus_default_laplace_opts(&o);
+  if (opts) o = *opts;
+  if (sp->K != 1) return fail(POTUS_ERR_UNSUPPORTED, "%s: needs one workgroup per chain (cus_per_chain = 1); this handle runs %d per chain", what, sp->K);
+  if (sp->dense) return fail(POTUS_ERR_UNSUPPORTED, "%s: the dense metric is not supported (metric = POTUS_METRIC_DIAG only)", what);
+  if (!sp->k1_unsupported.empty()) return fail(POTUS_ERR_UNSUPPORTED, "%s: %s", what, sp->k1_unsupported.c_str());
+  if (n_modes <= 0) return fail(POTUS_ERR_ARG, "%s: n_modes = %d, at least 1", what, n_modes);
+  if (sp->n_ds && n_modes % sp->n_ds) return fail(POTUS_ERR_ARG, "%s: n_modes = %d is not a multiple of the handle's %d data sets", what, n_modes, sp->n_ds);
+  if (n_draws < 0) return fail(POTUS_ERR_ARG, "%s: n_draws = %d", what, n_draws);
+  if (!(o.h > 0.0) || !std::isfinite(o.h)) return fail(POTUS_ERR_ARG, "%s: h = %g, must be positive and finite", what, o.h);
+  if (o.jacobian != 0 && o.jacobian != 1) return fail(POTUS_ERR_ARG, "%s: jacobian = %d, 0 or 1", what, o.jacobian);
+  if (o.draw_offset < 0 || (long long)o.draw_offset + n_draws >= 0xFFFFFFFFll) return fail(POTUS_ERR_ARG, "%s: draw_offset = %d with %d draws", what, o.draw_offset, n_draws);
+  if (!mode || !info_out) return fail(POTUS_ERR_ARG, "%s: null argument (mode and info_out are required)", what);
+  const int D = sp->L.D, row = POTUS_N_SAMPLER_COLS + D, Dpad = (D + 7) & ~7, LD = Dpad;
+  const size_t mat = (size_t)D * LD, rows_total = (size_t)n_modes * n_draws;
+  if (3ull * Dpad * 8ull >= 0x7fffffffull) return fail(POTUS_ERR_UNSUPPORTED, "%s: D = %d: a workgroup's working set must stay below 2 GB", what, D);
+  if (rows_total * row >= (1ull << 40)) return fail(POTUS_ERR_ARG, "%s: %d modes x %d draws of %d coordinates", what, n_modes, n_draws, D);
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  // the modes that are finite go through the kernels, in blocks of as many matrices as the budget holds
+  std::vector<int> live, code(n_modes, LAP_OK);
+  for (int m = 0; m < n_modes; m++) {
+    bool fin = true;
+    for (int i = 0; i < D && fin; i++) fin = std::isfinite(mode[(size_t)m * D + i]);
+    if (fin) live.push_back(m); else code[m] = LAP_NOT_FINITE;
+  }
+  size_t budget = LAP_MATRIX_BUDGET;
+  if (const char *e = getenv("POTUS_LAPLACE_MATRIX_BUDGET")) budget = std::max<size_t>(1, (size_t)atoll(e));
+  const int nlive = (int)live.size(), nmat = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::max(nlive, 1), budget / (mat * 8)));
+  int G = std::max(1, std::min(D, 512 / std::min(nmat, 512)));   // workgroups per mode: the chip's 256 compute units twice over
+  if (const char *e = getenv("POTUS_LAPLACE_G")) G = std::max(1, std::min(D, atoi(e)));   // tests: the rows do not depend on it
+
+  DeviceGuard guard;
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_lap_hess), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp->lds_bytes));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_lap_lp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp->lds_bytes));
+  hipStream_t st = sp->stream;
+  DsPlan pl;
+  pl.of(sp);
+  const int per_ds = n_modes / pl.n_ds;
+  // the handle's rows of the last call go first: a call that fails leaves none behind
+  HIP_TRY(hipStreamSynchronize(st));
+  if (sp->lap_rows) { (void)hipFree(sp->lap_rows); sp->lap_rows = nullptr; }
+  sp->lap_modes = sp->lap_draws = 0; sp->lap_code.clear();
+  DevBufs tmp;
+  int rc;
+  double *rows = nullptr;
+  if (n_draws > 0) {
+    void *p = nullptr;
+    if (hipMalloc(&p, rows_total * row * 8) != hipSuccess) { (void)hipGetLastError(); return fail(POTUS_ERR_DEVICE, "%s: hipMalloc of %zu bytes for the rows failed", what, rows_total * row * 8); }
+    rows = static_cast<double *>(p);
+  }
+  struct RowsOwner { double *p; ~RowsOwner() { if (p) (void)hipFree(p); } } owner{rows};   // until the call has succeeded
+  double *H = nullptr, *work = nullptr, *dmode = nullptr, *dgn = nullptr, *dinfo = nullptr, *U = nullptr, *dlp = nullptr, *dla = nullptr, *gscr = nullptr;
+  int *dds = nullptr, *dfail = nullptr;
+  LapHessParams *dP = nullptr;
+  const int lp_grid = std::max(1, std::min(n_draws, 1024));
+  if ((rc = tmp.get(&H, (size_t)nmat * mat * 8, what)) || (rc = tmp.get(&work, (size_t)nmat * G * 3 * Dpad * 8, what)) ||
+      (rc = tmp.get(&dmode, (size_t)n_modes * D * 8, what)) || (rc = tmp.get(&dgn, (size_t)n_modes * 8, what)) ||
+      (rc = tmp.get(&dinfo, (size_t)nmat * 4 * 8, what)) || (rc = tmp.get(&dds, (size_t)n_modes * 4, what)) ||
+      (rc = tmp.get(&dfail, (size_t)n_modes * 4, what)) || (rc = tmp.get(&dP, sizeof(LapHessParams), what))) return rc;
+  if (n_draws > 0 && ((rc = tmp.get(&U, (size_t)n_draws * LD * 8, what)) || (rc = tmp.get(&dlp, rows_total * 8, what)) ||
+                      (rc = tmp.get(&dla, rows_total * 8, what)) || (rc = tmp.get(&gscr, (size_t)lp_grid * Dpad * 8, what)))) return rc;
+  // (live modes compacted: entry k of dmode / dds / dgn / dfail is mode live[k])
+  std::vector<double> hmode((size_t)std::max(nlive, 1) * D);
+  std::vector<int> hds(std::max(nlive, 1), 0);
+  for (int k = 0; k < nlive; k++) {
+    std::copy(mode + (size_t)live[k] * D, mode + (size_t)(live[k] + 1) * D, hmode.begin() + (size_t)k * D);
+    hds[k] = live[k] / per_ds;
+  }
+  HIP_TRY(hipMemcpyAsync(dmode, hmode.data(), (size_t)std::max(nlive, 1) * D * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dds, hds.data(), (size_t)std::max(nlive, 1) * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(dfail, 0, (size_t)n_modes * 4, st));
+  std::vector<double> hinfo((size_t)std::max(nlive, 1) * 4, nan), hgn(std::max(nlive, 1), nan);
+  std::vector<int> hfail(std::max(nlive, 1), 0);
+  LapSpans t_hess, t_fac, t_solve, t_lp;
+  const int nbk = (D + DN_NB - 1) / DN_NB;
+  for (int k0 = 0; k0 < nlive; k0 += nmat) {
+    const int nk = std::min(nmat, nlive - k0);
+    LapHessParams P{dmode + (size_t)k0 * D, dds + k0, work, H, dgn + k0, G, Dpad, LD, o.jacobian, o.h};
+    HIP_TRY(hipMemcpyAsync(dP, &P, sizeof(P), hipMemcpyHostToDevice, st));   // (pageable source: copied before the call returns)
+    if ((rc = t_hess.begin(st))) return rc;
+    hipLaunchKernelGGL(k_lap_hess, dim3(G, nk), dim3(PT_THREADS), sp->lds_bytes, st, pl.Mg, (const LapHessParams *)dP);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_lap_sym, dim3(nbk, nbk, nk), dim3(256), 0, st, H, D, LD);
+    HIP_TRY(hipGetLastError());
+    if ((rc = t_hess.end(st))) return rc;
+    if (precision_out)
+      for (int k = 0; k < nk; k++)
+        HIP_TRY(hipMemcpy2DAsync(precision_out + (size_t)live[k0 + k] * D * D, (size_t)D * 8, H + (size_t)k * mat, (size_t)LD * 8, (size_t)D * 8, D, hipMemcpyDeviceToHost, st));
+    if ((rc = t_fac.begin(st))) return rc;
+    for (int k = 0; k < nk; k++) {   // one matrix per launch set: its own fail word
+      DnParams F{};
+      F.chains = 1; F.D = D; F.LD = LD; F.A = H + (size_t)k * mat; F.fail = dfail + k0 + k;
+      dense_cholesky_launch(st, F, 1);
+      HIP_TRY(hipGetLastError());
+    }
+    hipLaunchKernelGGL(k_lap_diag, dim3(nk), dim3(256), 0, st, (const double *)H, D, LD, dinfo);
+    HIP_TRY(hipGetLastError());
+    if ((rc = t_fac.end(st))) return rc;
+    HIP_TRY(hipMemcpyAsync(hinfo.data() + (size_t)k0 * 4, dinfo, (size_t)nk * 4 * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hfail.data() + k0, dfail + k0, (size_t)nk * 4, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));   // who has a factor decides what the draws of the block become
+    for (int k = 0; k < nk && n_draws > 0; k++) {
+      const int m = live[k0 + k], ok = hfail[k0 + k] == 0;
+      const double *Lk = H + (size_t)k * mat;
+      double *mrows = rows + (size_t)m * n_draws * row, *mlp = dlp + (size_t)m * n_draws, *mla = dla + (size_t)m * n_draws;
+      const int dgrid = std::min(n_draws, 4096), nt = (n_draws + DN_NB - 1) / DN_NB;
+      if ((rc = t_solve.begin(st))) return rc;
+      if (ok) {
+        if (u) HIP_TRY(hipMemcpy2DAsync(U, (size_t)LD * 8, u + (size_t)m * n_draws * D, (size_t)D * 8, (size_t)D * 8, n_draws, hipMemcpyHostToDevice, st));
+        else {
+          hipLaunchKernelGGL(k_lap_normals, dim3((unsigned)std::min<long long>(((long long)n_draws * ((D + 1) / 2) + 255) / 256, 65535)), dim3(256), 0, st,
+                             U, n_draws, D, LD, o.draw_offset, sp->R.seed_lo, sp->R.seed_hi);
+          HIP_TRY(hipGetLastError());
+        }
+        hipLaunchKernelGGL(k_lap_norm, dim3(dgrid), dim3(256), 0, st, (const double *)U, n_draws, D, LD, mla);
+        HIP_TRY(hipGetLastError());
+        for (int pe = nbk; pe > 0;) {                       // the panel of blocks [pb, pe), last panel first
+          const int pb = std::max(0, pe - LAP_PANEL);
+          for (int b = pe - 1; b >= pb; b--) {
+            hipLaunchKernelGGL(k_lap_solve_diag, dim3(nt), dim3(256), 0, st, Lk, U, D, LD, n_draws, b);
+            if (b > pb) hipLaunchKernelGGL(k_lap_solve_update, dim3(b - pb, nt), dim3(256), 0, st, Lk, U, D, LD, n_draws, b, b + 1, pb);
+          }
+          if (pb > 0) hipLaunchKernelGGL(k_lap_solve_update, dim3(pb, nt), dim3(256), 0, st, Lk, U, D, LD, n_draws, pb, pe, 0);
+          pe = pb;
+        }
+        HIP_TRY(hipGetLastError());
+      }
+      hipLaunchKernelGGL(k_lap_rows, dim3(dgrid), dim3(256), 0, st, (const double *)U, (const double *)(dmode + (size_t)(k0 + k) * D), n_draws, D, LD, ok, mrows, mlp, mla);
+      HIP_TRY(hipGetLastError());
+      if ((rc = t_solve.end(st))) return rc;
+      if (ok) {
+        if ((rc = t_lp.begin(st))) return rc;
+        hipLaunchKernelGGL(k_lap_lp, dim3(lp_grid), dim3(PT_THREADS), sp->lds_bytes, st, pl.Mg + hds[k0 + k], mrows, n_draws, gscr, Dpad, mlp);
+        HIP_TRY(hipGetLastError());
+        if ((rc = t_lp.end(st))) return rc;
+      }
+    }
+  }
+  if (nlive) HIP_TRY(hipMemcpyAsync(hgn.data(), dgn, (size_t)nlive * 8, hipMemcpyDeviceToHost, st));
+  if (n_draws > 0) {
+    for (int m = 0; m < n_modes; m++) if (code[m] == LAP_NOT_FINITE) {   // no kernel has written these rows
+      hipLaunchKernelGGL(k_lap_rows, dim3(std::min(n_draws, 4096)), dim3(256), 0, st, (const double *)U, (const double *)dmode, n_draws, D, LD, 0,
+                         rows + (size_t)m * n_draws * row, dlp + (size_t)m * n_draws, dla + (size_t)m * n_draws);
+      HIP_TRY(hipGetLastError());
+    }
+    if (q_out) HIP_TRY(hipMemcpy2DAsync(q_out, (size_t)D * 8, rows + POTUS_N_SAMPLER_COLS, (size_t)row * 8, (size_t)D * 8, rows_total, hipMemcpyDeviceToHost, st));
+    if (lp_out) HIP_TRY(hipMemcpyAsync(lp_out, dlp, rows_total * 8, hipMemcpyDeviceToHost, st));
+    if (lp_approx_out) HIP_TRY(hipMemcpyAsync(lp_approx_out, dla, rows_total * 8, hipMemcpyDeviceToHost, st));
+  }
+  HIP_TRY(hipStreamSynchronize(st));
+  double ms[4];
+  if ((rc = t_hess.sum(&ms[0])) || (rc = t_fac.sum(&ms[1])) || (rc = t_solve.sum(&ms[2])) || (rc = t_lp.sum(&ms[3]))) return rc;
+  std::copy(ms, ms + 4, g_lap_ms);
+  for (int m = 0; m < n_modes; m++) for (int i = 0; i < 4; i++) info_out[(size_t)m * 4 + i] = i == 0 ? (double)LAP_NOT_FINITE : nan;
+  for (int k = 0; k < nlive; k++) {
+    const int m = live[k];
+    code[m] = hfail[k] ? LAP_NOT_PD : LAP_OK;
+    double *io = info_out + (size_t)m * 4;
+    io[0] = code[m]; io[1] = hfail[k] ? nan : hinfo[(size_t)k * 4 + 1]; io[2] = hgn[k]; io[3] = hfail[k] ? nan : hinfo[(size_t)k * 4 + 3];
+  }
+  if (precision_out)
+    for (int m = 0; m < n_modes; m++) if (code[m] == LAP_NOT_FINITE) std::fill(precision_out + (size_t)m * D * D, precision_out + (size_t)(m + 1) * D * D, nan);
+  if (n_draws > 0) { sp->lap_rows = rows; owner.p = nullptr; sp->lap_modes = n_modes; sp->lap_draws = n_draws; sp->lap_code = code; }
+  return 0;
+}
+
+int potus_laplace_write_array_device(int handle, int col_begin, int col_end, void *out_device) {
+  const char *what = "potus_laplace_write_array_device";
+  Sampler *sp = get(handle);
+  if (!sp || !out_device) return fail(POTUS_ERR_STATE, "bad handle or null output");
+  if (const int rc_ = lap_have_rows(what, sp)) return rc_;
+  if (const int rc_ = check_cols(sp, col_begin, col_end)) return rc_;
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, sp->device, out_device, "output")) return rc_;
+  DevBufs tmp;
+  const int n = sp->lap_modes * sp->lap_draws, nsel = col_end - col_begin;
+  DsPlan pl;
+  pl.of(sp);
+  WAParams W{RowSrc{sp->lap_rows, n, 1, POTUS_N_SAMPLER_COLS + sp->L.D, 0}, 1, sp->L.ncols, col_begin, col_end, nullptr, (double *)out_device, nsel};   // one saved draw of n chains
+  if (const int rc_ = launch_rows(sp, tmp, what, pl.Mg, sp->n_ds ? lap_per_ds(sp) : 0, W)) return rc_;
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  return 0;
+}
+
+namespace {
+int lap_scores(Sampler *sp, int day_begin, int day_end, const int *dskip, double *out) {
+  const int n = sp->lap_modes * sp->lap_draws;
+  DsPlan pl;
+  pl.of(sp);
+  TlScoreParams P{RowSrc{sp->lap_rows, n, 1, POTUS_N_SAMPLER_COLS + sp->L.D, 0}, 1, lap_per_ds(sp), day_begin, day_end, dskip, out};
+  hipLaunchKernelGGL(k_tl_scores, dim3((unsigned)std::min<long long>(((long long)n + 3) / 4, 65535)), dim3(256), 0, sp->stream, pl.Mg, P);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+int lap_check_days(const char *what, const Sampler *sp, int day_begin, int day_end) {
+  if (day_begin < 0 || day_end > sp->M.T || day_begin >= day_end) return fail(POTUS_ERR_ARG, "%s: bad day range [%d,%d) of %d days", what, day_begin, day_end, sp->M.T);
+  return 0;
+}
+} // namespace
+
+int potus_laplace_scores_device(int handle, int day_begin, int day_end, void *out_device) {
+  const char *what = "potus_laplace_scores_device";
+  Sampler *sp = get(handle);
+  if (!sp || !out_device) return fail(POTUS_ERR_STATE, "bad handle or null output");
+  if (const int rc_ = lap_have_rows(what, sp)) return rc_;
+  if (const int rc_ = lap_check_days(what, sp, day_begin, day_end)) return rc_;
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, sp->device, out_device, "output")) return rc_;
+  DevBufs tmp;
+  int *dskip = nullptr;
+  const int n_ds = std::max(sp->n_ds, 1);
+  if (const int rc_ = tmp.get(&dskip, (size_t)n_ds * 4, what)) return rc_;
+  HIP_TRY(hipMemsetAsync(dskip, 0, (size_t)n_ds * 4, sp->stream));   // (a mode without a factor has NaN rows: its scores are NaN without a flag)
+  if (const int rc_ = lap_scores(sp, day_begin, day_end, dskip, (double *)out_device)) return rc_;
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  return 0;
+}
+
+int potus_laplace_summary(int handle, int day_begin, int day_end, const double *ev, int ev_to_win, double *state_out, double *natl_out, double *ev_out, int32_t *n_draws_out) {
+  const char *what = "potus_laplace_summary";
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  if (!ev || !state_out || !natl_out || !ev_out || !n_draws_out) return fail(POTUS_ERR_ARG, "%s: null argument", what);
+  if (const int rc_ = lap_have_rows(what, sp)) return rc_;
+  if (const int rc_ = lap_check_days(what, sp, day_begin, day_end)) return rc_;
+  if (sp->lap_draws > TL_MAX_DRAWS) return fail(POTUS_ERR_UNSUPPORTED, "%s: %d draws per mode: a mode's draws are sorted in LDS, at most %d", what, sp->lap_draws, TL_MAX_DRAWS);
+  DeviceGuard guard;
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  const int S = sp->M.S, nd = day_end - day_begin, n = sp->lap_draws, nm = sp->lap_modes, n_ds = std::max(sp->n_ds, 1);
+  DevBufs tmp;
+  double *x = nullptr, *dw = nullptr, *dev_ = nullptr, *dout = nullptr;
+  int *dskip = nullptr, *dzero = nullptr;
+  int rc;
+  const size_t n_out = (size_t)nm * nd * ((size_t)S * 4 + 9);
+  if ((rc = tmp.get(&x, (size_t)nm * n * nd * S * 8, what)) || (rc = tmp.get(&dw, (size_t)S * 8, what)) || (rc = tmp.get(&dev_, (size_t)S * 8, what)) ||
+      (rc = tmp.get(&dout, n_out * 8, what)) || (rc = tmp.get(&dskip, (size_t)nm * 4, what)) || (rc = tmp.get(&dzero, (size_t)n_ds * 4, what))) return rc;
+  HIP_TRY(hipMemcpyAsync(dskip, sp->lap_code.data(), (size_t)nm * 4, hipMemcpyHostToDevice, sp->stream));   // per mode: a code that is not 0 gives NaN
+  HIP_TRY(hipMemsetAsync(dzero, 0, (size_t)n_ds * 4, sp->stream));
+  HIP_TRY(hipMemcpyAsync(dw, sp->h_w.data(), (size_t)S * 8, hipMemcpyHostToDevice, sp->stream));
+  HIP_TRY(hipMemcpyAsync(dev_, ev, (size_t)S * 8, hipMemcpyHostToDevice, sp->stream));
+  if ((rc = lap_scores(sp, day_begin, day_end, dzero, x))) return rc;
+  int npad = 1;
+  while (npad < n) npad <<= 1;
+  const size_t lds = (size_t)npad * 8;
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_tl_summary), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  double *o_state = dout, *o_natl = o_state + (size_t)nm * nd * S * 4, *o_ev = o_natl + (size_t)nm * nd * 4;
+  TlSumParams Q{x, nm, n, nd, S, dw, dev_, (double)ev_to_win, dskip, o_state, o_natl, o_ev};
+  hipLaunchKernelGGL(k_tl_summary, dim3((unsigned)std::min<long long>((long long)nm * nd * (S + 2), 65535)), dim3(TL_THREADS), lds, sp->stream, Q);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpyAsync(state_out, o_state, (size_t)nm * nd * S * 4 * 8, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipMemcpyAsync(natl_out, o_natl, (size_t)nm * nd * 4 * 8, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipMemcpyAsync(ev_out, o_ev, (size_t)nm * nd * 5 * 8, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  for (int m = 0; m < nm; m++) n_draws_out[m] = sp->lap_code[m] ? 0 : n;
+  return 0;
+}
+
+int potus_laplace_timing(double *ms) {
+  return timing_out("potus_laplace_timing", g_lap_ms, 4, ms);
+}
+
 int potus_simulate_prior(int handle, uint64_t seed, int n_sims, int sim_offset, double *q_out, int32_t *n_democrat_state_out, int32_t *n_democrat_national_out) {
   Sampler *sp = get(handle);
   if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
@@ -4915,6 +5226,15 @@ void potus_R_optimize(int *handle, int *iopts /*[7]: jacobian, history_size, ite
   o.jacobian = iopts[0]; o.history_size = iopts[1]; o.iter = iopts[2]; o.path_offset = iopts[3];
   o.init_alpha = dopts[0]; o.tol_obj = dopts[1]; o.tol_rel_obj = dopts[2]; o.tol_grad = dopts[3]; o.tol_rel_grad = dopts[4]; o.tol_param = dopts[5];
   *status = potus_optimize(*handle, &o, iopts[5] ? q0 : nullptr, iopts[4], q_out, lp_out, gnorm_out, info_out, cols[0], cols[1], iopts[6] ? row_out : nullptr);
+}
+void potus_R_laplace(int *handle, int *iopts /*[6]: jacobian, draw_offset, n_modes, n_draws, u given, precision wanted*/, double *h, double *mode, double *u,
+                     double *q_out, double *lp_out, double *lp_approx_out, double *info_out, double *precision_out, int *status) {
+  potus_laplace_opts o;
+  potus_default_laplace_opts(&o);
+  o.jacobian = iopts[0]; o.draw_offset = iopts[1]; o.h = *h;
+  const bool draws = iopts[3] > 0;
+  *status = potus_laplace(*handle, &o, mode, iopts[2], iopts[4] ? u : nullptr, iopts[3], draws ? q_out : nullptr, draws ? lp_out : nullptr,
+                          draws ? lp_approx_out : nullptr, info_out, iopts[5] ? precision_out : nullptr);
 }
 void potus_R_set_datasets(int *handle, int *n_datasets, int *n_democrat_state, int *n_democrat_national, int *status) {
   *status = potus_set_datasets(*handle, *n_datasets, n_democrat_state, n_democrat_national);

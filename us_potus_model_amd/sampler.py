@@ -135,6 +135,17 @@ def load_library():
         L.potus_optimize_timing.argtypes = [dp]
         L.potus_R_optimize.argtypes = [ip, ip, dp, dp, dp, dp, dp, ip, ip, dp, ip]
         L.potus_R_optimize.restype = None
+    if hasattr(L, "potus_laplace"):                     # the Laplace approximation (Handle.laplace, PotusModel.laplace)
+        i32p, lop = C.POINTER(C.c_int32), C.POINTER(_abi.PotusLaplaceOpts)
+        L.potus_default_laplace_opts.argtypes = [lop]
+        L.potus_default_laplace_opts.restype = None
+        L.potus_laplace.argtypes = [C.c_int, lop, dp, C.c_int, dp, C.c_int, dp, dp, dp, dp, dp]
+        L.potus_laplace_write_array_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.potus_laplace_scores_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.potus_laplace_summary.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, dp, dp, i32p]
+        L.potus_laplace_timing.argtypes = [dp]
+        L.potus_R_laplace.argtypes = [ip, ip, dp, dp, dp, dp, dp, dp, dp, dp, ip]
+        L.potus_R_laplace.restype = None
     _LIB = L
     return L
 
@@ -151,6 +162,8 @@ EXPORTS = [
     "potus_log_lik_device", "potus_loo_device", "potus_loo",
     "potus_cv_log_lik_device", "potus_cv_lpd", "potus_cv_timing",
     "potus_default_optimize_opts", "potus_optimize", "potus_optimize_timing",
+    "potus_default_laplace_opts", "potus_laplace", "potus_laplace_write_array_device", "potus_laplace_scores_device", "potus_laplace_summary",
+    "potus_laplace_timing", "potus_R_laplace",
     "potus_outcomes", "potus_outcomes_device", "potus_outcomes_timing",
     "potus_monitor", "potus_monitor_device",
     "potus_scenario", "potus_scenario_device", "potus_scenario_timing",
@@ -474,6 +487,94 @@ class Handle:
         ms = np.zeros(1)
         _check(self.L, self.L.potus_optimize_timing(_dp(ms)))
         return float(ms[0])
+
+    def laplace_opts(self, **opts):
+        """potus_default_laplace_opts with the given fields replaced (jacobian, draw_offset, h)."""
+        o = _abi.PotusLaplaceOpts()
+        self.L.potus_default_laplace_opts(C.byref(o))
+        for k, v in opts.items():
+            if k.startswith("pad") or not hasattr(o, k):
+                raise TypeError(f"unknown Laplace option {k!r}")
+            setattr(o, k, v)
+        return o
+
+    def laplace(self, mode, draws, u=None, precision=False, opts=None, **fields):
+        """potus_laplace: the normal approximation around mode [modes, D] (or [D]): P = minus the Hessian of log_prob<jacobian> by central
+        differences on the device, P = L L', `draws` draws x = mode + L^-T u per mode.  u [modes, draws, D]: the caller's standard normals, None:
+        the library's (Philox purpose 8, draw n of a call is draw draw_offset + n).  On a handle with data sets mode m uses data set
+        m // (modes // n_datasets).  fields: those of potus_laplace_opts (or opts: a filled struct).  Returns dict(q [modes, draws, D], lp,
+        lp_approx [modes, draws], return_code, log_det, grad_norm, min_pivot [modes] and, with precision, precision [modes, D, D])."""
+        o = opts if opts is not None else self.laplace_opts(**fields)
+        mode = np.ascontiguousarray(np.atleast_2d(np.asarray(mode, dtype=np.float64)))
+        if mode.ndim != 2 or mode.shape[1] != self.D:
+            raise ValueError(f"laplace: mode has shape {mode.shape}, [modes, {self.D}] expected")
+        m, n = mode.shape[0], int(draws)
+        pu = None
+        if u is not None:
+            u = np.ascontiguousarray(np.asarray(u, dtype=np.float64))
+            if u.shape == (n, self.D) and m == 1:
+                u = u.reshape(1, n, self.D)
+            if u.shape != (m, n, self.D):
+                raise ValueError(f"laplace: u has shape {u.shape}, [{m}, {n}, {self.D}] expected")
+            pu = _dp(u)
+        k = max(n, 0)
+        q, lp, la, info = np.zeros((m, k, self.D)), np.zeros((m, k)), np.zeros((m, k)), np.zeros((m, 4))
+        prec = np.zeros((m, self.D, self.D)) if precision else None
+        _check(self.L, self.L.potus_laplace(self.h, C.byref(o), _dp(mode), m, pu, n, _dp(q) if k else None, _dp(lp) if k else None,
+                                            _dp(la) if k else None, _dp(info), None if prec is None else _dp(prec)))
+        self._laplace_shape = (m, k)
+        out = dict(q=q, lp=lp, lp_approx=la, return_code=info[:, 0].astype(np.int32), log_det=info[:, 1].copy(), grad_norm=info[:, 2].copy(),
+                   min_pivot=info[:, 3].copy())
+        if prec is not None:
+            out["precision"] = prec
+        return out
+
+    def _laplace_block(self, what):
+        shape = getattr(self, "_laplace_shape", None)
+        if not shape or not shape[1]:
+            raise PotusError(f"{what}: no Laplace draws on this handle (laplace(mode, draws >= 1) first)")
+        return shape
+
+    def laplace_rows_device(self, cols=None):
+        """potus_laplace_write_array_device: the CmdStan output columns (begin, end) (default: all) of the last laplace() call's draws, a torch
+        tensor [modes * draws, end - begin] on this handle's GPU -- what monitor_device takes."""
+        import torch
+        m, n = self._laplace_block("laplace_rows_device")
+        a, b = (0, self.n_cols) if cols is None else (int(cols[0]), int(cols[1]))
+        out = torch.empty((m * n, max(b - a, 1)), dtype=torch.float64, device=f"cuda:{self.opts.device}")
+        torch.cuda.current_stream(out.device).synchronize()
+        _check(self.L, self.L.potus_laplace_write_array_device(self.h, a, b, C.c_void_p(out.data_ptr())))
+        return out
+
+    def laplace_scores(self, days=None):
+        """potus_laplace_scores_device: predicted_score of the days (begin, end) (0-based, default: election day) of the last laplace() call's
+        draws, a torch tensor [modes, draws, days, S] on this handle's GPU; a mode's block is what outcomes_device / scenario_device take."""
+        import torch
+        m, n = self._laplace_block("laplace_scores")
+        S = int(self.data["S"])
+        t0, t1 = self._day_range(days)
+        out = torch.empty((m, n, max(t1 - t0, 1), S), dtype=torch.float64, device=f"cuda:{self.opts.device}")
+        torch.cuda.current_stream(out.device).synchronize()
+        _check(self.L, self.L.potus_laplace_scores_device(self.h, t0, t1, C.c_void_p(out.data_ptr())))
+        return out
+
+    def laplace_summary(self, ev, days=None, ev_to_win=270):
+        """potus_laplace_summary: timeline()'s outputs with the modes of the last laplace() call in the place of data sets:
+        dict(state [modes, days, S, 4], national [modes, days, 4], electoral_votes [modes, days, 5], n_draws [modes])."""
+        m, _ = self._laplace_block("laplace_summary")
+        S = int(self.data["S"])
+        t0, t1 = self._day_range(days)
+        nd = max(t1 - t0, 0)
+        ev = np.ascontiguousarray(ev, dtype=np.float64).reshape(S)
+        st, na, eo, cnt = np.zeros((m, nd, S, 4)), np.zeros((m, nd, 4)), np.zeros((m, nd, 5)), np.zeros(m, np.int32)
+        _check(self.L, self.L.potus_laplace_summary(self.h, t0, t1, _dp(ev), int(ev_to_win), _dp(st), _dp(na), _dp(eo), _ip(cnt)))
+        return dict(state=st, national=na, electoral_votes=eo, n_draws=cnt)
+
+    def laplace_timing(self):
+        """Milliseconds (HIP events) of the stages of this thread's last laplace(): Hessian, factor, solve, lp__."""
+        ms = np.zeros(4)
+        _check(self.L, self.L.potus_laplace_timing(_dp(ms)))
+        return dict(hessian_ms=float(ms[0]), factor_ms=float(ms[1]), solve_ms=float(ms[2]), lp_ms=float(ms[3]))
 
     def simulate_prior(self, seed, n_sims, sim_offset=0):
         """potus_simulate_prior: (q [n_sims, D], n_democrat_state [n_sims, Ns], n_democrat_national [n_sims, Nn]) drawn from the prior
@@ -861,6 +962,74 @@ class Optimum:
         self._h.close()
 
 
+class Laplace:
+    """What cmdstanr's model$laplace() returns for one mode: q [draws, D] (unconstrained draws of N(mode, P^-1), P = minus the Hessian of
+    log_prob<jacobian> at the mode), lp (log_prob<jacobian = true> of every draw, as the sampler's lp__), lp_approx = -1/2 |u|^2,
+    log_ratio = lp - lp(mode) - lp_approx (the log importance ratio of the draw up to a constant), log_det = log det P, grad_norm at the
+    mode, return_code (_abi.LAPLACE_CODES).  The draws' rows stay on the handle: scores / summary / outcomes / scenario work on them there."""
+
+    def __init__(self, handle, mode, res, lp_mode, jacobian):
+        self._h, self.mode, self.jacobian = handle, np.asarray(mode, dtype=np.float64).reshape(-1), bool(jacobian)
+        self.return_code = int(res["return_code"][0])
+        if self.return_code != 0:
+            raise PotusError(f"laplace: the mode has no Laplace approximation (return code {_abi.LAPLACE_CODES.get(self.return_code, self.return_code)}: "
+                             "minus the Hessian is not positive definite there, or the point is not finite)")
+        self.q, self.lp, self.lp_approx = res["q"][0], res["lp"][0], res["lp_approx"][0]
+        self.log_det, self.grad_norm, self.min_pivot = float(res["log_det"][0]), float(res["grad_norm"][0]), float(res["min_pivot"][0])
+        self.lp_mode = float(lp_mode)
+        self.log_ratio = self.lp - self.lp_mode - self.lp_approx
+        self._row = self._k = None
+
+    def draws(self, par):
+        """fit$draws(par): the constrained values of every draw, shaped as Optimum.mle shapes one, with a leading draw axis."""
+        if par == "lp__":
+            return self.lp.copy()
+        if par == "lp_approx__":
+            return self.lp_approx.copy()
+        if par not in self._h.layout:
+            raise KeyError(f"unknown parameter {par!r}")
+        if self._row is None:
+            self._row = self._h.laplace_rows_device().cpu().numpy()
+        a, b, dims = self._h.layout[par]
+        v = self._row[:, a:b]
+        if not dims:
+            return v[:, 0].copy()
+        nd = len(dims)
+        return v.reshape((v.shape[0],) + tuple(reversed(dims))).transpose((0,) + tuple(range(nd, 0, -1))).copy()    # column-major -> dims
+
+    @property
+    def pareto_k(self):
+        """k-hat of the importance ratios: the library's PSIS (potus_loo_device) on a one-column block whose log-likelihood is -log_ratio."""
+        if self._k is None:
+            import torch
+            from .loo import loo_of_block
+            blk = torch.as_tensor(-self.log_ratio, device=f"cuda:{self._h.opts.device}").reshape(1, 1, -1).contiguous()
+            self._k = float(loo_of_block(blk).pareto_k[0])
+        return self._k
+
+    def scores(self, days=None):
+        """predicted_score of `days` = (begin, end) (0-based; default election day) of every draw: a torch tensor [draws, days, S] on the GPU."""
+        return self._h.laplace_scores(days)[0]
+
+    def summary(self, ev, days=None, ev_to_win=270):
+        """timeline()'s summaries over the draws: dict(state [days, S, 4], national [days, 4], electoral_votes [days, 5], n_draws)."""
+        r = self._h.laplace_summary(ev, days, ev_to_win)
+        return dict(state=r["state"][0], national=r["national"][0], electoral_votes=r["electoral_votes"][0], n_draws=int(r["n_draws"][0]))
+
+    def outcomes(self, ev, actual=None, days=None, ev_to_win=270, states=None):
+        """Joint election outcomes over the draws (potus_outcomes_device on their scores)."""
+        from .outcomes import outcomes_of_block
+        return outcomes_of_block(self.scores(days).contiguous(), self._h.data["state_weights"], ev, actual=actual, ev_to_win=ev_to_win, states=states)
+
+    def scenario(self, ev=None, given=None, day=-1, days=None, ev_to_win=270, states=None):
+        """Conditional forecast over the draws (potus_scenario_device on their scores); `day` indexes the range `days`."""
+        from .scenario import scenario_of_block
+        return scenario_of_block(self.scores(days).contiguous(), self._h.data["state_weights"], ev=ev, given=given, day=day, ev_to_win=ev_to_win, states=states)
+
+    def close(self):
+        self._h.close()
+
+
 class PotusModel:
     """cmdstanr::cmdstan_model() for the two poll models (final_2016.R:532, final_2012.R:558)."""
 
@@ -889,6 +1058,36 @@ class PotusModel:
             return Optimum(h, res, jacobian)
         except Exception:
             h.close()
+            raise
+
+    def laplace(self, data, mode=None, draws=1000, jacobian=True, seed=1843, h=None, u=None, draw_offset=0, device=0):
+        """cmdstanr's model$laplace(data, mode =, draws =, jacobian = TRUE): draws from the normal approximation at the mode, on the device.
+        mode: an Optimum (its best path; found with the same `jacobian`), an array [D] of unconstrained coordinates, or None -- then
+        optimize(jacobian=jacobian) runs first with tol_grad = 1e-2 as its only stopping rule (CmdStan's default rules stop this model at
+        |g| of 2-4, DESIGN.md section 4k, too far from the mode for a Hessian).  u [draws, D]: the caller's standard normals."""
+        if isinstance(mode, Optimum):
+            if mode.jacobian != bool(jacobian):
+                raise ValueError(f"laplace: the mode was found with jacobian = {mode.jacobian}, the approximation is asked for jacobian = {bool(jacobian)}")
+            q = mode.q[mode.best]
+        elif mode is None:
+            opt = self.optimize(data, jacobian=jacobian, seed=seed, tol_obj=0.0, tol_rel_obj=0.0, tol_grad=1e-2, tol_rel_grad=0.0, tol_param=0.0, device=device)
+            try:
+                q = opt.q[opt.best].copy()
+            finally:
+                opt.close()
+        else:
+            q = np.asarray(mode, dtype=np.float64).reshape(-1)
+        hd = Handle(data, self.variant, chains=1, num_warmup=0, num_samples=0, seed=int(seed), device=int(device), cus_per_chain=1, twin=0)
+        try:
+            if q.shape != (hd.D,):
+                raise ValueError(f"laplace: the mode has {q.size} coordinates, {hd.D} expected")
+            fields = dict(jacobian=int(bool(jacobian)), draw_offset=int(draw_offset))
+            if h is not None:
+                fields["h"] = float(h)
+            res = hd.laplace(q, int(draws), u=u, **fields)
+            return Laplace(hd, q, res, hd.log_prob_grad(q)[0][0], jacobian)
+        except Exception:
+            hd.close()
             raise
 
     def sample(self, data, seed=1843, chains=4, parallel_chains=None, iter_warmup=1000, iter_sampling=1000,

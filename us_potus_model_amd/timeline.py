@@ -212,6 +212,36 @@ def modes(design, variant="full", paths_per_date=1, device=0, seed=1843, init_ra
         h.close()
 
 
+def laplace(design, variant="full", draws=1000, ev=None, days=None, ev_to_win=270, jacobian=True, device=0, seed=1843, h=None):
+    """The approximate forecast of a whole campaign without a sampler run: the modes of all run dates (modes(), tol_grad = 1e-2 as the only
+    stopping rule), then ONE potus_laplace call on a potus_set_datasets_ex handle -- date d's Hessian, factor and `draws` draws with the
+    date's own model -- and, with ev, the per-date summary of potus_laplace_summary over `days` (default: election day).  dict(mode [dates, D],
+    return_code, log_det, grad_norm [dates], lp, lp_approx, log_ratio [dates, draws] (lp - lp(mode) - lp_approx; with jacobian = False up to a
+    constant per date), optimize (what modes() returned), timing (laplace_timing), and with ev: state [dates, days, S, 4], national,
+    electoral_votes, n_draws).  A date whose code is not 0 has NaN."""
+    n = int(design["keep_state"].shape[0])
+    if int(draws) < 1 or (ev is not None and int(draws) > MAX_DRAWS):
+        raise ValueError(f"timeline.laplace: {draws} draws per date (1 .. {MAX_DRAWS} with a summary)")
+    opt = modes(design, variant, paths_per_date=1, device=device, seed=seed, jacobian=int(bool(jacobian)), tol_obj=0.0, tol_rel_obj=0.0,
+                tol_grad=1e-2, tol_rel_grad=0.0, tol_param=0.0)
+    q = np.ascontiguousarray(opt["q"][:, 0])
+    hd = Handle(design["data"], variant, chains=n, num_warmup=0, num_samples=0, seed=int(seed), device=int(device), **_BATCHED)
+    try:
+        set_design(hd, design)
+        fields = dict(jacobian=int(bool(jacobian)))
+        if h is not None:
+            fields["h"] = float(h)
+        res = hd.laplace(q, int(draws), **fields)
+        out = dict(mode=q, return_code=res["return_code"], log_det=res["log_det"], grad_norm=res["grad_norm"], lp=res["lp"], lp_approx=res["lp_approx"],
+                   log_ratio=res["lp"] - opt["lp"][:, :1] - res["lp_approx"], optimize=opt, timing=hd.laplace_timing(),
+                   run_dates=list(design.get("run_dates", range(n))))
+        if ev is not None:
+            out.update(hd.laplace_summary(ev, days, ev_to_win))
+        return out
+    finally:
+        hd.close()
+
+
 def save_fixture(path, design):
     """The per-date part of a design (masks, priors, scales, dates) as one .npz: data only."""
     np.savez_compressed(path, keep_state=np.packbits(design["keep_state"], axis=1), keep_national=np.packbits(design["keep_national"], axis=1),
