@@ -47,6 +47,14 @@ int potus_dense_pool_matvec_probe(int device, int chains, int D, int nrhs, const
                                   double *ms, long long *pass_bytes);
 int potus_dense_pool_factor_probe(int device, int chains, int D, int n, const double *draws_host, const double *u_host, double *Minv_host, double *L_host,
                                   double *p_host, double *ms);
+/* The per-poll scalar arithmetic, without a sampler (tests/test_gpu_poll_terms.py).  potus_poll_ll_probe: out[i] = loo_poll_ll(y[i], n[i],
+ * eta[i], sigma[i], z[i], integrate) -- the log-likelihood term of k_loo_loglik / k_cv_loglik without log C(n, y) -- one thread per item and
+ * nothing else.  potus_binomial_draw_probe: out[item][draw] = binomial_logit_draw(n[item], eta[item]) of k_simulate_prior with the Philox key
+ * (seed, chain field item + 1) and counter index = draw number. */
+int potus_poll_ll_probe(int device, int n_items, const double *y, const double *n, const double *eta, const double *sigma, const double *z, int integrate,
+                        double *out);
+int potus_binomial_draw_probe(int device, unsigned long long seed, int n_items, const int *n, const double *eta, int draws_per_item,
+                              int *out /*int32 [n_items][draws_per_item]*/);
 
 #ifdef __cplusplus
 }

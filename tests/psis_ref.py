@@ -7,7 +7,7 @@ import numpy as np
 from scipy.special import gammaln, logsumexp
 
 GH_NODES = 16             # Q of the device's quadrature (potus_loo.hpp LOO_GH)
-NEWTON_STEPS = 8
+MODE_CAP = 100            # most trips of the mode search (potus_loo.hpp LOO_MODE_CAP)
 
 
 def ess_rfun(x):
@@ -136,42 +136,77 @@ def softplus(x):
     return np.maximum(x, 0.0) + np.log1p(np.exp(-np.abs(x)))
 
 
+def binom_term(y, n, x):
+    """y log inv_logit(x) + (n - y) log inv_logit(-x) = y x - n softplus(x), in the form without cancellation that loo_poll_ll uses."""
+    return y * np.minimum(x, 0.0) - (n - y) * np.maximum(x, 0.0) - n * np.log1p(np.exp(-np.abs(x)))
+
+
 def log_lik_plain(y, n, x):
     """binomial_logit_lpmf(y | n, x), with log C(n, y)."""
-    return lchoose(n, y) + y * x - n * softplus(x)
+    return lchoose(n, y) + binom_term(y, n, x)
 
 
-def log_lik_integrated(y, n, eta, sigma, Q=GH_NODES, newton=NEWTON_STEPS):
-    """log int Binomial(y | n, inv_logit(eta + sigma z)) phi(z) dz by adaptive Gauss-Hermite quadrature: the mode of the strictly concave
-    f(z) = y x - n softplus(x) - z^2 / 2 (x = eta + sigma z) by Newton steps from z = 0, nodes scaled by sqrt(2 / -f''(mode)).  Broadcasts."""
+def _expit(x):
+    with np.errstate(over="ignore"):
+        return 1.0 / (1.0 + np.exp(-x))
+
+
+def integrand_mode(y, n, eta, sigma, cap=MODE_CAP):
+    """The mode of f(z) = y x - n softplus(x) - z^2 / 2, x = eta + sigma z, as loo_poll_ll finds it: f'(z) = sigma (y - n p(x)) - z is strictly
+    decreasing with its root in [sigma (y - n), sigma y]; Newton steps from 0, the bracket narrowed by the sign of every f', a step that does not
+    land strictly inside it replaced by the midpoint; an element stops when a step no longer moves it.  Broadcasts."""
     y, n, eta, sigma = (np.asarray(a, dtype=np.float64) for a in np.broadcast_arrays(y, n, eta, sigma))
-    z = np.zeros_like(eta)
-    for _ in range(newton):
-        p = 1.0 / (1.0 + np.exp(-(eta + sigma * z)))
-        z = z - (sigma * (y - n * p) - z) / (-sigma * sigma * n * p * (1 - p) - 1.0)
-    p = 1.0 / (1.0 + np.exp(-(eta + sigma * z)))
+    z, lo, hi = np.zeros_like(eta), sigma * (y - n), sigma * y
+    live = np.ones(z.shape, bool)
+    for _ in range(cap):
+        p = _expit(eta + sigma * z)
+        g = sigma * (y - n * p) - z
+        live = live & (g != 0)
+        lo, hi = np.where(live & (g > 0), z, lo), np.where(live & (g < 0), z, hi)
+        zn = z - g / (-sigma * sigma * n * p * (1 - p) - 1.0)
+        live = live & (zn != z)
+        zn = np.where((zn > lo) & (zn < hi), zn, 0.5 * (lo + hi))
+        live = live & (zn != z)
+        if not live.any():
+            break
+        z = np.where(live, zn, z)
+    return z
+
+
+def log_lik_integrated(y, n, eta, sigma, Q=GH_NODES):
+    """log int Binomial(y | n, inv_logit(eta + sigma z)) phi(z) dz by adaptive Gauss-Hermite quadrature: the mode of the strictly concave
+    f(z) = y x - n softplus(x) - z^2 / 2 (x = eta + sigma z) by integrand_mode, nodes scaled by sqrt(2 / -f''(mode)).  Broadcasts."""
+    y, n, eta, sigma = (np.asarray(a, dtype=np.float64) for a in np.broadcast_arrays(y, n, eta, sigma))
+    z = integrand_mode(y, n, eta, sigma)
+    p = _expit(eta + sigma * z)
     s = np.sqrt(2.0 / (sigma * sigma * n * p * (1 - p) + 1.0))
     xk, wk = np.polynomial.hermite.hermgauss(Q)
     zk = z[..., None] + s[..., None] * xk
     xx = eta[..., None] + sigma[..., None] * zk
-    f = y[..., None] * xx - n[..., None] * softplus(xx) - 0.5 * zk * zk + xk * xk + np.log(wk)
+    f = binom_term(y[..., None], n[..., None], xx) - 0.5 * zk * zk + xk * xk + np.log(wk)
     out = lchoose(n, y) + logsumexp(f, axis=-1) + np.log(s) - 0.5 * np.log(2 * np.pi)
     return np.where(sigma == 0, log_lik_plain(y, n, eta), out)
 
 
 def log_lik_quad(y, n, eta, sigma):
-    """The same integral by scipy.integrate.quad around the mode (the independent check)."""
-    from scipy import integrate
-    z = 0.0
-    for _ in range(50):
-        p = 1.0 / (1.0 + np.exp(-(eta + sigma * z)))
-        z = z - (sigma * (y - n * p) - z) / (-sigma * sigma * n * p * (1 - p) - 1.0)
-    p = 1.0 / (1.0 + np.exp(-(eta + sigma * z)))
+    """The same integral by scipy.integrate.quad around the mode (the independent check): the mode is the root of the strictly decreasing
+    f'(z) = sigma (y - n p) - z, bracketed by [sigma (y - n), sigma y], by scipy.optimize.brentq."""
+    from scipy import integrate, optimize
+    y, n, eta, sigma = float(y), float(n), float(eta), float(sigma)
+    if sigma == 0.0:
+        return float(log_lik_plain(y, n, eta))
+
+    def df(u):
+        return sigma * (y - n * float(_expit(eta + sigma * u))) - u
+
+    a, b = sigma * (y - n), sigma * y
+    z = a if a == b else optimize.brentq(df, a, b, xtol=1e-300, rtol=4 * np.finfo(float).eps, maxiter=500)
+    p = float(_expit(eta + sigma * z))
     sd = 1.0 / np.sqrt(sigma * sigma * n * p * (1 - p) + 1.0)
 
     def f(u):
         x = eta + sigma * u
-        return y * x - n * softplus(x) - 0.5 * u * u
+        return binom_term(y, n, x) - 0.5 * u * u
 
     f0 = f(z)
     val, _ = integrate.quad(lambda u: np.exp(f(u) - f0), z - 40 * sd, z + 40 * sd, epsabs=0, epsrel=1e-13, limit=400, points=[z])

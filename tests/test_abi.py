@@ -36,6 +36,26 @@ def test_library_exports_every_declared_symbol():
     assert exported == declared | dbg, exported ^ (declared | dbg)
 
 
+def test_scalar_probes_are_debug_exports_and_refuse_bad_arguments():
+    """potus_poll_ll_probe / potus_binomial_draw_probe (tests/test_gpu_poll_terms.py): declared in the debug header, not in the boundary, and an
+    argument refusal comes back before any device call."""
+    dbg = (ROOT / "include" / "potus_hmc_debug.h").read_text()
+    L = sampler.load_library()
+    for name in ("potus_poll_ll_probe", "potus_binomial_draw_probe"):
+        assert re.search(rf"\b{name}\s*\(", dbg) and name not in sampler.EXPORTS and hasattr(L, name)
+    L.potus_poll_ll_probe.argtypes = [C.c_int, C.c_int] + [C.c_void_p] * 5 + [C.c_int, C.c_void_p]
+    L.potus_binomial_draw_probe.argtypes = [C.c_int, C.c_uint64, C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_void_p]
+    x = np.zeros(4)
+    p = x.ctypes.data_as(C.c_void_p)
+    buf = C.create_string_buffer(256)
+    assert L.potus_poll_ll_probe(0, 0, p, p, p, p, p, 1, p) != 0 and L.potus_poll_ll_probe(0, 4, p, p, p, None, p, 1, p) != 0
+    L.potus_last_error(buf, 256)
+    assert b"potus_poll_ll_probe" in buf.value
+    assert L.potus_binomial_draw_probe(0, 1, 2, p, p, 0, p) != 0 and L.potus_binomial_draw_probe(0, 1, 2, None, p, 8, p) != 0
+    L.potus_last_error(buf, 256)
+    assert b"potus_binomial_draw_probe" in buf.value
+
+
 def test_struct_layout_matches_header():
     # potus_data: 7 int32 + pad, 13 + 4 pointers, 6 doubles, pointer, 3 doubles, int32 (+pad)
     assert C.sizeof(_abi.PotusData) == 32 + 17 * 8 + 6 * 8 + 8 + 3 * 8 + 8

@@ -124,6 +124,40 @@ def test_integrated_values_equal_quadrature(cv):
     assert worst < 1e-9
 
 
+def test_integrated_value_of_a_held_out_outlier_poll_with_a_large_sample():
+    """One more fold: a state poll of synthetic.small edited to 38 800 of 40 000 (97 %, about 3.5 logits from its state) and held out by the data
+    set that is scored on it.  sigma^2 n = 64 and a mismatch beyond 2.2 logits is where undamped Newton steps from 0 oscillate: before the
+    bracketed mode search of loo_poll_ll this "exact predictive density" of exactly the poll cross-validation exists to flag was off by orders.
+    Every draw of the pair against quadrature (psis_ref.log_lik_quad: brentq for the mode) on the row's own logit_pi column."""
+    data = dict(synthetic.small("full"))
+    k = 11
+    n2, nd = np.array(data["n_two_share_state"]), np.array(data["n_democrat_state"])
+    n2[k], nd[k] = 40_000, 38_800
+    data["n_two_share_state"], data["n_democrat_state"] = n2, nd
+    Ns, Nn = int(data["N_state_polls"]), int(data["N_national_polls"])
+    keep_s, keep_n = np.ones((2, Ns), bool), np.ones((2, Nn), bool)
+    keep_s[1, k] = False
+    design = timeline.design_of(data, keep_s, keep_n, np.tile(np.asarray(data["mu_b_prior"], float), (2, 1)), np.full(2, data["mu_b_T_scale"]))
+    h = Handle(design["data"], "full", chains=2 * CPD, num_warmup=NW, num_samples=NS, **OPTS)
+    timeline.set_design(h, design)
+    h.init()
+    h.run(NW + NS)
+    assert h.chain_status()[0] == [0] * (2 * CPD)
+    ll = h.cv_log_lik_device(~keep_s, ~keep_n, integrate=True).cpu().numpy()
+    assert ll.shape == (1, ND)
+    lay = h.layout
+    x = np.concatenate([h.write_array(lay[c][0] + k, lay[c][0] + k + 1, NS) for c in ("logit_pi_democrat_state", "raw_measure_noise_state")], axis=2)
+    x = x[:, CPD:].transpose(1, 0, 2).reshape(ND, 2)                    # the draws of data set 1, chain after chain
+    sig = float(data["sigma_measure_noise_state"])
+    eta = x[:, 0] - sig * x[:, 1]
+    mismatch = eta - np.log(38_800 / 1_200)
+    assert np.abs(mismatch).min() > 2.5, mismatch                       # every draw is in the regime in question
+    worst = max(abs(ll[0, i] - psis_ref.log_lik_quad(38_800, 40_000, eta[i], sig)) for i in range(ND))
+    print(f"held-out outlier poll: eta - logit(y / n) in [{mismatch.min():.2f}, {mismatch.max():.2f}]; largest |device - quad| over {ND} draws: {worst:.2e}")
+    assert worst < 1e-9
+    h.close()
+
+
 _CHILD = """
 import sys
 sys.path[:0] = [{root!r}, {tests!r}]

@@ -4937,6 +4937,59 @@ int potus_debug_build_tag(int handle) {
   return sp ? (sp->K > 1 ? sp->cl_dw : 0) : -1;
 }
 
+// The per-poll scalar arithmetic on caller data (tests/test_gpu_poll_terms.py): one thread per item calls loo_poll_ll, one thread per draw
+// calls binomial_logit_draw with key chain field item + 1 and the draw number as the counter index.  Nothing else runs in these kernels.
+namespace {
+__global__ __launch_bounds__(256) void k_poll_ll_probe(int n_items, const double *y, const double *n, const double *eta, const double *sigma, const double *z,
+                                                       int integrate, double *out) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i < n_items) out[i] = loo_poll_ll(y[i], n[i], eta[i], sigma[i], z[i], integrate);
+}
+__global__ __launch_bounds__(256) void k_binomial_draw_probe(unsigned seed_lo, unsigned seed_hi, int n_items, const int *n, const double *eta, int draws, int *out) {
+  const long long j = (long long)blockIdx.x * 256 + threadIdx.x;
+  if (j >= (long long)n_items * draws) return;
+  const int item = (int)(j / draws), d = (int)(j % draws);
+  const RngKey key{seed_lo, seed_hi, (uint32_t)(item + 1)};
+  out[j] = binomial_logit_draw(key, (uint32_t)d, n[item], eta[item]);
+}
+}
+
+int potus_poll_ll_probe(int device, int n_items, const double *y, const double *n, const double *eta, const double *sigma, const double *z, int integrate,
+                        double *out) {
+  if (n_items < 1 || !y || !n || !eta || !sigma || !z || !out) return fail(POTUS_ERR_ARG, "potus_poll_ll_probe: bad arguments");
+  HIP_TRY(hipSetDevice(device));
+  DevBufs bufs;
+  const size_t nb = (size_t)n_items * 8;
+  double *d[6];
+  const double *src[5] = {y, n, eta, sigma, z};
+  for (int k = 0; k < 6; k++) HIP_TRY(bufs.alloc(&d[k], nb));
+  for (int k = 0; k < 5; k++) HIP_TRY(hipMemcpy(d[k], src[k], nb, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_poll_ll_probe, dim3((n_items + 255) / 256), dim3(256), 0, 0, n_items, d[0], d[1], d[2], d[3], d[4], integrate, d[5]);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, d[5], nb, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int potus_binomial_draw_probe(int device, unsigned long long seed, int n_items, const int *n, const double *eta, int draws_per_item, int *out) {
+  if (n_items < 1 || draws_per_item < 1 || !n || !eta || !out || (long long)n_items * draws_per_item > (1LL << 28))
+    return fail(POTUS_ERR_ARG, "potus_binomial_draw_probe: bad arguments");
+  HIP_TRY(hipSetDevice(device));
+  DevBufs bufs;
+  const size_t total = (size_t)n_items * draws_per_item;
+  int *dn, *dout;
+  double *deta;
+  HIP_TRY(bufs.alloc(&dn, (size_t)n_items * 4)); HIP_TRY(bufs.alloc(&deta, (size_t)n_items * 8)); HIP_TRY(bufs.alloc(&dout, total * 4));
+  HIP_TRY(hipMemcpy(dn, n, (size_t)n_items * 4, hipMemcpyHostToDevice));
+  HIP_TRY(hipMemcpy(deta, eta, (size_t)n_items * 8, hipMemcpyHostToDevice));
+  hipLaunchKernelGGL(k_binomial_draw_probe, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, 0, (unsigned)(seed & 0xFFFFFFFFu), (unsigned)(seed >> 32), n_items,
+                     (const int *)dn, (const double *)deta, draws_per_item, dout);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipDeviceSynchronize());
+  HIP_TRY(hipMemcpy(out, dout, total * 4, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // Development entry points (not in include/potus_hmc.h) that run single pieces of the dense-metric path on caller data,
 // so that each can be checked against numpy and timed on its own (tests/test_gpu_dense.py, scripts/micro/dense_probe.py).
 namespace {

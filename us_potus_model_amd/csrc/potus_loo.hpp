@@ -3,10 +3,10 @@
 // Polls are numbered as the output row numbers them: state polls in data order, then national polls (logit_pi_democrat_state, then
 // logit_pi_democrat_national).  For poll i with outcome y of n and noise scale sigma_i (psig), eta_i is logit_pi_i without its noise term
 // raw_measure_noise_i * sigma_i (stan:102, stan:111), computed directly from the output row:
-//   plain       log C(n, y) + y x - n softplus(x),  x = eta_i + sigma_i z_i (the draw's own noise coordinate): binomial_logit_lpmf
+//   plain       log C(n, y) + y log inv_logit(x) + (n - y) log inv_logit(-x),  x = eta_i + sigma_i z_i (the draw's own noise coordinate): binomial_logit_lpmf
 //   integrated  log int Binomial(y | n, inv_logit(eta_i + sigma_i z)) phi(z) dz: the poll's own noise coordinate integrated out
-//               (Vehtari et al. 2016, JMLR 17, "integrated importance sampling"), by adaptive Gauss-Hermite quadrature: Newton steps
-//               from z = 0 to the mode of the strictly concave f(z) = y x - n softplus(x) - z^2 / 2, nodes scaled by sqrt(2 / -f''(mode)).
+//               (Vehtari et al. 2016, JMLR 17, "integrated importance sampling"), by adaptive Gauss-Hermite quadrature: bracketed Newton
+//               steps from z = 0 to the mode of the strictly concave f(z) = y x - n softplus(x) - z^2 / 2 (x = eta_i + sigma_i z), nodes scaled by sqrt(2 / -f''(mode)).
 // Kernels:
 //   1. k_loo_loglik: one 256-thread workgroup per saved draw rebuilds the output row (wa_build_row, as k_sbc_ranks does) and writes the
 //      log-likelihoods of a block of polls as one row [draw][chain][poll]; k_dg_transpose turns the block into [poll][chain][draw]
@@ -22,7 +22,7 @@
 #include "potus_diag.hpp"
 
 #define LOO_GH 16             // Gauss-Hermite nodes of the integrated form (the error against scipy.integrate.quad)
-#define LOO_NEWTON 8          // Newton steps to the mode
+#define LOO_MODE_CAP 100      // most trips of the safeguarded mode search (it stops when a step no longer moves the mode: 3 - 60 trips)
 #define LOO_NPW 5             // pointwise outputs: elpd_loo, p_loo, looic, pareto_k, r_eff
 
 // physicists' Gauss-Hermite nodes x_k and log(w_k) + x_k^2 (numpy.polynomial.hermite.hermgauss(16))
@@ -35,19 +35,32 @@ __constant__ double loo_gh_lw[LOO_GH] = {
     -0.5934069056473787, -0.6026207792767783, -0.6026207792767783, -0.5934069056473787, -0.5740888178776504, -0.5425790095739411,
     -0.4947276307888995, -0.4219670092986956, -0.3034786882399878, -0.0652059514099399};
 
-__device__ __forceinline__ double loo_softplus(double x) { return fmax(x, 0.0) + log1p(exp(-fabs(x))); }
+// y log inv_logit(x) + (n - y) log inv_logit(-x), each factor formed without cancellation (the model passes' form).  y x - n softplus(x) is the
+// same number but subtracts two products of size n |x| when x > 0: with y = n at x = 745 the result, 0, came out as 4.5e-9.
+__device__ __forceinline__ double loo_binom_term(double y, double n, double x) {
+  return y * fmin(x, 0.0) - (n - y) * fmax(x, 0.0) - n * log1p(exp(-fabs(x)));
+}
 __device__ __forceinline__ double loo_inv_logit(double x) { return 1.0 / (1.0 + exp(-x)); }
 
 // log p(y | n, eta, sigma) without log C(n, y): plain at the draw's noise coordinate z, or z integrated out (sigma = 0: plain at z = 0)
 __device__ double loo_poll_ll(double y, double n, double eta, double sig, double z, int integrate) {
   if (!integrate || sig == 0.0) {
     const double x = integrate ? eta : eta + sig * z;
-    return y * x - n * loo_softplus(x);
+    return loo_binom_term(y, n, x);
   }
-  double m = 0.0;
-  for (int it = 0; it < LOO_NEWTON; it++) {
+  // the mode: f'(m) = sig (y - n p(eta + sig m)) - m is strictly decreasing with its root in [sig (y - n), sig y].  Newton steps from 0
+  // inside that bracket, which every f' narrows by its sign; a step that does not land strictly inside is replaced by the midpoint
+  // (undamped steps oscillate once the poll is ~2.2 logits from eta and sig^2 n is not small: DESIGN.md 4e).
+  double m = 0.0, lo = sig * (y - n), hi = sig * y;
+  for (int it = 0; it < LOO_MODE_CAP; it++) {
     const double p = loo_inv_logit(eta + sig * m);
-    m -= (sig * (y - n * p) - m) / (-sig * sig * n * p * (1.0 - p) - 1.0);
+    const double g = sig * (y - n * p) - m;
+    if (g > 0.0) lo = m; else if (g < 0.0) hi = m; else break;
+    double mn = m - g / (-sig * sig * n * p * (1.0 - p) - 1.0);
+    if (mn == m) break;
+    if (!(mn > lo && mn < hi)) mn = 0.5 * (lo + hi);
+    if (mn == m) break;
+    m = mn;
   }
   const double p = loo_inv_logit(eta + sig * m);
   const double s = sqrt(2.0 / (sig * sig * n * p * (1.0 - p) + 1.0));
@@ -55,7 +68,7 @@ __device__ double loo_poll_ll(double y, double n, double eta, double sig, double
 #pragma unroll
   for (int k = 0; k < LOO_GH; k++) {
     const double zk = m + s * loo_gh_x[k], x = eta + sig * zk;
-    f[k] = y * x - n * loo_softplus(x) - 0.5 * zk * zk + loo_gh_lw[k];
+    f[k] = loo_binom_term(y, n, x) - 0.5 * zk * zk + loo_gh_lw[k];
     fm = fmax(fm, f[k]);
   }
   double a = 0.0;
