@@ -38,6 +38,10 @@
 #define CL_DW4_MAXAVG 26                 // days per member on average up to which the 4-days-per-wave build of the pass is used
 #define CL_AUX_SC1 16                    // cache-policy bit of the buffer intrinsics: sc1 (agent scope)
 #define CL_NCHUNK PT_NW                  // chunks the member's polls are cut into for the adjoint gather (host: build_cluster)
+#define CL_WALK_FX0 16                   // the fixed builds unroll their chunk (at most 32 polls) at constant lanes: a group of this many polls, always,
+#define CL_WALK_FX1 8                    // then groups of this many where the chunk has them
+#define CL_WALK_GROUP 16                 // polls per group of the adjoint gather's walk in the dynamic builds (the fixed builds unroll their chunk: 16 + 8 + 8)
+#define CL_L1_LANE 32                    // lane of ClStatic::s2info (every wave) that holds the member's level-1 task counts; + 1, + 2: the wave's chunk bounds
 #define CL_SEG_SHIFT 64                  // the level-2 segment sums of phase E start at this thread: wave 0 turns the chunk totals into prefixes there
 #define CL_SPIN_LIMIT 8000000u
 #ifndef CL_SPIN_SLEEP
@@ -79,17 +83,20 @@ struct ClLay {
   int total;
 };
 constexpr int cl_ev(int n) { return (n + 1) & ~1; }   // LDS blocks start on 16-byte boundaries
+constexpr int cl_subpad(int nsub) { return nsub > PT_THREADS ? (nsub + PT_THREADS - 1) / PT_THREADS * PT_THREADS : PT_THREADS; }   // level-1 task lists in LDS: whole trips of the workgroup, at least one (phase D)
+constexpr int cl_ndp(int ndmax) { return (ndmax + 1) | 1; }   // row stride of C[state][local day]: odd, and one column more than any member has days -- the walk's dump column
 constexpr ClLay cl_layout(int S, int SE, int SP, int NDP, int npcap, int nsubcap, int nrepcap, int nrcap, int tcap, int g_doubles, int necap = 0) {
   ClLay L{};
   int o = 0;
-  L.l_C = o; o += cl_ev(S * NDP);                         // C[state][local day]: suffix sums, then the adjoint's running sums
+  L.l_C = o; o += cl_ev(S * NDP + NDP + 64);              // C[state][local day]: suffix sums, then the adjoint's running sums; column NDP - 1 is a dump (cl_ndp), and so
+                                                          // is the block behind the rows: lane S + j of the walk stores at S * NDP + j + column
   L.l_G = g_doubles ? o : 0; o += cl_ev(g_doubles);       // G[pseudo-state][local day] (matrix-core build only)
   L.l_Lw = o; o += cl_ev((SE + 1) * SP);                  // the walk's factor, the row v = L_W' w and a zero row
   L.l_prior = o; o += cl_ev(SE);
   L.l_pm = o; o += cl_ev(npcap + 8);                      // per-poll constants: {state, day, pollster, mode, population}
   L.l_py = o; o += cl_ev(npcap + 8);                      // {y, N} as two int32
   L.l_pun = o; o += cl_ev(npcap + 8);
-  L.l_sub = o; o += cl_ev(nsubcap * 4 + 4);               // level-1 task lists, 16-bit entries
+  L.l_sub = o; o += cl_ev(cl_subpad(nsubcap) * 4 + 4);    // level-1 task lists, 16-bit entries, padded to whole trips (cl_setup_lds)
   L.l_tab = o; o += cl_ev((npcap + 64) / 2 + 2);          // gather program words
   L.l_ru = o; o += cl_ev(npcap + 2);
   L.l_wide = o; o += cl_ev(CL_WIDE * PT_NW);
@@ -136,6 +143,7 @@ struct ClFixed {
   CLF(l_r); CLF(l_rep); CLF(l_bT); CLF(l_e); CLF(l_c1); CLF(l_c2); CLF(l_c3); CLF(l_ge); CLF(l_P); CLF(l_scal); CLF(l_red); CLF(l_st); CLF(l_prof); CLF(l_rm); CLF(l_rpf); CLF(l_rrs);
 #undef CLF
   static constexpr int lds_doubles = L.total;
+  static_assert(NDP == cl_ndp(32) && NPCAP <= 32 * CL_NCHUNK && NSUBCAP <= PT_THREADS, "phase D of the fixed builds: 32 days and a dump column, chunks of at most 32 polls, one trip of level-1 tasks");
 };
 template <int TAG> struct ClTag {
   static constexpr int DW = (TAG == 12 || TAG == 16 || TAG == 17) ? 4 : TAG;   // days per wave
@@ -144,6 +152,7 @@ template <int TAG> struct ClTag {
   static constexpr int FULL = TAG == 16 ? 1 : 0;                      // ... and the model variant: 16 = poll_model_2020.stan, 17 = poll_model_2020_no_mode_adjustment.stan
 };
 typedef const int AS_C *cip;
+template <int N> struct ClInt { static constexpr int value = N; };   // a compile-time count handed to a lambda
 
 __device__ __forceinline__ double bld_s(rsrc_t r, unsigned voff, unsigned soff) {
   return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(r, voff, soff, CL_AUX_SC1));
@@ -640,9 +649,10 @@ struct ClLeapPolicyRes {
 
 struct ClStatic {           // per-thread registers that never change during a kernel
   int s2info;               // lane j < CL_DW of wave w, for the wave's j-th day: (last polled local day <= it) + 1 (0 = none)
-                            //   | chunk holding that day's last poll << 8
+                            //   | chunk holding that day's last poll << 8; lane CL_L1_LANE: level-1 tasks | first task of the day sums << 16 (CP_NSUB, CP_WB),
+                            //   the two lanes behind it: the wave's chunk [ca, cb) of the member's polls (day order) in the adjoint gather -- wave-uniform
+                            //   statics of phase D live in lanes of this register instead of a register each
   int wd0, wnd;             // the wave's days: local days [wd0, wd0 + wnd), wnd <= CL_DW
-  int ca, cb;               // the wave's chunk of the member's polls (day order) in the adjoint gather
   unsigned rep_vo[2];       // byte offsets of the small parameters this thread fetches for the workgroup
   unsigned rep_xo[2];       // the same parameters as exchange words of their owners (member * XW + XQ0 + index) * 16
   int sg_a, sg_b, sg_kind, sg_index;   // level-2 segment summed by this thread: task range, what the sum feeds
@@ -656,7 +666,6 @@ __device__ __forceinline__ ClStatic cl_load_static(CCp CL, cip part) {
   const int tid = threadIdx.x;
   c.s2info = sc[tid];
   c.wd0 = sc[PT_THREADS + (tid >> 6)]; c.wnd = sc[PT_THREADS + PT_NW + (tid >> 6)];
-  c.ca = sc[PT_THREADS + 2 * PT_NW + (tid >> 6)]; c.cb = sc[PT_THREADS + 3 * PT_NW + (tid >> 6)];
   gcip rp = as_g(CL->rep_pos);
   const int NREP = CL->NREP;
   gcip ro = as_g(CL->rep_owner);
@@ -673,11 +682,15 @@ __device__ __forceinline__ ClStatic cl_load_static(CCp CL, cip part) {
     // waves first (waves 0-3 run the MFMA chains)
     // (walk build: wave 0 turns the chunk totals into prefixes in that interval, so it gets segments last)
     const int sg = CL->l_G ? ((tid + PT_THREADS / 2) & (PT_THREADS - 1)) : ((tid + PT_THREADS - CL_SEG_SHIFT) & (PT_THREADS - 1));
+    // (every thread loads, idle ones entry 0 -- the lists are followed by padding --, and selects: a load under `if (ok)` is a region of narrowed
+    //  EXEC in which the allocator may place the spill of one of these long-lived values, scripts/check_spill_exec.py)
     const bool ok = sg < nseg;
-    c.sg_a = ok ? sch[part[CP_O_SEGPTR] + sg] : 0;
-    c.sg_b = ok ? sch[part[CP_O_SEGPTR] + sg + 1] : 0;
-    c.sg_kind = ok ? sch[part[CP_O_SEGKIND] + sg] : 3;
-    c.sg_index = ok ? sch[part[CP_O_SEGIDX] + sg] : 0;
+    const int sgl = ok ? sg : 0;
+    const int sa_ = sch[part[CP_O_SEGPTR] + sgl], sb_ = sch[part[CP_O_SEGPTR] + sgl + 1], sk_ = sch[part[CP_O_SEGKIND] + sgl], si_ = sch[part[CP_O_SEGIDX] + sgl];
+    c.sg_a = ok ? sa_ : 0;
+    c.sg_b = ok ? sb_ : 0;
+    c.sg_kind = ok ? sk_ : 3;
+    c.sg_index = ok ? si_ : 0;
 #pragma unroll
     for (int h = 0; h < CL_CELLS_PER_THREAD; h++) c.cellw[h] = CL->l_G ? sch[part[CP_O_CELL] + h * PT_THREADS + tid] : 0;
     const int jr = tid - 128;
@@ -731,15 +744,24 @@ __device__ __forceinline__ ClStatic cl_setup_lds(CMp M, CCp CL, cip part, ldp ld
       }
       pm[i] = v; pyn[i] = (unsigned long long)(unsigned)(int)y | ((unsigned long long)(unsigned)(int)N << 32); pun[i] = un;
     }
-    // gather program: per poll (day order) state | local day << 8 | flags << 16
+    // gather program: the host's word per poll (day order) is state | local day << 8 | last poll of its day << 16.  What the walk of phase D
+    // needs of it are two LDS byte offsets, and both depend on the layout (row stride of the factor, NDP of the launch), so the word is
+    // translated here, once per kernel: bits 0-15 the poll's row of the factor (state * SP * 8 <= 63 * 63 * 8), bits 16-31 the column of C that
+    // takes the running sum behind this poll -- its day if it is the last poll of that day, else the dump column NDP - 1 (cl_ndp: no day).
+    // The padding slots (np ..) are row 0 and the dump column; their residual is 0.
     unsigned AS_L *tab = (unsigned AS_L *)(lds + CL->l_tab);
     gcip src_tab = as_g(CL->sched) + part[CP_O_MASK];
-    for (int i = threadIdx.x; i < np + 64; i += PT_THREADS) tab[i] = i < np ? (unsigned)src_tab[i] : 0u;
-    // level-1 task lists (16 local poll indices each) as 16-bit entries
+    const unsigned tab_dump = (unsigned)(CL->NDP - 1) * 8u << 16;
+    for (int i = threadIdx.x; i < np + 64; i += PT_THREADS) {
+      const unsigned hw = i < np ? (unsigned)src_tab[i] : 0u;
+      tab[i] = (hw & 0xffu) * (unsigned)M->SP * 8u | ((hw & 0x10000u) ? ((hw >> 8) & 0xffu) * 8u << 16 : tab_dump);
+    }
+    // level-1 task lists (16 local poll indices each) as 16-bit entries, padded to whole trips of the workgroup with lists of the zero slot np:
+    // phase D then reads them without a guard
     unsigned short AS_L *sb = (unsigned short AS_L *)(lds + CL->l_sub);
     gcip src_sub = as_g(CL->sched) + part[CP_O_SUB];
-    const int n16 = part[CP_NSUB] * PT_SUBLEN;
-    for (int i = threadIdx.x; i < n16; i += PT_THREADS) sb[i] = (unsigned short)src_sub[i];
+    const int n16 = part[CP_NSUB] * PT_SUBLEN, n16pad = cl_subpad(part[CP_NSUB]) * PT_SUBLEN;
+    for (int i = threadIdx.x; i < n16pad; i += PT_THREADS) sb[i] = (unsigned short)(i < n16 ? src_sub[i] : np);
   }
   // G: zero once; the scatter of every pass rewrites the same cells (the poll structure is static), everything else stays zero
   if (CL->l_G) for (int i = threadIdx.x; i < CL->GROWS * CL->GS + CL_G_PAD; i += PT_THREADS) (lds + CL->l_G)[i] = 0.0;
@@ -1112,38 +1134,65 @@ __device__ __forceinline__ double cl_pass_partial(CMp M_in, CCp CL_in, cip part_
 
   // ---------------- phase D: adjoint of the walk, gC[:,t] = sum_i r_i Lw_ext[s_i,:] summed over days <= t.
   // The member's polls (day order) are cut into PT_NW equal chunks, one per wave, whatever the days: a wave
-  // fetches (program word, residual, unadjusted flag) of 64 polls with one LDS round, then walks them through
-  // readlane; lanes < S keep the running sum over the chunk, lane 63 the day's sum of unadjusted * residual
-  // (the adjoint input of e_bias[t]).  At the last poll of a day the running values go to LDS; the owners
-  // of the days pick them up in phase E.  Level-1 segment sums follow.
+  // fetches (program word, residual) of 64 polls with one LDS round, then walks them through readlane; lanes < S
+  // keep the running sum over the chunk.  Behind EVERY poll the running sum goes to LDS: to the poll's day if it is
+  // the last poll of that day, else to a dump column -- the program word carries the column's byte offset, so the
+  // day end costs no test and no EXEC change (a day may straddle two chunks: only its last poll may write its cell).
+  // The owners of the days pick the sums up in phase E.  Level-1 segment sums follow.
+  // The walk is bound by instruction issue, not by LDS latency (two waves per SIMD, all eight walking): what counts
+  // is instructions per poll.  A poll is 3 v_readlane (word, residual), s_and + v_add + ds_read (factor row: byte
+  // offset in the word), v_fmac, s_lshr + v_add + ds_write -- 10.5 with its share of the waits, against 18.8 when
+  // the word held state | day | flag and the store sat under its own EXEC mask.  On the MI355X phase D went from
+  // 4.8 k to 3.4 k cycles per leaf on the members with 125-148 polls (profiles/r08_cl_gather_walk.txt).
+  // Nothing here loads from global memory: the counts of the level-1 tasks and the chunk bounds are lanes of
+  // ClStatic::s2info.
   if constexpr (!MF) {
     const unsigned AS_L *tab = (const unsigned AS_L *)(lds + LAY(l_tab));
-    const int lk = lane < S ? lane : 0;
-    const int ca = __builtin_amdgcn_readfirstlane(cst.ca), cb = __builtin_amdgcn_readfirstlane(cst.cb);
+    const int ca = __builtin_amdgcn_readlane(cst.s2info, CL_L1_LANE + 1), cb = __builtin_amdgcn_readlane(cst.s2info, CL_L1_LANE + 2);
+    // this lane's column of the factor and its row of C; the program word adds byte offsets to both.  Lanes S .. 63 have no state: they run along
+    // at full EXEC (the walk reads (ev, rv) of EVERY lane through readlane, so nothing of it may sit under a narrowed mask), read column 0 and
+    // store into the block behind C's rows, one double apart
+    const char AS_L *Lw_me = (const char AS_L *)(Lw + (lane < S ? lane : 0));
+    char AS_L *C_me = (char AS_L *)(C + (lane < S ? lane * NDP : S * NDP + (lane - S)));
     double acc = 0.0;
-    for (int base = ca; base < cb; base += 64) {
-      const int mine = base + lane < cb ? base + lane : np;   // slot np: program word 0, residual 0
+    // G polls from lane p0 of (ev, rv): the loads of the whole group, then the multiply-adds in poll order, each followed by the store of the
+    // running sum -- to the poll's day if it is the last poll of that day, else to the dump column (the word says which: no test, no EXEC change)
+    auto walk = [&](unsigned ev, double rv, int p0, auto gw) {
+      constexpr int G = decltype(gw)::value;
+      unsigned e[G];
+      double r[G], l[G];
+#pragma unroll
+      for (int u = 0; u < G; u++) {
+        const int pu = p0 + u;                      // < 64; lanes beyond the chunk hold the zero slot
+        e[u] = (unsigned)__builtin_amdgcn_readlane((int)ev, pu);
+        r[u] = readlane_d(rv, pu);
+        l[u] = *(const double AS_L *)(Lw_me + (e[u] & 0xffffu));   // (the polls of day T too: their running sum feeds mu_b_T and the polling bias only, phase E2)
+      }
+      ISSUE_FENCE();
+#pragma unroll
+      for (int u = 0; u < G; u++) {
+        acc += r[u] * l[u];
+        *(double AS_L *)(C_me + (e[u] >> 16)) = acc;
+      }
+    };
+    if constexpr (FX) {
+      // at most 32 polls per chunk (ClFixed::NPCAP): one LDS round, and every group at constant lanes -- sixteen polls, then eight and eight
+      // more where the chunk has them (a heavy member of the reference's posteriors has 16 to 19 polls per chunk)
+      const int cnt = cb - ca;
+      const int mine = lane < cnt ? ca + lane : np;           // slot np: row 0 into the dump column, residual 0
       const unsigned ev = tab[mine];
       const double rv = r_lds[mine];
-      const int cnt = min(64, cb - base);
-      for (int p0 = 0; p0 < cnt; p0 += 8) {
-        unsigned e8[8];
-        double r8[8], l8[8];
+      walk(ev, rv, 0, ClInt<CL_WALK_FX0>());
 #pragma unroll
-        for (int u = 0; u < 8; u++) {
-          const int pu = p0 + u;                    // < 64; lanes beyond the chunk hold the zero slot
-          e8[u] = (unsigned)__builtin_amdgcn_readlane((int)ev, pu);
-          r8[u] = readlane_d(rv, pu);
-          l8[u] = Lw[(int)(e8[u] & 0xffu) * SP + lk];   // (the polls of day T too: their running sum feeds mu_b_T and the polling bias only, phase E2)
-        }
-        ISSUE_FENCE();
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-          acc += r8[u] * l8[u];
-          if (e8[u] & 0x10000u) {                   // last poll of its day (wave-uniform): running sum to LDS
-            if (lane < S) C[lane * NDP + (int)((e8[u] >> 8) & 0xffu)] = acc;
-          }
-        }
+      for (int p0 = CL_WALK_FX0; p0 < 32; p0 += CL_WALK_FX1)
+        if (cnt > p0) walk(ev, rv, p0, ClInt<CL_WALK_FX1>());
+    } else {
+      for (int base = ca; base < cb; base += 64) {
+        const int mine = base + lane < cb ? base + lane : np;
+        const unsigned ev = tab[mine];
+        const double rv = r_lds[mine];
+        const int cnt = min(64, cb - base);
+        for (int p0 = 0; p0 < cnt; p0 += CL_WALK_GROUP) walk(ev, rv, p0, ClInt<CL_WALK_GROUP>());
       }
     }
     if (lane < S) X[w * SE + lane] = acc;          // chunk total
@@ -1164,24 +1213,26 @@ __device__ __forceinline__ double cl_pass_partial(CMp M_in, CCp CL_in, cip part_
     }
   }
   {
-    const int nsub = part[CP_NSUB], wb = part[CP_WB];   // tasks from wb on sum unadjusted * residual (day sums)
+    // the number of tasks and the first task that sums unadjusted * residual (day sums) are static: they come with the thread's statics
+    // (ClStatic::s2info, lane CL_L1_LANE), not from memory.  The lists in LDS are padded to whole trips with the zero slot (cl_setup_lds): only
+    // the store is guarded.
+    const int l1 = __builtin_amdgcn_readlane(cst.s2info, CL_L1_LANE), nsub = l1 & 0xffff, wb = (int)((unsigned)l1 >> 16);
     const u32x4 AS_L *sb = (const u32x4 AS_L *)(lds + LAY(l_sub));
-    for (int sub0 = 0; sub0 < nsub; sub0 += PT_THREADS) {
+    for (int sub0 = 0; sub0 < (FX ? 1 : nsub); sub0 += PT_THREADS) {   // (fixed builds: one trip, ClFixed::NSUBCAP)
       const int sub = sub0 + tid;
-      const bool ok = sub < nsub;
-      const u32x4 ia = sb[ok ? 2 * sub : 0], ib = sb[ok ? 2 * sub + 1 : 0];
+      const u32x4 ia = sb[2 * sub], ib = sb[2 * sub + 1];
       double rr[PT_SUBLEN];
       ldp rsrc_ = sub >= wb ? ru_lds : r_lds;
 #pragma unroll
       for (int j = 0; j < 4; j++) {
-        rr[2 * j] = rsrc_[ok ? (int)(ia[j] & 0xffffu) : np]; rr[2 * j + 1] = rsrc_[ok ? (int)(ia[j] >> 16) : np];
-        rr[8 + 2 * j] = rsrc_[ok ? (int)(ib[j] & 0xffffu) : np]; rr[9 + 2 * j] = rsrc_[ok ? (int)(ib[j] >> 16) : np];
+        rr[2 * j] = rsrc_[(int)(ia[j] & 0xffffu)]; rr[2 * j + 1] = rsrc_[(int)(ia[j] >> 16)];
+        rr[8 + 2 * j] = rsrc_[(int)(ib[j] & 0xffffu)]; rr[9 + 2 * j] = rsrc_[(int)(ib[j] >> 16)];
       }
       ISSUE_FENCE();
       double sum = 0.0;
 #pragma unroll
       for (int j = 0; j < PT_SUBLEN; j++) sum += rr[j];
-      if (ok) Y[sub] = sum;
+      if (sub < nsub) Y[sub] = sum;
     }
   }
   WAVE_ARRIVE(4);

@@ -1609,6 +1609,13 @@ int build_cluster(Sampler *sp, const potus_data *d, int K) {
     seg_ptr.push_back(nsub);
     if ((int)seg_kind.size() > PT_THREADS) return fail(POTUS_ERR_UNSUPPORTED, "cluster mode: member %d has %zu segments (> %d)", m, seg_kind.size(), PT_THREADS);
     pt_[CP_NSUB] = nsub; pt_[CP_NSEG] = (int)seg_kind.size(); pt_[CP_WB] = wb;
+    // phase D takes the two counts and the wave's chunk bounds from spare lanes of the per-thread statics (lanes 0 .. CL_DW - 1 describe the wave's days)
+    static_assert(CL_L1_LANE >= 8 && CL_L1_LANE + 2 < 64, "lanes 0-7 of s2info are the wave's days");
+    if (nsub > 0xffff) return fail(POTUS_ERR_UNSUPPORTED, "cluster mode: member %d has %d level-1 tasks (> 65535)", m, nsub);
+    for (int wv = 0; wv < PT_NW; wv++) {
+      int *sl = &s2info[wv * 64 + CL_L1_LANE];
+      sl[0] = nsub | (wb << 16); sl[1] = ca[wv]; sl[2] = cb[wv];
+    }
     nsubmax = std::max(nsubmax, nsub);
     auto appi = [&](const std::vector<int> &v) {
       while (sched.size() % 4) sched.push_back(0);
@@ -1650,7 +1657,8 @@ int build_cluster(Sampler *sp, const potus_data *d, int K) {
 
   int ndmax = 1, nemax = 0;
   for (int m = 0; m < K; m++) { ndmax = std::max(ndmax, part[(size_t)m * CP_N + CP_ND]); nemax = std::max(nemax, part[(size_t)m * CP_N + CP_NE]); }
-  C.NDP = ndmax | 1;   // odd row stride of the member's C[state][local day] block
+  C.NDP = cl_ndp(ndmax);   // odd row stride of the member's C[state][local day] block, with a spare column behind the days (the dump column of the walk)
+  if (M.SE * M.SP * 8 > 0x10000 || C.NDP * 8 > 0x10000) return fail(POTUS_ERR_UNSUPPORTED, "cluster mode: the gather program holds byte offsets in 16 bits");
   C.GS = GS; C.GROWS = GROWS;
   ClLay lay = cl_layout(S, M.SE, M.SP, C.NDP, npmax, nsubmax, C.NREP, C.NR, T, mfma ? GROWS * GS + CL_G_PAD : 0);
   // The builds with the layout fixed at compile time (tags 16 and 17 = full model / no_mode_adjustment variant, ClFixed): 51 states, members of
