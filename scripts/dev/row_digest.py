@@ -14,7 +14,7 @@ import numpy as np
 
 ROOT = Path(__file__).resolve().parent.parent.parent
 sys.path.insert(0, str(ROOT))
-from us_potus_model_amd import Handle, synthetic  # noqa: E402
+from us_potus_model_amd import Handle, _abi, synthetic  # noqa: E402
 
 import torch  # noqa: E402
 torch.cuda.init()          # torch's GPU runtime comes up before the library's first call, as in bench.py and the tests
@@ -45,6 +45,7 @@ def log_lik(h, p0, p1, integrate):
     return h.log_lik_device(p0, p1, t, integrate=integrate).cpu().numpy()
 
 
+outcomes = {}
 for variant in ("full", "no_mode_adjustment"):
     data = synthetic.small(variant)
     Ns, Nn, S = int(data["N_state_polls"]), int(data["N_national_polls"]), int(data["S"])
@@ -57,6 +58,7 @@ for variant in ("full", "no_mode_adjustment"):
     show(f"{variant} write_array [{a},{b})", h.write_array(a, b, NS))
     show(f"{variant} constrain", h.constrain(h.draws()[1, 5:12, 7:]))
     q_sim, ys, yn = h.simulate_prior(SEED, 3, sim_offset=5)
+    outcomes[variant] = (ys, yn)
     show(f"{variant} simulate_prior q", q_sim)
     show(f"{variant} simulate_prior y_state", ys)
     show(f"{variant} simulate_prior y_national", yn)
@@ -91,3 +93,19 @@ for variant in ("full", "no_mode_adjustment"):
         show(f"{variant} cv_log_lik integrate={int(integrate)}", e.cv_log_lik_device(held_s, held_n, integrate=integrate).cpu().numpy())
     show(f"{variant} optimize rows, set_datasets_ex", e.optimize(paths=4, cols=(a, b), iter=40)["rows"])
     e.close()
+
+# ---- every sampler: draws and adaptation of a short warm-up that holds one window end (30 warm-up iterations: buffers 4 | 23 | 3)
+data = synthetic.small("full")
+SAMPLERS = [("one workgroup", dict(cus_per_chain=1, twin=0)), ("two workgroups", dict(cus_per_chain=1, twin=1)),
+            ("cluster of 4", dict(cus_per_chain=4, twin=0)), ("two clusters of 4", dict(cus_per_chain=4, twin=1)),
+            ("dense_e", dict(metric=_abi.METRICS["dense_e"], cus_per_chain=1)), ("set_datasets 2 x 1", dict(cus_per_chain=1, twin=0))]
+for name, kw in SAMPLERS:
+    h = Handle(data, "full", chains=2, num_warmup=30, num_samples=10, save_warmup=1, seed=SEED, **kw)
+    if name.startswith("set_datasets"):
+        h.set_datasets(outcomes["full"][0][:2], outcomes["full"][1][:2])
+    h.init()
+    h.run(40)
+    assert h.chain_status()[0] == [0, 0], (name, h.chain_status())
+    show(f"sampler {name} draws", h.draws())
+    show(f"sampler {name} adaptation", *h.adaptation())
+    h.close()

@@ -2150,22 +2150,7 @@ __device__ __forceinline__ void cl_init_stepsize(ClChain &c, uint32_t iter) {
     ClLeapPolicy lp{c.st, c.soff(V_QA1), c.soff(V_QB1), c.soff(V_PH1), c.soff(V_MINV), c.soff(V_SCR0), 0.5 * eps, eps, 0u, 0u, false, {0.0, 0.0, 0.0}};
     const double lpv = cl_pass<CL_DW>(c.M, c.CL, c.part, c.lds, c.cst, c.x, lp);
     __syncthreads();
-    if (tid == 0) {
-      double h = 0.5 * lp.extra[0] - lpv;
-      if (isnan(h)) h = INFINITY;
-      const double delta_H = H0 - h, thr = log(0.8);
-      if (attempt == 0) ts->direction = delta_H > thr ? 1 : -1;
-      else {
-        const int dirn = ts->direction;
-        if (dirn == 1 && !(delta_H > thr)) ts->done = 1;
-        else if (dirn == -1 && !(delta_H < thr)) ts->done = 1;
-        else {
-          const double ne = dirn == 1 ? 2.0 * eps : 0.5 * eps;
-          c.sc->nom_eps = ne;
-          if (ne > 1e7 || ne == 0) { ts->done = 1; c.sc->status = POTUS_ERR_STEPSIZE; } // upstream throws here
-        }
-      }
-    }
+    if (tid == 0) rule_init_stepsize_verdict(ts, c.sc, attempt == 0, H0, lp.extra[0], lpv, eps);
     __syncthreads();
     if (uni_i(ts->done) || uni_i(cl_dead)) break;
   }
@@ -2179,6 +2164,10 @@ __device__ __forceinline__ void cl_adapt_after_transition(ClChain &c, uint32_t i
   gsc sc = c.sc;
   const int tid = c.tid;
   if (tid == 0) {
+    // rule_learn_stepsize and rule_window_flags (potus_rules.hpp) in this file's own words, to be kept in step with them: this
+    // function is inlined into cl_cold_transition_end / cl_cold_twin_end, and what those clobber is what k_cl_run's registers are
+    // allocated around -- k_cl_run is kept the instructions it was.  (s_bar: the compiler fuses the first product, x_bar the second,
+    // as the rule writes them out.)  The replay tests hold both copies to the same oracle.
     const double cnt = sc->ad_counter + 1;       // stepsize_adaptation::learn_stepsize
     sc->ad_counter = cnt;
     const double as = ts->accept_stat > 1 ? 1.0 : ts->accept_stat;
@@ -2189,7 +2178,8 @@ __device__ __forceinline__ void cl_adapt_after_transition(ClChain &c, uint32_t i
     const double x_eta = pow(cnt, -c.kappa);
     sc->x_bar = (1.0 - x_eta) * sc->x_bar + x_eta * xx;
     sc->nom_eps = exp(xx);
-    const int nw = c.num_warmup, ib = c.init_buffer, tb = c.term_buffer, wc = sc->win_counter;   // var_adaptation::learn_variance
+    // var_adaptation::learn_variance
+    const int nw = c.num_warmup, ib = c.init_buffer, tb = c.term_buffer, wc = sc->win_counter;
     int fa = 0, fb = 0;
     if (nw >= 20) {
       fa = wc >= ib && wc < nw - tb && wc != nw;
@@ -2220,16 +2210,8 @@ __device__ __forceinline__ void cl_adapt_after_transition(ClChain &c, uint32_t i
   __syncthreads();
   if (tid == 0 && c.num_warmup >= 20) {
     if (end_window) { // windowed_adaptation::compute_next_window
-      const int last = c.num_warmup - c.term_buffer - 1;
       int wn = sc->win_next, wsz = sc->win_size;
-      if (wn != last) {
-        wsz *= 2;
-        wn = sc->win_counter + wsz;
-        if (wn != last) {
-          const int boundary = wn + 2 * wsz;
-          if (boundary >= c.num_warmup - c.term_buffer) wn = last;
-        }
-      }
+      rule_next_window(c.num_warmup, c.term_buffer, sc->win_counter, wn, wsz);
       sc->win_next = wn; sc->win_size = wsz;
       sc->wf_n = 0;
     }
@@ -2242,9 +2224,9 @@ __device__ __forceinline__ void cl_adapt_after_transition(ClChain &c, uint32_t i
     if (tid == 0) sc->lp_cur = lpq;
     __syncthreads();
     cl_init_stepsize<CL_DW>(c, iter);
-    if (tid == 0) { sc->mu = log(10.0 * sc->nom_eps); sc->s_bar = 0; sc->x_bar = 0; sc->ad_counter = 0; }
+    if (tid == 0) rule_restart_stepsize(sc);
     __syncthreads();
   }
-  if (tid == 0 && (int)iter == c.num_warmup - 1) sc->nom_eps = exp(sc->x_bar); // complete_adaptation
+  if (tid == 0 && (int)iter == c.num_warmup - 1) rule_complete_adaptation(sc);
   __syncthreads();
 }

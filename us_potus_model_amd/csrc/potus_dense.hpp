@@ -538,19 +538,14 @@ __global__ __launch_bounds__(DN_THREADS) void k_dn_step(const DnParams P, const 
     const int n = ts.m;                        // leaf number inside the doubling (kept in ts.m between launches)
     const int depth = ts.depth, dir = ts.dir, leaf = ts.leaf_id;
     if (tid == 0) {
-      const double kin = kin_pass, lpv = P.lpbuf[chain], H0 = ts.H0;
-      double h = 0.5 * kin - lpv;
-      if (isnan(h)) h = INFINITY;
-      const int div = (h - H0 > 1000.0) ? 1 : ts.divergent;
-      ts.divergent = div;
-      const double wgt = H0 - h;
-      ts.sum_metro += wgt > 0 ? 1.0 : exp(wgt);
-      ts.n_leap += 1;
+      const double lpv = P.lpbuf[chain];
+      double h;
+      const double wgt = rule_leaf(&ts, kin_pass, lpv, h);
       const int inq = ts.nextq[dir];
       ts.cur_beg = ts.cur_end = leaf; ts.cur_lsw = wgt; ts.cur_prop = inq;
       ts.q_lp[inq] = lpv; ts.q_h[inq] = h;
       ts.nextq[dir] = ts.out_q;               // the next leaf of this end evaluates the position just written
-      ts.abort = div;
+      ts.abort = ts.divergent;
     }
     __syncthreads();
     const int m = __builtin_ctz(~(unsigned)n);
@@ -561,25 +556,10 @@ __global__ __launch_bounds__(DN_THREADS) void k_dn_step(const DnParams P, const 
                       DV_POOLP + cb, DV_POOLPS + cb, DV_POOLP + ce, DV_POOLPS + ce, j == 1 ? DV_POOLP + cb : DV_SCR0 + ((j - 1) & 1),
                       j == m ? DV_RHOLEV + j : DV_SCR0 + (j & 1)};
       const bool persist = dn_merge(P, chain, s, red);
-      if (tid == 0) {
-        const double cur_lsw = ts.cur_lsw;
-        const double lsw_sub = d_lse(ts.pend_lsw[j - 1], cur_lsw);
-        bool take_final;
-        if (cur_lsw > lsw_sub) take_final = true;
-        else {
-          const uint32_t slot = ((uint32_t)depth << 24) | ((uint32_t)j << 16) | (uint32_t)(n >> j);
-          take_final = rng_uniform(key, iter, RNG_SUB_ACCEPT, 0, slot) < exp(cur_lsw - lsw_sub);
-        }
-        unsigned qm = ts.qmask, pm = ts.pmask;
-        if (take_final) pool_free(qm, ts.pend_prop[j - 1]);
-        else { pool_free(qm, ts.cur_prop); ts.cur_prop = ts.pend_prop[j - 1]; }
-        if (ie != ib) pool_free(pm, ie);
-        if (cb != ce) pool_free(pm, cb);
-        ts.qmask = qm; ts.pmask = pm;
-        ts.cur_beg = ib;
-        ts.cur_lsw = lsw_sub;
-        ts.abort = !persist;
-      }
+      if (tid == 0)
+        rule_merge_step(&ts, j, ib, ie, cb, ce, persist, [&] {
+          return rng_uniform(key, iter, RNG_SUB_ACCEPT, 0, ((uint32_t)depth << 24) | ((uint32_t)j << 16) | (uint32_t)(n >> j));
+        });
       __syncthreads();
     }
     if (!ts.abort) {
@@ -595,19 +575,7 @@ __global__ __launch_bounds__(DN_THREADS) void k_dn_step(const DnParams P, const 
         const DnSweep s{DV_PF1 - dir, DV_PSF1 - dir, DV_PNEAR, DV_PSNEAR, DV_RHOTOP,
                         DV_POOLP + nb, DV_POOLPS + nb, DV_POOLP + leaf, DV_POOLPS + leaf, depth == 0 ? DV_POOLP + leaf : DV_RHOLEV + depth, DV_RHOTOP};
         const bool persist = dn_merge(P, chain, s, red);
-        if (tid == 0) {
-          ts.depth = depth + 1;
-          const double lsw_sub = ts.pend_lsw[depth], lsw = ts.lsw;
-          bool accept;
-          if (lsw_sub > lsw) accept = true;
-          else accept = rng_uniform(key, iter, RNG_TOP_ACCEPT, 0, (uint32_t)depth) < exp(lsw_sub - lsw);
-          unsigned qm = ts.qmask;
-          if (accept) { pool_free(qm, ts.sample_qid); ts.sample_qid = ts.pend_prop[depth]; }
-          else pool_free(qm, ts.pend_prop[depth]);
-          ts.qmask = qm;
-          ts.lsw = d_lse(lsw, lsw_sub);
-          if (!persist) ts.stop = 1;
-        }
+        if (tid == 0) rule_top_accept(&ts, depth, persist, [&] { return rng_uniform(key, iter, RNG_TOP_ACCEPT, 0, (uint32_t)depth); });
         new_doubling = true;
         __syncthreads();
       } else if (tid == 0) {
@@ -698,23 +666,13 @@ __global__ __launch_bounds__(DN_THREADS) void k_dn_end(const DnParams P, const R
   if (tid == 0) {
     const double accept_stat = ts.sum_metro / (double)ts.n_leap;
     if (save) {
-      row[0] = ts.q_lp[sample]; row[1] = accept_stat; row[2] = ts.eps; row[3] = ts.depth; row[4] = ts.n_leap; row[5] = ts.divergent;
-      row[6] = ts.q_h[sample];
+      rule_sampler_cols(row, &ts, ts.q_lp[sample], accept_stat, ts.q_h[sample]);
       sc.saved += 1;
     }
     sc.total_leapfrogs += ts.n_leap; sc.n_divergent += ts.divergent; sc.lp_cur = ts.q_lp[sample];
-    if (warm) {   // stepsize_adaptation::learn_stepsize
-      const double cnt = sc.ad_counter + 1;
-      sc.ad_counter = cnt;
-      const double as = accept_stat > 1 ? 1.0 : accept_stat;
-      const double eta = 1.0 / (cnt + Rg->t0);
-      const double s_bar = (1.0 - eta) * sc.s_bar + eta * (Rg->delta - as);
-      sc.s_bar = s_bar;
-      const double x = sc.mu - s_bar * sqrt(cnt) / Rg->gamma;
-      const double x_eta = pow(cnt, -Rg->kappa);
-      sc.x_bar = (1.0 - x_eta) * sc.x_bar + x_eta * x;
-      sc.nom_eps = exp(x);
-      if (!(flags & 2) && it == Rg->num_warmup - 1) sc.nom_eps = exp(sc.x_bar);   // complete_adaptation
+    if (warm) {
+      rule_learn_stepsize(&sc, accept_stat, Rg->delta, Rg->gamma, Rg->kappa, Rg->t0);
+      if (!(flags & 2) && it == Rg->num_warmup - 1) rule_complete_adaptation(&sc);
     }
     sc.iter = it + 1;
   }
@@ -725,8 +683,8 @@ __global__ void k_dn_window_done(const DnParams P, const RunParams *Rg, int it) 
   if (chain >= P.chains) return;
   ChainScalars &sc = Rg->scal[(size_t)chain * P.sc_stride];
   if (sc.status != 0) return;
-  sc.mu = log(10.0 * sc.nom_eps); sc.s_bar = 0; sc.x_bar = 0; sc.ad_counter = 0;
-  if (it == Rg->num_warmup - 1) sc.nom_eps = exp(sc.x_bar);
+  rule_restart_stepsize(&sc);
+  if (it == Rg->num_warmup - 1) rule_complete_adaptation(&sc);
 }
 
 // ---------------------------------------------------------------- base_hmc::init_stepsize, one attempt per round
@@ -740,7 +698,7 @@ __global__ void k_dn_eps_arm(const DnParams P, const RunParams *Rg) {
   const int on = sc.status == 0 && !(e0 == 0 || e0 > 1e7 || isnan(e0));
   DnRound &rd = P.rd[chain];
   rd.active = on; rd.aux = 0; rd.qin = DV_QC; rd.gout = DV_GC;
-  P.ts[chain].direction = 0; P.ts[chain].done = 0;
+  P.ts[chain].direction = 0; P.ts[chain].done = 0;   // (done: set by rule_init_stepsize_verdict in k_dn_eps_step, which reads it back)
   P.active[chain] = on;
 }
 __global__ __launch_bounds__(256) void k_dn_eps_prekick(const DnParams P, const RunParams *Rg) {
@@ -773,24 +731,10 @@ __global__ void k_dn_eps_step(const DnParams P, const RunParams *Rg) {
   if (!rd.active) return;
   TS &ts = P.ts[chain];
   ChainScalars &sc = Rg->scal[(size_t)chain * P.sc_stride];
-  double h = 0.5 * dn_partial_sum(P, chain) - P.lpbuf[chain];
-  if (isnan(h)) h = INFINITY;
-  const double delta_H = ts.H0 - h, thr = log(0.8), eps = sc.nom_eps;
-  int done = 0;
-  if (rd.aux == 0) ts.direction = delta_H > thr ? 1 : -1;
-  else {
-    const int dirn = ts.direction;
-    if (dirn == 1 && !(delta_H > thr)) done = 1;
-    else if (dirn == -1 && !(delta_H < thr)) done = 1;
-    else {
-      const double ne = dirn == 1 ? 2.0 * eps : 0.5 * eps;
-      sc.nom_eps = ne;
-      if (ne > 1e7 || ne == 0) { done = 1; sc.status = POTUS_ERR_STEPSIZE; }   // upstream throws here
-    }
-  }
+  rule_init_stepsize_verdict(&ts, &sc, rd.aux == 0, ts.H0, dn_partial_sum(P, chain), P.lpbuf[chain], sc.nom_eps);   // (ts.done: 0 since k_dn_eps_arm)
   rd.aux += 1;
   rd.qin = DV_QC; rd.gout = DV_GC;
-  if (done) rd.active = 0;
+  if (ts.done) rd.active = 0;
   P.active[chain] = rd.active;
 }
 

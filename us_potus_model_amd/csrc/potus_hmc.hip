@@ -2,7 +2,8 @@
 //
 // Host side: validates the Stan data block, builds transformed data (stan:42-55) and the
 // static poll schedule, owns device memory / stream / events behind an integer handle.
-// Device side: potus_model.hpp (log-density + gradient), potus_nuts.hpp (NUTS + adaptation).
+// Device side: potus_model.hpp (log-density + gradient), potus_nuts.hpp (NUTS + adaptation), potus_rules.hpp (their scalar
+// rules, shared with the host's dense window schedule).
 #include "../../include/potus_hmc.h"
 #include "potus_nuts.hpp"
 #include "potus_cluster.hpp"
@@ -64,21 +65,13 @@ __device__ __forceinline__ Chain make_chain(CMp M, CRp R, int chain, int side = 
 
 // Initial values (stan::services::util::initialize: U(-R,R), <= 100 attempts), unit metric,
 // adaptation windows (windowed_adaptation), mu = log(10*stepsize), initial init_stepsize.
-__global__ __launch_bounds__(PT_THREADS) void k_init(const DevModel *Mg, const RunParams *Rg, const double *q0) {
-  CMp M = (CMp)Mg;
-  CRp R = (CRp)Rg;
-  const int chain = blockIdx.x % R->chains, side = blockIdx.x / R->chains;   // side 1: two workgroups per chain only
+__device__ __forceinline__ void init_one_workgroup(CMp M, CRp R, int chain, int side, const double *q0) {
   Chain c = make_chain(M, R, chain, side);
   c.pst = model_setup_lds(M, c.lds);
   const int tid = c.tid;
   gdp Q0 = c.vec(V_QC), G0 = c.vec(V_GC), minv = c.vec(V_MINV), mean = c.vec(V_WMEAN), m2 = c.vec(V_WM2);
   for (int i = tid; i < c.D; i += PT_THREADS) { minv[i] = 1.0; mean[i] = 0.0; m2[i] = 0.0; }
-  if (tid == 0) {
-    gsc sc = c.sc;
-    sc->nom_eps = R->stepsize; sc->mu = log(10.0 * R->stepsize); sc->s_bar = 0; sc->x_bar = 0; sc->ad_counter = 0;
-    sc->wf_n = 0; sc->total_leapfrogs = 0; sc->iter = 0; sc->status = 0; sc->n_divergent = 0; sc->saved = 0; sc->leaves_run = 0; sc->spec_limit = 0x7f7f7f7f;
-    sc->win_counter = 0; sc->win_size = R->window; sc->win_next = R->init_buffer + R->window - 1;
-  }
+  if (tid == 0) rule_reset_chain(c.sc, R->stepsize, R->init_buffer, R->window);
   __syncthreads();
   bool ok = false;
   const double radius = R->init_radius;
@@ -100,7 +93,11 @@ __global__ __launch_bounds__(PT_THREADS) void k_init(const DevModel *Mg, const R
   }
   if (!ok) { if (tid == 0) c.sc->status = POTUS_ERR_INIT; return; }
   init_stepsize(c, PT_ITER_PRE);
-  if (tid == 0 && R->num_warmup == 0) c.sc->nom_eps = exp(c.sc->x_bar); // engage+disengage: complete_adaptation
+  if (tid == 0 && R->num_warmup == 0) rule_complete_adaptation(c.sc); // engage+disengage
+}
+__global__ __launch_bounds__(PT_THREADS) void k_init(const DevModel *Mg, const RunParams *Rg, const double *q0) {
+  CRp R = (CRp)Rg;
+  init_one_workgroup((CMp)Mg, R, blockIdx.x % R->chains, blockIdx.x / R->chains, q0);   // side 1: two workgroups per chain only
 }
 
 // The once-per-transition work is kept out of line so that the register allocator only sees the
@@ -113,6 +110,31 @@ __device__ __noinline__ void cold_transition_begin(const DevModel *Mg, const Run
   transition_begin(c, uni32(iter));
 }
 
+// The end of a transition, the pieces every diagonal sampler shares.  Thread 0: the trajectory's scalars -> ts and the
+// chain's counters, from the sampler's own tree (end_trajectory) or from the state the two sides combined (end_trajectory_twin).
+__device__ __forceinline__ void end_trajectory(ltp ts, gsc sc) {
+  ts->accept_stat = ts->sum_metro / (double)ts->n_leap;
+  ts->out_lp = ts->q_lp[ts->sample_qid];
+  ts->out_h = ts->q_h[ts->sample_qid];
+  sc->total_leapfrogs += ts->n_leap;
+  sc->n_divergent += ts->divergent;
+}
+__device__ __forceinline__ void end_trajectory_twin(ltp ts, gsc sc) {
+  ts->n_leap = (int)ts->tt[TT_NLEAP]; ts->divergent = (int)ts->tt[TT_DIV]; ts->depth = (int)ts->tt[TT_DEPTH];
+  ts->accept_stat = ts->tt[TT_METRO] / ts->tt[TT_NLEAP];
+  ts->out_lp = ts->tt[TT_SLP]; ts->out_h = ts->tt[TT_SH];
+  sc->total_leapfrogs += ts->n_leap;
+  sc->n_divergent += ts->divergent;
+  sc->spec_limit = (int)(((unsigned)sc->spec_limit << 8) | (unsigned)ts->tw_seq);   // doublings of the last four transitions, a byte each
+}
+// the row of the draws array this transition is saved in, its sampler columns, and the chain's scalars once it is written
+__device__ __forceinline__ gdp draw_row(CRp R, int chain, gsc sc) { return as_g(R->draws) + ((size_t)chain * R->n_save_max + sc->saved) * R->row; }
+__device__ __forceinline__ void draw_row_head(gdp row, ltp ts) { rule_sampler_cols(row, ts, ts->out_lp, ts->accept_stat, ts->out_h); }
+__device__ __forceinline__ void end_commit(ltp ts, gsc sc, bool saved) {
+  sc->lp_cur = ts->out_lp;
+  if (saved) sc->saved += 1;
+}
+
 // New sample -> chain position and draws array; warmup adaptation.
 __device__ __noinline__ void cold_transition_end(const DevModel *Mg, const RunParams *Rg, int chain_, uint32_t iter) {
   CMp M = (CMp)uni_ptr(Mg);
@@ -123,35 +145,22 @@ __device__ __noinline__ void cold_transition_end(const DevModel *Mg, const RunPa
   c.pst = model_load_static(M);
   ltp ts = c.ts;
   const int tid = c.tid;
-  if (tid == 0) {
-    ts->accept_stat = ts->sum_metro / (double)ts->n_leap;
-    ts->out_lp = ts->q_lp[ts->sample_qid];
-    ts->out_h = ts->q_h[ts->sample_qid];
-    c.sc->total_leapfrogs += ts->n_leap;
-    c.sc->n_divergent += ts->divergent;
-  }
+  if (tid == 0) end_trajectory(ts, c.sc);
   __syncthreads();
   CPROF_START(c);
   gcdp qs = c.vec(V_POOLQ + ts->sample_qid);
   gdp Q0 = c.vec(V_QC);
   const bool warm = it < R->num_warmup;
   const bool save = !warm || R->save_warmup;
-  const int row_len = R->row;
-  gdp row = as_g(R->draws) + ((size_t)chain * R->n_save_max + c.sc->saved) * row_len;
-  if (save && tid == 0) {
-    row[0] = ts->out_lp; row[1] = ts->accept_stat; row[2] = ts->eps; row[3] = ts->depth; row[4] = ts->n_leap;
-    row[5] = ts->divergent; row[6] = ts->out_h;
-  }
+  gdp row = draw_row(R, chain, c.sc);
+  if (save && tid == 0) draw_row_head(row, ts);
   for (int i = tid; i < c.D; i += PT_THREADS) {
     const double v = qs[i];
     Q0[i] = v;
     if (save) row[POTUS_N_SAMPLER_COLS + i] = v;
   }
   __syncthreads();
-  if (tid == 0) {
-    c.sc->lp_cur = ts->out_lp;
-    if (save) c.sc->saved += 1;
-  }
+  if (tid == 0) end_commit(ts, c.sc, save);
   CPROF_MARK(c, PF_SAVE);
   if (warm) adapt_after_transition(c, (uint32_t)it, Q0);
   CPROF_MARK(c, PF_ADAPT);
@@ -161,10 +170,9 @@ __device__ __noinline__ void cold_transition_end(const DevModel *Mg, const RunPa
 }
 
 // n_iter transitions per chain, adaptation during warmup, draws appended to the draws array.
-__global__ __launch_bounds__(PT_THREADS) void k_run(const DevModel *Mg, const RunParams *Rg, int n_iter) {
+__device__ __forceinline__ void run_one_workgroup(const DevModel *Mg, const RunParams *Rg, int chain, int n_iter) {
   CMp M = (CMp)Mg;
   CRp R = (CRp)Rg;
-  const int chain = blockIdx.x;
   Chain c = make_chain(M, R, chain);
   if (c.sc->status != 0) return;
   c.pst = model_setup_lds(M, c.lds);
@@ -180,28 +188,28 @@ __global__ __launch_bounds__(PT_THREADS) void k_run(const DevModel *Mg, const Ru
   if (R->prof) for (int i = c.tid; i < PT_NPROF; i += PT_THREADS) as_g(R->prof)[(size_t)chain * PT_NPROF + i] += c.prof[i];
 #endif
 }
-
+__global__ __launch_bounds__(PT_THREADS) void k_run(const DevModel *Mg, const RunParams *Rg, int n_iter) { run_one_workgroup(Mg, Rg, blockIdx.x, n_iter); }
 
 // ------------------------------------------------------------------------ two workgroups per chain (potus_nuts_twin.hpp): the cold parts
 // The combine of doubling d by the side that built its subtree (valid: the subtree completed without an internal U-turn or
-// divergence and was not dropped).  Sets ts->tw_over when the trajectory is over.  Follows cl_cold_twin_combine below.
-__device__ __noinline__ void cold_twin1_combine(const DevModel *Mg, const RunParams *Rg, int chain_, int side_, unsigned launch_, uint32_t iter_,
-                                                int depth_, int valid_) {
-  CMp M = (CMp)uni_ptr(Mg);
-  CRp R = (CRp)uni_ptr(Rg);
-  const int chain = (int)uni32((unsigned)chain_), side = (int)uni32((unsigned)side_), d = (int)uni32((unsigned)depth_);
-  const int valid = (int)uni32((unsigned)valid_);
-  const uint32_t iter = uni32(iter_);
-  Chain c = make_chain(M, R, chain, side);
-  const Xch x = tw1_watch(R, chain + side * R->chains, launch_);
-  const Twin t = make_twin(R, chain, side, x.launch, iter);
+// divergence and was not dropped).  Sets ts->tw_over when the trajectory is over.  One body for the two twin samplers; what
+// differs between them comes in through `o`:
+//   o.c            the chain (Chain / ClChain: same member names)
+//   o.x()          the exchange handle the mailbox waits watch
+//   o.UNR, o.first(), o.end()   the elements of this workgroup's share of a vector, UNR in flight per trip
+//   o.leaf(ts, d)  momentum slot of the subtree's last leaf
+//   o.reduce(v, first)          sum of v over the chain; every store before it is complete when it returns
+//   o.publishes()  whether this workgroup writes the chain's mailbox
+template <class Ops>
+__device__ __forceinline__ void twin_combine(Ops &o, const Twin &t, int side, int d, int valid, uint32_t iter) {
+  auto &c = o.c;
   ltp ts = c.ts;
   const int tid = c.tid;
   __syncthreads();
   if (tid == 0) c.sc->leaves_run += ts->n_leap;       // whether the subtree ends up in the trajectory or not
   // 1. the state this combine starts from: published by the combine of doubling d - 1 (or the end of the trajectory)
   if (uni_i(ts->tw_seq) < d) {
-    if (tid < 64) tw_catch_up(x, t, ts, d);
+    if (tid < 64) tw_catch_up(o.x(), t, ts, d);
     __syncthreads();
   }
   if (uni_i((int)ts->tt[TT_STOP])) {                 // the trajectory ended before this doubling: the subtree is dropped
@@ -215,30 +223,31 @@ __device__ __noinline__ void cold_twin1_combine(const DevModel *Mg, const RunPar
     // 2. rho_top += rho_subtree and the three checks of transition() across the whole trajectory; the other end's momentum
     //    and (if the last combine was the other side's) rho_top come from the other side's state block, where they were
     //    stored write-through before that combine was published.  The subtree's last leaf becomes this side's end point.
+    constexpr int UNR = Ops::UNR;
     const bool other_moved = ((side ? ~dirs : dirs) & ((1 << d) - 1)) != 0;
     const rsrc_t rA = other_moved ? t.ost : c.st, rR = rho_side == 1 - side ? t.ost : c.st;
-    const int leaf = uni_i(ts->pend_end[d]);
+    const int leaf = o.leaf(ts, d);
     const unsigned sM = c.soff(V_MINV), a_beg = c.soff(V_PF0 + (1 - side)), a_end = c.soff(V_PNEAR), s_rt = c.soff(V_RHOTOP);
     const unsigned b_beg = c.soff(V_POOLP + uni_i(ts->pend_beg[d])), b_end = c.soff(V_POOLP + leaf);
     const unsigned b_rho = d == 0 ? c.soff(V_POOLP + leaf) : c.soff(V_RHOLEV + d), s_pf = c.soff(V_PF0 + side);
     double v[6] = {0, 0, 0, 0, 0, 0};
-    const int tid0 = fresh_tid(c);
-    for (int base = tid0; base < c.D; base += PT_UNR * PT_THREADS) {
-      double mi[PT_UNR], ab[PT_UNR], ae[PT_UNR], ar[PT_UNR], bb[PT_UNR], be[PT_UNR], br[PT_UNR];
+    const int first = o.first(), end = o.end();
+    for (int base = first; base < end; base += UNR * PT_THREADS) {
+      double mi[UNR], ab[UNR], ae[UNR], ar[UNR], bb[UNR], be[UNR], br[UNR];
 #pragma unroll
-      for (int k = 0; k < PT_UNR; k++) {
+      for (int k = 0; k < UNR; k++) {
         const int i = base + k * PT_THREADS;
-        const unsigned o = i < c.D ? 8u * i : PT_OOB;   // masked elements read zeros and add nothing
-        mi[k] = bld(c.st, o, sM); ab[k] = bld_s(rA, o, a_beg); ae[k] = bld(c.st, o, a_end); ar[k] = bld_s(rR, o, s_rt);
-        bb[k] = bld(c.st, o, b_beg); be[k] = bld(c.st, o, b_end); br[k] = bld(c.st, o, b_rho);
+        const unsigned off = i < end ? 8u * i : PT_OOB;   // masked elements read zeros and add nothing
+        mi[k] = bld(c.st, off, sM); ab[k] = bld_s(rA, off, a_beg); ae[k] = bld(c.st, off, a_end); ar[k] = bld_s(rR, off, s_rt);
+        bb[k] = bld(c.st, off, b_beg); be[k] = bld(c.st, off, b_end); br[k] = bld(c.st, off, b_rho);
       }
 #pragma unroll
-      for (int k = 0; k < PT_UNR; k++) {
+      for (int k = 0; k < UNR; k++) {
         const int i = base + k * PT_THREADS;
-        const unsigned o = i < c.D ? 8u * i : PT_OOB;
+        const unsigned off = i < end ? 8u * i : PT_OOB;
         const double rs = ar[k] + br[k];
-        bst_s(c.st, o, s_rt, rs);
-        bst_s(c.st, o, s_pf, be[k]);
+        bst_s(c.st, off, s_rt, rs);
+        bst_s(c.st, off, s_pf, be[k]);
         const double sab = mi[k] * ab[k], sbe = mi[k] * be[k];
         v[0] += sab * rs;                 // p#_beg . rho
         v[1] += sbe * rs;                 // p#_end . rho
@@ -250,8 +259,7 @@ __device__ __noinline__ void cold_twin1_combine(const DevModel *Mg, const RunPar
         v[5] += sbe * e2;
       }
     }
-    drain_vmem();                         // the stores above are complete before anything is published (barriers in block_sum)
-    block_sum(v, c.red(), tid0);
+    o.reduce(v, first);                   // also: the stores above are complete before anything is published
     const bool persist = v[0] > 0 && v[1] > 0 && v[2] > 0 && v[3] > 0 && v[4] > 0 && v[5] > 0;
     stop = (!persist || d + 1 >= c.max_depth) ? 1 : 0;
   }
@@ -279,7 +287,7 @@ __device__ __noinline__ void cold_twin1_combine(const DevModel *Mg, const RunPar
   }
   __syncthreads();
   // 3. publish: the state after combine d, and the STOP word if the trajectory is over
-  if (tid < 64) {
+  if (o.publishes() && tid < 64) {
     const double val = ts->tt[tid < TT_N ? tid : 0];
     tw_st(t, tid < TT_N ? 16u * (unsigned)(TWB_TOP + 16 * ((d + 1) & 1) + tid) : PT_OOB, val, t.ittag | (unsigned)(d + 2));
     tw_st(t, (stop && tid == 0) ? 16u * (unsigned)TWB_STOP : PT_OOB, (double)(d + 1), t.ittag);
@@ -287,8 +295,35 @@ __device__ __noinline__ void cold_twin1_combine(const DevModel *Mg, const RunPar
   __syncthreads();
 }
 
+// two workgroups per chain: the whole vector, the workgroup's own sum, both sides publish their combines
+struct Tw1CombineOps {
+  const Chain &c;
+  const Xch &xw;
+  static constexpr int UNR = PT_UNR;
+  __device__ __forceinline__ const Xch &x() const { return xw; }
+  __device__ __forceinline__ int first() const { return fresh_tid(c); }
+  __device__ __forceinline__ int end() const { return c.D; }
+  __device__ __forceinline__ int leaf(ltp ts, int d) const { return uni_i(ts->pend_end[d]); }
+  __device__ __forceinline__ void reduce(double (&v)[6], int first) const { drain_vmem(); block_sum(v, c.red(), first); }   // (barriers in block_sum)
+  __device__ __forceinline__ bool publishes() const { return true; }
+};
+__device__ __noinline__ void cold_twin1_combine(const DevModel *Mg, const RunParams *Rg, int chain_, int side_, unsigned launch_, uint32_t iter_,
+                                                int depth_, int valid_) {
+  CMp M = (CMp)uni_ptr(Mg);
+  CRp R = (CRp)uni_ptr(Rg);
+  const int chain = (int)uni32((unsigned)chain_), side = (int)uni32((unsigned)side_), d = (int)uni32((unsigned)depth_);
+  const int valid = (int)uni32((unsigned)valid_);
+  const uint32_t iter = uni32(iter_);
+  Chain c = make_chain(M, R, chain, side);
+  const Xch x = tw1_watch(R, chain + side * R->chains, launch_);
+  const Twin t = make_twin(R, chain, side, x.launch, iter);
+  Tw1CombineOps o{c, x};
+  twin_combine(o, t, side, d, valid, iter);
+}
+
 // New sample -> this side's chain position (from its own pool or from the other side's QC), draws array (side 0),
-// adaptation (both sides, same inputs, same bits), rendezvous with the other side.  Follows cl_cold_twin_end below.
+// adaptation (both sides, same inputs, same bits), rendezvous with the other side.  (cl_cold_twin_end below is the cluster's; the two
+// move the sample differently: here the side that holds it publishes it in V_SCR1.)
 __device__ __noinline__ void cold_twin1_end(const DevModel *Mg, const RunParams *Rg, int chain_, int side_, unsigned launch_, uint32_t iter_) {
   CMp M = (CMp)uni_ptr(Mg);
   CRp R = (CRp)uni_ptr(Rg);
@@ -305,22 +340,12 @@ __device__ __noinline__ void cold_twin1_end(const DevModel *Mg, const RunParams 
     __syncthreads();
   }
   const int owner = uni_i((int)ts->tt[TT_SSIDE]), slot = uni_i((int)ts->tt[TT_SSLOT]);
-  if (tid == 0) {
-    ts->n_leap = (int)ts->tt[TT_NLEAP]; ts->divergent = (int)ts->tt[TT_DIV]; ts->depth = (int)ts->tt[TT_DEPTH];
-    ts->accept_stat = ts->tt[TT_METRO] / ts->tt[TT_NLEAP];
-    ts->out_lp = ts->tt[TT_SLP]; ts->out_h = ts->tt[TT_SH];
-    c.sc->total_leapfrogs += ts->n_leap;
-    c.sc->n_divergent += ts->divergent;
-    c.sc->spec_limit = (int)(((unsigned)c.sc->spec_limit << 8) | (unsigned)ts->tw_seq);   // doublings of the last four transitions, a byte each
-  }
+  if (tid == 0) end_trajectory_twin(ts, c.sc);
   __syncthreads();
   const bool warm = it < R->num_warmup;
   const bool save = (!warm || R->save_warmup) && side == 0;
-  gdp row = as_g(R->draws) + ((size_t)chain * R->n_save_max + c.sc->saved) * R->row;
-  if (save && tid == 0) {
-    row[0] = ts->out_lp; row[1] = ts->accept_stat; row[2] = ts->eps; row[3] = ts->depth; row[4] = ts->n_leap;
-    row[5] = ts->divergent; row[6] = ts->out_h;
-  }
+  gdp row = draw_row(R, chain, c.sc);
+  if (save && tid == 0) draw_row_head(row, ts);
   const unsigned sQ = c.soff(V_QC);
   if (owner == 1 - side) {
     if (tid < 64) { double dummy; tw_wait(x, t, TWB_QC, 1, t.ittag, dummy); }
@@ -342,10 +367,7 @@ __device__ __noinline__ void cold_twin1_end(const DevModel *Mg, const RunParams 
   drain_vmem();
   __syncthreads();
   if (owner == side && tid < 64) tw_st(t, tid == 0 ? 16u * (unsigned)TWB_QC : PT_OOB, 1.0, t.ittag);
-  if (tid == 0) {
-    c.sc->lp_cur = ts->out_lp;
-    if (!warm || R->save_warmup) c.sc->saved += 1;
-  }
+  if (tid == 0) end_commit(ts, c.sc, !warm || R->save_warmup);
   if (warm) adapt_after_transition(c, (uint32_t)it, c.vec(V_QC));
   __syncthreads();
   if (tid == 0) c.sc->iter = it + 1;
@@ -445,12 +467,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_cl_init(const DevModel *Mg, cons
   const int tid = c.tid;
   const unsigned sQ = c.soff(V_QC), sG = c.soff(V_GC);
   for (int i = c.e0 + tid; i < c.e1; i += PT_THREADS) { bst(c.st, 8u * i, c.soff(V_MINV), 1.0); bst(c.st, 8u * i, c.soff(V_WMEAN), 0.0); bst(c.st, 8u * i, c.soff(V_WM2), 0.0); }
-  if (tid == 0) {
-    gsc sc = c.sc;
-    sc->nom_eps = R->stepsize; sc->mu = log(10.0 * R->stepsize); sc->s_bar = 0; sc->x_bar = 0; sc->ad_counter = 0;
-    sc->wf_n = 0; sc->total_leapfrogs = 0; sc->iter = 0; sc->status = 0; sc->n_divergent = 0; sc->saved = 0; sc->leaves_run = 0; sc->spec_limit = 0x7f7f7f7f;
-    sc->win_counter = 0; sc->win_size = R->window; sc->win_next = R->init_buffer + R->window - 1;
-  }
+  if (tid == 0) rule_reset_chain(c.sc, R->stepsize, R->init_buffer, R->window);
   __syncthreads();
   bool ok = false;
   const double radius = R->init_radius;
@@ -474,7 +491,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_cl_init(const DevModel *Mg, cons
   }
   if (!ok) { if (tid == 0) c.sc->status = POTUS_ERR_INIT; return; }   // every member takes this branch together
   cl_init_stepsize<CL_DW>(c, PT_ITER_PRE);
-  if (tid == 0 && R->num_warmup == 0) c.sc->nom_eps = exp(c.sc->x_bar);
+  if (tid == 0 && R->num_warmup == 0) rule_complete_adaptation(c.sc);
 }
 
 // New sample -> chain position and draws array (Stan order); warmup adaptation.
@@ -482,21 +499,12 @@ template <int CL_DW>
 __device__ __forceinline__ void cl_transition_end(ClChain &c, CRp R, int chain, int it) {
   ltp ts = c.ts;
   const int tid = c.tid;
-  if (tid == 0) {
-    ts->accept_stat = ts->sum_metro / (double)ts->n_leap;
-    ts->out_lp = ts->q_lp[ts->sample_qid];
-    ts->out_h = ts->q_h[ts->sample_qid];
-    c.sc->total_leapfrogs += ts->n_leap;
-    c.sc->n_divergent += ts->divergent;
-  }
+  if (tid == 0) end_trajectory(ts, c.sc);
   __syncthreads();
   const bool warm = it < R->num_warmup;
   const bool save = !warm || R->save_warmup;
-  gdp row = as_g(R->draws) + ((size_t)chain * R->n_save_max + c.sc->saved) * R->row;
-  if (save && tid == 0 && c.x.m == 0) {
-    row[0] = ts->out_lp; row[1] = ts->accept_stat; row[2] = ts->eps; row[3] = ts->depth; row[4] = ts->n_leap;
-    row[5] = ts->divergent; row[6] = ts->out_h;
-  }
+  gdp row = draw_row(R, chain, c.sc);
+  if (save && tid == 0 && c.x.m == 0) draw_row_head(row, ts);
   const unsigned s_src = c.soff(V_POOLQ + ts->sample_qid), sQ = c.soff(V_QC);
   for (int i = c.e0 + tid; i < c.e1; i += PT_THREADS) {
     const double v = bld_s(c.st, 8u * i, s_src);   // positions are read with sc1 loads (see potus_cluster.hpp)
@@ -505,10 +513,7 @@ __device__ __forceinline__ void cl_transition_end(ClChain &c, CRp R, int chain, 
     if (save && si >= 0) row[POTUS_N_SAMPLER_COLS + si] = v;
   }
   cl_sync(c.x, c.red());
-  if (tid == 0) {
-    c.sc->lp_cur = ts->out_lp;
-    if (save) c.sc->saved += 1;
-  }
+  if (tid == 0) end_commit(ts, c.sc, save);
   if (warm) cl_adapt_after_transition<CL_DW>(c, (uint32_t)it);
   __syncthreads();
   if (tid == 0) c.sc->iter = it + 1;
@@ -550,8 +555,19 @@ __device__ __noinline__ unsigned cl_cold_transition_end(const DevModel *Mg, cons
 }
 
 // ------------------------------------------------------------------------ twin mode (potus_cluster.hpp): the cold parts
-// The combine of doubling d by the side that built its subtree (valid: the subtree completed without an internal U-turn
-// or divergence; leaf: momentum slot of its last leaf).  Sets ts->tw_over when the trajectory is over.
+// The combine of doubling d (twin_combine above) by the cluster that built its subtree; leaf: momentum slot of its last leaf.
+// A member's share of the vector, the cluster's all-reduce (after which every member's stores are complete), member 0 publishes.
+struct ClCombineOps {
+  ClChain &c;
+  int last_leaf;
+  static constexpr int UNR = CL_UNR;
+  __device__ __forceinline__ const Xch &x() const { return c.x; }
+  __device__ __forceinline__ int first() const { return cl_first(c); }
+  __device__ __forceinline__ int end() const { return c.e1; }
+  __device__ __forceinline__ int leaf(ltp, int) const { return last_leaf; }
+  __device__ __forceinline__ void reduce(double (&v)[6], int) const { cl_allreduce(v, c.red(), c.x, c.tid); }
+  __device__ __forceinline__ bool publishes() const { return c.x.m == 0; }
+};
 template <int CL_DW>
 __device__ __noinline__ unsigned cl_cold_twin_combine(const DevModel *Mg, const ClModel *CLg, const RunParams *Rg, int chain_, int m_, int side_,
                                                       unsigned launch_, unsigned epoch_, uint32_t iter_, int depth_, int valid_, int leaf_) {
@@ -564,93 +580,8 @@ __device__ __noinline__ unsigned cl_cold_twin_combine(const DevModel *Mg, const 
   ClChain c = make_clchain(M, CL, R, chain, (int)uni32((unsigned)m_), uni32(launch_), side);
   c.x.epoch = uni32(epoch_); c.x.local = uni_i(cl_local);   // (what k_cl_run found out about this launch's placement)
   const Twin t = make_twin(R, chain, side, c.x.launch, iter);
-  ltp ts = c.ts;
-  const int tid = c.tid;
-  __syncthreads();
-  if (tid == 0) c.sc->leaves_run += ts->n_leap;       // whether the subtree ends up in the trajectory or not
-  // 1. the state this combine starts from: published by the combine of doubling d - 1 (or the end of the trajectory)
-  if (uni_i(ts->tw_seq) < d) {
-    if (tid < 64) tw_catch_up(c.x, t, ts, d);
-    __syncthreads();
-  }
-  if (uni_i((int)ts->tt[TT_STOP])) {                 // the trajectory ended before this doubling: the subtree is dropped
-    if (tid == 0) ts->tw_over = 1;
-    __syncthreads();
-    return c.x.epoch;
-  }
-  const int rho_side = uni_i((int)ts->tt[TT_RHOSIDE]), dirs = uni_i(ts->tw_dirs);
-  int stop = 1;
-  if (valid) {
-    // 2. rho_top += rho_subtree and the three checks of transition() across the whole trajectory; the other end's momentum
-    //    and (if the last combine was the other side's) rho_top come from the other side's state block, where they were
-    //    stored write-through before that combine was published.  The subtree's last leaf becomes this side's end point.
-    const bool other_moved = ((side ? ~dirs : dirs) & ((1 << d) - 1)) != 0;
-    const rsrc_t rA = other_moved ? t.ost : c.st, rR = rho_side == 1 - side ? t.ost : c.st;
-    const unsigned sM = c.soff(V_MINV), a_beg = c.soff(V_PF0 + (1 - side)), a_end = c.soff(V_PNEAR), s_rt = c.soff(V_RHOTOP);
-    const unsigned b_beg = c.soff(V_POOLP + uni_i(ts->pend_beg[d])), b_end = c.soff(V_POOLP + leaf);
-    const unsigned b_rho = d == 0 ? c.soff(V_POOLP + leaf) : c.soff(V_RHOLEV + d), s_pf = c.soff(V_PF0 + side);
-    double v[6] = {0, 0, 0, 0, 0, 0};
-    for (int base = cl_first(c); base < c.e1; base += CL_UNR * PT_THREADS) {
-      double mi[CL_UNR], ab[CL_UNR], ae[CL_UNR], ar[CL_UNR], bb[CL_UNR], be[CL_UNR], br[CL_UNR];
-#pragma unroll
-      for (int k = 0; k < CL_UNR; k++) {
-        const int i = base + k * PT_THREADS;
-        const unsigned o = i < c.e1 ? 8u * i : PT_OOB;   // masked elements read zeros and add nothing
-        mi[k] = bld(c.st, o, sM); ab[k] = bld_s(rA, o, a_beg); ae[k] = bld(c.st, o, a_end); ar[k] = bld_s(rR, o, s_rt);
-        bb[k] = bld(c.st, o, b_beg); be[k] = bld(c.st, o, b_end); br[k] = bld(c.st, o, b_rho);
-      }
-#pragma unroll
-      for (int k = 0; k < CL_UNR; k++) {
-        const int i = base + k * PT_THREADS;
-        const unsigned o = i < c.e1 ? 8u * i : PT_OOB;
-        const double rs = ar[k] + br[k];
-        bst_s(c.st, o, s_rt, rs);
-        bst_s(c.st, o, s_pf, be[k]);
-        const double sab = mi[k] * ab[k], sbe = mi[k] * be[k];
-        v[0] += sab * rs;                 // p#_beg . rho
-        v[1] += sbe * rs;                 // p#_end . rho
-        const double e1 = ar[k] + bb[k];  // rho_old + p of the subtree's first leaf
-        v[2] += sab * e1;
-        v[3] += mi[k] * bb[k] * e1;
-        const double e2 = br[k] + ae[k];  // rho_subtree + p of the old end
-        v[4] += mi[k] * ae[k] * e2;
-        v[5] += sbe * e2;
-      }
-    }
-    cl_allreduce(v, c.red(), c.x, tid);   // also: every member's stores above are complete before anything is published
-    const bool persist = v[0] > 0 && v[1] > 0 && v[2] > 0 && v[3] > 0 && v[4] > 0 && v[5] > 0;
-    stop = (!persist || d + 1 >= c.max_depth) ? 1 : 0;
-  }
-  __syncthreads();
-  if (tid == 0) {
-    // the subtree's leaves count whether it is valid or not (base_nuts: n_leapfrog_, sum_metro_prob, divergent_)
-    ts->tt[TT_METRO] += ts->sum_metro; ts->tt[TT_NLEAP] += (double)ts->n_leap;
-    if (ts->divergent) ts->tt[TT_DIV] = 1.0;
-    if (valid) {
-      const double lsw_top = ts->tt[TT_LSW], lsw_sub = ts->pend_lsw[d];
-      const int prop = ts->pend_prop[d];
-      bool accept;
-      if (lsw_sub > lsw_top) accept = true;
-      else accept = rng_uniform(c.key, iter, RNG_TOP_ACCEPT, 0, (uint32_t)d) < exp(lsw_sub - lsw_top);
-      if (accept) {
-        ts->tt[TT_SSIDE] = (double)side; ts->tt[TT_SSLOT] = (double)prop; ts->tt[TT_SLP] = ts->q_lp[prop]; ts->tt[TT_SH] = ts->q_h[prop];
-        ts->tw_keep = prop;
-      }
-      ts->tt[TT_LSW] = d_lse(lsw_top, lsw_sub);
-      ts->tt[TT_DEPTH] = (double)(d + 1);
-      ts->tt[TT_RHOSIDE] = (double)side;
-    }
-    ts->tt[TT_STOP] = (double)stop;
-    ts->tw_seq = d + 1; ts->tw_over = stop;
-  }
-  __syncthreads();
-  // 3. publish (member 0): the state after combine d, and the STOP word if the trajectory is over
-  if (c.x.m == 0 && tid < 64) {
-    const double val = ts->tt[tid < TT_N ? tid : 0];
-    tw_st(t, tid < TT_N ? 16u * (unsigned)(TWB_TOP + 16 * ((d + 1) & 1) + tid) : PT_OOB, val, t.ittag | (unsigned)(d + 2));
-    tw_st(t, (stop && tid == 0) ? 16u * (unsigned)TWB_STOP : PT_OOB, (double)(d + 1), t.ittag);
-  }
-  __syncthreads();
+  ClCombineOps o{c, leaf};
+  twin_combine(o, t, side, d, valid, iter);
   return c.x.epoch;
 }
 
@@ -676,22 +607,12 @@ __device__ __noinline__ unsigned cl_cold_twin_end(const DevModel *Mg, const ClMo
     __syncthreads();
   }
   const int owner = uni_i((int)ts->tt[TT_SSIDE]), slot = uni_i((int)ts->tt[TT_SSLOT]);
-  if (tid == 0) {
-    ts->n_leap = (int)ts->tt[TT_NLEAP]; ts->divergent = (int)ts->tt[TT_DIV]; ts->depth = (int)ts->tt[TT_DEPTH];
-    ts->accept_stat = ts->tt[TT_METRO] / ts->tt[TT_NLEAP];
-    ts->out_lp = ts->tt[TT_SLP]; ts->out_h = ts->tt[TT_SH];
-    c.sc->total_leapfrogs += ts->n_leap;
-    c.sc->n_divergent += ts->divergent;
-    c.sc->spec_limit = (int)(((unsigned)c.sc->spec_limit << 8) | (unsigned)ts->tw_seq);   // doublings of the last four transitions, a byte each
-  }
+  if (tid == 0) end_trajectory_twin(ts, c.sc);
   __syncthreads();
   const bool warm = it < R->num_warmup;
   const bool save = (!warm || R->save_warmup) && side == 0;
-  gdp row = as_g(R->draws) + ((size_t)chain * R->n_save_max + c.sc->saved) * R->row;
-  if (save && tid == 0 && c.x.m == 0) {
-    row[0] = ts->out_lp; row[1] = ts->accept_stat; row[2] = ts->eps; row[3] = ts->depth; row[4] = ts->n_leap;
-    row[5] = ts->divergent; row[6] = ts->out_h;
-  }
+  gdp row = draw_row(R, chain, c.sc);
+  if (save && tid == 0 && c.x.m == 0) draw_row_head(row, ts);
   const unsigned sQ = c.soff(V_QC);
   if (owner == 1 - side) {
     if (tid < 64) { double dummy; tw_wait(c.x, t, TWB_QC, 1, t.ittag, dummy); }
@@ -709,10 +630,7 @@ __device__ __noinline__ unsigned cl_cold_twin_end(const DevModel *Mg, const ClMo
   }
   cl_sync(c.x, c.red());
   if (owner == side && c.x.m == 0 && tid < 64) tw_st(t, tid == 0 ? 16u * (unsigned)TWB_QC : PT_OOB, 1.0, t.ittag);
-  if (tid == 0) {
-    c.sc->lp_cur = ts->out_lp;
-    if (!warm || R->save_warmup) c.sc->saved += 1;
-  }
+  if (tid == 0) end_commit(ts, c.sc, !warm || R->save_warmup);
   if (warm) cl_adapt_after_transition<CL_DW>(c, (uint32_t)it);
   __syncthreads();
   if (tid == 0) c.sc->iter = it + 1;
@@ -829,63 +747,12 @@ __global__ void k_dn_import_q(const RunParams *Rg, const DnParams P, const int *
 #include "potus_rows.hpp"   // the output row of a draw: its column blocks, its builder and the kernels around it
 
 // Many data sets in one handle (potus_set_datasets): Mg = [n_datasets] models that differ only in the poll outcomes (pd), chain c
-// uses data set c / chains_per_ds.  One workgroup per chain, diagonal metric.  The bodies are those of k_init / k_run line for line
-// with the chain's model in place of Mg: written out rather than shared, so that k_init and k_run stay the instructions they were.
+// uses data set c / chains_per_ds.  One workgroup per chain, diagonal metric: the bodies of k_init / k_run with the chain's model.
 __global__ __launch_bounds__(PT_THREADS) void k_init_ds(const DevModel *Mg, const RunParams *Rg, const double *q0, int chains_per_ds) {
-  const int chain = blockIdx.x;
-  CMp M = (CMp)(Mg + chain / chains_per_ds);
-  CRp R = (CRp)Rg;
-  Chain c = make_chain(M, R, chain);
-  c.pst = model_setup_lds(M, c.lds);
-  const int tid = c.tid;
-  gdp Q0 = c.vec(V_QC), G0 = c.vec(V_GC), minv = c.vec(V_MINV), mean = c.vec(V_WMEAN), m2 = c.vec(V_WM2);
-  for (int i = tid; i < c.D; i += PT_THREADS) { minv[i] = 1.0; mean[i] = 0.0; m2[i] = 0.0; }
-  if (tid == 0) {
-    gsc sc = c.sc;
-    sc->nom_eps = R->stepsize; sc->mu = log(10.0 * R->stepsize); sc->s_bar = 0; sc->x_bar = 0; sc->ad_counter = 0;
-    sc->wf_n = 0; sc->total_leapfrogs = 0; sc->iter = 0; sc->status = 0; sc->n_divergent = 0; sc->saved = 0; sc->leaves_run = 0; sc->spec_limit = 0x7f7f7f7f;
-    sc->win_counter = 0; sc->win_size = R->window; sc->win_next = R->init_buffer + R->window - 1;
-  }
-  __syncthreads();
-  bool ok = false;
-  const double radius = R->init_radius;
-  for (uint32_t attempt = 0; attempt < 100 && !ok; attempt++) {
-    for (int i = tid; i < c.D; i += PT_THREADS) {
-      if (q0) Q0[i] = as_g(q0)[(size_t)chain * c.D + i];
-      else Q0[i] = radius * (2.0 * rng_uniform(c.key, PT_ITER_PRE, RNG_INITS, attempt, (uint32_t)i) - 1.0);
-    }
-    __syncthreads();
-    PlainPolicy pol{c.st, c.st, c.soff(V_QC), c.soff(V_GC), {0}};
-    const double lp = model_pass(M, c.lds, c.pst, pol);
-    double bad[1] = {0.0};
-    for (int i = tid; i < c.D; i += PT_THREADS) bad[0] += isfinite(G0[i]) ? 0.0 : 1.0;
-    block_sum(bad, c.red(), tid);
-    ok = isfinite(lp) && bad[0] == 0.0;
-    if (tid == 0 && ok) c.sc->lp_cur = lp;
-    __syncthreads();
-    if (q0) break;
-  }
-  if (!ok) { if (tid == 0) c.sc->status = POTUS_ERR_INIT; return; }
-  init_stepsize(c, PT_ITER_PRE);
-  if (tid == 0 && R->num_warmup == 0) c.sc->nom_eps = exp(c.sc->x_bar); // engage+disengage: complete_adaptation
+  init_one_workgroup((CMp)(Mg + blockIdx.x / chains_per_ds), (CRp)Rg, blockIdx.x, 0, q0);
 }
-
 __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, const RunParams *Rg, int n_iter, int chains_per_ds) {
-  const int chain = blockIdx.x;
-  const DevModel *Mg = Mg_all + chain / chains_per_ds;
-  CMp M = (CMp)Mg;
-  CRp R = (CRp)Rg;
-  Chain c = make_chain(M, R, chain);
-  if (c.sc->status != 0) return;
-  c.pst = model_setup_lds(M, c.lds);
-  const int total = R->num_warmup + R->num_samples;
-  for (int k = 0; k < n_iter; k++) {
-    const int it = c.sc->iter;
-    if (it >= total) break;
-    cold_transition_begin(Mg, Rg, chain, (uint32_t)it);
-    transition_tree(c, (uint32_t)it);
-    cold_transition_end(Mg, Rg, chain, (uint32_t)it);
-  }
+  run_one_workgroup(Mg_all + blockIdx.x / chains_per_ds, Rg, blockIdx.x, n_iter);
 }
 
 #include "potus_loo.hpp"   // per-poll log-likelihoods and PSIS-LOO (after potus_rows.hpp, whose row builder it shares)
@@ -1876,7 +1743,7 @@ int dense_alloc(Sampler *sp) {
   hipLaunchKernelGGL(k_dn_identity, dim3((D + 255) / 256, mchains), dim3(256), 0, sp->stream, P);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipStreamSynchronize(sp->stream));
-  sp->dn_win_counter = 0; sp->dn_win_size = sp->R.window; sp->dn_win_next = sp->R.init_buffer + sp->R.window - 1; sp->dn_wf_n = 0;
+  sp->dn_win_counter = 0; sp->dn_win_size = sp->R.window; sp->dn_win_next = rule_first_window_end(sp->R.init_buffer, sp->R.window); sp->dn_wf_n = 0;
   sp->dn_pass_bytes[0] = dense_pass_bytes(D, P.LD, DN_RB) / (P.f32 ? 2 : 1); sp->dn_pass_bytes[1] = dense_pass_bytes(D, P.LD, P.rb) / (P.f32 ? 2 : 1);   // ([1]: at the handle's own block size)
   if (P.pooled) sp->dn_pass_bytes[0] = sp->dn_pass_bytes[1] = (long long)D * P.LD * (P.f32 ? 4 : 8);   // the whole symmetric matrix, once per pass whatever the number of chains
   return 0;
@@ -2117,24 +1984,16 @@ int dense_run(Sampler *sp, int n_iter) {
       while (retired < q) { if ((rc = retire(retired))) return rc; retired++; }
     }
     // adapt_dense_e_nuts::transition: the warm-up schedule is the same for every chain, so the host keeps its own copy
-    int flags = 0;
     const bool warm = it < nw;
-    if (warm && nw >= 20) {
-      const int wc = sp->dn_win_counter;
-      if (wc >= ib && wc < nw - tb && wc != nw) flags |= 1;
-      if (wc == sp->dn_win_next && wc != nw) flags |= 2;
-    }
+    int in_window = 0, end_window = 0;
+    if (warm) rule_window_flags(nw, ib, tb, sp->dn_win_counter, sp->dn_win_next, in_window, end_window);
+    const int flags = in_window | end_window << 1;
     hipLaunchKernelGGL(k_dn_end, dim3(chains), dim3(DN_THREADS), 0, sp->stream, P, (const RunParams *)sp->dR, it, flags, sp->dn_wf_n, total);
     HIP_TRY(hipGetLastError());
-    if (flags & 1) sp->dn_wf_n += 1;
-    if (flags & 2) {
+    if (in_window) sp->dn_wf_n += 1;
+    if (end_window) {
       if ((rc = dense_window_end(sp, sp->dn_wf_n, (unsigned)it))) return rc;
-      const int last = nw - tb - 1;                                       // windowed_adaptation::compute_next_window
-      if (sp->dn_win_next != last) {
-        sp->dn_win_size *= 2;
-        sp->dn_win_next = sp->dn_win_counter + sp->dn_win_size;
-        if (sp->dn_win_next != last && sp->dn_win_next + 2 * sp->dn_win_size >= nw - tb) sp->dn_win_next = last;
-      }
+      rule_next_window(nw, tb, sp->dn_win_counter, sp->dn_win_next, sp->dn_win_size);
       sp->dn_wf_n = 0;
     }
     if (warm && nw >= 20) sp->dn_win_counter += 1;
@@ -2158,7 +2017,7 @@ int dense_import_init(Sampler *sp) {
     P.identity = 1;
   }
   sp->dn_pending = false;
-  sp->dn_win_counter = 0; sp->dn_win_size = sp->R.window; sp->dn_win_next = sp->R.init_buffer + sp->R.window - 1; sp->dn_wf_n = 0;
+  sp->dn_win_counter = 0; sp->dn_win_size = sp->R.window; sp->dn_win_next = rule_first_window_end(sp->R.init_buffer, sp->R.window); sp->dn_wf_n = 0;
   hipLaunchKernelGGL(k_dn_import_q, dim3(64, sp->R.chains), dim3(256), 0, sp->stream, (const RunParams *)sp->dR, sp->dn,
                      sp->K > 1 ? sp->CL.perm : (const int *)nullptr, sp->K > 1 ? sp->CL.Dint : 0);
   HIP_TRY(hipGetLastError());
@@ -2533,7 +2392,7 @@ int potus_create(const potus_data *d, const potus_opts *o, int *handle) {
   R.max_depth = o->max_depth; R.save_warmup = o->save_warmup;
   // windowed_adaptation::set_window_params
   int ib = o->init_buffer, tb = o->term_buffer, bw = o->window;
-  if (o->num_warmup >= 20 && (long long)ib + bw + tb > o->num_warmup) { ib = (int)(0.15 * o->num_warmup); tb = (int)(0.1 * o->num_warmup); bw = o->num_warmup - (ib + tb); }
+  rule_window_params(o->num_warmup, ib, tb, bw);
   R.init_buffer = ib; R.term_buffer = tb; R.window = bw;
   R.delta = o->delta; R.gamma = o->gamma; R.kappa = o->kappa; R.t0 = o->t0; R.stepsize = o->stepsize; R.init_radius = o->init_radius;
   R.seed_lo = (unsigned)(o->seed & 0xFFFFFFFFu); R.seed_hi = (unsigned)(o->seed >> 32);

@@ -9,11 +9,13 @@
 // other -- no lock-step, no divergence cost from different tree depths.
 //
 // The algorithm is Stan 2.24's (third-party sources, cited by upstream file name):
-//   base_nuts.hpp::transition / build_tree   -> nuts_transition (iterative, see below)
+//   base_nuts.hpp::transition / build_tree   -> transition_tree / build_subtree (iterative, see below)
 //   expl_leapfrog.hpp, diag_e_metric.hpp      -> LeapPolicy fused into model_pass
-//   stepsize_adaptation.hpp                   -> learn_stepsize
-//   windowed_adaptation.hpp, var_adaptation.hpp, welford_var_estimator.hpp -> adapt_*
+//   stepsize_adaptation.hpp, windowed_adaptation.hpp -> potus_rules.hpp, called from adapt_after_transition
+//   var_adaptation.hpp, welford_var_estimator.hpp    -> adapt_after_transition
 //   base_hmc.hpp::init_stepsize               -> init_stepsize
+// The scalar rules (a leaf's energy, the merge and accept steps, step-size and window rules) are potus_rules.hpp's, shared with
+// the other samplers; this file owns the vectors, the barriers and the order of things.
 // build_tree's recursion is restated as a loop over leaves with a cascade of merges after
 // every leaf (a subtree of level j is merged when its last leaf has j trailing one bits), so
 // only O(depth) vectors are live:
@@ -26,6 +28,7 @@
 // counter, so results do not depend on scheduling or on how chains are split across GPUs.
 #pragma once
 #include "potus_model.hpp"
+#include "potus_rules.hpp"   // the scalar rules every sampler shares (also d_lse, pool_alloc, pool_free)
 
 extern __shared__ __attribute__((aligned(16))) double lds_dyn[];
 
@@ -231,17 +234,6 @@ struct Chain {
 #define CPROF_COUNT(c, k) do { } while (0)
 #endif
 
-__device__ __forceinline__ double d_lse(double a, double b) {
-  if (a == -INFINITY) return b;
-  if (a == INFINITY && b == INFINITY) return INFINITY;
-  return a > b ? a + log1p(exp(b - a)) : b + log1p(exp(a - b));
-}
-__device__ __forceinline__ int pool_alloc(unsigned &mask, int n) {
-  for (int i = 0; i < n; i++) if (!(mask & (1u << i))) { mask |= 1u << i; return i; }
-  return n - 1; // cannot happen: pools are sized for PT_MAXD
-}
-__device__ __forceinline__ void pool_free(unsigned &mask, int i) { if (i >= 0) mask &= ~(1u << i); }
-
 // ---------------------------------------------------------------- block-wide vector sweeps (all end with a barrier)
 // Each thread handles elements tid, tid+PT_THREADS, ...; PT_UNR elements are in flight per trip so the
 // loads of a trip are issued together (the sweeps are latency-, not bandwidth-limited).
@@ -394,7 +386,83 @@ __device__ __forceinline__ void transition_begin(const Chain &c, uint32_t iter) 
   __syncthreads();
 }
 
-// Part 2 (the hot loop, inlined into the kernel): doublings, leaves, merges.
+// The leaves of one doubling (2^depth of them, towards end `dir`) with the cascade of merges after each: base_nuts::build_tree.
+// Returns whether the subtree was completed: no divergence, no U-turn inside it, not called off by the hook.  On success level
+// `depth` of ts->pend_* describes it.  The hook is what a sampler adds per leaf: leaf_start(c) runs while the pass starts, ext(ts)
+// is or-ed into the leaf's abort flag by thread 0 (NoLeafHook: nothing; potus_nuts_twin.hpp: has the other side ended the trajectory?).
+struct NoLeafHook {
+  __device__ __forceinline__ void leaf_start(const Chain &) const { }
+  __device__ __forceinline__ int ext(ltp) const { return 0; }
+};
+template <class Hook>
+__device__ __forceinline__ bool build_subtree(const Chain &c, uint32_t iter, int depth, int dir, double eps, const Hook &hook) {
+  ltp ts = c.ts;
+  const int tid = c.tid;
+  const int nleaf = 1 << depth;
+  for (int n = 0; n < nleaf; n++) {
+    if (tid == 0) { unsigned pm = ts->pmask; ts->leaf_id = pool_alloc(pm, PT_NPP); ts->pmask = pm; }
+    __syncthreads();
+    hook.leaf_start(c);
+    const double e = dir ? eps : -eps;
+    const int sel = ts->qsel[dir];              // buffer holding this leaf's position
+    const unsigned s_leaf = c.soff(V_POOLP + ts->leaf_id);
+    const int pair = n & 1, m_leaf = __builtin_ctz(~(unsigned)n);
+    LeapPolicy lp{c.st, c.soff((sel ? V_QB0 : V_QA0) + dir), c.soff((sel ? V_QA0 : V_QB0) + dir), c.soff(V_PH0 + dir), c.soff(V_MINV),
+                  s_leaf, 0.5 * e, e, c.soff(V_POOLP + (pair ? ts->pend_beg[0] : ts->leaf_id)), m_leaf == 1 ? c.soff(V_RHOLEV + 1) : c.soff(V_SCR1),
+                  pair, {0.0, 0.0, 0.0}};
+    const double lpv = model_pass(c.M, c.lds, c.pst, lp);
+    CPROF_START(c);
+    CPROF_COUNT(c, PF_LEAVES);
+    if (tid == 0) {
+      double h;
+      const double wgt = rule_leaf(ts, lp.extra[0], lpv, h);
+      ts->cur_beg = ts->cur_end = ts->leaf_id;
+      ts->cur_lsw = wgt; ts->cur_prop = -1; ts->cur_lp = lpv; ts->cur_h = h;
+      ts->abort = ts->divergent | hook.ext(ts);
+      ts->m = __builtin_ctz(~(unsigned)n);
+      ts->qsel[dir] = sel ^ 1;                  // the next leaf of this end reads the buffer just written
+    }
+    __syncthreads();
+    CPROF_MARK(c, PF_LEAF_SCALAR);
+    if (ts->abort) return false;
+    const int m = ts->m;
+    for (int j = 1; j <= m; j++) {
+      const int ib = ts->pend_beg[j - 1], ie = ts->pend_end[j - 1], cb = ts->cur_beg, ce = ts->cur_end;
+      const unsigned a_rho = j == 1 ? c.soff(V_POOLP + ib) : c.soff(V_RHOLEV + j - 1);
+      const unsigned b_rho = j == 1 ? c.soff(V_POOLP + cb) : c.soff(V_SCR0 + ((j - 1) & 1));
+      const unsigned out = j == m ? c.soff(V_RHOLEV + j) : c.soff(V_SCR0 + (j & 1));
+      // (level 1 came out of the leaf's epilogue: begin = end = rho on both sides, so v0 = v2 = v4 and v1 = v3 = v5)
+      const bool persist = j == 1 ? (lp.extra[1] > 0 && lp.extra[2] > 0)
+                                  : vop_merge(c, c.soff(V_POOLP + ib), c.soff(V_POOLP + ie), a_rho, c.soff(V_POOLP + cb), c.soff(V_POOLP + ce), b_rho, out);
+      CPROF_COUNT(c, PF_MERGES);
+      if (tid == 0)
+        rule_merge_step(ts, j, ib, ie, cb, ce, persist, [&] {
+          return rng_uniform(c.key, iter, RNG_SUB_ACCEPT, 0, ((uint32_t)depth << 24) | ((uint32_t)j << 16) | (uint32_t)(n >> j));
+        });
+      __syncthreads();
+      CPROF_MARK(c, PF_MERGE);
+      if (ts->abort) return false;
+    }
+    if (tid == 0) {
+      int cq = -1, prop = ts->cur_prop;
+      if (prop < 0) { // the leaf itself is this subtree's proposal: keep its position
+        unsigned qm = ts->qmask;
+        const int id = pool_alloc(qm, PT_NPQ);
+        ts->qmask = qm;
+        ts->q_lp[id] = ts->cur_lp; ts->q_h[id] = ts->cur_h;
+        prop = id; cq = id;
+      }
+      ts->copy_q_id = cq;
+      ts->pend_beg[m] = ts->cur_beg; ts->pend_end[m] = ts->cur_end; ts->pend_lsw[m] = ts->cur_lsw; ts->pend_prop[m] = prop;
+    }
+    __syncthreads();
+    if (ts->copy_q_id >= 0) vop_copy(c, c.soff(V_POOLQ + ts->copy_q_id), c.soff((sel ? V_QB0 : V_QA0) + dir));
+    CPROF_MARK(c, PF_COPYQ);
+  }
+  return true;
+}
+
+// Part 2 (the hot loop, inlined into the kernel): doublings, each a subtree merged into the trajectory.
 __device__ __forceinline__ void transition_tree(const Chain &c, uint32_t iter) {
   ltp ts = c.ts;
   const int tid = c.tid;
@@ -416,89 +484,7 @@ __device__ __forceinline__ void transition_tree(const Chain &c, uint32_t iter) {
     CPROF_START(c);
     vop_copy(c, c.soff(V_PNEAR), c.soff(V_PF0 + dir));
     CPROF_MARK(c, PF_PNEAR);
-    bool valid = true;
-    const int nleaf = 1 << depth;
-    for (int n = 0; n < nleaf; n++) {
-      if (tid == 0) { unsigned pm = ts->pmask; ts->leaf_id = pool_alloc(pm, PT_NPP); ts->pmask = pm; }
-      __syncthreads();
-      const double e = dir ? eps : -eps;
-      const int sel = ts->qsel[dir];              // buffer holding this leaf's position
-      const unsigned s_leaf = c.soff(V_POOLP + ts->leaf_id);
-      const int pair = n & 1, m_leaf = __builtin_ctz(~(unsigned)n);
-      LeapPolicy lp{c.st, c.soff((sel ? V_QB0 : V_QA0) + dir), c.soff((sel ? V_QA0 : V_QB0) + dir), c.soff(V_PH0 + dir), c.soff(V_MINV),
-                    s_leaf, 0.5 * e, e, c.soff(V_POOLP + (pair ? ts->pend_beg[0] : ts->leaf_id)), m_leaf == 1 ? c.soff(V_RHOLEV + 1) : c.soff(V_SCR1),
-                    pair, {0.0, 0.0, 0.0}};
-      const double lpv = model_pass(c.M, c.lds, c.pst, lp);
-      CPROF_START(c);
-      CPROF_COUNT(c, PF_LEAVES);
-      if (tid == 0) {
-        const double H0 = ts->H0;
-        double h = 0.5 * lp.extra[0] - lpv;
-        if (isnan(h)) h = INFINITY;
-        const int div = (h - H0 > 1000.0) ? 1 : ts->divergent;
-        ts->divergent = div;
-        const double wgt = H0 - h;
-        ts->sum_metro += wgt > 0 ? 1.0 : exp(wgt);
-        ts->n_leap += 1;
-        ts->cur_beg = ts->cur_end = ts->leaf_id;
-        ts->cur_lsw = wgt; ts->cur_prop = -1; ts->cur_lp = lpv; ts->cur_h = h;
-        ts->abort = div;
-        ts->m = __builtin_ctz(~(unsigned)n);
-        ts->qsel[dir] = sel ^ 1;                  // the next leaf of this end reads the buffer just written
-      }
-      __syncthreads();
-      CPROF_MARK(c, PF_LEAF_SCALAR);
-      if (ts->abort) { valid = false; break; }
-      const int m = ts->m;
-      for (int j = 1; j <= m; j++) {
-        const int ib = ts->pend_beg[j - 1], ie = ts->pend_end[j - 1], cb = ts->cur_beg, ce = ts->cur_end;
-        const unsigned a_rho = j == 1 ? c.soff(V_POOLP + ib) : c.soff(V_RHOLEV + j - 1);
-        const unsigned b_rho = j == 1 ? c.soff(V_POOLP + cb) : c.soff(V_SCR0 + ((j - 1) & 1));
-        const unsigned out = j == m ? c.soff(V_RHOLEV + j) : c.soff(V_SCR0 + (j & 1));
-        // (level 1 came out of the leaf's epilogue: begin = end = rho on both sides, so v0 = v2 = v4 and v1 = v3 = v5)
-        const bool persist = j == 1 ? (lp.extra[1] > 0 && lp.extra[2] > 0)
-                                    : vop_merge(c, c.soff(V_POOLP + ib), c.soff(V_POOLP + ie), a_rho, c.soff(V_POOLP + cb), c.soff(V_POOLP + ce), b_rho, out);
-        CPROF_COUNT(c, PF_MERGES);
-        if (tid == 0) {
-          const double cur_lsw = ts->cur_lsw;
-          const double lsw_sub = d_lse(ts->pend_lsw[j - 1], cur_lsw);
-          bool take_final;
-          if (cur_lsw > lsw_sub) take_final = true;
-          else {
-            const uint32_t slot = ((uint32_t)depth << 24) | ((uint32_t)j << 16) | (uint32_t)(n >> j);
-            take_final = rng_uniform(c.key, iter, RNG_SUB_ACCEPT, 0, slot) < exp(cur_lsw - lsw_sub);
-          }
-          unsigned qm = ts->qmask, pm = ts->pmask;
-          if (take_final) pool_free(qm, ts->pend_prop[j - 1]);
-          else { pool_free(qm, ts->cur_prop); ts->cur_prop = ts->pend_prop[j - 1]; }
-          if (ie != ib) pool_free(pm, ie);
-          if (cb != ce) pool_free(pm, cb);
-          ts->qmask = qm; ts->pmask = pm;
-          ts->cur_beg = ib;
-          ts->cur_lsw = lsw_sub;
-          ts->abort = !persist;
-        }
-        __syncthreads();
-        CPROF_MARK(c, PF_MERGE);
-        if (ts->abort) { valid = false; break; }
-      }
-      if (!valid) break;
-      if (tid == 0) {
-        int cq = -1, prop = ts->cur_prop;
-        if (prop < 0) { // the leaf itself is this subtree's proposal: keep its position
-          unsigned qm = ts->qmask;
-          const int id = pool_alloc(qm, PT_NPQ);
-          ts->qmask = qm;
-          ts->q_lp[id] = ts->cur_lp; ts->q_h[id] = ts->cur_h;
-          prop = id; cq = id;
-        }
-        ts->copy_q_id = cq;
-        ts->pend_beg[m] = ts->cur_beg; ts->pend_end[m] = ts->cur_end; ts->pend_lsw[m] = ts->cur_lsw; ts->pend_prop[m] = prop;
-      }
-      __syncthreads();
-      if (ts->copy_q_id >= 0) vop_copy(c, c.soff(V_POOLQ + ts->copy_q_id), c.soff((sel ? V_QB0 : V_QA0) + dir));
-      CPROF_MARK(c, PF_COPYQ);
-    }
+    const bool valid = build_subtree(c, iter, depth, dir, eps, NoLeafHook{});
     if (tid == 0) ts->sum_metro += ts->metro_base;
     if (!valid) break;
     // merge the finished subtree with the old trajectory (the checks at the end of transition())
@@ -507,19 +493,7 @@ __device__ __forceinline__ void transition_tree(const Chain &c, uint32_t iter) {
     const unsigned n_rho = depth == 0 ? c.soff(V_POOLP + nb) : c.soff(V_RHOLEV + depth);
     const bool persist = vop_merge(c, c.soff(V_PF1 - dir), c.soff(V_PNEAR), c.soff(V_RHOTOP), c.soff(V_POOLP + nb), c.soff(V_POOLP + ne),
                                    n_rho, c.soff(V_RHOTOP));
-    if (tid == 0) {
-      ts->depth = depth + 1;
-      const double lsw_sub = ts->pend_lsw[depth], lsw = ts->lsw;
-      bool accept;
-      if (lsw_sub > lsw) accept = true;
-      else accept = rng_uniform(c.key, iter, RNG_TOP_ACCEPT, 0, (uint32_t)depth) < exp(lsw_sub - lsw);
-      unsigned qm = ts->qmask;
-      if (accept) { pool_free(qm, ts->sample_qid); ts->sample_qid = ts->pend_prop[depth]; }
-      else pool_free(qm, ts->pend_prop[depth]);
-      ts->qmask = qm;
-      ts->lsw = d_lse(lsw, lsw_sub);
-      if (!persist) ts->stop = 1;
-    }
+    if (tid == 0) rule_top_accept(ts, depth, persist, [&] { return rng_uniform(c.key, iter, RNG_TOP_ACCEPT, 0, (uint32_t)depth); });
     CPROF_MARK(c, PF_MERGE);
   }
   __syncthreads();
@@ -544,22 +518,7 @@ __device__ __forceinline__ void init_stepsize(const Chain &c, uint32_t iter) {
     vop_prekick(c, c.soff(V_QC), c.soff(V_PC), c.soff(V_GC), c.soff(V_PH1), c.soff(V_QA1), c.soff(V_PF1), 0.5 * eps, eps);
     LeapPolicy lp{c.st, c.soff(V_QA1), c.soff(V_QB1), c.soff(V_PH1), c.soff(V_MINV), c.soff(V_SCR0), 0.5 * eps, eps, c.soff(V_SCR0), c.soff(V_SCR1), 0, {0.0, 0.0, 0.0}};
     const double lpv = model_pass(c.M, c.lds, c.pst, lp);
-    if (tid == 0) {
-      double h = 0.5 * lp.extra[0] - lpv;
-      if (isnan(h)) h = INFINITY;
-      const double delta_H = H0 - h, thr = log(0.8);
-      if (attempt == 0) ts->direction = delta_H > thr ? 1 : -1;
-      else {
-        const int dirn = ts->direction;
-        if (dirn == 1 && !(delta_H > thr)) ts->done = 1;
-        else if (dirn == -1 && !(delta_H < thr)) ts->done = 1;
-        else {
-          const double ne = dirn == 1 ? 2.0 * eps : 0.5 * eps;
-          c.sc->nom_eps = ne;
-          if (ne > 1e7 || ne == 0) { ts->done = 1; c.sc->status = POTUS_ERR_STEPSIZE; } // upstream throws here
-        }
-      }
-    }
+    if (tid == 0) rule_init_stepsize_verdict(ts, c.sc, attempt == 0, H0, lp.extra[0], lpv, eps);
     __syncthreads();
     if (ts->done) break;
   }
@@ -573,25 +532,11 @@ __device__ __forceinline__ void adapt_after_transition(const Chain &c, uint32_t 
   gsc sc = c.sc;
   const int tid = c.tid;
   if (tid == 0) {
-    // stepsize_adaptation::learn_stepsize
-    const double cnt = sc->ad_counter + 1;
-    sc->ad_counter = cnt;
-    const double as = ts->accept_stat > 1 ? 1.0 : ts->accept_stat;
-    const double eta = 1.0 / (cnt + c.t0);
-    const double s_bar = (1.0 - eta) * sc->s_bar + eta * (c.delta - as);
-    sc->s_bar = s_bar;
-    const double x = sc->mu - s_bar * sqrt(cnt) / c.gamma;
-    const double x_eta = pow(cnt, -c.kappa);
-    sc->x_bar = (1.0 - x_eta) * sc->x_bar + x_eta * x;
-    sc->nom_eps = exp(x);
+    rule_learn_stepsize(sc, ts->accept_stat, c.delta, c.gamma, c.kappa, c.t0);
     // var_adaptation::learn_variance window logic
-    const int nw = c.num_warmup, ib = c.init_buffer, tb = c.term_buffer, wc = sc->win_counter;
-    int fa = 0, fb = 0;
-    if (nw >= 20) {
-      fa = wc >= ib && wc < nw - tb && wc != nw;
-      fb = wc == sc->win_next && wc != nw;
-      if (fa) sc->wf_n += 1;
-    }
+    int fa, fb;
+    rule_window_flags(c.num_warmup, c.init_buffer, c.term_buffer, sc->win_counter, sc->win_next, fa, fb);
+    if (fa) sc->wf_n += 1;
     ts->flag_a = fa; ts->flag_b = fb;
   }
   __syncthreads();
@@ -616,16 +561,8 @@ __device__ __forceinline__ void adapt_after_transition(const Chain &c, uint32_t 
   __syncthreads();
   if (tid == 0 && c.num_warmup >= 20) {
     if (end_window) { // windowed_adaptation::compute_next_window
-      const int last = c.num_warmup - c.term_buffer - 1;
       int wn = sc->win_next, wsz = sc->win_size;
-      if (wn != last) {
-        wsz *= 2;
-        wn = sc->win_counter + wsz;
-        if (wn != last) {
-          const int boundary = wn + 2 * wsz;
-          if (boundary >= c.num_warmup - c.term_buffer) wn = last;
-        }
-      }
+      rule_next_window(c.num_warmup, c.term_buffer, sc->win_counter, wn, wsz);
       sc->win_next = wn; sc->win_size = wsz;
       sc->wf_n = 0;
     }
@@ -639,9 +576,9 @@ __device__ __forceinline__ void adapt_after_transition(const Chain &c, uint32_t 
     if (tid == 0) sc->lp_cur = lpq;
     __syncthreads();
     init_stepsize(c, iter);
-    if (tid == 0) { sc->mu = log(10.0 * sc->nom_eps); sc->s_bar = 0; sc->x_bar = 0; sc->ad_counter = 0; }
+    if (tid == 0) rule_restart_stepsize(sc);
     __syncthreads();
   }
-  if (tid == 0 && (int)iter == c.num_warmup - 1) sc->nom_eps = exp(sc->x_bar); // complete_adaptation
+  if (tid == 0 && (int)iter == c.num_warmup - 1) rule_complete_adaptation(sc);
   __syncthreads();
 }

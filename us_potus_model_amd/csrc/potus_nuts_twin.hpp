@@ -6,7 +6,7 @@
 // in its own state block (block chain + side * chains of RunParams::state / scal); the bookkeeping of transition() -- accept
 // step of the new subtree, rho over the whole trajectory, the U-turn checks across it -- is a "combine" taken strictly in
 // doubling order by the side that built the subtree, with the trajectory-level state travelling as TT_N tagged words through
-// the chain's mailbox (RunParams::twbuf).  This file is that protocol on top of potus_nuts.hpp's tree loop; the mailbox
+// the chain's mailbox (RunParams::twbuf).  This file is that protocol on top of potus_nuts.hpp's build_subtree; the mailbox
 // helpers (tw_*), the word layout (TT_*, TWB_*) and the watchdog are potus_cluster.hpp's.
 // Same arithmetic in the same order as the one-workgroup sampler (which sums the metropolis terms per doubling for that
 // reason): the draws of the two are the same bytes.
@@ -49,6 +49,22 @@ struct Tw1Args { const DevModel *Mg; const RunParams *Rg; int chain, side; unsig
 
 __device__ __noinline__ void cold_twin1_combine(const DevModel *Mg, const RunParams *Rg, int chain_, int side_, unsigned launch_, uint32_t iter_,
                                                 int depth_, int valid_);
+
+// What the twin adds to a leaf of build_subtree: has the trajectory ended at the other end?  One look per leaf, by the last
+// wave while the others start the pass; a subtree of a trajectory that is over is dropped at its combine.
+struct Tw1LeafHook {
+  const Xch &x; const Tw1Args &ta; uint32_t iter;
+  __device__ __forceinline__ void leaf_start(const Chain &c) const {
+    if (c.tid >= PT_THREADS - 64) {
+      CRp R = (CRp)uni_ptr(ta.Rg);
+      const Twin t = make_twin(R, ta.chain, ta.side, x.launch, iter);
+      double sv;
+      const bool over = tw_try(t, TWB_STOP, 1, t.ittag, sv);
+      if (c.tid == PT_THREADS - 64) c.ts->tw_ext = over ? 1 : 0;
+    }
+  }
+  __device__ __forceinline__ int ext(ltp ts) const { return ts->tw_ext; }
+};
 
 // The doublings of one transition that go this side's way, each followed by its combine.
 __device__ __forceinline__ void transition_tree_twin(const Chain &c, const Xch &x, const Tw1Args &ta, uint32_t iter) {
@@ -97,90 +113,7 @@ __device__ __forceinline__ void transition_tree_twin(const Chain &c, const Xch &
     __syncthreads();
     const int dir = side;
     vop_copy_s<false, true>(c, c.soff(V_PNEAR), c.soff(V_PF0 + dir));   // (the end momentum was stored write-through by the last combine)
-    bool valid = true;
-    const int nleaf = 1 << depth;
-    for (int n = 0; n < nleaf; n++) {
-      if (tid == 0) { unsigned pm = ts->pmask; ts->leaf_id = pool_alloc(pm, PT_NPP); ts->pmask = pm; }
-      __syncthreads();
-      if (tid >= PT_THREADS - 64) {
-        // has the trajectory ended at the other end?  One look per leaf, by this wave while the others start the pass
-        CRp R = (CRp)uni_ptr(ta.Rg);
-        const Twin t = make_twin(R, ta.chain, side, x.launch, iter);
-        double sv;
-        const bool over = tw_try(t, TWB_STOP, 1, t.ittag, sv);
-        if (tid == PT_THREADS - 64) ts->tw_ext = over ? 1 : 0;
-      }
-      const double e = dir ? eps : -eps;
-      const int sel = ts->qsel[dir];              // buffer holding this leaf's position
-      const unsigned s_leaf = c.soff(V_POOLP + ts->leaf_id);
-      const int pair = n & 1, m_leaf = __builtin_ctz(~(unsigned)n);
-      LeapPolicy lp{c.st, c.soff((sel ? V_QB0 : V_QA0) + dir), c.soff((sel ? V_QA0 : V_QB0) + dir), c.soff(V_PH0 + dir), c.soff(V_MINV),
-                    s_leaf, 0.5 * e, e, c.soff(V_POOLP + (pair ? ts->pend_beg[0] : ts->leaf_id)), m_leaf == 1 ? c.soff(V_RHOLEV + 1) : c.soff(V_SCR1),
-                    pair, {0.0, 0.0, 0.0}};
-      const double lpv = model_pass(c.M, c.lds, c.pst, lp);
-      if (tid == 0) {
-        const double H0 = ts->H0;
-        double h = 0.5 * lp.extra[0] - lpv;
-        if (isnan(h)) h = INFINITY;
-        const int div = (h - H0 > 1000.0) ? 1 : ts->divergent;
-        ts->divergent = div;
-        const double wgt = H0 - h;
-        ts->sum_metro += wgt > 0 ? 1.0 : exp(wgt);
-        ts->n_leap += 1;
-        ts->cur_beg = ts->cur_end = ts->leaf_id;
-        ts->cur_lsw = wgt; ts->cur_prop = -1; ts->cur_lp = lpv; ts->cur_h = h;
-        ts->abort = div | ts->tw_ext;             // (a trajectory that is over: this subtree is dropped at its combine)
-        ts->m = __builtin_ctz(~(unsigned)n);
-        ts->qsel[dir] = sel ^ 1;                  // the next leaf of this end reads the buffer just written
-      }
-      __syncthreads();
-      if (ts->abort) { valid = false; break; }
-      const int m = ts->m;
-      for (int j = 1; j <= m; j++) {
-        const int ib = ts->pend_beg[j - 1], ie = ts->pend_end[j - 1], cb = ts->cur_beg, ce = ts->cur_end;
-        const unsigned a_rho = j == 1 ? c.soff(V_POOLP + ib) : c.soff(V_RHOLEV + j - 1);
-        const unsigned b_rho = j == 1 ? c.soff(V_POOLP + cb) : c.soff(V_SCR0 + ((j - 1) & 1));
-        const unsigned out = j == m ? c.soff(V_RHOLEV + j) : c.soff(V_SCR0 + (j & 1));
-        const bool persist = j == 1 ? (lp.extra[1] > 0 && lp.extra[2] > 0)      // (level 1 came out of the leaf's epilogue)
-                                    : vop_merge(c, c.soff(V_POOLP + ib), c.soff(V_POOLP + ie), a_rho, c.soff(V_POOLP + cb), c.soff(V_POOLP + ce), b_rho, out);
-        if (tid == 0) {
-          const double cur_lsw = ts->cur_lsw;
-          const double lsw_sub = d_lse(ts->pend_lsw[j - 1], cur_lsw);
-          bool take_final;
-          if (cur_lsw > lsw_sub) take_final = true;
-          else {
-            const uint32_t slot = ((uint32_t)depth << 24) | ((uint32_t)j << 16) | (uint32_t)(n >> j);
-            take_final = rng_uniform(c.key, iter, RNG_SUB_ACCEPT, 0, slot) < exp(cur_lsw - lsw_sub);
-          }
-          unsigned qm = ts->qmask, pm = ts->pmask;
-          if (take_final) pool_free(qm, ts->pend_prop[j - 1]);
-          else { pool_free(qm, ts->cur_prop); ts->cur_prop = ts->pend_prop[j - 1]; }
-          if (ie != ib) pool_free(pm, ie);
-          if (cb != ce) pool_free(pm, cb);
-          ts->qmask = qm; ts->pmask = pm;
-          ts->cur_beg = ib;
-          ts->cur_lsw = lsw_sub;
-          ts->abort = !persist;
-        }
-        __syncthreads();
-        if (ts->abort) { valid = false; break; }
-      }
-      if (!valid) break;
-      if (tid == 0) {
-        int cq = -1, prop = ts->cur_prop;
-        if (prop < 0) { // the leaf itself is this subtree's proposal: keep its position
-          unsigned qm = ts->qmask;
-          const int id = pool_alloc(qm, PT_NPQ);
-          ts->qmask = qm;
-          ts->q_lp[id] = ts->cur_lp; ts->q_h[id] = ts->cur_h;
-          prop = id; cq = id;
-        }
-        ts->copy_q_id = cq;
-        ts->pend_beg[m] = ts->cur_beg; ts->pend_end[m] = ts->cur_end; ts->pend_lsw[m] = ts->cur_lsw; ts->pend_prop[m] = prop;
-      }
-      __syncthreads();
-      if (ts->copy_q_id >= 0) vop_copy(c, c.soff(V_POOLQ + ts->copy_q_id), c.soff((sel ? V_QB0 : V_QA0) + dir));
-    }
+    const bool valid = build_subtree(c, iter, depth, dir, eps, Tw1LeafHook{x, ta, iter});
     cold_twin1_combine(ta.Mg, ta.Rg, ta.chain, side, ta.launch, iter, depth, valid ? 1 : 0);
     depth++;
   }
