@@ -477,6 +477,35 @@ potus_laplace <- function(data, mode, variant = c("full", "no_mode_adjustment"),
        min_pivot = info4[, 4], precision = if (isTRUE(precision)) array(r$precision, c(D, D, modes)) else NULL)
 }
 
+# ---- Pathfinder (DESIGN.md section 4o): cmdstanr's model$pathfinder(data, num_paths = 4, draws = 1000, psis_resample = FALSE) ----
+# `paths` L-BFGS paths from init (a radius, or a matrix [paths, D] of unconstrained starts), a normal approximation around every iterate, the
+# ELBO of each from num_elbo_draws draws, and ceiling(draws / paths) draws per path from the path's best iterate.  Returns q [paths * draws per
+# path, D] (path-major), lp, lq, log_ratio = lp - lq, and per path return_code (0 ok, 1 NO_ELBO: NaN draws), iterations, best_iteration,
+# optimize_code, elbo [paths, max_lbfgs_iters + 1] indexed by the iterate (column l + 1 is iterate l) and kept, the pairs the history may use.
+potus_pathfinder <- function(data, variant = c("full", "no_mode_adjustment"), paths = 4, draws = 1000, init = 2, seed = 1843, history_size = 6,
+                             num_elbo_draws = 25, max_lbfgs_iters = 1000, lbfgs_history_size = 5, init_alpha = 1e-3, tol_obj = 1e-12, tol_rel_obj = 1e4,
+                             tol_grad = 1e-8, tol_rel_grad = 1e7, tol_param = 1e-8, draw_offset = 0, path_offset = 0, device = 0) {
+  variant <- match.arg(variant)
+  q0 <- if (is.matrix(init)) init else NULL
+  if (!is.null(q0)) paths <- nrow(q0)
+  radius <- if (is.null(q0)) init else 2
+  res <- .potus_create(data, variant, c(1L, 0L, 0L, 0L, 10L, as.integer(device), 0L, 1L, 0L, 0L, 0L, 0L), c(0.8, 0.05, 0.75, 10, 1, radius, seed))
+  .potus_check(res$status)
+  on.exit(.C("potus_R_destroy", res$handle, status = integer(1)))
+  D <- .C("potus_R_num_columns", res$handle, D = integer(1), n_cols = integer(1), status = integer(1))$D
+  m <- as.integer(ceiling(draws / paths)); n <- paths * m; rows <- as.integer(max_lbfgs_iters) + 1L
+  r <- .C("potus_R_pathfinder", res$handle,
+          as.integer(c(history_size, num_elbo_draws, m, draw_offset, path_offset, max_lbfgs_iters, lbfgs_history_size, paths, !is.null(q0))),
+          as.double(c(init_alpha, tol_obj, tol_rel_obj, tol_grad, tol_rel_grad, tol_param)), if (is.null(q0)) double(1) else as.double(t(q0)),
+          info = integer(4 * paths), elbo = double(paths * rows), kept = integer(paths * rows), q = double(max(n * D, 1)), lp = double(max(n, 1)),
+          lq = double(max(n, 1)), status = integer(1))
+  .potus_check(r$status)
+  info4 <- matrix(r$info, paths, 4, byrow = TRUE)
+  list(q = matrix(r$q[seq_len(n * D)], n, D, byrow = TRUE), lp = r$lp[seq_len(n)], lq = r$lq[seq_len(n)], log_ratio = r$lp[seq_len(n)] - r$lq[seq_len(n)],
+       return_code = info4[, 1], iterations = info4[, 2], best_iteration = info4[, 3], optimize_code = info4[, 4],
+       elbo = matrix(r$elbo, paths, rows, byrow = TRUE), kept = matrix(r$kept, paths, rows, byrow = TRUE))
+}
+
 # ---- joint election outcomes (us_potus_model_amd/outcomes.py is the same in Python; DESIGN.md section 4f) ----
 # What the run scripts compute from the JOINT outcome of a draw, counted on the device over the post-warm-up draws of every chain of the fit:
 # the distribution of Democratic electoral votes (final_2016.R:904-920), the tipping-point state (final_2012.R:809-843), how often states i and j

@@ -473,6 +473,53 @@ int potus_laplace_scores_device(int handle, int day_begin, int day_end, void *ou
 int potus_laplace_summary(int handle, int day_begin, int day_end, const double *ev, int ev_to_win,
                           double *state_out, double *natl_out, double *ev_out, int32_t *n_draws_out);
 int potus_laplace_timing(double *ms /*[4]: Hessian, factor, solve, lp__; HIP events, calling thread's last potus_laplace*/);
+/* ---- Pathfinder: cmdstanr's $pathfinder(psis_resample = FALSE), Zhang, Carpenter, Gelman and Vehtari (2022) ----
+ * Along an L-BFGS path x_0 .. x_L of log_prob<jacobian = true> with gradients g_l, s_l = x_l - x_{l-1}, z_l = g_{l-1} - g_l: pair l is kept
+ * when s'z > 0 and z'z <= 1e12 s'z; alpha_0 = 1 and a kept pair updates the diagonal, with a = z'diag(alpha)z, b = z's, c = s'diag(alpha)^-1 s
+ * at alpha_{l-1}, to alpha_l = 1 / (a / (b alpha) + z^2 / b - a s^2 / (b c alpha^2)) elementwise.  With S, Z the last min(history_size, kept so
+ * far) kept pairs up to l (oldest first), R = triu(S'Z), E = diag(S'Z), beta = [diag(alpha_l) Z, S],
+ * gamma = [[0, -R^-1], [-R^-T, R^-T (E + Z'diag(alpha_l)Z) R^-1]]: Sigma_l = diag(alpha_l) + beta gamma beta', mu_l = x_l + Sigma_l g_l.
+ * Draws: thin QR diag(alpha_l^-1/2) beta = Q R~, L~ = chol(I + R~ gamma R~'), phi = mu_l + alpha_l^1/2 (u + Q (L~ - I) Q'u),
+ * log q(phi) = -1/2 (sum log alpha_l + 2 sum log L~_ii + u'u + D log 2 pi).  ELBO_l, l = 1 .. L: the mean over num_elbo_draws draws of
+ * log p(phi) - log q(phi); a non-finite log p in any of them, or a Sigma_l that is not positive definite, makes it -inf.  l* = argmax, the
+ * lowest l on ties; the path's num_draws draws come from (mu_l*, Sigma_l*).  Every ELBO -inf: the path's code is 1 (NO_ELBO), its draws are
+ * NaN, the call does not fail.  There is no D x D matrix: a fit costs O(D history_size^2), a draw O(D history_size) and one model pass.
+ * Normals, when the caller gives none: Philox4x32-10 as the sampler's, key = the handle's seed, the NEW purpose 9; coordinates 2 i, 2 i + 1 are
+ * the Box-Muller pair of counter
+ *   ELBO draw k of iterate l of path p    {i, 9 | k << 8, l, path_offset + p + 1}
+ *   final draw n of path p                {i, 9 | 0xFF << 8, draw_offset + n + 1, path_offset + p + 1}
+ * so a path's bytes depend on neither the batch, nor the number of draws asked for, nor the number of workgroups (environment variable
+ * POTUS_PATHFINDER_G, default: the compute units; tests).  Paths per handle as in potus_optimize: path p uses data set p / (n_paths / n_datasets).
+ * potus_pathfinder runs k_opt_lbfgs first (opt: potus_optimize's options; opt.jacobian is taken as 1 and opt.path_offset as path_offset;
+ * opt.iter is CmdStan's max_lbfgs_iters) and takes the accepted points as the path; potus_pathfinder_path takes the caller's x, g
+ * [n_paths][rows][D] with lengths L[p] <= rows - 1, and with u_elbo [n_paths][rows - 1][num_elbo_draws][D] / u_draws [n_paths][num_draws][D]
+ * the caller's normals; for want_l[p] it also returns mu, alpha and log det Sigma of that iterate (NaN outside 1 .. L; alpha from 0), the
+ * draws phi_out and their log q lqw_out that THAT iterate gives from the final normals (no model pass), and Q'Q of its thin QR (2j x 2j of a
+ * 20 x 20 block, NaN elsewhere).
+ * Outputs: info_out [n_paths][4] = code, L, l*, the optimiser's return code (0 from potus_pathfinder_path); elbo_out, kept_out
+ * [n_paths][rows] indexed by l (rows = opt.iter + 1 in potus_pathfinder; NaN / 0 outside 1 .. L); q_out [n_paths][num_draws][D]; lp_out: log_prob of
+ * the draw with the bytes of potus_log_prob_grad; lq_out: log q.  Any output but info_out may be NULL.  traj_x_out, traj_g_out
+ * [n_paths][opt.iter + 1][D] or NULL: the path itself, NaN behind its end.  The rows [lp__, six NaN, phi] of the last call stay on the handle for
+ * the three accessors, which are potus_laplace's with a path in the place of a mode.  Refused before any kernel runs, as in potus_optimize:
+ * cus_per_chain > 1, the dense metric (POTUS_ERR_UNSUPPORTED); history_size outside 1..10,
+ * num_elbo_draws outside 1..255, negative num_draws or offsets, n_paths no multiple of the data sets (POTUS_ERR_ARG).  No chain state is touched. */
+typedef struct potus_pathfinder_opts {
+  potus_optimize_opts opt;
+  int32_t history_size, num_elbo_draws, num_draws, draw_offset, path_offset, pad0;
+} potus_pathfinder_opts;   /* 88 bytes */
+void potus_default_pathfinder_opts(potus_pathfinder_opts *o);   /* opt: potus_optimize's with jacobian 1, iter 1000; 6, 25, 1000, 0, 0 */
+int potus_pathfinder(int handle, const potus_pathfinder_opts *o, const double *q0 /*[n_paths][D] or NULL*/, int n_paths, int32_t *info_out,
+                     double *elbo_out, int32_t *kept_out, double *q_out, double *lp_out, double *lq_out, double *traj_x_out, double *traj_g_out);
+int potus_pathfinder_path(int handle, const potus_pathfinder_opts *o, const double *x, const double *g, const int32_t *L, int rows, int n_paths,
+                          const double *u_elbo, const double *u_draws, const int32_t *want_l, int32_t *info_out, double *elbo_out,
+                          int32_t *kept_out, double *q_out, double *lp_out, double *lq_out, double *mu_out /*[n_paths][D]*/,
+                          double *alpha_out /*[n_paths][D]*/, double *logdet_out /*[n_paths]*/, double *phi_out /*[n_paths][num_draws][D]*/,
+                          double *lqw_out /*[n_paths][num_draws]*/, double *qtq_out /*[n_paths][20][20]*/);
+int potus_pathfinder_write_array_device(int handle, int col_begin, int col_end, void *out_device);
+int potus_pathfinder_scores_device(int handle, int day_begin, int day_end, void *out_device);
+int potus_pathfinder_summary(int handle, int day_begin, int day_end, const double *ev, int ev_to_win,
+                             double *state_out, double *natl_out, double *ev_out, int32_t *n_draws_out);
+int potus_pathfinder_timing(double *ms /*[4]: L-BFGS, alpha, ELBO, draws; HIP events, calling thread's last potus_pathfinder[_path]*/);
 /* Prior predictive simulation: n_sims draws theta ~ prior (poll_model_2020.stan:116-128) on the unconstrained scale (q_out [n_sims][D];
  * rho_e_bias ~ normal(0.7, 0.1) restricted to (0, 1), stored as logit(rho)) and y ~ binomial(n_two_share, inv_logit(logit_pi(theta)))
  * (stan:85-113; exact sampler: inversion when n min(p, 1 - p) < 10, BTRS above) in the caller's poll order.  Any output may be null.
@@ -619,6 +666,9 @@ void potus_R_cv_lpd(int *handle, int *held_state, int *held_national, int *integ
 void potus_R_optimize(int *handle, int *iopts /*[7]: jacobian, history_size, iter, path_offset, n_paths, q0 given, rows wanted*/,
                       double *dopts /*[6]: init_alpha, tol_obj, tol_rel_obj, tol_grad, tol_rel_grad, tol_param*/, double *q0, double *q_out, double *lp_out,
                       double *gnorm_out, int *info_out, int *cols /*[2]: col_begin, col_end*/, double *row_out, int *status);
+void potus_R_pathfinder(int *handle, int *iopts /*[9]: history_size, num_elbo_draws, num_draws, draw_offset, path_offset, max_lbfgs_iters, L-BFGS history, n_paths, q0 given*/,
+                        double *dopts /*[6]: init_alpha, tol_obj, tol_rel_obj, tol_grad, tol_rel_grad, tol_param*/, double *q0, int *info_out /*[n_paths][4]*/,
+                        double *elbo_out, int *kept_out /*[n_paths][max_lbfgs_iters + 1]*/, double *q_out, double *lp_out, double *lq_out, int *status);
 void potus_R_laplace(int *handle, int *iopts /*[6]: jacobian, draw_offset, n_modes, n_draws, u given, precision wanted*/, double *h, double *mode, double *u,
                      double *q_out, double *lp_out, double *lp_approx_out, double *info_out, double *precision_out, int *status);
 void potus_R_simulate_prior(int *handle, double *seed, int *dims /*[2]: n_sims, sim_offset*/, double *q_out, int *n_democrat_state_out,

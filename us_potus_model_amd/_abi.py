@@ -72,7 +72,17 @@ class PotusLaplaceOpts(C.Structure):
     ]
 
 
+class PotusPathfinderOpts(C.Structure):
+    """potus_pathfinder_opts (88 bytes); start from potus_default_pathfinder_opts()."""
+    _fields_ = [
+        ("opt", PotusOptimizeOpts),
+        ("history_size", C.c_int32), ("num_elbo_draws", C.c_int32), ("num_draws", C.c_int32), ("draw_offset", C.c_int32),
+        ("path_offset", C.c_int32), ("pad0", C.c_int32),
+    ]
+
+
 LAPLACE_CODES = {0: "OK", 1: "NOT_PD", 2: "NOT_FINITE"}
+PATHFINDER_CODES = {0: "OK", 1: "NO_ELBO"}
 OPTIMIZE_CODES = {1: "ABSF", 2: "RELF", 3: "ABSGRAD", 4: "RELGRAD", 5: "ABSX", 6: "MAXIT", 7: "LSFAIL", 8: "INIT"}
 
 

@@ -762,6 +762,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, c
 #include "potus_crossval.hpp"   // exact cross-validation: held-out polls under the draws of the data set that did not see them
 #include "potus_optimize.hpp"   // the posterior mode: batched L-BFGS, one workgroup per path
 #include "potus_laplace.hpp"    // the Laplace approximation at a mode: Hessian, factor, draws
+#include "potus_pathfinder.hpp" // Pathfinder: a normal around every iterate of an L-BFGS path, the best ELBO, draws
 
 // ======================================================================== host
 namespace {
@@ -934,6 +935,10 @@ struct Sampler {
   double *lap_rows = nullptr;
   int lap_modes = 0, lap_draws = 0;
   std::vector<int> lap_code;   // per mode: 0 = its rows are draws
+  // potus_pathfinder[_path]: the same for the last call's draws, [pf_paths][pf_draws][7 + D]
+  double *pf_rows = nullptr;
+  int pf_paths = 0, pf_draws = 0;
+  std::vector<int> pf_code;    // per path: 0 = its rows are draws
 };
 
 std::mutex g_mu;
@@ -2461,6 +2466,7 @@ int potus_destroy(int handle) {
   (void)hipStreamSynchronize(sp->stream);
   for (void *p : sp->allocs) (void)hipFree(p);
   if (sp->lap_rows) (void)hipFree(sp->lap_rows);
+  if (sp->pf_rows) (void)hipFree(sp->pf_rows);
   (void)hipEventDestroy(sp->ev0); (void)hipEventDestroy(sp->ev1); (void)hipStreamDestroy(sp->stream);
   if (sp->mv0) (void)hipEventDestroy(sp->mv0);
   if (sp->mv1) (void)hipEventDestroy(sp->mv1);
@@ -4308,20 +4314,20 @@ void potus_default_optimize_opts(potus_optimize_opts *o) {
   o->init_alpha = 1e-3; o->tol_obj = 1e-12; o->tol_rel_obj = 1e4; o->tol_grad = 1e-8; o->tol_rel_grad = 1e7; o->tol_param = 1e-8;
 }
 
-int potus_optimize(int handle, const potus_optimize_opts *opts, const double *q0, int n_paths, double *q_out, double *lp_out, double *gnorm_out,
-                   int32_t *info_out, int col_begin, int col_end, double *row_out) {
-  const char *what = "potus_optimize";
-  Sampler *sp = get(handle);
-  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
-  potus_optimize_opts o;
-  potus_default_optimize_opts(&o);
-  if (opts) o = *opts;
+namespace {
+// what every call that deals paths to a handle's data sets refuses first: the handle's layout, then the number of paths
+int paths_check(const Sampler *sp, const char *what, int n_paths) {
   if (sp->K != 1) return fail(POTUS_ERR_UNSUPPORTED, "%s: needs one workgroup per chain (cus_per_chain = 1); this handle runs %d per chain", what, sp->K);
   if (sp->dense) return fail(POTUS_ERR_UNSUPPORTED, "%s: the dense metric is not supported (metric = POTUS_METRIC_DIAG only)", what);
   if (!sp->k1_unsupported.empty()) return fail(POTUS_ERR_UNSUPPORTED, "%s: %s", what, sp->k1_unsupported.c_str());
   if (n_paths <= 0) return fail(POTUS_ERR_ARG, "%s: n_paths = %d, at least 1", what, n_paths);
   if (sp->n_ds && n_paths % sp->n_ds) return fail(POTUS_ERR_ARG, "%s: n_paths = %d is not a multiple of the handle's %d data sets", what, n_paths, sp->n_ds);
-  if (!q_out || !lp_out || !info_out) return fail(POTUS_ERR_ARG, "%s: null output (q_out, lp_out and info_out are required)", what);
+  return 0;
+}
+// what potus_optimize and potus_pathfinder refuse alike, before any kernel runs
+int opt_check(const Sampler *sp, const char *what, const potus_optimize_opts &o, int n_paths, const char *null_outputs) {
+  if (const int rc_ = paths_check(sp, what, n_paths)) return rc_;
+  if (null_outputs) return fail(POTUS_ERR_ARG, "%s: null output (%s are required)", what, null_outputs);
   if (o.history_size < 1 || o.history_size > OPT_MAX_HISTORY) return fail(POTUS_ERR_ARG, "%s: history_size = %d outside 1..%d", what, o.history_size, OPT_MAX_HISTORY);
   if (o.iter < 1) return fail(POTUS_ERR_ARG, "%s: iter = %d, at least 1", what, o.iter);
   const double tols[5] = {o.tol_obj, o.tol_rel_obj, o.tol_grad, o.tol_rel_grad, o.tol_param};
@@ -4330,47 +4336,74 @@ int potus_optimize(int handle, const potus_optimize_opts *opts, const double *q0
   if (!(o.init_alpha > 0.0) || !std::isfinite(o.init_alpha)) return fail(POTUS_ERR_ARG, "%s: init_alpha = %g, must be positive and finite", what, o.init_alpha);
   if (o.jacobian != 0 && o.jacobian != 1) return fail(POTUS_ERR_ARG, "%s: jacobian = %d, 0 or 1", what, o.jacobian);
   if (o.path_offset < 0 || (long long)o.path_offset + n_paths >= 0xFFFFFFFFll) return fail(POTUS_ERR_ARG, "%s: path_offset = %d with %d paths", what, o.path_offset, n_paths);
-  if (row_out) if (const int rc_ = check_cols(sp, col_begin, col_end)) return rc_;
-  const int D = sp->L.D, row = POTUS_N_SAMPLER_COLS + D, Dpad = (D + 7) & ~7, nvec = 2 * o.history_size + 5;
+  const int D = sp->L.D, Dpad = (D + 7) & ~7, nvec = 2 * o.history_size + 5;
   if ((unsigned long long)nvec * Dpad * 8ull >= 0x7fffffffull) return fail(POTUS_ERR_UNSUPPORTED, "%s: D = %d with history_size = %d: a path's working set must stay below 2 GB", what, D, o.history_size);
-  DeviceGuard guard;
-  DeviceLocks lock(sp->device);
-  HIP_TRY(hipSetDevice(sp->device));
+  return 0;
+}
+
+// One k_opt_lbfgs launch on the handle's stream, under the caller's device lock: the working set comes from `tmp`, the event pair is around the
+// kernel.  traj_x, traj_g [n_paths][traj_rows][Dpad] (or null): the accepted points and gradients of every path (potus_pathfinder).
+struct OptRun { double *rows = nullptr, *dlp = nullptr, *dgn = nullptr; int *dinfo = nullptr; int per_ds = 1; const DevModel *Mg = nullptr; };
+int opt_launch(Sampler *sp, const char *what, const potus_optimize_opts &o, const double *q0, int n_paths, DevBufs &tmp,
+               double *traj_x, double *traj_g, int traj_rows, EventTimer &ev, OptRun &r) {
+  const int D = sp->L.D, row = POTUS_N_SAMPLER_COLS + D, Dpad = (D + 7) & ~7, nvec = 2 * o.history_size + 5;
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_opt_lbfgs), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sp->lds_bytes));
-  DevBufs tmp;   // the working set is the call's own: the sampler's chain state is not touched
-  double *dq0 = nullptr, *work = nullptr, *rows = nullptr, *dlp = nullptr, *dgn = nullptr;
-  int *dinfo = nullptr;
+  double *dq0 = nullptr, *work = nullptr;
   int rc;
-  if ((rc = tmp.get(&work, (size_t)n_paths * nvec * Dpad * 8, what)) || (rc = tmp.get(&rows, (size_t)n_paths * row * 8, what)) ||
-      (rc = tmp.get(&dlp, (size_t)n_paths * 8, what)) || (rc = tmp.get(&dgn, (size_t)n_paths * 8, what)) || (rc = tmp.get(&dinfo, (size_t)n_paths * 3 * 4, what))) return rc;
+  if ((rc = tmp.get(&work, (size_t)n_paths * nvec * Dpad * 8, what)) || (rc = tmp.get(&r.rows, (size_t)n_paths * row * 8, what)) ||
+      (rc = tmp.get(&r.dlp, (size_t)n_paths * 8, what)) || (rc = tmp.get(&r.dgn, (size_t)n_paths * 8, what)) || (rc = tmp.get(&r.dinfo, (size_t)n_paths * 3 * 4, what))) return rc;
   if (q0) {
     if ((rc = tmp.get(&dq0, (size_t)n_paths * D * 8, what))) return rc;
     HIP_TRY(hipMemcpyAsync(dq0, q0, (size_t)n_paths * D * 8, hipMemcpyHostToDevice, sp->stream));
   }
-  EventTimer ev;
   HIP_TRY(ev.made);
   DsPlan pl;   // the models of the handle's data sets; the paths are dealt to them as chains are
   pl.of(sp);
-  const int per_ds = n_paths / pl.n_ds;
-  const DevModel *Mg = pl.Mg;
-  OptParams P{dq0, work, rows, dlp, dgn, dinfo, per_ds, o.history_size, o.iter, o.jacobian, o.path_offset, Dpad,
-              o.init_alpha, o.tol_obj, o.tol_rel_obj, o.tol_grad, o.tol_rel_grad, o.tol_param, sp->R.init_radius, sp->R.seed_lo, sp->R.seed_hi};
+  r.per_ds = n_paths / pl.n_ds;
+  r.Mg = pl.Mg;
+  OptParams P{dq0, work, r.rows, r.dlp, r.dgn, r.dinfo, r.per_ds, o.history_size, o.iter, o.jacobian, o.path_offset, Dpad,
+              o.init_alpha, o.tol_obj, o.tol_rel_obj, o.tol_grad, o.tol_rel_grad, o.tol_param, sp->R.init_radius, sp->R.seed_lo, sp->R.seed_hi,
+              traj_x, traj_g, traj_rows};
   OptParams *dP = nullptr;
   if ((rc = tmp.get(&dP, sizeof(OptParams), what))) return rc;
   HIP_TRY(hipMemcpyAsync(dP, &P, sizeof(OptParams), hipMemcpyHostToDevice, sp->stream));
   HIP_TRY(ev.start(sp->stream));
-  hipLaunchKernelGGL(k_opt_lbfgs, dim3(n_paths), dim3(PT_THREADS), sp->lds_bytes, sp->stream, Mg, (const OptParams *)dP);
+  hipLaunchKernelGGL(k_opt_lbfgs, dim3(n_paths), dim3(PT_THREADS), sp->lds_bytes, sp->stream, r.Mg, (const OptParams *)dP);
   HIP_TRY(hipGetLastError());
   HIP_TRY(ev.stop(sp->stream));
+  return 0;
+}
+} // namespace
+
+int potus_optimize(int handle, const potus_optimize_opts *opts, const double *q0, int n_paths, double *q_out, double *lp_out, double *gnorm_out,
+                   int32_t *info_out, int col_begin, int col_end, double *row_out) {
+  const char *what = "potus_optimize";
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  potus_optimize_opts o;
+  potus_default_optimize_opts(&o);
+  if (opts) o = *opts;
+  if (const int rc_ = opt_check(sp, what, o, n_paths, q_out && lp_out && info_out ? nullptr : "q_out, lp_out and info_out")) return rc_;
+  if (row_out) if (const int rc_ = check_cols(sp, col_begin, col_end)) return rc_;
+  const int D = sp->L.D, row = POTUS_N_SAMPLER_COLS + D;
+  DeviceGuard guard;
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  DevBufs tmp;   // the working set is the call's own: the sampler's chain state is not touched
+  EventTimer ev;
+  OptRun r;
+  int rc;
+  if ((rc = opt_launch(sp, what, o, q0, n_paths, tmp, nullptr, nullptr, 0, ev, r))) return rc;
+  double *rows = r.rows;
   std::vector<double> hrows((size_t)n_paths * row);
   HIP_TRY(hipMemcpyAsync(hrows.data(), rows, hrows.size() * 8, hipMemcpyDeviceToHost, sp->stream));
-  HIP_TRY(hipMemcpyAsync(lp_out, dlp, (size_t)n_paths * 8, hipMemcpyDeviceToHost, sp->stream));
-  if (gnorm_out) HIP_TRY(hipMemcpyAsync(gnorm_out, dgn, (size_t)n_paths * 8, hipMemcpyDeviceToHost, sp->stream));
-  HIP_TRY(hipMemcpyAsync(info_out, dinfo, (size_t)n_paths * 3 * 4, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipMemcpyAsync(lp_out, r.dlp, (size_t)n_paths * 8, hipMemcpyDeviceToHost, sp->stream));
+  if (gnorm_out) HIP_TRY(hipMemcpyAsync(gnorm_out, r.dgn, (size_t)n_paths * 8, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipMemcpyAsync(info_out, r.dinfo, (size_t)n_paths * 3 * 4, hipMemcpyDeviceToHost, sp->stream));
   if (row_out) {   // the CmdStan row of every path's point, built with the path's own model
     const int nsel = col_end - col_begin;
     WAParams W{RowSrc{rows, n_paths, 1, row, 0}, 1, sp->L.ncols, col_begin, col_end, nullptr, nullptr, nsel};   // one saved draw of n_paths chains
-    if ((rc = launch_rows(sp, tmp, what, Mg, sp->n_ds ? per_ds : 0, W))) return rc;
+    if ((rc = launch_rows(sp, tmp, what, r.Mg, sp->n_ds ? r.per_ds : 0, W))) return rc;
     HIP_TRY(hipMemcpyAsync(row_out, W.out, (size_t)n_paths * nsel * 8, hipMemcpyDeviceToHost, sp->stream));
   }
   HIP_TRY(hipStreamSynchronize(sp->stream));
@@ -4405,12 +4438,25 @@ struct LapSpans {
   }
 };
 
-// what the three accessors check first: a successful potus_laplace with draws on this handle
-int lap_have_rows(const char *what, const Sampler *sp) {
-  if (!sp->lap_rows || sp->lap_draws < 1) return fail(POTUS_ERR_STATE, "%s: no Laplace draws on this handle (potus_laplace with n_draws >= 1 first)", what);
+// The rows [lp__, six NaN, x] a handle keeps of its last potus_laplace (groups = modes) or potus_pathfinder[_path] (groups = paths): what the
+// three accessors of either read.  ONE body per accessor takes this view.
+struct KeptRows {
+  const char *missing;           // what to say when there are none
+  const char *group;             // "mode" or "path"
+  double *rows; int groups, draws; const std::vector<int> *code;
+  int n() const { return groups * draws; }
+  int per_ds(const Sampler *sp) const { return groups / std::max(sp->n_ds, 1) * draws; }   // rows per data set, group-major
+};
+enum { KEPT_LAPLACE = 0, KEPT_PATHFINDER = 1 };
+KeptRows kept_rows(const Sampler *sp, int which) {
+  if (which == KEPT_PATHFINDER) return KeptRows{"no Pathfinder draws on this handle (potus_pathfinder or potus_pathfinder_path with num_draws >= 1 first)", "path", sp->pf_rows, sp->pf_paths, sp->pf_draws, &sp->pf_code};
+  return KeptRows{"no Laplace draws on this handle (potus_laplace with n_draws >= 1 first)", "mode", sp->lap_rows, sp->lap_modes, sp->lap_draws, &sp->lap_code};
+}
+// what the three accessors check first: a successful call with draws on this handle
+int kept_have_rows(const char *what, const KeptRows &kr) {
+  if (!kr.rows || kr.draws < 1) return fail(POTUS_ERR_STATE, "%s: %s", what, kr.missing);
   return 0;
 }
-int lap_per_ds(const Sampler *sp) { return sp->lap_modes / std::max(sp->n_ds, 1) * sp->lap_draws; }   // rows per data set, mode-major
 } // namespace
 
 void potus_default_laplace_opts(potus_laplace_opts *o) {
@@ -4591,30 +4637,30 @@ int potus_laplace(int handle, const potus_laplace_opts *opts, const double *mode
   return 0;
 }
 
-int potus_laplace_write_array_device(int handle, int col_begin, int col_end, void *out_device) {
-  const char *what = "potus_laplace_write_array_device";
+namespace {
+int kept_write_array_device(const char *what, int which, int handle, int col_begin, int col_end, void *out_device) {
   Sampler *sp = get(handle);
   if (!sp || !out_device) return fail(POTUS_ERR_STATE, "bad handle or null output");
-  if (const int rc_ = lap_have_rows(what, sp)) return rc_;
+  const KeptRows kr = kept_rows(sp, which);
+  if (const int rc_ = kept_have_rows(what, kr)) return rc_;
   if (const int rc_ = check_cols(sp, col_begin, col_end)) return rc_;
   DeviceBlock dev;
   if (const int rc_ = dev.open(what, sp->device, out_device, "output")) return rc_;
   DevBufs tmp;
-  const int n = sp->lap_modes * sp->lap_draws, nsel = col_end - col_begin;
+  const int n = kr.n(), nsel = col_end - col_begin;
   DsPlan pl;
   pl.of(sp);
-  WAParams W{RowSrc{sp->lap_rows, n, 1, POTUS_N_SAMPLER_COLS + sp->L.D, 0}, 1, sp->L.ncols, col_begin, col_end, nullptr, (double *)out_device, nsel};   // one saved draw of n chains
-  if (const int rc_ = launch_rows(sp, tmp, what, pl.Mg, sp->n_ds ? lap_per_ds(sp) : 0, W)) return rc_;
+  WAParams W{RowSrc{kr.rows, n, 1, POTUS_N_SAMPLER_COLS + sp->L.D, 0}, 1, sp->L.ncols, col_begin, col_end, nullptr, (double *)out_device, nsel};   // one saved draw of n chains
+  if (const int rc_ = launch_rows(sp, tmp, what, pl.Mg, sp->n_ds ? kr.per_ds(sp) : 0, W)) return rc_;
   HIP_TRY(hipStreamSynchronize(sp->stream));
   return 0;
 }
 
-namespace {
-int lap_scores(Sampler *sp, int day_begin, int day_end, const int *dskip, double *out) {
-  const int n = sp->lap_modes * sp->lap_draws;
+int lap_scores(Sampler *sp, const KeptRows &kr, int day_begin, int day_end, const int *dskip, double *out) {
+  const int n = kr.n();
   DsPlan pl;
   pl.of(sp);
-  TlScoreParams P{RowSrc{sp->lap_rows, n, 1, POTUS_N_SAMPLER_COLS + sp->L.D, 0}, 1, lap_per_ds(sp), day_begin, day_end, dskip, out};
+  TlScoreParams P{RowSrc{kr.rows, n, 1, POTUS_N_SAMPLER_COLS + sp->L.D, 0}, 1, kr.per_ds(sp), day_begin, day_end, dskip, out};
   hipLaunchKernelGGL(k_tl_scores, dim3((unsigned)std::min<long long>(((long long)n + 3) / 4, 65535)), dim3(256), 0, sp->stream, pl.Mg, P);
   HIP_TRY(hipGetLastError());
   return 0;
@@ -4623,13 +4669,12 @@ int lap_check_days(const char *what, const Sampler *sp, int day_begin, int day_e
   if (day_begin < 0 || day_end > sp->M.T || day_begin >= day_end) return fail(POTUS_ERR_ARG, "%s: bad day range [%d,%d) of %d days", what, day_begin, day_end, sp->M.T);
   return 0;
 }
-} // namespace
 
-int potus_laplace_scores_device(int handle, int day_begin, int day_end, void *out_device) {
-  const char *what = "potus_laplace_scores_device";
+int kept_scores_device(const char *what, int which, int handle, int day_begin, int day_end, void *out_device) {
   Sampler *sp = get(handle);
   if (!sp || !out_device) return fail(POTUS_ERR_STATE, "bad handle or null output");
-  if (const int rc_ = lap_have_rows(what, sp)) return rc_;
+  const KeptRows kr = kept_rows(sp, which);
+  if (const int rc_ = kept_have_rows(what, kr)) return rc_;
   if (const int rc_ = lap_check_days(what, sp, day_begin, day_end)) return rc_;
   DeviceBlock dev;
   if (const int rc_ = dev.open(what, sp->device, out_device, "output")) return rc_;
@@ -4638,23 +4683,23 @@ int potus_laplace_scores_device(int handle, int day_begin, int day_end, void *ou
   const int n_ds = std::max(sp->n_ds, 1);
   if (const int rc_ = tmp.get(&dskip, (size_t)n_ds * 4, what)) return rc_;
   HIP_TRY(hipMemsetAsync(dskip, 0, (size_t)n_ds * 4, sp->stream));   // (a mode without a factor has NaN rows: its scores are NaN without a flag)
-  if (const int rc_ = lap_scores(sp, day_begin, day_end, dskip, (double *)out_device)) return rc_;
+  if (const int rc_ = lap_scores(sp, kr, day_begin, day_end, dskip, (double *)out_device)) return rc_;
   HIP_TRY(hipStreamSynchronize(sp->stream));
   return 0;
 }
 
-int potus_laplace_summary(int handle, int day_begin, int day_end, const double *ev, int ev_to_win, double *state_out, double *natl_out, double *ev_out, int32_t *n_draws_out) {
-  const char *what = "potus_laplace_summary";
+int kept_summary(const char *what, int which, int handle, int day_begin, int day_end, const double *ev, int ev_to_win, double *state_out, double *natl_out, double *ev_out, int32_t *n_draws_out) {
   Sampler *sp = get(handle);
   if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
   if (!ev || !state_out || !natl_out || !ev_out || !n_draws_out) return fail(POTUS_ERR_ARG, "%s: null argument", what);
-  if (const int rc_ = lap_have_rows(what, sp)) return rc_;
+  const KeptRows kr = kept_rows(sp, which);
+  if (const int rc_ = kept_have_rows(what, kr)) return rc_;
   if (const int rc_ = lap_check_days(what, sp, day_begin, day_end)) return rc_;
-  if (sp->lap_draws > TL_MAX_DRAWS) return fail(POTUS_ERR_UNSUPPORTED, "%s: %d draws per mode: a mode's draws are sorted in LDS, at most %d", what, sp->lap_draws, TL_MAX_DRAWS);
+  if (kr.draws > TL_MAX_DRAWS) return fail(POTUS_ERR_UNSUPPORTED, "%s: %d draws per %s: a %s's draws are sorted in LDS, at most %d", what, kr.draws, kr.group, kr.group, TL_MAX_DRAWS);
   DeviceGuard guard;
   DeviceLocks lock(sp->device);
   HIP_TRY(hipSetDevice(sp->device));
-  const int S = sp->M.S, nd = day_end - day_begin, n = sp->lap_draws, nm = sp->lap_modes, n_ds = std::max(sp->n_ds, 1);
+  const int S = sp->M.S, nd = day_end - day_begin, n = kr.draws, nm = kr.groups, n_ds = std::max(sp->n_ds, 1);
   DevBufs tmp;
   double *x = nullptr, *dw = nullptr, *dev_ = nullptr, *dout = nullptr;
   int *dskip = nullptr, *dzero = nullptr;
@@ -4662,11 +4707,11 @@ int potus_laplace_summary(int handle, int day_begin, int day_end, const double *
   const size_t n_out = (size_t)nm * nd * ((size_t)S * 4 + 9);
   if ((rc = tmp.get(&x, (size_t)nm * n * nd * S * 8, what)) || (rc = tmp.get(&dw, (size_t)S * 8, what)) || (rc = tmp.get(&dev_, (size_t)S * 8, what)) ||
       (rc = tmp.get(&dout, n_out * 8, what)) || (rc = tmp.get(&dskip, (size_t)nm * 4, what)) || (rc = tmp.get(&dzero, (size_t)n_ds * 4, what))) return rc;
-  HIP_TRY(hipMemcpyAsync(dskip, sp->lap_code.data(), (size_t)nm * 4, hipMemcpyHostToDevice, sp->stream));   // per mode: a code that is not 0 gives NaN
+  HIP_TRY(hipMemcpyAsync(dskip, kr.code->data(), (size_t)nm * 4, hipMemcpyHostToDevice, sp->stream));   // per mode: a code that is not 0 gives NaN
   HIP_TRY(hipMemsetAsync(dzero, 0, (size_t)n_ds * 4, sp->stream));
   HIP_TRY(hipMemcpyAsync(dw, sp->h_w.data(), (size_t)S * 8, hipMemcpyHostToDevice, sp->stream));
   HIP_TRY(hipMemcpyAsync(dev_, ev, (size_t)S * 8, hipMemcpyHostToDevice, sp->stream));
-  if ((rc = lap_scores(sp, day_begin, day_end, dzero, x))) return rc;
+  if ((rc = lap_scores(sp, kr, day_begin, day_end, dzero, x))) return rc;
   int npad = 1;
   while (npad < n) npad <<= 1;
   const size_t lds = (size_t)npad * 8;
@@ -4679,12 +4724,278 @@ int potus_laplace_summary(int handle, int day_begin, int day_end, const double *
   HIP_TRY(hipMemcpyAsync(natl_out, o_natl, (size_t)nm * nd * 4 * 8, hipMemcpyDeviceToHost, sp->stream));
   HIP_TRY(hipMemcpyAsync(ev_out, o_ev, (size_t)nm * nd * 5 * 8, hipMemcpyDeviceToHost, sp->stream));
   HIP_TRY(hipStreamSynchronize(sp->stream));
-  for (int m = 0; m < nm; m++) n_draws_out[m] = sp->lap_code[m] ? 0 : n;
+  for (int m = 0; m < nm; m++) n_draws_out[m] = (*kr.code)[m] ? 0 : n;
   return 0;
+}
+} // namespace
+
+int potus_laplace_write_array_device(int handle, int col_begin, int col_end, void *out_device) {
+  return kept_write_array_device("potus_laplace_write_array_device", KEPT_LAPLACE, handle, col_begin, col_end, out_device);
+}
+int potus_laplace_scores_device(int handle, int day_begin, int day_end, void *out_device) {
+  return kept_scores_device("potus_laplace_scores_device", KEPT_LAPLACE, handle, day_begin, day_end, out_device);
+}
+int potus_laplace_summary(int handle, int day_begin, int day_end, const double *ev, int ev_to_win, double *state_out, double *natl_out, double *ev_out, int32_t *n_draws_out) {
+  return kept_summary("potus_laplace_summary", KEPT_LAPLACE, handle, day_begin, day_end, ev, ev_to_win, state_out, natl_out, ev_out, n_draws_out);
+}
+int potus_pathfinder_write_array_device(int handle, int col_begin, int col_end, void *out_device) {
+  return kept_write_array_device("potus_pathfinder_write_array_device", KEPT_PATHFINDER, handle, col_begin, col_end, out_device);
+}
+int potus_pathfinder_scores_device(int handle, int day_begin, int day_end, void *out_device) {
+  return kept_scores_device("potus_pathfinder_scores_device", KEPT_PATHFINDER, handle, day_begin, day_end, out_device);
+}
+int potus_pathfinder_summary(int handle, int day_begin, int day_end, const double *ev, int ev_to_win, double *state_out, double *natl_out, double *ev_out, int32_t *n_draws_out) {
+  return kept_summary("potus_pathfinder_summary", KEPT_PATHFINDER, handle, day_begin, day_end, ev, ev_to_win, state_out, natl_out, ev_out, n_draws_out);
 }
 
 int potus_laplace_timing(double *ms) {
   return timing_out("potus_laplace_timing", g_lap_ms, 4, ms);
+}
+
+// ---------------------------------------------------------------------------------------------- Pathfinder (potus_pathfinder.hpp)
+namespace {
+thread_local double g_pf_ms[4] = {0.0, 0.0, 0.0, 0.0};   // the calling thread's last potus_pathfinder[_path]: L-BFGS, alpha, ELBO, draws (HIP events)
+
+struct PfOut {
+  int32_t *info; double *elbo; int32_t *kept; double *q, *lp, *lq, *mu, *alpha, *logdet, *phi, *lqw, *qtq;
+};
+
+int pf_check(const Sampler *sp, const char *what, const potus_pathfinder_opts &o, int n_paths) {
+  if (const int rc_ = paths_check(sp, what, n_paths)) return rc_;
+  if (o.history_size < 1 || o.history_size > PF_MAX_J) return fail(POTUS_ERR_ARG, "%s: history_size = %d outside 1..%d", what, o.history_size, PF_MAX_J);
+  if (o.num_elbo_draws < 1 || o.num_elbo_draws > PF_MAX_K) return fail(POTUS_ERR_ARG, "%s: num_elbo_draws = %d outside 1..%d", what, o.num_elbo_draws, PF_MAX_K);
+  if (o.num_draws < 0) return fail(POTUS_ERR_ARG, "%s: num_draws = %d", what, o.num_draws);
+  if (o.draw_offset < 0 || (long long)o.draw_offset + o.num_draws >= 0xFFFFFFFFll) return fail(POTUS_ERR_ARG, "%s: draw_offset = %d with %d draws", what, o.draw_offset, o.num_draws);
+  if (o.path_offset < 0 || (long long)o.path_offset + n_paths >= 0xFFFFFFFFll) return fail(POTUS_ERR_ARG, "%s: path_offset = %d with %d paths", what, o.path_offset, n_paths);
+  const int D = sp->L.D, Dpad = (D + 7) & ~7;
+  if ((unsigned long long)(2 * o.history_size + 4) * Dpad * 8ull >= 0x7fffffffull) return fail(POTUS_ERR_UNSUPPORTED, "%s: D = %d: a workgroup's working set must stay below 2 GB", what, D);
+  if ((unsigned long long)n_paths * std::max(o.num_draws, 1) * (POTUS_N_SAMPLER_COLS + D) >= (1ull << 40)) return fail(POTUS_ERR_ARG, "%s: %d paths x %d draws of %d coordinates", what, n_paths, o.num_draws, D);
+  return 0;
+}
+
+// From a trajectory on the device (dX, dG [n_paths][rows][Dpad], hL its lengths) to the outputs, under the caller's device lock.
+int pf_core(Sampler *sp, const char *what, const potus_pathfinder_opts &o, DevBufs &tmp, const double *dX, const double *dG, const std::vector<int> &hL, int rows,
+            int n_paths, const double *u_elbo, const double *u_draws, const int32_t *want_l, const int *opt_code, const PfOut &out, double *ms /*[3]*/) {
+  const int D = sp->L.D, row = POTUS_N_SAMPLER_COLS + D, Dpad = (D + 7) & ~7, J = o.history_size, K = o.num_elbo_draws, Mn = o.num_draws;
+  const double nan = std::numeric_limits<double>::quiet_NaN();
+  hipStream_t st = sp->stream;
+  int G = 0;
+  HIP_TRY(hipDeviceGetAttribute(&G, hipDeviceAttributeMultiprocessorCount, sp->device));
+  G = std::max(G, 1);
+  if (const char *e = getenv("POTUS_PATHFINDER_G")) G = std::max(1, atoi(e));   // tests: no output depends on it
+  const size_t lds = sp->lds_bytes;
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pf_elbo), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_pf_draws), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  DsPlan pl;
+  pl.of(sp);
+  // the handle's rows of the last call go first: a call that fails leaves none behind
+  HIP_TRY(hipStreamSynchronize(st));
+  if (sp->pf_rows) { (void)hipFree(sp->pf_rows); sp->pf_rows = nullptr; }
+  sp->pf_paths = sp->pf_draws = 0; sp->pf_code.clear();
+  int rc;
+  double *drows = nullptr;
+  const size_t rows_total = (size_t)n_paths * Mn;
+  if (Mn > 0) {
+    void *p = nullptr;
+    if (hipMalloc(&p, rows_total * row * 8) != hipSuccess) { (void)hipGetLastError(); return fail(POTUS_ERR_DEVICE, "%s: hipMalloc of %zu bytes for the rows failed", what, rows_total * row * 8); }
+    drows = static_cast<double *>(p);
+  }
+  struct RowsOwner { double *p; ~RowsOwner() { if (p) (void)hipFree(p); } } owner{drows};   // until the call has succeeded
+  const size_t nl = (size_t)n_paths * rows;
+  double *alpha = nullptr, *abc = nullptr, *work = nullptr, *delbo = nullptr, *due = nullptr, *dud = nullptr, *dmu = nullptr, *dld = nullptr, *dlp = nullptr, *dlq = nullptr;
+  int *dkept = nullptr, *dL = nullptr, *dsel = nullptr, *dwant = nullptr;
+  PfParams *dP = nullptr, *dP2 = nullptr;
+  PfSmall *dsmall = nullptr;
+  double *dphi = nullptr, *dlqw = nullptr, *dqtq = nullptr;
+  const bool want_draws = want_l && Mn > 0 && (out.phi || out.lqw || out.qtq);
+  if ((rc = tmp.get(&alpha, nl * Dpad * 8, what)) || (rc = tmp.get(&abc, nl * 3 * 8, what)) || (rc = tmp.get(&work, (size_t)G * (2 * J + 4) * Dpad * 8, what)) ||
+      (rc = tmp.get(&delbo, nl * 8, what)) || (rc = tmp.get(&dkept, nl * 4, what)) || (rc = tmp.get(&dL, (size_t)n_paths * 4, what)) ||
+      (rc = tmp.get(&dsel, (size_t)n_paths * 4, what)) || (rc = tmp.get(&dwant, (size_t)n_paths * 4, what)) || (rc = tmp.get(&dmu, (size_t)n_paths * D * 8, what)) ||
+      (rc = tmp.get(&dld, (size_t)n_paths * 8, what)) || (rc = tmp.get(&dlp, std::max<size_t>(rows_total, 1) * 8, what)) ||
+      (rc = tmp.get(&dlq, std::max<size_t>(rows_total, 1) * 8, what)) || (rc = tmp.get(&dP, sizeof(PfParams), what)) || (rc = tmp.get(&dP2, sizeof(PfParams), what)) ||
+      (rc = tmp.get(&dsmall, (size_t)G * sizeof(PfSmall), what))) return rc;
+  if (u_elbo) {
+    const size_t nb = (size_t)n_paths * (rows - 1) * K * D * 8;
+    if ((rc = tmp.get(&due, nb, what))) return rc;
+    HIP_TRY(hipMemcpyAsync(due, u_elbo, nb, hipMemcpyHostToDevice, st));
+  }
+  if (u_draws && Mn > 0) {
+    if ((rc = tmp.get(&dud, rows_total * D * 8, what))) return rc;
+    HIP_TRY(hipMemcpyAsync(dud, u_draws, rows_total * D * 8, hipMemcpyHostToDevice, st));
+  }
+  HIP_TRY(hipMemcpyAsync(dL, hL.data(), (size_t)n_paths * 4, hipMemcpyHostToDevice, st));
+  std::vector<int> hwant(n_paths, -1);
+  if (want_l) for (int p = 0; p < n_paths; p++) hwant[p] = want_l[p];
+  HIP_TRY(hipMemcpyAsync(dwant, hwant.data(), (size_t)n_paths * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemsetAsync(dmu, 0xFF, (size_t)n_paths * D * 8, st));   // (NaN: an iterate nobody asked for, or outside 1 .. L)
+  HIP_TRY(hipMemsetAsync(dld, 0xFF, (size_t)n_paths * 8, st));
+  if (want_draws) {
+    if ((rc = tmp.get(&dphi, rows_total * D * 8, what)) || (rc = tmp.get(&dlqw, rows_total * 8, what)) || (rc = tmp.get(&dqtq, (size_t)n_paths * PF_MAX_N * PF_MAX_N * 8, what))) return rc;
+    HIP_TRY(hipMemsetAsync(dphi, 0xFF, rows_total * D * 8, st));
+    HIP_TRY(hipMemsetAsync(dlqw, 0xFF, rows_total * 8, st));
+    HIP_TRY(hipMemsetAsync(dqtq, 0xFF, (size_t)n_paths * PF_MAX_N * PF_MAX_N * 8, st));
+  }
+  PfParams P{dX, dG, dL, alpha, dkept, abc, work, dsmall, delbo, due, dud, dsel, want_l ? dwant : nullptr, dmu, dld, drows, dlp, dlq, dphi, dlqw, dqtq,
+             n_paths, rows, n_paths / pl.n_ds, J, K, Mn, 1, D, Dpad, o.path_offset, o.draw_offset, sp->R.seed_lo, sp->R.seed_hi};
+  HIP_TRY(hipMemcpyAsync(dP, &P, sizeof(P), hipMemcpyHostToDevice, st));
+  EventTimer t_alpha, t_elbo, t_draws;
+  HIP_TRY(t_alpha.made); HIP_TRY(t_elbo.made); HIP_TRY(t_draws.made);
+  HIP_TRY(t_alpha.start(st));
+  hipLaunchKernelGGL(k_pf_alpha, dim3(n_paths), dim3(PT_THREADS), 0, st, (const PfParams *)dP);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(t_alpha.stop(st));
+  const long long n_items = (long long)n_paths * (rows - 1);
+  HIP_TRY(t_elbo.start(st));
+  if (n_items > 0) {
+    hipLaunchKernelGGL(k_pf_elbo, dim3((unsigned)std::min<long long>(G, n_items)), dim3(PT_THREADS), lds, st, pl.Mg, (const PfParams *)dP);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(t_elbo.stop(st));
+  std::vector<double> helbo(nl, nan);
+  std::vector<int> hkept(nl, 0);
+  HIP_TRY(hipMemcpyAsync(helbo.data(), delbo, nl * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(hkept.data(), dkept, nl * 4, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));   // the ELBOs decide which iterate the draws come from
+  std::vector<int> hsel(n_paths, 0), code(n_paths, PF_NO_ELBO);
+  for (int p = 0; p < n_paths; p++) {
+    double best = -std::numeric_limits<double>::infinity();
+    for (int l = 0; l < rows; l++) {
+      double &e = helbo[(size_t)p * rows + l];
+      if (l < 1 || l > hL[p]) { e = nan; hkept[(size_t)p * rows + l] = 0; continue; }
+      if (std::isfinite(e) && e > best) { best = e; hsel[p] = l; }   // (strict: the lowest l on ties)
+    }
+    if (hsel[p]) code[p] = PF_OK;
+  }
+  HIP_TRY(t_draws.start(st));
+  if (Mn > 0) {
+    const int nchunk = std::max(1, std::min(Mn, G / n_paths));
+    P.chunk = (Mn + nchunk - 1) / nchunk;
+    const long long d_items = (long long)n_paths * ((Mn + P.chunk - 1) / P.chunk);
+    HIP_TRY(hipMemcpyAsync(dsel, hsel.data(), (size_t)n_paths * 4, hipMemcpyHostToDevice, st));
+    P.want_l = nullptr;
+    HIP_TRY(hipMemcpyAsync(dP2, &P, sizeof(P), hipMemcpyHostToDevice, st));
+    hipLaunchKernelGGL(k_pf_draws, dim3((unsigned)std::min<long long>(G, d_items)), dim3(PT_THREADS), lds, st, pl.Mg, (const PfParams *)dP2);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(t_draws.stop(st));
+  if (Mn > 0) {
+    if (out.q) HIP_TRY(hipMemcpy2DAsync(out.q, (size_t)D * 8, drows + POTUS_N_SAMPLER_COLS, (size_t)row * 8, (size_t)D * 8, rows_total, hipMemcpyDeviceToHost, st));
+    if (out.lp) HIP_TRY(hipMemcpyAsync(out.lp, dlp, rows_total * 8, hipMemcpyDeviceToHost, st));
+    if (out.lq) HIP_TRY(hipMemcpyAsync(out.lq, dlq, rows_total * 8, hipMemcpyDeviceToHost, st));
+  }
+  if (out.mu) HIP_TRY(hipMemcpyAsync(out.mu, dmu, (size_t)n_paths * D * 8, hipMemcpyDeviceToHost, st));
+  if (out.logdet) HIP_TRY(hipMemcpyAsync(out.logdet, dld, (size_t)n_paths * 8, hipMemcpyDeviceToHost, st));
+  if (want_draws) {
+    if (out.phi) HIP_TRY(hipMemcpyAsync(out.phi, dphi, rows_total * D * 8, hipMemcpyDeviceToHost, st));
+    if (out.lqw) HIP_TRY(hipMemcpyAsync(out.lqw, dlqw, rows_total * 8, hipMemcpyDeviceToHost, st));
+    if (out.qtq) HIP_TRY(hipMemcpyAsync(out.qtq, dqtq, (size_t)n_paths * PF_MAX_N * PF_MAX_N * 8, hipMemcpyDeviceToHost, st));
+  }
+  if (out.alpha)
+    for (int p = 0; p < n_paths; p++) {
+      const int l = hwant[p];
+      if (l >= 0 && l <= hL[p]) HIP_TRY(hipMemcpyAsync(out.alpha + (size_t)p * D, alpha + ((size_t)p * rows + l) * Dpad, (size_t)D * 8, hipMemcpyDeviceToHost, st));
+      else std::fill(out.alpha + (size_t)p * D, out.alpha + (size_t)(p + 1) * D, nan);
+    }
+  HIP_TRY(hipStreamSynchronize(st));
+  if ((rc = t_alpha.elapsed_or_fail(&ms[0])) || (rc = t_elbo.elapsed_or_fail(&ms[1])) || (rc = t_draws.elapsed_or_fail(&ms[2]))) return rc;
+  for (int p = 0; p < n_paths; p++) {
+    int32_t *io = out.info + (size_t)p * 4;
+    io[0] = code[p]; io[1] = hL[p]; io[2] = hsel[p]; io[3] = opt_code ? opt_code[p] : 0;
+  }
+  if (out.elbo) std::copy(helbo.begin(), helbo.end(), out.elbo);
+  if (out.kept) std::copy(hkept.begin(), hkept.end(), out.kept);
+  if (Mn > 0) { sp->pf_rows = drows; owner.p = nullptr; sp->pf_paths = n_paths; sp->pf_draws = Mn; sp->pf_code = code; }
+  return 0;
+}
+} // namespace
+
+void potus_default_pathfinder_opts(potus_pathfinder_opts *o) {
+  if (!o) return;
+  potus_default_optimize_opts(&o->opt);
+  o->opt.jacobian = 1; o->opt.iter = 1000;
+  o->history_size = 6; o->num_elbo_draws = 25; o->num_draws = 1000; o->draw_offset = 0; o->path_offset = 0; o->pad0 = 0;
+}
+
+int potus_pathfinder(int handle, const potus_pathfinder_opts *opts, const double *q0, int n_paths, int32_t *info_out, double *elbo_out, int32_t *kept_out,
+                     double *q_out, double *lp_out, double *lq_out, double *traj_x_out, double *traj_g_out) {
+  const char *what = "potus_pathfinder";
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  potus_pathfinder_opts o;
+  potus_default_pathfinder_opts(&o);
+  if (opts) o = *opts;
+  o.opt.jacobian = 1; o.opt.path_offset = o.path_offset;   // the density the sampler draws from; one offset for the starts and the normals
+  if (const int rc_ = pf_check(sp, what, o, n_paths)) return rc_;
+  if (const int rc_ = opt_check(sp, what, o.opt, n_paths, info_out ? nullptr : "info_out")) return rc_;
+  const int D = sp->L.D, Dpad = (D + 7) & ~7, rows = o.opt.iter + 1;
+  DeviceGuard guard;
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  DevBufs tmp;
+  double *dX = nullptr, *dG = nullptr;
+  int rc;
+  if ((rc = tmp.get(&dX, (size_t)n_paths * rows * Dpad * 8, what)) || (rc = tmp.get(&dG, (size_t)n_paths * rows * Dpad * 8, what))) return rc;
+  EventTimer ev;
+  OptRun r;
+  if ((rc = opt_launch(sp, what, o.opt, q0, n_paths, tmp, dX, dG, rows, ev, r))) return rc;
+  std::vector<int> hinfo((size_t)n_paths * 3), hL(n_paths), ocode(n_paths);
+  HIP_TRY(hipMemcpyAsync(hinfo.data(), r.dinfo, hinfo.size() * 4, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  for (int p = 0; p < n_paths; p++) { ocode[p] = hinfo[(size_t)p * 3]; hL[p] = ocode[p] == OPT_INIT ? 0 : std::min(hinfo[(size_t)p * 3 + 1], rows - 1); }
+  double ms[4] = {0.0, 0.0, 0.0, 0.0};
+  if ((rc = ev.elapsed_or_fail(&ms[0]))) return rc;
+  const PfOut out{info_out, elbo_out, kept_out, q_out, lp_out, lq_out, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr};
+  if ((rc = pf_core(sp, what, o, tmp, dX, dG, hL, rows, n_paths, nullptr, nullptr, nullptr, ocode.data(), out, ms + 1))) return rc;
+  for (int k = 0; k < 2; k++) if (double *t = k ? traj_g_out : traj_x_out)
+    HIP_TRY(hipMemcpy2D(t, (size_t)D * 8, k ? dG : dX, (size_t)Dpad * 8, (size_t)D * 8, (size_t)n_paths * rows, hipMemcpyDeviceToHost));
+  if (traj_x_out || traj_g_out) {   // rows behind a path's end were never written
+    const double nan = std::numeric_limits<double>::quiet_NaN();
+    for (int p = 0; p < n_paths; p++) {
+      const int first = ocode[p] == OPT_INIT ? 0 : hL[p] + 1;
+      for (double *t : {traj_x_out, traj_g_out}) if (t) std::fill(t + ((size_t)p * rows + first) * D, t + (size_t)(p + 1) * rows * D, nan);
+    }
+  }
+  std::copy(ms, ms + 4, g_pf_ms);
+  return 0;
+}
+
+int potus_pathfinder_path(int handle, const potus_pathfinder_opts *opts, const double *x, const double *g, const int32_t *L, int rows, int n_paths,
+                          const double *u_elbo, const double *u_draws, const int32_t *want_l, int32_t *info_out, double *elbo_out, int32_t *kept_out,
+                          double *q_out, double *lp_out, double *lq_out, double *mu_out, double *alpha_out, double *logdet_out,
+                          double *phi_out, double *lqw_out, double *qtq_out) {
+  const char *what = "potus_pathfinder_path";
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  potus_pathfinder_opts o;
+  potus_default_pathfinder_opts(&o);
+  if (opts) o = *opts;
+  if (const int rc_ = pf_check(sp, what, o, n_paths)) return rc_;
+  if (!x || !g || !L || !info_out) return fail(POTUS_ERR_ARG, "%s: null argument (x, g, L and info_out are required)", what);
+  if (rows < 2) return fail(POTUS_ERR_ARG, "%s: rows = %d: a trajectory has at least the rows 0 and 1", what, rows);
+  std::vector<int> hL(n_paths);
+  for (int p = 0; p < n_paths; p++) {
+    if (L[p] < 0 || L[p] > rows - 1) return fail(POTUS_ERR_ARG, "%s: L[%d] = %d outside 0..%d", what, p, L[p], rows - 1);
+    hL[p] = L[p];
+  }
+  const int D = sp->L.D, Dpad = (D + 7) & ~7;
+  DeviceGuard guard;
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  DevBufs tmp;
+  double *dX = nullptr, *dG = nullptr;
+  int rc;
+  if ((rc = tmp.get(&dX, (size_t)n_paths * rows * Dpad * 8, what)) || (rc = tmp.get(&dG, (size_t)n_paths * rows * Dpad * 8, what))) return rc;
+  HIP_TRY(hipMemcpy2DAsync(dX, (size_t)Dpad * 8, x, (size_t)D * 8, (size_t)D * 8, (size_t)n_paths * rows, hipMemcpyHostToDevice, sp->stream));
+  HIP_TRY(hipMemcpy2DAsync(dG, (size_t)Dpad * 8, g, (size_t)D * 8, (size_t)D * 8, (size_t)n_paths * rows, hipMemcpyHostToDevice, sp->stream));
+  double ms[4] = {0.0, 0.0, 0.0, 0.0};
+  const PfOut out{info_out, elbo_out, kept_out, q_out, lp_out, lq_out, mu_out, alpha_out, logdet_out, phi_out, lqw_out, qtq_out};
+  if ((rc = pf_core(sp, what, o, tmp, dX, dG, hL, rows, n_paths, u_elbo, u_draws, want_l, nullptr, out, ms + 1))) return rc;
+  std::copy(ms, ms + 4, g_pf_ms);
+  return 0;
+}
+
+int potus_pathfinder_timing(double *ms) {
+  return timing_out("potus_pathfinder_timing", g_pf_ms, 4, ms);
 }
 
 int potus_simulate_prior(int handle, uint64_t seed, int n_sims, int sim_offset, double *q_out, int32_t *n_democrat_state_out, int32_t *n_democrat_national_out) {
@@ -5155,6 +5466,18 @@ void potus_R_laplace(int *handle, int *iopts /*[6]: jacobian, draw_offset, n_mod
   const bool draws = iopts[3] > 0;
   *status = potus_laplace(*handle, &o, mode, iopts[2], iopts[4] ? u : nullptr, iopts[3], draws ? q_out : nullptr, draws ? lp_out : nullptr,
                           draws ? lp_approx_out : nullptr, info_out, iopts[5] ? precision_out : nullptr);
+}
+void potus_R_pathfinder(int *handle, int *iopts /*[9]: history_size, num_elbo_draws, num_draws, draw_offset, path_offset, max_lbfgs_iters, L-BFGS history, n_paths, q0 given*/,
+                        double *dopts /*[6]: init_alpha, tol_obj, tol_rel_obj, tol_grad, tol_rel_grad, tol_param*/, double *q0, int *info_out, double *elbo_out,
+                        int *kept_out, double *q_out, double *lp_out, double *lq_out, int *status) {
+  potus_pathfinder_opts o;
+  potus_default_pathfinder_opts(&o);
+  o.history_size = iopts[0]; o.num_elbo_draws = iopts[1]; o.num_draws = iopts[2]; o.draw_offset = iopts[3]; o.path_offset = iopts[4];
+  o.opt.iter = iopts[5]; o.opt.history_size = iopts[6];
+  o.opt.init_alpha = dopts[0]; o.opt.tol_obj = dopts[1]; o.opt.tol_rel_obj = dopts[2]; o.opt.tol_grad = dopts[3]; o.opt.tol_rel_grad = dopts[4]; o.opt.tol_param = dopts[5];
+  const bool draws = iopts[2] > 0;
+  *status = potus_pathfinder(*handle, &o, iopts[8] ? q0 : nullptr, iopts[7], info_out, elbo_out, kept_out, draws ? q_out : nullptr, draws ? lp_out : nullptr,
+                             draws ? lq_out : nullptr, nullptr, nullptr);
 }
 void potus_R_set_datasets(int *handle, int *n_datasets, int *n_democrat_state, int *n_democrat_national, int *status) {
   *status = potus_set_datasets(*handle, *n_datasets, n_democrat_state, n_democrat_national);

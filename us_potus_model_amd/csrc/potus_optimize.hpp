@@ -51,6 +51,8 @@ struct OptParams {
   int m, iter, jacobian, path_offset, Dpad;
   double init_alpha, tol_obj, tol_rel_obj, tol_grad, tol_rel_grad, tol_param, radius;
   unsigned seed_lo, seed_hi;
+  double *traj_x, *traj_g;   // [n_paths][traj_rows][Dpad] or null: the accepted (x_l, g_l), l = 0 .. iterations (potus_pathfinder.hpp)
+  int traj_rows;
 };
 
 // The state machine's memory, in the LDS that the sampler kernels use for their transition state (after DevModel::lds_doubles).
@@ -302,6 +304,21 @@ __device__ __noinline__ int opt_step(const DevModel *Mg, const OptParams *Pg, in
   return 0;
 }
 
+// The trajectory, for a caller that gave buffers for it: a step that accepted a point (the start included) has flipped `cur` and left the
+// point in the current pair; it becomes row `it` of the path.  Out of line and behind a scalar test, so potus_optimize's loop is the pass and opt_step.
+__device__ __noinline__ void opt_record(const DevModel *Mg, const OptParams *Pg, int p_, int cur_before_) {
+  CMp M = (CMp)uni_ptr(Mg);
+  COp P = (COp)uni_ptr(Pg);
+  const int p = (int)uni32((unsigned)p_), cur_before = (int)uni32((unsigned)cur_before_);
+  const OptPath o = opt_path(M, P, p);
+  const int cur = opt_uni(o.st->s.cur), l = opt_uni(o.st->s.it), tid = threadIdx.x, D = o.D, Dpad = o.Dpad;
+  if (cur == cur_before || l >= P->traj_rows) return;
+  gcdp x = o.W + (size_t)(2 * cur) * Dpad, g = x + Dpad;
+  const size_t at = ((size_t)p * P->traj_rows + l) * Dpad;
+  gdp tx = as_g(P->traj_x) + at, tg = as_g(P->traj_g) + at;
+  for (int i = tid; i < D; i += PT_THREADS) { tx[i] = x[i]; tg[i] = g[i]; }
+}
+
 __global__ __launch_bounds__(PT_THREADS) void k_opt_lbfgs(const DevModel *Mg_all, const OptParams *Pg) {
   COp P = (COp)Pg;
   const int p = blockIdx.x;
@@ -327,6 +344,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_opt_lbfgs(const DevModel *Mg_all
     PlainPolicy pol{rw, rw, 8u * (unsigned)Dpad * (unsigned)xt_slot, 8u * (unsigned)Dpad * (unsigned)(xt_slot + 1), {0}};
     const double lp = model_pass(M, lds, pst, pol);
     code = opt_uni(opt_step(Mg, Pg, p, lp));
+    if (P->traj_x) opt_record(Mg, Pg, p, 1 - xt_slot / 2);
   }
   if (!code) code = OPT_MAXIT;                          // every pass is used up
 

@@ -146,6 +146,18 @@ def load_library():
         L.potus_laplace_timing.argtypes = [dp]
         L.potus_R_laplace.argtypes = [ip, ip, dp, dp, dp, dp, dp, dp, dp, dp, ip]
         L.potus_R_laplace.restype = None
+    if hasattr(L, "potus_pathfinder"):                  # Pathfinder (Handle.pathfinder, PotusModel.pathfinder)
+        i32p, pop = C.POINTER(C.c_int32), C.POINTER(_abi.PotusPathfinderOpts)
+        L.potus_default_pathfinder_opts.argtypes = [pop]
+        L.potus_default_pathfinder_opts.restype = None
+        L.potus_pathfinder.argtypes = [C.c_int, pop, dp, C.c_int, i32p, dp, i32p, dp, dp, dp, dp, dp]
+        L.potus_pathfinder_path.argtypes = [C.c_int, pop, dp, dp, i32p, C.c_int, C.c_int, dp, dp, i32p, i32p, dp, i32p, dp, dp, dp, dp, dp, dp, dp, dp, dp]
+        L.potus_pathfinder_write_array_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.potus_pathfinder_scores_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.potus_pathfinder_summary.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, dp, dp, i32p]
+        L.potus_pathfinder_timing.argtypes = [dp]
+        L.potus_R_pathfinder.argtypes = [ip, ip, dp, dp, ip, dp, ip, dp, dp, dp, ip]
+        L.potus_R_pathfinder.restype = None
     _LIB = L
     return L
 
@@ -164,6 +176,8 @@ EXPORTS = [
     "potus_default_optimize_opts", "potus_optimize", "potus_optimize_timing",
     "potus_default_laplace_opts", "potus_laplace", "potus_laplace_write_array_device", "potus_laplace_scores_device", "potus_laplace_summary",
     "potus_laplace_timing", "potus_R_laplace",
+    "potus_default_pathfinder_opts", "potus_pathfinder", "potus_pathfinder_path", "potus_pathfinder_write_array_device",
+    "potus_pathfinder_scores_device", "potus_pathfinder_summary", "potus_pathfinder_timing", "potus_R_pathfinder",
     "potus_outcomes", "potus_outcomes_device", "potus_outcomes_timing",
     "potus_monitor", "potus_monitor_device",
     "potus_scenario", "potus_scenario_device", "potus_scenario_timing",
@@ -575,6 +589,144 @@ class Handle:
         ms = np.zeros(4)
         _check(self.L, self.L.potus_laplace_timing(_dp(ms)))
         return dict(hessian_ms=float(ms[0]), factor_ms=float(ms[1]), solve_ms=float(ms[2]), lp_ms=float(ms[3]))
+
+    def pathfinder_opts(self, **opts):
+        """potus_default_pathfinder_opts with the given fields replaced: history_size, num_elbo_draws, num_draws, draw_offset, path_offset, and,
+        for the L-BFGS run, max_lbfgs_iters (opt.iter), lbfgs_history_size (opt.history_size), init_alpha, tol_*."""
+        o = _abi.PotusPathfinderOpts()
+        self.L.potus_default_pathfinder_opts(C.byref(o))
+        for k, v in opts.items():
+            if k == "max_lbfgs_iters":
+                o.opt.iter = int(v)
+            elif k == "lbfgs_history_size":
+                o.opt.history_size = int(v)
+            elif k in ("init_alpha", "tol_obj", "tol_rel_obj", "tol_grad", "tol_rel_grad", "tol_param"):
+                setattr(o.opt, k, float(v))
+            elif k in ("history_size", "num_elbo_draws", "num_draws", "draw_offset", "path_offset"):
+                setattr(o, k, int(v))
+            else:
+                raise TypeError(f"unknown Pathfinder option {k!r}")
+        return o
+
+    def _pathfinder_out(self, n, rows, m):
+        return dict(info=np.zeros((n, 4), np.int32), elbo=np.zeros((n, rows)), kept=np.zeros((n, rows), np.int32), q=np.zeros((n, m, self.D)),
+                    lp=np.zeros((n, m)), lq=np.zeros((n, m)))
+
+    def _pathfinder_result(self, o, n, m):
+        info = o.pop("info")
+        self._pathfinder_shape = (n, m)
+        o.update(return_code=info[:, 0].copy(), iterations=info[:, 1].copy(), best_iteration=info[:, 2].copy(), optimize_code=info[:, 3].copy())
+        return o
+
+    def pathfinder(self, q0=None, paths=None, trajectory=False, opts=None, **fields):
+        """potus_pathfinder: an L-BFGS path per start (q0 [paths, D], or None for `paths` library starts), the normal approximation of every
+        iterate, the ELBO of each, num_draws draws from the best one.  On a handle with data sets path p uses data set p // (paths // n_datasets).
+        fields: see pathfinder_opts (or opts: a filled struct).  Returns dict(q [paths, draws, D], lp, lq [paths, draws], elbo, kept
+        [paths, max_lbfgs_iters + 1] indexed by the iterate, return_code, iterations, best_iteration, optimize_code [paths] and, with
+        trajectory, x, g [paths, max_lbfgs_iters + 1, D])."""
+        o = opts if opts is not None else self.pathfinder_opts(**fields)
+        p0 = None
+        if q0 is not None:
+            q0 = np.ascontiguousarray(np.atleast_2d(q0), dtype=np.float64)
+            if q0.shape[1] != self.D or (paths is not None and int(paths) != q0.shape[0]):
+                raise ValueError(f"pathfinder: q0 has shape {q0.shape}, [{paths if paths is not None else 'paths'}, {self.D}] expected")
+            paths, p0 = q0.shape[0], _dp(q0)
+        n, rows, m = int(1 if paths is None else paths), max(int(o.opt.iter), 0) + 1, max(int(o.num_draws), 0)
+        r = self._pathfinder_out(max(n, 0), rows, m)
+        tx, tg = (np.zeros((max(n, 0), rows, self.D)), np.zeros((max(n, 0), rows, self.D))) if trajectory else (None, None)
+        _check(self.L, self.L.potus_pathfinder(self.h, C.byref(o), p0, n, _ip(r["info"]), _dp(r["elbo"]), _ip(r["kept"]), _dp(r["q"]) if m else None,
+                                               _dp(r["lp"]) if m else None, _dp(r["lq"]) if m else None, None if tx is None else _dp(tx),
+                                               None if tg is None else _dp(tg)))
+        if trajectory:
+            r.update(x=tx, g=tg)
+        return self._pathfinder_result(r, n, m)
+
+    def pathfinder_path(self, x, g, L=None, u_elbo=None, u_draws=None, want=None, opts=None, **fields):
+        """potus_pathfinder_path: pathfinder() from the caller's trajectory x, g [paths, rows, D] (or [rows, D]) with lengths L [paths]
+        (default rows - 1), no optimiser run.  u_elbo [paths, rows - 1, num_elbo_draws, D], u_draws [paths, num_draws, D]: the caller's
+        standard normals.  want [paths]: the iterate whose mu, alpha [paths, D] and log_det [paths] are also returned, with phi [paths, draws, D] and
+        lq_want [paths, draws], the draws that iterate gives from the final normals, and qtq [paths, 20, 20], Q'Q of its thin QR (NaN beyond 2j)."""
+        o = opts if opts is not None else self.pathfinder_opts(**fields)
+        x, g = (np.ascontiguousarray(np.asarray(a, dtype=np.float64)) for a in (x, g))
+        if x.ndim == 2:
+            x, g = x[None], g[None]
+        if x.ndim != 3 or x.shape != g.shape or x.shape[2] != self.D:
+            raise ValueError(f"pathfinder_path: x {x.shape} and g {g.shape}, [paths, rows, {self.D}] expected of both")
+        n, rows, m, K = x.shape[0], x.shape[1], max(int(o.num_draws), 0), int(o.num_elbo_draws)
+        Lv = np.ascontiguousarray(np.full(n, rows - 1) if L is None else np.asarray(L).reshape(-1), dtype=np.int32)
+        if Lv.shape != (n,):
+            raise ValueError(f"pathfinder_path: L has {Lv.size} entries, {n} expected")
+        pe = pd = pw = None
+        if u_elbo is not None:
+            u_elbo = np.ascontiguousarray(np.asarray(u_elbo, dtype=np.float64))
+            if u_elbo.size != n * (rows - 1) * K * self.D:
+                raise ValueError(f"pathfinder_path: u_elbo has shape {u_elbo.shape}, [{n}, {rows - 1}, {K}, {self.D}] expected")
+            pe = _dp(u_elbo)
+        if u_draws is not None:
+            u_draws = np.ascontiguousarray(np.asarray(u_draws, dtype=np.float64))
+            if u_draws.size != n * m * self.D:
+                raise ValueError(f"pathfinder_path: u_draws has shape {u_draws.shape}, [{n}, {m}, {self.D}] expected")
+            pd = _dp(u_draws)
+        r = self._pathfinder_out(n, rows, m)
+        mu = al = ld = ph = lw = qq = None
+        if want is not None:
+            want = np.ascontiguousarray(np.broadcast_to(np.asarray(want), (n,)), dtype=np.int32)
+            pw, mu, al, ld = _ip(want), np.zeros((n, self.D)), np.zeros((n, self.D)), np.zeros(n)
+            ph, lw, qq = np.zeros((n, m, self.D)), np.zeros((n, m)), np.full((n, 20, 20), np.nan)
+        _check(self.L, self.L.potus_pathfinder_path(self.h, C.byref(o), _dp(x), _dp(g), _ip(Lv), rows, n, pe, pd, pw, _ip(r["info"]), _dp(r["elbo"]),
+                                                    _ip(r["kept"]), _dp(r["q"]) if m else None, _dp(r["lp"]) if m else None, _dp(r["lq"]) if m else None,
+                                                    None if mu is None else _dp(mu), None if al is None else _dp(al), None if ld is None else _dp(ld),
+                                                    _dp(ph) if ph is not None and m else None, _dp(lw) if lw is not None and m else None,
+                                                    None if qq is None else _dp(qq)))
+        if want is not None:
+            r.update(mu=mu, alpha=al, log_det=ld, phi=ph, lq_want=lw, qtq=qq)
+        return self._pathfinder_result(r, n, m)
+
+    def _pathfinder_block(self, what):
+        shape = getattr(self, "_pathfinder_shape", None)
+        if not shape or not shape[1]:
+            raise PotusError(f"{what}: no Pathfinder draws on this handle (pathfinder(...) with num_draws >= 1 first)")
+        return shape
+
+    def pathfinder_rows_device(self, cols=None):
+        """potus_pathfinder_write_array_device: the CmdStan output columns (begin, end) (default: all) of the last pathfinder call's draws, a
+        torch tensor [paths * draws, end - begin] on this handle's GPU."""
+        import torch
+        n, m = self._pathfinder_block("pathfinder_rows_device")
+        a, b = (0, self.n_cols) if cols is None else (int(cols[0]), int(cols[1]))
+        out = torch.empty((n * m, max(b - a, 1)), dtype=torch.float64, device=f"cuda:{self.opts.device}")
+        torch.cuda.current_stream(out.device).synchronize()
+        _check(self.L, self.L.potus_pathfinder_write_array_device(self.h, a, b, C.c_void_p(out.data_ptr())))
+        return out
+
+    def pathfinder_scores(self, days=None):
+        """potus_pathfinder_scores_device: predicted_score of the days (begin, end) (0-based, default: election day) of the last pathfinder
+        call's draws, a torch tensor [paths, draws, days, S] on this handle's GPU."""
+        import torch
+        n, m = self._pathfinder_block("pathfinder_scores")
+        S = int(self.data["S"])
+        t0, t1 = self._day_range(days)
+        out = torch.empty((n, m, max(t1 - t0, 1), S), dtype=torch.float64, device=f"cuda:{self.opts.device}")
+        torch.cuda.current_stream(out.device).synchronize()
+        _check(self.L, self.L.potus_pathfinder_scores_device(self.h, t0, t1, C.c_void_p(out.data_ptr())))
+        return out
+
+    def pathfinder_summary(self, ev, days=None, ev_to_win=270):
+        """potus_pathfinder_summary: laplace_summary with the paths of the last pathfinder call in the place of modes."""
+        n, _ = self._pathfinder_block("pathfinder_summary")
+        S = int(self.data["S"])
+        t0, t1 = self._day_range(days)
+        nd = max(t1 - t0, 0)
+        ev = np.ascontiguousarray(ev, dtype=np.float64).reshape(S)
+        st, na, eo, cnt = np.zeros((n, nd, S, 4)), np.zeros((n, nd, 4)), np.zeros((n, nd, 5)), np.zeros(n, np.int32)
+        _check(self.L, self.L.potus_pathfinder_summary(self.h, t0, t1, _dp(ev), int(ev_to_win), _dp(st), _dp(na), _dp(eo), _ip(cnt)))
+        return dict(state=st, national=na, electoral_votes=eo, n_draws=cnt)
+
+    def pathfinder_timing(self):
+        """Milliseconds (HIP events) of the stages of this thread's last pathfinder call: L-BFGS, alpha, ELBO, draws."""
+        ms = np.zeros(4)
+        _check(self.L, self.L.potus_pathfinder_timing(_dp(ms)))
+        return dict(lbfgs_ms=float(ms[0]), alpha_ms=float(ms[1]), elbo_ms=float(ms[2]), draws_ms=float(ms[3]))
 
     def simulate_prior(self, seed, n_sims, sim_offset=0):
         """potus_simulate_prior: (q [n_sims, D], n_democrat_state [n_sims, Ns], n_democrat_national [n_sims, Nn]) drawn from the prior
@@ -1030,6 +1182,71 @@ class Laplace:
         self._h.close()
 
 
+class Pathfinder:
+    """What cmdstanr's model$pathfinder(psis_resample = FALSE) returns: draws [paths * draws_per_path, D] (unconstrained, the pooled draws of
+    every path, path-major), lp (log_prob<jacobian = true> of every draw, as the sampler's lp__), lq (the log density of the path's normal
+    at the draw), log_ratio = lp - lq, and per path elbo (of its best iterate), best_iteration, iterations, return_code
+    (_abi.PATHFINDER_CODES; a path without an ELBO has NaN draws).  The draws' rows stay on the handle for scores / summary / outcomes / scenario."""
+
+    def __init__(self, handle, res):
+        self._h, self.res = handle, res
+        self.return_code, self.iterations, self.best_iteration = res["return_code"], res["iterations"], res["best_iteration"]
+        self.paths, self.draws_per_path = res["q"].shape[0], res["q"].shape[1]
+        if not (self.return_code == 0).any():
+            raise PotusError("pathfinder: no path has an iterate with a finite ELBO (return code NO_ELBO on every path)")
+        self.draws = res["q"].reshape(-1, res["q"].shape[2])
+        self.lp, self.lq = res["lp"].reshape(-1), res["lq"].reshape(-1)
+        self.log_ratio = self.lp - self.lq
+        self.elbo = np.array([res["elbo"][p, l] if l > 0 else np.nan for p, l in enumerate(self.best_iteration)])
+        self.elbo_path = res["elbo"]
+        self._k = None
+
+    @property
+    def pareto_k(self):
+        """k-hat of the importance ratios of the pooled draws: the library's PSIS (potus_loo_device), exactly as Laplace.pareto_k."""
+        if self._k is None:
+            import torch
+            from .loo import loo_of_block
+            lr = self.log_ratio[np.isfinite(self.log_ratio)]
+            blk = torch.as_tensor(-lr, device=f"cuda:{self._h.opts.device}").reshape(1, 1, -1).contiguous()
+            self._k = float(loo_of_block(blk).pareto_k[0])
+        return self._k
+
+    def inits(self, chains, seed=0):
+        """[chains, D] starting points for sample(inits=...) / Handle.init: distinct draws spread evenly over the paths that have draws
+        (chain c takes one from path c mod paths), chosen by numpy's default_rng(seed)."""
+        ok = np.flatnonzero(self.return_code == 0)
+        m = self.draws_per_path
+        per = -(-int(chains) // ok.size)
+        if per > m:
+            raise ValueError(f"inits: {chains} chains from {ok.size} paths of {m} draws")
+        rng = np.random.default_rng(seed)
+        pick = {int(p): rng.choice(m, size=per, replace=False) for p in ok}
+        return np.stack([self.draws[int(ok[c % ok.size]) * m + pick[int(ok[c % ok.size])][c // ok.size]] for c in range(int(chains))])
+
+    def scores(self, days=None):
+        """predicted_score of `days` = (begin, end) (0-based; default election day) of every draw: a torch tensor [paths * draws, days, S] on the GPU."""
+        s = self._h.pathfinder_scores(days)
+        return s.reshape((-1,) + tuple(s.shape[2:]))
+
+    def summary(self, ev, days=None, ev_to_win=270):
+        """timeline()'s summaries per path: dict(state [paths, days, S, 4], national [paths, days, 4], electoral_votes [paths, days, 5], n_draws [paths])."""
+        return self._h.pathfinder_summary(ev, days, ev_to_win)
+
+    def outcomes(self, ev, actual=None, days=None, ev_to_win=270, states=None):
+        """Joint election outcomes over the pooled draws (potus_outcomes_device on their scores)."""
+        from .outcomes import outcomes_of_block
+        return outcomes_of_block(self.scores(days).contiguous(), self._h.data["state_weights"], ev, actual=actual, ev_to_win=ev_to_win, states=states)
+
+    def scenario(self, ev=None, given=None, day=-1, days=None, ev_to_win=270, states=None):
+        """Conditional forecast over the pooled draws (potus_scenario_device on their scores); `day` indexes the range `days`."""
+        from .scenario import scenario_of_block
+        return scenario_of_block(self.scores(days).contiguous(), self._h.data["state_weights"], ev=ev, given=given, day=day, ev_to_win=ev_to_win, states=states)
+
+    def close(self):
+        self._h.close()
+
+
 class PotusModel:
     """cmdstanr::cmdstan_model() for the two poll models (final_2016.R:532, final_2012.R:558)."""
 
@@ -1088,6 +1305,21 @@ class PotusModel:
             return Laplace(hd, q, res, hd.log_prob_grad(q)[0][0], jacobian)
         except Exception:
             hd.close()
+            raise
+
+    def pathfinder(self, data, paths=4, draws=1000, init=2.0, seed=1843, history_size=6, num_elbo_draws=25, max_lbfgs_iters=1000, device=0, **opt):
+        """cmdstanr's model$pathfinder(data, num_paths = 4, draws = 1000, psis_resample = FALSE): `paths` L-BFGS paths, the ELBO of the normal
+        around every iterate, `draws` draws IN ALL, dealt evenly to the paths from each path's best iterate.  init as in optimize(); opt: init_alpha, tol_*."""
+        radius = 2.0 if not np.isscalar(init) else float(init)
+        h = Handle(data, self.variant, chains=1, num_warmup=0, num_samples=0, seed=int(seed), init_radius=radius, device=int(device), cus_per_chain=1, twin=0)
+        try:
+            q0 = None if np.isscalar(init) else np.atleast_2d(np.asarray(init, dtype=np.float64))
+            n = int(paths) if q0 is None else q0.shape[0]
+            res = h.pathfinder(q0, None if q0 is not None else n, history_size=int(history_size), num_elbo_draws=int(num_elbo_draws),
+                               num_draws=-(-int(draws) // n), max_lbfgs_iters=int(max_lbfgs_iters), **opt)
+            return Pathfinder(h, res)
+        except Exception:
+            h.close()
             raise
 
     def sample(self, data, seed=1843, chains=4, parallel_chains=None, iter_warmup=1000, iter_sampling=1000,

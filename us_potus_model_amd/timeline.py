@@ -242,6 +242,32 @@ def laplace(design, variant="full", draws=1000, ev=None, days=None, ev_to_win=27
         hd.close()
 
 
+def pathfinder(design, variant="full", draws=1000, paths_per_date=1, ev=None, days=None, ev_to_win=270, device=0, seed=1843, init_radius=2.0, **opts):
+    """Pathfinder for every run date of a campaign in ONE potus_pathfinder call on a potus_set_datasets_ex handle: `paths_per_date` L-BFGS paths
+    per date with the date's own model, the ELBO of every iterate, `draws` draws per path from the path's best iterate, and, with ev, the summary
+    of potus_pathfinder_summary over `days` (default: election day) per path.  opts: Handle.pathfinder_opts' fields.  dict(lp, lq, log_ratio
+    [dates, paths, draws], return_code, iterations, best_iteration, elbo [dates, paths], timing, and with ev: state [dates, paths, days, S, 4],
+    national, electoral_votes, n_draws).  A path whose code is not 0 has NaN."""
+    n, k = int(design["keep_state"].shape[0]), int(paths_per_date)
+    if int(draws) < 1 or (ev is not None and int(draws) > MAX_DRAWS):
+        raise ValueError(f"timeline.pathfinder: {draws} draws per path (1 .. {MAX_DRAWS} with a summary)")
+    hd = Handle(design["data"], variant, chains=n, num_warmup=0, num_samples=0, seed=int(seed), init_radius=float(init_radius), device=int(device), **_BATCHED)
+    try:
+        set_design(hd, design)
+        res = hd.pathfinder(None, n * k, num_draws=int(draws), **opts)
+        best = res["best_iteration"]
+        out = dict(lp=res["lp"].reshape(n, k, -1), lq=res["lq"].reshape(n, k, -1), log_ratio=(res["lp"] - res["lq"]).reshape(n, k, -1),
+                   return_code=res["return_code"].reshape(n, k), iterations=res["iterations"].reshape(n, k), best_iteration=best.reshape(n, k),
+                   elbo=np.array([res["elbo"][p, l] if l > 0 else np.nan for p, l in enumerate(best)]).reshape(n, k), timing=hd.pathfinder_timing(),
+                   run_dates=list(design.get("run_dates", range(n))))
+        if ev is not None:
+            sm = hd.pathfinder_summary(ev, days, ev_to_win)
+            out.update({key: v.reshape((n, k) + v.shape[1:]) for key, v in sm.items()})
+        return out
+    finally:
+        hd.close()
+
+
 def save_fixture(path, design):
     """The per-date part of a design (masks, priors, scales, dates) as one .npz: data only."""
     np.savez_compressed(path, keep_state=np.packbits(design["keep_state"], axis=1), keep_national=np.packbits(design["keep_national"], axis=1),
