@@ -506,6 +506,39 @@ potus_pathfinder <- function(data, variant = c("full", "no_mode_adjustment"), pa
        elbo = matrix(r$elbo, paths, rows, byrow = TRUE), kept = matrix(r$kept, paths, rows, byrow = TRUE))
 }
 
+# ---- mean-field ADVI (DESIGN.md section 4p): cmdstanr's model$variational(data, algorithm = "meanfield", ...) with its argument names ----
+# `runs` independent runs in one call (cmdstanr runs one) from init (a radius, or a matrix [runs, D] of unconstrained starts), output_samples
+# draws per run.  Returns mean, sd = exp(omega) [runs, D], q [runs * output_samples, D] (run-major), lp, lq, log_ratio = lp - lq, and per run
+# return_code (1 MEAN_CONVERGED, 2 MEDIAN_CONVERGED, 3 MAXIT, 4 NONFINITE, 5 INIT, 6 ADAPT_FAILED; 5 and 6: NaN draws), flags (1: may be
+# diverging), iterations, eta, elbo [runs, iter %/% eval_elbo + 1] (column 1 the initial ELBO, NaN behind the end), adapt_elbo [runs, 5].
+potus_variational <- function(data, variant = c("full", "no_mode_adjustment"), runs = 1, init = 2, seed = 1843, algorithm = "meanfield", iter = 10000,
+                              grad_samples = 1, elbo_samples = 100, eta = 1, adapt_engaged = TRUE, adapt_iter = 50, tol_rel_obj = 0.01, eval_elbo = 100,
+                              output_samples = 1000, elbo_offset = 0, draw_offset = 0, run_offset = 0, device = 0) {
+  variant <- match.arg(variant)
+  if (!identical(algorithm, "meanfield")) stop("potus_variational: algorithm = \"", algorithm, "\" is not built (meanfield only)")
+  q0 <- if (is.matrix(init)) init else NULL
+  if (!is.null(q0)) runs <- nrow(q0)
+  radius <- if (is.null(q0)) init else 2
+  res <- .potus_create(data, variant, c(1L, 0L, 0L, 0L, 10L, as.integer(device), 0L, 1L, 0L, 0L, 0L, 0L), c(0.8, 0.05, 0.75, 10, 1, radius, seed))
+  .potus_check(res$status)
+  on.exit(.C("potus_R_destroy", res$handle, status = integer(1)))
+  D <- .C("potus_R_num_columns", res$handle, D = integer(1), n_cols = integer(1), status = integer(1))$D
+  m <- as.integer(output_samples); n <- runs * m; trace <- as.integer(iter) %/% as.integer(eval_elbo) + 1L
+  r <- .C("potus_R_variational", res$handle,
+          as.integer(c(iter, grad_samples, elbo_samples, eval_elbo, isTRUE(adapt_engaged), adapt_iter, m, draw_offset, run_offset, runs, !is.null(q0))),
+          as.double(c(eta, tol_rel_obj, elbo_offset)), if (is.null(q0)) double(1) else as.double(t(q0)),
+          info = integer(6 * runs), mu = double(runs * D), omega = double(runs * D), elbo = double(runs * trace), adapt_elbo = double(runs * 5),
+          q = double(max(n * D, 1)), lp = double(max(n, 1)), lq = double(max(n, 1)), status = integer(1))
+  .potus_check(r$status)
+  info6 <- matrix(r$info, runs, 6, byrow = TRUE)
+  etas <- c(100, 10, 1, 0.1, 0.01)
+  list(mean = matrix(r$mu, runs, D, byrow = TRUE), sd = exp(matrix(r$omega, runs, D, byrow = TRUE)),
+       q = matrix(r$q[seq_len(n * D)], n, D, byrow = TRUE), lp = r$lp[seq_len(n)], lq = r$lq[seq_len(n)], log_ratio = r$lp[seq_len(n)] - r$lq[seq_len(n)],
+       return_code = info6[, 1], flags = info6[, 2], iterations = info6[, 3],
+       eta = ifelse(info6[, 4] >= 0, etas[pmax(info6[, 4], 0) + 1], if (isTRUE(adapt_engaged)) NA_real_ else eta),
+       elbo = matrix(r$elbo, runs, trace, byrow = TRUE), adapt_elbo = matrix(r$adapt_elbo, runs, 5, byrow = TRUE))
+}
+
 # ---- joint election outcomes (us_potus_model_amd/outcomes.py is the same in Python; DESIGN.md section 4f) ----
 # What the run scripts compute from the JOINT outcome of a draw, counted on the device over the post-warm-up draws of every chain of the fit:
 # the distribution of Democratic electoral votes (final_2016.R:904-920), the tipping-point state (final_2012.R:809-843), how often states i and j

@@ -520,6 +520,57 @@ int potus_pathfinder_scores_device(int handle, int day_begin, int day_end, void 
 int potus_pathfinder_summary(int handle, int day_begin, int day_end, const double *ev, int ev_to_win,
                              double *state_out, double *natl_out, double *ev_out, int32_t *n_draws_out);
 int potus_pathfinder_timing(double *ms /*[4]: L-BFGS, alpha, ELBO, draws; HIP events, calling thread's last potus_pathfinder[_path]*/);
+/* ---- mean-field ADVI: cmdstanr's $variational(algorithm = "meanfield"), batched; the rules of CmdStan 2.24's advi.hpp ----
+ * q = N(mu, diag(exp(omega))^2) on the unconstrained scale.  Start: mu_0 = q0 or U(-r, r) with the handle's init_radius, omega_0 = 0.
+ * Gradient step t = 1, 2, ...: for m = 1 .. grad_samples, eps_m ~ N(0, I), zeta = mu + exp(omega) o eps_m, (lp, g) = log_prob_grad<jacobian = true>
+ * (zeta); g_mu = mean g, g_omega = mean(g o eps) o exp(omega) + 1; for mu and omega alike s = g^2 at t = 1, afterwards s <- 0.9 g^2 + 0.1 s, and
+ * theta <- theta + (eta / sqrt(t)) g / (1 + sqrt(s)).  A non-finite lp or gradient entry ends the run (NONFINITE) at the last finished iterate.
+ * ELBO(mu, omega) = mean over elbo_samples draws of lp(zeta_k) + 1/2 D (1 + log 2 pi) + sum omega + elbo_offset.
+ *   Deviation 1: Stan redraws a non-finite lp up to elbo_samples times; here any non-finite lp makes that ELBO -inf (Pathfinder's rule in this
+ *   library: fixed counters cannot redraw).  Deviation 2: lp is the library's lp__, constants dropped, where Stan uses log_prob<propto = false>;
+ *   elbo_offset adds the constant for a caller who wants it: it enters the relative differences below and nothing else.
+ * Adaptation (adapt_engaged): elbo_init = ELBO(mu_0, omega_0), not finite: INIT.  Each eta of (100, 10, 1, 0.1, 0.01) runs adapt_iter steps from
+ * (mu_0, omega_0) with s reset, then its ELBO (a NONFINITE candidate counts as -inf).  In sequence order: if elbo < best and best > elbo_init,
+ * stop; else if elbo > best, best = elbo and eta* = eta; after the last candidate, its elbo <= elbo_init is ADAPT_FAILED.  The five candidates
+ * are independent and run at once; the sequential rule is applied to the five ELBOs afterwards and gives the sequential algorithm's result.
+ * Main run from (mu_0, omega_0), s reset, eta* (eta as given with adapt_engaged = 0).  Every eval_elbo iterations: prev = elbo (starts at 0, so
+ * the first relative difference is 1), elbo = ELBO, delta = |(elbo - prev) / elbo| into a circular buffer of max(floor(0.1 iter / eval_elbo), 2)
+ * entries; the run ends MEAN_CONVERGED when mean(buffer) < tol_rel_obj, else MEDIAN_CONVERGED when median(buffer) < tol_rel_obj (Stan's
+ * circ_buff_median: nth_element at n / 2, the UPPER middle entry of an even number), else MAXIT at t = iter (iter < eval_elbo: no evaluation).
+ * Flag bit 1 of the info word: t > 10 eval_elbo and mean or median > 0.5 (Stan's "may be diverging").
+ * Codes: 1 MEAN_CONVERGED, 2 MEDIAN_CONVERGED, 3 MAXIT, 4 NONFINITE, 5 INIT, 6 ADAPT_FAILED.  INIT and ADAPT_FAILED leave no approximation:
+ * mu, omega and the run's draws are NaN; a code fails its run alone, never the call.
+ * Normals: Philox4x32-10 as the sampler's, key = the handle's seed, the NEW purpose 10; coordinates 2 j, 2 j + 1 are the Box-Muller pair of counter
+ * {j, 10 | aux << 8, iter word, run_offset + r + 1} with aux = stage | draw << 4:
+ *   gradient draw m of step t, main run                 stage 0,      draw m, iter word t
+ *   gradient draw m of step t, adaptation candidate c   stage 1 + c,  draw m, iter word t          (c = 0 .. 4)
+ *   ELBO draw k at iterate t (t = 0: the initial ELBO)  stage 8 (main) or 9 + c, draw k, iter word t
+ *   library start, coordinate i (a uniform)             {i, 10 | 14 << 8, 0, run_offset + r + 1}
+ *   final draw n                                        stage 15,     draw 0, iter word draw_offset + n + 1
+ * so a run's bytes depend on neither the batch, nor the number of workgroups of the ELBO grid (environment variable POTUS_ADVI_G, default: the
+ * compute units; tests), nor output_samples, nor draw_offset.  Runs per handle as in potus_optimize: run r uses data set r / (n_runs / n_datasets).
+ * Outputs: info_out [n_runs][6] = code, flag bits, iterations, index of eta* (-1: none), model passes, ELBO evaluations of the main run;
+ * mu_out, omega_out [n_runs][D]; elbo_out [n_runs][iter / eval_elbo + 1]: the initial ELBO at 0, entry j the ELBO at t = j eval_elbo, NaN behind
+ * the end; adapt_elbo_out [n_runs][5] (NaN with adapt_engaged = 0); q_out [n_runs][output_samples][D]: zeta_n = mu + exp(omega) o eps_n; lp_out:
+ * log_prob of the draw with the bytes of potus_log_prob_grad; lq_out = -1/2 |eps|^2 - sum omega - 1/2 D log 2 pi.  Any output but info_out may be
+ * NULL.  The rows [lp__, six NaN, zeta] of the last call stay on the handle for the three accessors, which are potus_laplace's with a run in the
+ * place of a mode.  Refused before any kernel runs, as in potus_optimize: cus_per_chain > 1, the dense metric, algorithm = fullrank
+ * (POTUS_ERR_UNSUPPORTED); n_runs no multiple of the data sets, iter / eval_elbo / adapt_iter < 1, grad_samples or elbo_samples outside
+ * 1..1048575, eta not positive, negative tol_rel_obj, output_samples or offsets (POTUS_ERR_ARG).  No chain state is touched. */
+#define POTUS_ADVI_MEANFIELD 0
+#define POTUS_ADVI_FULLRANK 1
+typedef struct potus_advi_opts {
+  int32_t algorithm, iter, grad_samples, elbo_samples, eval_elbo, adapt_engaged, adapt_iter, output_samples, draw_offset, run_offset;
+  double eta, tol_rel_obj, elbo_offset;
+} potus_advi_opts;   /* 64 bytes */
+void potus_default_advi_opts(potus_advi_opts *o);   /* meanfield, 10000, 1, 100, 100, adapt on / 50, 1000 draws, offsets 0; 1.0, 0.01, 0 */
+int potus_advi(int handle, const potus_advi_opts *o, const double *q0 /*[n_runs][D] or NULL*/, int n_runs, int32_t *info_out, double *mu_out,
+               double *omega_out, double *elbo_out, double *adapt_elbo_out, double *q_out, double *lp_out, double *lq_out);
+int potus_advi_write_array_device(int handle, int col_begin, int col_end, void *out_device);
+int potus_advi_scores_device(int handle, int day_begin, int day_end, void *out_device);
+int potus_advi_summary(int handle, int day_begin, int day_end, const double *ev, int ev_to_win,
+                       double *state_out, double *natl_out, double *ev_out, int32_t *n_draws_out);
+int potus_advi_timing(double *ms /*[4]: adaptation, gradient segments, ELBO, draws; HIP events, calling thread's last potus_advi*/);
 /* Prior predictive simulation: n_sims draws theta ~ prior (poll_model_2020.stan:116-128) on the unconstrained scale (q_out [n_sims][D];
  * rho_e_bias ~ normal(0.7, 0.1) restricted to (0, 1), stored as logit(rho)) and y ~ binomial(n_two_share, inv_logit(logit_pi(theta)))
  * (stan:85-113; exact sampler: inversion when n min(p, 1 - p) < 10, BTRS above) in the caller's poll order.  Any output may be null.
@@ -669,6 +720,10 @@ void potus_R_optimize(int *handle, int *iopts /*[7]: jacobian, history_size, ite
 void potus_R_pathfinder(int *handle, int *iopts /*[9]: history_size, num_elbo_draws, num_draws, draw_offset, path_offset, max_lbfgs_iters, L-BFGS history, n_paths, q0 given*/,
                         double *dopts /*[6]: init_alpha, tol_obj, tol_rel_obj, tol_grad, tol_rel_grad, tol_param*/, double *q0, int *info_out /*[n_paths][4]*/,
                         double *elbo_out, int *kept_out /*[n_paths][max_lbfgs_iters + 1]*/, double *q_out, double *lp_out, double *lq_out, int *status);
+void potus_R_variational(int *handle, int *iopts /*[11]: iter, grad_samples, elbo_samples, eval_elbo, adapt_engaged, adapt_iter, output_samples, draw_offset, run_offset, n_runs, q0 given*/,
+                         double *dopts /*[3]: eta, tol_rel_obj, elbo_offset*/, double *q0, int *info_out /*[n_runs][6]*/, double *mu_out, double *omega_out,
+                         double *elbo_out /*[n_runs][iter / eval_elbo + 1]*/, double *adapt_elbo_out /*[n_runs][5]*/, double *q_out, double *lp_out,
+                         double *lq_out, int *status);
 void potus_R_laplace(int *handle, int *iopts /*[6]: jacobian, draw_offset, n_modes, n_draws, u given, precision wanted*/, double *h, double *mode, double *u,
                      double *q_out, double *lp_out, double *lp_approx_out, double *info_out, double *precision_out, int *status);
 void potus_R_simulate_prior(int *handle, double *seed, int *dims /*[2]: n_sims, sim_offset*/, double *q_out, int *n_democrat_state_out,

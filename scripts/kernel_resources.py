@@ -1,6 +1,7 @@
 #!/usr/bin/env python3
 """Register / scratch / LDS usage of every kernel in the built library (code-object metadata), e.g. to check spills:
-    python scripts/kernel_resources.py [path/to/libpotus_hmc.so]
+    python scripts/kernel_resources.py [path/to/libpotus_hmc.so] [name ...]
+With names, only the kernels whose symbol contains one of them, e.g. `k_vi_ k_opt_lbfgs` for ADVI's three kernels beside the optimiser's.
 """
 import re
 import subprocess
@@ -27,6 +28,10 @@ def resources(lib):
 
 
 if __name__ == "__main__":
-    lib = Path(sys.argv[1]) if len(sys.argv) > 1 else Path(__file__).resolve().parent.parent / "us_potus_model_amd" / "libpotus_hmc.so"
+    default = Path(__file__).resolve().parent.parent / "us_potus_model_amd" / "libpotus_hmc.so"
+    args = sys.argv[1:]
+    lib = Path(args.pop(0)) if args and args[0].endswith(".so") else default
     for r in resources(lib):
+        if args and not any(a in r["name"] for a in args):
+            continue
         print(f"{r['name'][:64]:64s} vgpr {r['vgpr']:>4s} sgpr {r['sgpr']:>4s} vspill {r['vspill']:>4s} sspill {r['sspill']:>4s} scratch {r['scratch']:>5s} lds {r['lds']:>6s}")

@@ -81,6 +81,18 @@ class PotusPathfinderOpts(C.Structure):
     ]
 
 
+class PotusAdviOpts(C.Structure):
+    """potus_advi_opts (64 bytes); start from potus_default_advi_opts()."""
+    _fields_ = [
+        ("algorithm", C.c_int32), ("iter", C.c_int32), ("grad_samples", C.c_int32), ("elbo_samples", C.c_int32), ("eval_elbo", C.c_int32),
+        ("adapt_engaged", C.c_int32), ("adapt_iter", C.c_int32), ("output_samples", C.c_int32), ("draw_offset", C.c_int32), ("run_offset", C.c_int32),
+        ("eta", C.c_double), ("tol_rel_obj", C.c_double), ("elbo_offset", C.c_double),
+    ]
+
+
+ADVI_ALGORITHMS = {"meanfield": 0, "fullrank": 1}
+ADVI_CODES = {1: "MEAN_CONVERGED", 2: "MEDIAN_CONVERGED", 3: "MAXIT", 4: "NONFINITE", 5: "INIT", 6: "ADAPT_FAILED"}
+ADVI_ETAS = (100.0, 10.0, 1.0, 0.1, 0.01)
 LAPLACE_CODES = {0: "OK", 1: "NOT_PD", 2: "NOT_FINITE"}
 PATHFINDER_CODES = {0: "OK", 1: "NO_ELBO"}
 OPTIMIZE_CODES = {1: "ABSF", 2: "RELF", 3: "ABSGRAD", 4: "RELGRAD", 5: "ABSX", 6: "MAXIT", 7: "LSFAIL", 8: "INIT"}

@@ -763,6 +763,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, c
 #include "potus_optimize.hpp"   // the posterior mode: batched L-BFGS, one workgroup per path
 #include "potus_laplace.hpp"    // the Laplace approximation at a mode: Hessian, factor, draws
 #include "potus_pathfinder.hpp" // Pathfinder: a normal around every iterate of an L-BFGS path, the best ELBO, draws
+#include "potus_advi.hpp"       // mean-field ADVI: stochastic-gradient tracks, the ELBO on a chip-wide grid, draws
 
 // ======================================================================== host
 namespace {
@@ -939,6 +940,10 @@ struct Sampler {
   double *pf_rows = nullptr;
   int pf_paths = 0, pf_draws = 0;
   std::vector<int> pf_code;    // per path: 0 = its rows are draws
+  // potus_advi: the same, [vi_runs][vi_draws][7 + D]
+  double *vi_rows = nullptr;
+  int vi_runs = 0, vi_draws = 0;
+  std::vector<int> vi_code;    // per run: 0 = its rows are draws
 };
 
 std::mutex g_mu;
@@ -2467,6 +2472,7 @@ int potus_destroy(int handle) {
   for (void *p : sp->allocs) (void)hipFree(p);
   if (sp->lap_rows) (void)hipFree(sp->lap_rows);
   if (sp->pf_rows) (void)hipFree(sp->pf_rows);
+  if (sp->vi_rows) (void)hipFree(sp->vi_rows);
   (void)hipEventDestroy(sp->ev0); (void)hipEventDestroy(sp->ev1); (void)hipStreamDestroy(sp->stream);
   if (sp->mv0) (void)hipEventDestroy(sp->mv0);
   if (sp->mv1) (void)hipEventDestroy(sp->mv1);
@@ -4316,12 +4322,12 @@ void potus_default_optimize_opts(potus_optimize_opts *o) {
 
 namespace {
 // what every call that deals paths to a handle's data sets refuses first: the handle's layout, then the number of paths
-int paths_check(const Sampler *sp, const char *what, int n_paths) {
+int paths_check(const Sampler *sp, const char *what, int n_paths, const char *noun = "n_paths") {
   if (sp->K != 1) return fail(POTUS_ERR_UNSUPPORTED, "%s: needs one workgroup per chain (cus_per_chain = 1); this handle runs %d per chain", what, sp->K);
   if (sp->dense) return fail(POTUS_ERR_UNSUPPORTED, "%s: the dense metric is not supported (metric = POTUS_METRIC_DIAG only)", what);
   if (!sp->k1_unsupported.empty()) return fail(POTUS_ERR_UNSUPPORTED, "%s: %s", what, sp->k1_unsupported.c_str());
-  if (n_paths <= 0) return fail(POTUS_ERR_ARG, "%s: n_paths = %d, at least 1", what, n_paths);
-  if (sp->n_ds && n_paths % sp->n_ds) return fail(POTUS_ERR_ARG, "%s: n_paths = %d is not a multiple of the handle's %d data sets", what, n_paths, sp->n_ds);
+  if (n_paths <= 0) return fail(POTUS_ERR_ARG, "%s: %s = %d, at least 1", what, noun, n_paths);
+  if (sp->n_ds && n_paths % sp->n_ds) return fail(POTUS_ERR_ARG, "%s: %s = %d is not a multiple of the handle's %d data sets", what, noun, n_paths, sp->n_ds);
   return 0;
 }
 // what potus_optimize and potus_pathfinder refuse alike, before any kernel runs
@@ -4447,8 +4453,9 @@ struct KeptRows {
   int n() const { return groups * draws; }
   int per_ds(const Sampler *sp) const { return groups / std::max(sp->n_ds, 1) * draws; }   // rows per data set, group-major
 };
-enum { KEPT_LAPLACE = 0, KEPT_PATHFINDER = 1 };
+enum { KEPT_LAPLACE = 0, KEPT_PATHFINDER = 1, KEPT_ADVI = 2 };
 KeptRows kept_rows(const Sampler *sp, int which) {
+  if (which == KEPT_ADVI) return KeptRows{"no ADVI draws on this handle (potus_advi with output_samples >= 1 first)", "run", sp->vi_rows, sp->vi_runs, sp->vi_draws, &sp->vi_code};
   if (which == KEPT_PATHFINDER) return KeptRows{"no Pathfinder draws on this handle (potus_pathfinder or potus_pathfinder_path with num_draws >= 1 first)", "path", sp->pf_rows, sp->pf_paths, sp->pf_draws, &sp->pf_code};
   return KeptRows{"no Laplace draws on this handle (potus_laplace with n_draws >= 1 first)", "mode", sp->lap_rows, sp->lap_modes, sp->lap_draws, &sp->lap_code};
 }
@@ -4998,6 +5005,252 @@ int potus_pathfinder_timing(double *ms) {
   return timing_out("potus_pathfinder_timing", g_pf_ms, 4, ms);
 }
 
+// ---------------------------------------------------------------------------------------------- mean-field ADVI (potus_advi.hpp)
+namespace {
+thread_local double g_vi_ms[4] = {0.0, 0.0, 0.0, 0.0};   // the calling thread's last potus_advi: adaptation, gradient segments, ELBO, draws (HIP events, summed)
+}
+
+void potus_default_advi_opts(potus_advi_opts *o) {
+  if (!o) return;
+  o->algorithm = POTUS_ADVI_MEANFIELD; o->iter = 10000; o->grad_samples = 1; o->elbo_samples = 100; o->eval_elbo = 100; o->adapt_engaged = 1;
+  o->adapt_iter = 50; o->output_samples = 1000; o->draw_offset = 0; o->run_offset = 0; o->eta = 1.0; o->tol_rel_obj = 0.01; o->elbo_offset = 0.0;
+}
+
+int potus_advi(int handle, const potus_advi_opts *opts, const double *q0, int n_runs, int32_t *info_out, double *mu_out, double *omega_out,
+               double *elbo_out, double *adapt_elbo_out, double *q_out, double *lp_out, double *lq_out) {
+  const char *what = "potus_advi";
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  potus_advi_opts o;
+  potus_default_advi_opts(&o);
+  if (opts) o = *opts;
+  if (const int rc_ = paths_check(sp, what, n_runs, "n_runs")) return rc_;
+  if (o.algorithm == POTUS_ADVI_FULLRANK) return fail(POTUS_ERR_UNSUPPORTED, "%s: algorithm = fullrank is not built (a D x D factor updated every iteration); meanfield only", what);
+  if (o.algorithm != POTUS_ADVI_MEANFIELD) return fail(POTUS_ERR_ARG, "%s: algorithm = %d, 0 (meanfield)", what, o.algorithm);
+  if (!info_out) return fail(POTUS_ERR_ARG, "%s: null output (info_out is required)", what);
+  if (o.iter < 1) return fail(POTUS_ERR_ARG, "%s: iter = %d, at least 1", what, o.iter);
+  if (o.grad_samples < 1 || o.grad_samples > VI_MAX_SAMPLES) return fail(POTUS_ERR_ARG, "%s: grad_samples = %d outside 1..%d", what, o.grad_samples, VI_MAX_SAMPLES);
+  if (o.elbo_samples < 1 || o.elbo_samples > VI_MAX_SAMPLES) return fail(POTUS_ERR_ARG, "%s: elbo_samples = %d outside 1..%d", what, o.elbo_samples, VI_MAX_SAMPLES);
+  if (o.eval_elbo < 1) return fail(POTUS_ERR_ARG, "%s: eval_elbo = %d, at least 1", what, o.eval_elbo);
+  if (o.adapt_engaged != 0 && o.adapt_engaged != 1) return fail(POTUS_ERR_ARG, "%s: adapt_engaged = %d, 0 or 1", what, o.adapt_engaged);
+  if (o.adapt_iter < 1) return fail(POTUS_ERR_ARG, "%s: adapt_iter = %d, at least 1", what, o.adapt_iter);
+  if (o.output_samples < 0) return fail(POTUS_ERR_ARG, "%s: output_samples = %d", what, o.output_samples);
+  if (!(o.eta > 0.0) || !std::isfinite(o.eta)) return fail(POTUS_ERR_ARG, "%s: eta = %g, must be positive and finite", what, o.eta);
+  if (!(o.tol_rel_obj >= 0.0) || !std::isfinite(o.tol_rel_obj)) return fail(POTUS_ERR_ARG, "%s: tol_rel_obj = %g, must be finite and not negative", what, o.tol_rel_obj);
+  if (!std::isfinite(o.elbo_offset)) return fail(POTUS_ERR_ARG, "%s: elbo_offset = %g, must be finite", what, o.elbo_offset);
+  if (o.draw_offset < 0 || (long long)o.draw_offset + o.output_samples >= 0xFFFFFFFFll) return fail(POTUS_ERR_ARG, "%s: draw_offset = %d with %d draws", what, o.draw_offset, o.output_samples);
+  if (o.run_offset < 0 || (long long)o.run_offset + n_runs >= 0xFFFFFFFFll) return fail(POTUS_ERR_ARG, "%s: run_offset = %d with %d runs", what, o.run_offset, n_runs);
+  const int D = sp->L.D, row = POTUS_N_SAMPLER_COLS + D, Dpad = (D + 7) & ~7, K = o.elbo_samples, Mn = o.output_samples;
+  const int n_stage = o.adapt_engaged ? 1 + ADVI_N_ETA : 1, n_tracks = n_stage * n_runs, trace = o.iter / o.eval_elbo + 1;
+  if ((unsigned long long)VI_NVEC * Dpad * 8ull >= 0x7fffffffull) return fail(POTUS_ERR_UNSUPPORTED, "%s: D = %d: a track's working set must stay below 2 GB", what, D);
+  if ((unsigned long long)n_runs * std::max(Mn, 1) * row >= (1ull << 40) || (unsigned long long)n_tracks * K >= (1ull << 31))
+    return fail(POTUS_ERR_ARG, "%s: %d runs x %d draws of %d coordinates, %d ELBO draws", what, n_runs, Mn, D, K);
+  const double nan = std::numeric_limits<double>::quiet_NaN(), ninf = -std::numeric_limits<double>::infinity();
+  DeviceGuard guard;
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  hipStream_t st = sp->stream;
+  int G = 0;
+  HIP_TRY(hipDeviceGetAttribute(&G, hipDeviceAttributeMultiprocessorCount, sp->device));
+  G = std::max(G, 1);
+  if (const char *e = getenv("POTUS_ADVI_G")) G = std::max(1, atoi(e));   // tests and scripts/variational.py: no output depends on it
+  const size_t lds = sp->lds_bytes;
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_vi_sga), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_vi_elbo), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_lap_lp), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  DsPlan pl;
+  pl.of(sp);
+  const int per_ds = n_runs / pl.n_ds;
+  // the handle's rows of the last call go first: a call that fails leaves none behind
+  HIP_TRY(hipStreamSynchronize(st));
+  if (sp->vi_rows) { (void)hipFree(sp->vi_rows); sp->vi_rows = nullptr; }
+  sp->vi_runs = sp->vi_draws = 0; sp->vi_code.clear();
+  int rc;
+  double *drows = nullptr;
+  const size_t rows_total = (size_t)n_runs * Mn;
+  if (Mn > 0) {
+    void *p = nullptr;
+    if (hipMalloc(&p, rows_total * row * 8) != hipSuccess) { (void)hipGetLastError(); return fail(POTUS_ERR_DEVICE, "%s: hipMalloc of %zu bytes for the rows failed", what, rows_total * row * 8); }
+    drows = static_cast<double *>(p);
+  }
+  struct RowsOwner { double *p; ~RowsOwner() { if (p) (void)hipFree(p); } } owner{drows};   // until the call has succeeded
+  DevBufs tmp;   // the working set is the call's own: the sampler's chain state is not touched
+  const int lp_grid = std::max(1, std::min(Mn, 1024));
+  double *dq0 = nullptr, *work = nullptr, *dslot = nullptr, *dent = nullptr, *escr = nullptr, *dlq = nullptr, *dlp = nullptr, *gscr = nullptr;
+  ViTrack *dtrack = nullptr;
+  int *det = nullptr, *dno = nullptr;
+  ViParams *dP = nullptr;
+  if ((rc = tmp.get(&work, (size_t)n_tracks * VI_NVEC * Dpad * 8, what)) || (rc = tmp.get(&dtrack, (size_t)n_tracks * sizeof(ViTrack), what)) ||
+      (rc = tmp.get(&det, (size_t)n_tracks * 4, what)) || (rc = tmp.get(&dslot, (size_t)n_tracks * K * 8, what)) || (rc = tmp.get(&dent, (size_t)n_tracks * 8, what)) ||
+      (rc = tmp.get(&escr, (size_t)G * 2 * Dpad * 8, what)) || (rc = tmp.get(&dlq, std::max<size_t>(rows_total, 1) * 8, what)) ||
+      (rc = tmp.get(&dlp, std::max<size_t>(rows_total, 1) * 8, what)) || (rc = tmp.get(&gscr, (size_t)lp_grid * Dpad * 8, what)) ||
+      (rc = tmp.get(&dno, (size_t)n_runs * 4, what)) || (rc = tmp.get(&dP, sizeof(ViParams), what))) return rc;
+  if (q0) {
+    if ((rc = tmp.get(&dq0, (size_t)n_runs * D * 8, what))) return rc;
+    HIP_TRY(hipMemcpyAsync(dq0, q0, (size_t)n_runs * D * 8, hipMemcpyHostToDevice, st));
+  }
+  std::vector<ViTrack> hT(n_tracks);
+  for (int k = 0; k < n_tracks; k++) {
+    const int stage = k / n_runs;
+    hT[k] = ViTrack{stage ? advi_eta(stage - 1) : o.eta, 0, 0, stage ? o.adapt_iter : 0, 0};
+  }
+  ViParams P{dq0, work, dtrack, det, dslot, dent, escr, drows, dlq, dno, n_runs, per_ds, D, Dpad, o.grad_samples, K, 0, Mn, o.run_offset, o.draw_offset, 1,
+             sp->R.init_radius, sp->R.seed_lo, sp->R.seed_hi};
+  LapSpans t_adapt, t_grad, t_elbo, t_draws;
+  // n_blocks tracks from 0 on, each for its own n_iter iterations (a track whose code is set returns at once)
+  auto sga = [&](int n_blocks, int init, LapSpans &span) -> int {
+    P.init = init;
+    HIP_TRY(hipMemcpyAsync(dtrack, hT.data(), (size_t)n_blocks * sizeof(ViTrack), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dP, &P, sizeof(P), hipMemcpyHostToDevice, st));   // (pageable sources: copied before the calls return)
+    if (const int r_ = span.begin(st)) return r_;
+    hipLaunchKernelGGL(k_vi_sga, dim3(n_blocks), dim3(PT_THREADS), lds, st, pl.Mg, (const ViParams *)dP);
+    HIP_TRY(hipGetLastError());
+    return span.end(st);
+  };
+  // the ELBO of the listed tracks at their iterates: one launch, one synchronisation; the mean over a track's slots in index order
+  std::vector<double> hslot((size_t)n_tracks * K), hent(n_tracks);
+  const double entropy0 = 0.5 * (double)D * (1.0 + 1.8378770664093454836);
+  auto elbo_of = [&](const std::vector<int> &tracks, std::vector<double> &out) -> int {
+    const int n_et = (int)tracks.size();
+    const long long n_items = (long long)n_et * K;
+    P.n_et = n_et;
+    HIP_TRY(hipMemcpyAsync(det, tracks.data(), (size_t)n_et * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dP, &P, sizeof(P), hipMemcpyHostToDevice, st));
+    if (const int r_ = t_elbo.begin(st)) return r_;
+    hipLaunchKernelGGL(k_vi_elbo, dim3((unsigned)std::min<long long>(G, n_items)), dim3(PT_THREADS), lds, st, pl.Mg, (const ViParams *)dP);
+    HIP_TRY(hipGetLastError());
+    if (const int r_ = t_elbo.end(st)) return r_;
+    HIP_TRY(hipMemcpyAsync(hslot.data(), dslot, (size_t)n_items * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hent.data(), dent, (size_t)n_et * 8, hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipMemcpyAsync(hT.data(), dtrack, (size_t)n_tracks * sizeof(ViTrack), hipMemcpyDeviceToHost, st));
+    HIP_TRY(hipStreamSynchronize(st));
+    out.assign(n_et, ninf);
+    for (int e = 0; e < n_et; e++) {
+      double acc = 0.0;
+      bool bad = false;
+      for (int k = 0; k < K; k++) { const double v = hslot[(size_t)e * K + k]; bad = bad || !std::isfinite(v); acc += v; }
+      if (!bad) out[e] = acc / (double)K + entropy0 + hent[e] + o.elbo_offset;
+    }
+    return 0;
+  };
+
+  // ---- the starts, the five candidates of every run at once, the initial ELBO and theirs, the sequential rule on the five numbers
+  std::vector<int> code(n_runs, 0), flags(n_runs, 0), eta_index(n_runs, -1), iters(n_runs, 0);
+  std::vector<long long> passes(n_runs, 0);
+  std::vector<double> htrace((size_t)n_runs * trace, nan), hadapt((size_t)n_runs * ADVI_N_ETA, nan), e0;
+  if ((rc = sga(n_tracks, 1, t_adapt))) return rc;
+  {
+    std::vector<int> all(n_tracks);
+    for (int k = 0; k < n_tracks; k++) all[k] = k;
+    if ((rc = elbo_of(all, e0))) return rc;
+  }
+  for (int r = 0; r < n_runs; r++) {
+    htrace[(size_t)r * trace] = e0[r];
+    passes[r] += K;
+    double eta = o.eta;
+    if (!std::isfinite(e0[r])) code[r] = ADVI_INIT;
+    if (o.adapt_engaged) {
+      double cand[ADVI_N_ETA];
+      for (int k = 0; k < ADVI_N_ETA; k++) {
+        const ViTrack &tk = hT[(size_t)(k + 1) * n_runs + r];
+        cand[k] = tk.code ? ninf : e0[(size_t)(k + 1) * n_runs + r];
+        hadapt[(size_t)r * ADVI_N_ETA + k] = cand[k];
+        passes[r] += (long long)tk.t * o.grad_samples + (tk.code ? 1 : K);
+      }
+      if (!code[r]) {
+        eta_index[r] = advi_pick_eta(e0[r], cand, nullptr);
+        if (eta_index[r] < 0) code[r] = ADVI_ADAPT_FAILED; else eta = advi_eta(eta_index[r]);
+      }
+    }
+    hT[r] = ViTrack{eta, 0, code[r], 0, 0};
+  }
+
+  // ---- the main runs: segments of eval_elbo iterations, one synchronisation each
+  std::vector<AdviConv> conv(n_runs, AdviConv(o.iter, o.eval_elbo));
+  std::vector<int> live;
+  std::vector<double> e1;
+  for (int t_now = 0;;) {
+    live.clear();
+    for (int r = 0; r < n_runs; r++) if (!code[r]) live.push_back(r);
+    if (live.empty()) break;
+    const int seg = std::min(o.eval_elbo, o.iter - t_now);
+    for (int r : live) hT[r].n_iter = seg;
+    if ((rc = sga(n_runs, 0, t_grad))) return rc;
+    t_now += seg;
+    const bool eval = t_now % o.eval_elbo == 0;
+    if (eval) { if ((rc = elbo_of(live, e1))) return rc; }
+    else {
+      HIP_TRY(hipMemcpyAsync(hT.data(), dtrack, (size_t)n_runs * sizeof(ViTrack), hipMemcpyDeviceToHost, st));
+      HIP_TRY(hipStreamSynchronize(st));
+    }
+    for (size_t e = 0; e < live.size(); e++) {
+      const int r = live[e];
+      if (hT[r].code == ADVI_NONFINITE) code[r] = ADVI_NONFINITE;     // found by the track itself: it stands at its last finished iterate
+      else if (eval) {
+        htrace[(size_t)r * trace + t_now / o.eval_elbo] = e1[e];
+        passes[r] += K;
+        code[r] = conv[r].push(e1[e], t_now, o.iter, o.eval_elbo, o.tol_rel_obj, &flags[r]);
+      } else code[r] = ADVI_MAXIT;                                      // iter is no multiple of eval_elbo: the tail has no evaluation
+      hT[r].code = code[r];
+    }
+  }
+  for (int r = 0; r < n_runs; r++) {
+    iters[r] = hT[r].t;
+    passes[r] += (long long)hT[r].t * o.grad_samples + (code[r] == ADVI_NONFINITE ? 1 : 0);
+  }
+
+  // ---- the draws, and what goes back
+  std::vector<int> no_draws(n_runs);
+  for (int r = 0; r < n_runs; r++) no_draws[r] = code[r] == ADVI_INIT || code[r] == ADVI_ADAPT_FAILED;
+  if (Mn > 0) {
+    HIP_TRY(hipMemcpyAsync(dno, no_draws.data(), (size_t)n_runs * 4, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(dP, &P, sizeof(P), hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemsetAsync(dlp, 0xFF, rows_total * 8, st));   // (NaN: a run without an approximation)
+    if ((rc = t_draws.begin(st))) return rc;
+    hipLaunchKernelGGL(k_vi_draws, dim3((unsigned)std::min<size_t>(rows_total, 65535)), dim3(PT_THREADS), 0, st, (const ViParams *)dP);
+    HIP_TRY(hipGetLastError());
+    for (int r = 0; r < n_runs; r++) if (!no_draws[r]) {   // lp__ with the run's model: Laplace's stage, the bytes of potus_log_prob_grad
+      hipLaunchKernelGGL(k_lap_lp, dim3(lp_grid), dim3(PT_THREADS), lds, st, pl.Mg + r / per_ds, drows + (size_t)r * Mn * row, Mn, gscr, Dpad, dlp + (size_t)r * Mn);
+      HIP_TRY(hipGetLastError());
+      passes[r] += Mn;
+    }
+    if ((rc = t_draws.end(st))) return rc;
+    if (q_out) HIP_TRY(hipMemcpy2DAsync(q_out, (size_t)D * 8, drows + POTUS_N_SAMPLER_COLS, (size_t)row * 8, (size_t)D * 8, rows_total, hipMemcpyDeviceToHost, st));
+    if (lp_out) HIP_TRY(hipMemcpyAsync(lp_out, dlp, rows_total * 8, hipMemcpyDeviceToHost, st));
+    if (lq_out) HIP_TRY(hipMemcpyAsync(lq_out, dlq, rows_total * 8, hipMemcpyDeviceToHost, st));
+  }
+  const size_t wpitch = (size_t)VI_NVEC * Dpad * 8;   // the main tracks are the first n_runs
+  if (mu_out) HIP_TRY(hipMemcpy2DAsync(mu_out, (size_t)D * 8, work + (size_t)VI_V_MU * Dpad, wpitch, (size_t)D * 8, n_runs, hipMemcpyDeviceToHost, st));
+  if (omega_out) HIP_TRY(hipMemcpy2DAsync(omega_out, (size_t)D * 8, work + (size_t)VI_V_OM * Dpad, wpitch, (size_t)D * 8, n_runs, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  double ms[4];
+  if ((rc = t_adapt.sum(&ms[0])) || (rc = t_grad.sum(&ms[1])) || (rc = t_elbo.sum(&ms[2])) || (rc = t_draws.sum(&ms[3]))) return rc;
+  std::copy(ms, ms + 4, g_vi_ms);
+  for (int r = 0; r < n_runs; r++) {
+    int32_t *io = info_out + (size_t)r * 6;
+    io[0] = code[r]; io[1] = flags[r]; io[2] = iters[r]; io[3] = eta_index[r]; io[4] = (int32_t)std::min<long long>(passes[r], 0x7fffffffll); io[5] = 0;
+    for (int k = 1; k < trace; k++) if (!std::isnan(htrace[(size_t)r * trace + k])) io[5] = k;   // evaluations of the main run
+    if (no_draws[r]) for (double *v : {mu_out, omega_out}) if (v) std::fill(v + (size_t)r * D, v + (size_t)(r + 1) * D, nan);
+  }
+  if (elbo_out) std::copy(htrace.begin(), htrace.end(), elbo_out);
+  if (adapt_elbo_out) std::copy(hadapt.begin(), hadapt.end(), adapt_elbo_out);
+  if (Mn > 0) { sp->vi_rows = drows; owner.p = nullptr; sp->vi_runs = n_runs; sp->vi_draws = Mn; sp->vi_code = no_draws; }
+  return 0;
+}
+
+int potus_advi_write_array_device(int handle, int col_begin, int col_end, void *out_device) {
+  return kept_write_array_device("potus_advi_write_array_device", KEPT_ADVI, handle, col_begin, col_end, out_device);
+}
+int potus_advi_scores_device(int handle, int day_begin, int day_end, void *out_device) {
+  return kept_scores_device("potus_advi_scores_device", KEPT_ADVI, handle, day_begin, day_end, out_device);
+}
+int potus_advi_summary(int handle, int day_begin, int day_end, const double *ev, int ev_to_win, double *state_out, double *natl_out, double *ev_out, int32_t *n_draws_out) {
+  return kept_summary("potus_advi_summary", KEPT_ADVI, handle, day_begin, day_end, ev, ev_to_win, state_out, natl_out, ev_out, n_draws_out);
+}
+int potus_advi_timing(double *ms) {
+  return timing_out("potus_advi_timing", g_vi_ms, 4, ms);
+}
+
 int potus_simulate_prior(int handle, uint64_t seed, int n_sims, int sim_offset, double *q_out, int32_t *n_democrat_state_out, int32_t *n_democrat_national_out) {
   Sampler *sp = get(handle);
   if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
@@ -5478,6 +5731,18 @@ void potus_R_pathfinder(int *handle, int *iopts /*[9]: history_size, num_elbo_dr
   const bool draws = iopts[2] > 0;
   *status = potus_pathfinder(*handle, &o, iopts[8] ? q0 : nullptr, iopts[7], info_out, elbo_out, kept_out, draws ? q_out : nullptr, draws ? lp_out : nullptr,
                              draws ? lq_out : nullptr, nullptr, nullptr);
+}
+void potus_R_variational(int *handle, int *iopts /*[11]: iter, grad_samples, elbo_samples, eval_elbo, adapt_engaged, adapt_iter, output_samples, draw_offset, run_offset, n_runs, q0 given*/,
+                         double *dopts /*[3]: eta, tol_rel_obj, elbo_offset*/, double *q0, int *info_out, double *mu_out, double *omega_out, double *elbo_out,
+                         double *adapt_elbo_out, double *q_out, double *lp_out, double *lq_out, int *status) {
+  potus_advi_opts o;
+  potus_default_advi_opts(&o);
+  o.iter = iopts[0]; o.grad_samples = iopts[1]; o.elbo_samples = iopts[2]; o.eval_elbo = iopts[3]; o.adapt_engaged = iopts[4]; o.adapt_iter = iopts[5];
+  o.output_samples = iopts[6]; o.draw_offset = iopts[7]; o.run_offset = iopts[8];
+  o.eta = dopts[0]; o.tol_rel_obj = dopts[1]; o.elbo_offset = dopts[2];
+  const bool draws = iopts[6] > 0;
+  *status = potus_advi(*handle, &o, iopts[10] ? q0 : nullptr, iopts[9], info_out, mu_out, omega_out, elbo_out, adapt_elbo_out, draws ? q_out : nullptr,
+                       draws ? lp_out : nullptr, draws ? lq_out : nullptr);
 }
 void potus_R_set_datasets(int *handle, int *n_datasets, int *n_democrat_state, int *n_democrat_national, int *status) {
   *status = potus_set_datasets(*handle, *n_datasets, n_democrat_state, n_democrat_national);

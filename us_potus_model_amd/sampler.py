@@ -158,6 +158,17 @@ def load_library():
         L.potus_pathfinder_timing.argtypes = [dp]
         L.potus_R_pathfinder.argtypes = [ip, ip, dp, dp, ip, dp, ip, dp, dp, dp, ip]
         L.potus_R_pathfinder.restype = None
+    if hasattr(L, "potus_advi"):                        # mean-field ADVI (Handle.variational, PotusModel.variational)
+        i32p, vop = C.POINTER(C.c_int32), C.POINTER(_abi.PotusAdviOpts)
+        L.potus_default_advi_opts.argtypes = [vop]
+        L.potus_default_advi_opts.restype = None
+        L.potus_advi.argtypes = [C.c_int, vop, dp, C.c_int, i32p, dp, dp, dp, dp, dp, dp, dp]
+        L.potus_advi_write_array_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.potus_advi_scores_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.potus_advi_summary.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, dp, dp, i32p]
+        L.potus_advi_timing.argtypes = [dp]
+        L.potus_R_variational.argtypes = [ip, ip, dp, dp, ip, dp, dp, dp, dp, dp, dp, dp, ip]
+        L.potus_R_variational.restype = None
     _LIB = L
     return L
 
@@ -178,6 +189,8 @@ EXPORTS = [
     "potus_laplace_timing", "potus_R_laplace",
     "potus_default_pathfinder_opts", "potus_pathfinder", "potus_pathfinder_path", "potus_pathfinder_write_array_device",
     "potus_pathfinder_scores_device", "potus_pathfinder_summary", "potus_pathfinder_timing", "potus_R_pathfinder",
+    "potus_default_advi_opts", "potus_advi", "potus_advi_write_array_device", "potus_advi_scores_device", "potus_advi_summary",
+    "potus_advi_timing", "potus_R_variational",
     "potus_outcomes", "potus_outcomes_device", "potus_outcomes_timing",
     "potus_monitor", "potus_monitor_device",
     "potus_scenario", "potus_scenario_device", "potus_scenario_timing",
@@ -728,6 +741,93 @@ class Handle:
         _check(self.L, self.L.potus_pathfinder_timing(_dp(ms)))
         return dict(lbfgs_ms=float(ms[0]), alpha_ms=float(ms[1]), elbo_ms=float(ms[2]), draws_ms=float(ms[3]))
 
+    def variational_opts(self, **opts):
+        """potus_default_advi_opts with the given fields replaced: algorithm ("meanfield"; "fullrank" is refused by the library), iter,
+        grad_samples, elbo_samples, eval_elbo, adapt_engaged, adapt_iter, output_samples, draw_offset, run_offset, eta, tol_rel_obj, elbo_offset."""
+        o = _abi.PotusAdviOpts()
+        self.L.potus_default_advi_opts(C.byref(o))
+        for k, v in opts.items():
+            if k == "algorithm":
+                o.algorithm = _abi.ADVI_ALGORITHMS[v] if isinstance(v, str) else int(v)
+            elif k in ("eta", "tol_rel_obj", "elbo_offset"):
+                setattr(o, k, float(v))
+            elif k in ("iter", "grad_samples", "elbo_samples", "eval_elbo", "adapt_engaged", "adapt_iter", "output_samples", "draw_offset", "run_offset"):
+                setattr(o, k, int(v))
+            else:
+                raise TypeError(f"unknown ADVI option {k!r}")
+        return o
+
+    def variational(self, q0=None, runs=None, opts=None, **fields):
+        """potus_advi: mean-field ADVI from every start (q0 [runs, D], or None for `runs` library starts).  On a handle with data sets run r
+        uses data set r // (runs // n_datasets).  fields: see variational_opts (or opts: a filled struct).  Returns dict(mu, omega [runs, D],
+        elbo [runs, iter // eval_elbo + 1] (the initial ELBO first, NaN behind the end), adapt_elbo [runs, 5], q [runs, draws, D], lp, lq
+        [runs, draws], return_code, flags, iterations, eta_index, eta, model_passes, evaluations [runs])."""
+        o = opts if opts is not None else self.variational_opts(**fields)
+        p0 = None
+        if q0 is not None:
+            q0 = np.ascontiguousarray(np.atleast_2d(q0), dtype=np.float64)
+            if q0.shape[1] != self.D or (runs is not None and int(runs) != q0.shape[0]):
+                raise ValueError(f"variational: q0 has shape {q0.shape}, [{runs if runs is not None else 'runs'}, {self.D}] expected")
+            runs, p0 = q0.shape[0], _dp(q0)
+        n, m = int(1 if runs is None else runs), max(int(o.output_samples), 0)
+        nn, trace = max(n, 0), max(int(o.iter), 0) // max(int(o.eval_elbo), 1) + 1
+        info = np.zeros((nn, 6), np.int32)
+        r = dict(mu=np.zeros((nn, self.D)), omega=np.zeros((nn, self.D)), elbo=np.zeros((nn, trace)), adapt_elbo=np.zeros((nn, 5)),
+                 q=np.zeros((nn, m, self.D)), lp=np.zeros((nn, m)), lq=np.zeros((nn, m)))
+        _check(self.L, self.L.potus_advi(self.h, C.byref(o), p0, n, _ip(info), _dp(r["mu"]), _dp(r["omega"]), _dp(r["elbo"]), _dp(r["adapt_elbo"]),
+                                         _dp(r["q"]) if m else None, _dp(r["lp"]) if m else None, _dp(r["lq"]) if m else None))
+        self._variational_shape = (n, m)
+        eta = np.array([_abi.ADVI_ETAS[k] if k >= 0 else (float(o.eta) if not o.adapt_engaged else np.nan) for k in info[:, 3]])
+        r.update(return_code=info[:, 0].copy(), flags=info[:, 1].copy(), iterations=info[:, 2].copy(), eta_index=info[:, 3].copy(), eta=eta,
+                 model_passes=info[:, 4].copy(), evaluations=info[:, 5].copy())
+        return r
+
+    def _variational_block(self, what):
+        shape = getattr(self, "_variational_shape", None)
+        if not shape or not shape[1]:
+            raise PotusError(f"{what}: no ADVI draws on this handle (variational(...) with output_samples >= 1 first)")
+        return shape
+
+    def variational_rows_device(self, cols=None):
+        """potus_advi_write_array_device: the CmdStan output columns (begin, end) (default: all) of the last variational call's draws, a
+        torch tensor [runs * draws, end - begin] on this handle's GPU."""
+        import torch
+        n, m = self._variational_block("variational_rows_device")
+        a, b = (0, self.n_cols) if cols is None else (int(cols[0]), int(cols[1]))
+        out = torch.empty((n * m, max(b - a, 1)), dtype=torch.float64, device=f"cuda:{self.opts.device}")
+        torch.cuda.current_stream(out.device).synchronize()
+        _check(self.L, self.L.potus_advi_write_array_device(self.h, a, b, C.c_void_p(out.data_ptr())))
+        return out
+
+    def variational_scores(self, days=None):
+        """potus_advi_scores_device: predicted_score of the days (begin, end) (0-based, default: election day) of the last variational
+        call's draws, a torch tensor [runs, draws, days, S] on this handle's GPU."""
+        import torch
+        n, m = self._variational_block("variational_scores")
+        S = int(self.data["S"])
+        t0, t1 = self._day_range(days)
+        out = torch.empty((n, m, max(t1 - t0, 1), S), dtype=torch.float64, device=f"cuda:{self.opts.device}")
+        torch.cuda.current_stream(out.device).synchronize()
+        _check(self.L, self.L.potus_advi_scores_device(self.h, t0, t1, C.c_void_p(out.data_ptr())))
+        return out
+
+    def variational_summary(self, ev, days=None, ev_to_win=270):
+        """potus_advi_summary: laplace_summary with the runs of the last variational call in the place of modes."""
+        n, _ = self._variational_block("variational_summary")
+        S = int(self.data["S"])
+        t0, t1 = self._day_range(days)
+        nd = max(t1 - t0, 0)
+        ev = np.ascontiguousarray(ev, dtype=np.float64).reshape(S)
+        st, na, eo, cnt = np.zeros((n, nd, S, 4)), np.zeros((n, nd, 4)), np.zeros((n, nd, 5)), np.zeros(n, np.int32)
+        _check(self.L, self.L.potus_advi_summary(self.h, t0, t1, _dp(ev), int(ev_to_win), _dp(st), _dp(na), _dp(eo), _ip(cnt)))
+        return dict(state=st, national=na, electoral_votes=eo, n_draws=cnt)
+
+    def variational_timing(self):
+        """Milliseconds (HIP events) of the stages of this thread's last variational call: adaptation, gradient segments, ELBO, draws."""
+        ms = np.zeros(4)
+        _check(self.L, self.L.potus_advi_timing(_dp(ms)))
+        return dict(adapt_ms=float(ms[0]), grad_ms=float(ms[1]), elbo_ms=float(ms[2]), draws_ms=float(ms[3]))
+
     def simulate_prior(self, seed, n_sims, sim_offset=0):
         """potus_simulate_prior: (q [n_sims, D], n_democrat_state [n_sims, Ns], n_democrat_national [n_sims, Nn]) drawn from the prior
         predictive distribution of this handle's design (its poll outcomes are not used)."""
@@ -1247,6 +1347,74 @@ class Pathfinder:
         self._h.close()
 
 
+class Variational:
+    """What cmdstanr's model$variational(algorithm = "meanfield") returns: draws [runs * draws_per_run, D] (unconstrained, the pooled draws of
+    every run, run-major), lp (log_prob<jacobian = true> of every draw, as the sampler's lp__), lq (the log density of the run's normal at the
+    draw), log_ratio = lp - lq, and per run mean, sd = exp(omega) [runs, D], elbo (the last one evaluated), elbo_path, eta, iterations,
+    return_code (_abi.ADVI_CODES; INIT and ADAPT_FAILED runs have NaN draws), flags.  The draws' rows stay on the handle for scores / summary /
+    outcomes / scenario."""
+
+    def __init__(self, handle, res):
+        self._h, self.res = handle, res
+        self.return_code, self.iterations, self.flags, self.eta = res["return_code"], res["iterations"], res["flags"], res["eta"]
+        self.runs, self.draws_per_run = res["q"].shape[0], res["q"].shape[1]
+        self.ok = ~np.isin(self.return_code, (5, 6))
+        if not self.ok.any():
+            raise PotusError("variational: no run has an approximation (return code INIT or ADAPT_FAILED on every run)")
+        self.mean, self.sd = res["mu"], np.exp(res["omega"])
+        self.draws = res["q"].reshape(-1, res["q"].shape[2])
+        self.lp, self.lq = res["lp"].reshape(-1), res["lq"].reshape(-1)
+        self.log_ratio = self.lp - self.lq
+        self.elbo_path = res["elbo"]
+        self.elbo = np.array([res["elbo"][r, k] for r, k in enumerate(res["evaluations"])])
+        self._k = None
+
+    @property
+    def pareto_k(self):
+        """k-hat of the importance ratios of the pooled draws: the library's PSIS (potus_loo_device), exactly as Laplace.pareto_k."""
+        if self._k is None:
+            import torch
+            from .loo import loo_of_block
+            lr = self.log_ratio[np.isfinite(self.log_ratio)]
+            blk = torch.as_tensor(-lr, device=f"cuda:{self._h.opts.device}").reshape(1, 1, -1).contiguous()
+            self._k = float(loo_of_block(blk).pareto_k[0])
+        return self._k
+
+    def inits(self, chains, seed=0):
+        """[chains, D] starting points for sample(inits=...) / Handle.init: distinct draws spread evenly over the runs that have draws
+        (chain c takes one from run c mod runs), chosen by numpy's default_rng(seed)."""
+        ok = np.flatnonzero(self.ok)
+        m = self.draws_per_run
+        per = -(-int(chains) // ok.size)
+        if per > m:
+            raise ValueError(f"inits: {chains} chains from {ok.size} runs of {m} draws")
+        rng = np.random.default_rng(seed)
+        pick = {int(p): rng.choice(m, size=per, replace=False) for p in ok}
+        return np.stack([self.draws[int(ok[c % ok.size]) * m + pick[int(ok[c % ok.size])][c // ok.size]] for c in range(int(chains))])
+
+    def scores(self, days=None):
+        """predicted_score of `days` = (begin, end) (0-based; default election day) of every draw: a torch tensor [runs * draws, days, S] on the GPU."""
+        s = self._h.variational_scores(days)
+        return s.reshape((-1,) + tuple(s.shape[2:]))
+
+    def summary(self, ev, days=None, ev_to_win=270):
+        """timeline()'s summaries per run: dict(state [runs, days, S, 4], national [runs, days, 4], electoral_votes [runs, days, 5], n_draws [runs])."""
+        return self._h.variational_summary(ev, days, ev_to_win)
+
+    def outcomes(self, ev, actual=None, days=None, ev_to_win=270, states=None):
+        """Joint election outcomes over the pooled draws (potus_outcomes_device on their scores)."""
+        from .outcomes import outcomes_of_block
+        return outcomes_of_block(self.scores(days).contiguous(), self._h.data["state_weights"], ev, actual=actual, ev_to_win=ev_to_win, states=states)
+
+    def scenario(self, ev=None, given=None, day=-1, days=None, ev_to_win=270, states=None):
+        """Conditional forecast over the pooled draws (potus_scenario_device on their scores); `day` indexes the range `days`."""
+        from .scenario import scenario_of_block
+        return scenario_of_block(self.scores(days).contiguous(), self._h.data["state_weights"], ev=ev, given=given, day=day, ev_to_win=ev_to_win, states=states)
+
+    def close(self):
+        self._h.close()
+
+
 class PotusModel:
     """cmdstanr::cmdstan_model() for the two poll models (final_2016.R:532, final_2012.R:558)."""
 
@@ -1318,6 +1486,25 @@ class PotusModel:
             res = h.pathfinder(q0, None if q0 is not None else n, history_size=int(history_size), num_elbo_draws=int(num_elbo_draws),
                                num_draws=-(-int(draws) // n), max_lbfgs_iters=int(max_lbfgs_iters), **opt)
             return Pathfinder(h, res)
+        except Exception:
+            h.close()
+            raise
+
+    def variational(self, data, runs=1, seed=1843, init=2.0, algorithm="meanfield", iter=10000, grad_samples=1, elbo_samples=100, eta=None,
+                    adapt_engaged=True, adapt_iter=50, tol_rel_obj=0.01, eval_elbo=100, output_samples=1000, device=0, **opt):
+        """cmdstanr's model$variational(data, algorithm = "meanfield", ...) with its argument names: `runs` independent ADVI runs in one call
+        (cmdstanr runs one), `output_samples` draws PER RUN.  init as in optimize(): a radius, or starts [runs, D].  eta: with adapt_engaged the
+        adaptation chooses it; given and adapt_engaged = False it is the step size.  opt: elbo_offset, draw_offset, run_offset."""
+        radius = 2.0 if not np.isscalar(init) else float(init)
+        h = Handle(data, self.variant, chains=1, num_warmup=0, num_samples=0, seed=int(seed), init_radius=radius, device=int(device), cus_per_chain=1, twin=0)
+        try:
+            q0 = None if np.isscalar(init) else np.atleast_2d(np.asarray(init, dtype=np.float64))
+            n = int(runs) if q0 is None else q0.shape[0]
+            res = h.variational(q0, None if q0 is not None else n, algorithm=algorithm, iter=int(iter), grad_samples=int(grad_samples),
+                                elbo_samples=int(elbo_samples), eta=1.0 if eta is None else float(eta), adapt_engaged=int(bool(adapt_engaged)),
+                                adapt_iter=int(adapt_iter), tol_rel_obj=float(tol_rel_obj), eval_elbo=int(eval_elbo),
+                                output_samples=int(output_samples), **opt)
+            return Variational(h, res)
         except Exception:
             h.close()
             raise

@@ -268,6 +268,31 @@ def pathfinder(design, variant="full", draws=1000, paths_per_date=1, ev=None, da
         hd.close()
 
 
+def variational(design, variant="full", draws=1000, runs_per_date=1, ev=None, days=None, ev_to_win=270, device=0, seed=1843, init_radius=2.0, **opts):
+    """Mean-field ADVI for every run date of a campaign in ONE potus_advi call on a potus_set_datasets_ex handle: `runs_per_date` runs per date
+    with the date's own model, `draws` draws per run, and, with ev, the summary of potus_advi_summary over `days` (default: election day) per
+    run.  opts: Handle.variational_opts' fields.  dict(lp, lq, log_ratio [dates, runs, draws], return_code, flags, iterations, eta, elbo
+    [dates, runs] (the last one evaluated), timing, and with ev: state [dates, runs, days, S, 4], national, electoral_votes, n_draws).  A run
+    without an approximation has NaN."""
+    n, k = int(design["keep_state"].shape[0]), int(runs_per_date)
+    if int(draws) < 1 or (ev is not None and int(draws) > MAX_DRAWS):
+        raise ValueError(f"timeline.variational: {draws} draws per run (1 .. {MAX_DRAWS} with a summary)")
+    hd = Handle(design["data"], variant, chains=n, num_warmup=0, num_samples=0, seed=int(seed), init_radius=float(init_radius), device=int(device), **_BATCHED)
+    try:
+        set_design(hd, design)
+        res = hd.variational(None, n * k, output_samples=int(draws), **opts)
+        out = dict(lp=res["lp"].reshape(n, k, -1), lq=res["lq"].reshape(n, k, -1), log_ratio=(res["lp"] - res["lq"]).reshape(n, k, -1),
+                   return_code=res["return_code"].reshape(n, k), flags=res["flags"].reshape(n, k), iterations=res["iterations"].reshape(n, k),
+                   eta=res["eta"].reshape(n, k), elbo=np.array([res["elbo"][r, j] for r, j in enumerate(res["evaluations"])]).reshape(n, k),
+                   timing=hd.variational_timing(), run_dates=list(design.get("run_dates", range(n))))
+        if ev is not None:
+            sm = hd.variational_summary(ev, days, ev_to_win)
+            out.update({key: v.reshape((n, k) + v.shape[1:]) for key, v in sm.items()})
+        return out
+    finally:
+        hd.close()
+
+
 def save_fixture(path, design):
     """The per-date part of a design (masks, priors, scales, dates) as one .npz: data only."""
     np.savez_compressed(path, keep_state=np.packbits(design["keep_state"], axis=1), keep_national=np.packbits(design["keep_national"], axis=1),
