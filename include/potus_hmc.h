@@ -410,7 +410,8 @@ int potus_cv_timing(double *ms /*[2]: k_cv_loglik, k_cv_reduce, HIP events, call
 /* ---- the posterior mode: cmdstanr's $optimize(), batched -- one workgroup per path, every path in ONE launch ----
  * L-BFGS (history_size pairs, two-loop recursion, initial scaling s'y / y'y; a pair with s'y <= 0 is skipped, a direction that is no ascent
  * direction resets the history) with a strong-Wolfe line search (c1 = 1e-4, c2 = 0.9; first trial step of the first iteration init_alpha,
- * afterwards 1; at most 20 evaluations per iteration, a non-finite trial shrinks the step) on log_prob<jacobian> of the unconstrained
+ * afterwards 1; at most 20 evaluations per search, a search that fails with a history is repeated once along the gradient with the history
+ * emptied, so at most 40 per iteration; a non-finite trial shrinks the step) on log_prob<jacobian> of the unconstrained
  * coordinates: jacobian = 1 is the mode of the density the sampler draws from, jacobian = 0 (CmdStan's default for optimisation) the
  * penalised maximum-likelihood point.  The no-mode variant has no constrained parameter: both settings are the same computation there.
  * Stopping rules are CmdStan 2.24's, tested after each accepted step with strict <, so a tolerance of 0 switches a rule off; eps = 2^-52:
@@ -418,7 +419,9 @@ int potus_cv_timing(double *ms /*[2]: k_cv_loglik, k_cv_reduce, HIP events, call
  *   2 RELF     |f_k - f_{k-1}| / max(|f_k|, |f_{k-1}|, tol_obj) < tol_rel_obj eps     6 MAXIT   iter iterations done
  *   3 ABSGRAD  ||g||_2 < tol_grad                                           7 LSFAIL  the line search failed; the last accepted point is returned
  *   4 RELGRAD  g' H g / max(|f|, tol_obj) < tol_rel_grad eps                8 INIT    no finite start; q, lp and the gradient norm of the path are NaN
- * (H the L-BFGS inverse-Hessian approximation).  A launch ends after at most 100 + 21 iter model passes per path whatever the data.
+ * (H the L-BFGS inverse-Hessian approximation with the newest pair in it, the identity after a reset).  A launch ends after at most
+ * 100 + 21 iter model passes per path whatever the data: a path whose iterations repeat their search can use them up before iter iterations
+ * and then ends MAXIT too.  info_out's gradient evaluations count every pass of the path, those of a failed search included.
  * Path p of a handle with data sets (potus_set_datasets[_ex]) uses the model of data set p / (n_paths / n_datasets), as the sampler picks a
  * chain's; on a plain handle every path uses the handle's model.  Starts: q0 [n_paths][D] is tried once per path; q0 = NULL draws
  * U(-init_radius, init_radius) starts, up to 100 attempts per path, from Philox4x32-10 as the sampler's (counter = {index, purpose | aux << 8,

@@ -12,6 +12,7 @@ import re
 import numpy as np
 import pytest
 
+import lbfgs_ref
 import optimize_ref as ref
 from conftest import GOLD
 from oracle_lib import OracleModel
@@ -192,10 +193,18 @@ def test_limits_and_failed_starts(small, variant):
     for p in (0, 1, 3):
         for k in ("q", "lp", "grad_norm", "return_code", "iterations", "grad_evals"):
             assert rb[k][p].tobytes() == r3[k][p].tobytes(), (p, k)
-    # defaults: a convergence code, further than three iterations get
+    # defaults: the code and the iteration count of the state machine in numpy (tests/lbfgs_ref.py) on the handle's own log_prob_grad with the
+    # Jacobian removed -- RELGRAD on the oracle (tests/test_optimize_host.py) -- and further than three iterations get
     rd = h.optimize(q0)
     print(variant, "defaults: codes", rd["return_code"], "iterations", rd["iterations"], "||g||", rd["grad_norm"])
-    assert ((rd["return_code"] >= 1) & (rd["return_code"] <= 5)).all() and (rd["lp"] > r3["lp"]).all()
+
+    def fun(q):
+        lp, g = h.log_prob_grad(q)
+        return ref.remove_jacobian(float(lp[0]), g[0], q, s["irho"])
+    want = [lbfgs_ref.LBFGS(fun).run(q0[p]) for p in range(4)]
+    assert all(st["rec"].clearance >= lbfgs_ref.CLEAR_MIN for w in want for st in w["steps"])
+    assert rd["return_code"].tolist() == [w["code"] for w in want] and rd["iterations"].tolist() == [w["iterations"] for w in want]
+    assert (rd["lp"] > r3["lp"]).all()
 
 
 def test_refusals_and_an_undisturbed_run(small):

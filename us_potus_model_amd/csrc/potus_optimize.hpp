@@ -18,12 +18,14 @@
 //   line search   strong Wolfe (c1 = 1e-4, c2 = 0.9): bracketing with secant extrapolation of the directional derivative (between 1.1
 //                 and 10 times the last step), then zoom with the secant of the two end derivatives kept inside the middle 80 % of the
 //                 bracket, bisection where that fails; a non-finite trial becomes the bracket's far end, i.e. shrinks the step.  First
-//                 trial of the first iteration init_alpha, afterwards 1.  At most OPT_LS_MAX evaluations; a search that fails with a
-//                 history is repeated once along the gradient, a search that fails along the gradient ends the path (LSFAIL) at the
-//                 last accepted point -- every accepted step increases the objective, so that is the best point seen.
+//                 trial of the first iteration init_alpha, afterwards 1.  At most OPT_LS_MAX evaluations per search; a search that fails
+//                 with a history is repeated once along the gradient (so an iteration takes at most 2 OPT_LS_MAX), a search that fails
+//                 along the gradient ends the path (LSFAIL) at the last accepted point -- every accepted step increases the objective,
+//                 so that is the best point seen.
 //   termination   CmdStan 2.24's rules after each accepted step, strict <, in the order of the codes (a tolerance of 0 switches a rule
 //                 off).  The loop runs at most 100 + 21 iter passes whatever the data: 100 start attempts, one pass for the start,
-//                 20 per iteration; a path that has used them ends MAXIT.
+//                 20 per iteration with one search; a path that has used them -- iterations that repeat their search can, before
+//                 `iter` iterations are done -- ends MAXIT.
 //   determinism   every dot product is a thread-strided partial sum followed by block_sum (fixed order, no atomics), and no path reads
 //                 what another writes: a path's bytes are a function of (model, start, options) alone.
 //   starts        q0 [n][D] tried once (non-finite value or gradient: INIT for that path alone), else U(-r, r) with the handle's
@@ -351,6 +353,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_opt_lbfgs(const DevModel *Mg_all
   // ---- results: the current point (INIT: NaN), as the row k_write_array[_ds] reads
   const int cur = opt_uni(st->s.cur), nev = st->s.nev, it = st->s.it;
   const bool none = code == OPT_INIT;
+  const bool uncounted = none || code == OPT_LSFAIL;    // opt_step returns these two before it stores the pass it has just counted
   gcdp xf = W + (size_t)(2 * cur) * Dpad;
   double *row = P->rows + (size_t)p * (POTUS_N_SAMPLER_COLS + D);
   const double lpf = none ? NAN : st->s.f;
@@ -358,6 +361,6 @@ __global__ __launch_bounds__(PT_THREADS) void k_opt_lbfgs(const DevModel *Mg_all
   if (tid < POTUS_N_SAMPLER_COLS) row[tid] = tid == 0 ? lpf : NAN;
   if (tid == 0) {
     P->lp[p] = lpf; P->gnorm[p] = none ? NAN : st->s.gnorm;
-    P->info[3 * p] = code; P->info[3 * p + 1] = it; P->info[3 * p + 2] = none ? nev + 1 : nev;
+    P->info[3 * p] = code; P->info[3 * p + 1] = it; P->info[3 * p + 2] = uncounted ? nev + 1 : nev;
   }
 }
