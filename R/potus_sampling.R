@@ -356,6 +356,33 @@ potus_loo <- function(fit, integrate = TRUE, r_eff = NULL) {
             class = "potus_loo")
 }
 
+# loo::loo_moment_match for the polls of `loo` (a potus_loo of this fit with the same `integrate`) whose Pareto k is above k_threshold
+# (0: min(1 - 1 / log10 S, 0.7)): potus_loo_moment_match (DESIGN.md section 4q; us_potus_model_amd/loo.py moment_match is the same in Python).
+# polls: poll numbers from 1 (state polls first, then national polls), or NULL for every poll.  model_handle: a handle of the fit's data that
+# runs one workgroup per chain with the diagonal metric (cus_per_chain = 1, twin = 0); NULL takes the fit's first handle, which a fit sampled
+# with other settings does not satisfy -- the library then says so.  cov = TRUE (loo's covariance step) is refused by the library.
+# Returns the potus_loo with the matched rows updated, plus k_before and mm_info [polls, 6] (accepted T1, accepted T2, candidates
+# evaluated, split done, stop reason, reserved); potus_loo_compare takes it.  Like the rest of this file: not run under R here.
+potus_loo_moment_match <- function(fit, loo, integrate = TRUE, polls = NULL, model_handle = NULL, max_iters = 30, split = TRUE, cov = FALSE,
+                                   k_threshold = 0) {
+  N <- nrow(loo$pointwise)
+  mh <- if (is.null(model_handle)) fit$handles[1] else model_handle
+  r <- .C("potus_R_loo_moment_match", as.integer(mh), as.integer(fit$handles), length(fit$handles),
+          as.integer(c(isTRUE(integrate), max_iters, isTRUE(split), isTRUE(cov), length(polls))), as.double(k_threshold),
+          as.integer(if (is.null(polls)) 0 else polls - 1), pointwise = as.double(t(loo$pointwise)), estimates = double(6), info = integer(N * 6),
+          status = integer(1))
+  .potus_check(r$status)
+  pw <- matrix(r$pointwise, N, 5, byrow = TRUE, dimnames = dimnames(loo$pointwise))
+  out <- loo
+  out$pointwise <- pw
+  out$estimates <- matrix(r$estimates, 3, 2, byrow = TRUE, dimnames = dimnames(loo$estimates))
+  out$diagnostics <- list(pareto_k = pw[, "pareto_k"])
+  out$k_before <- loo$pointwise[, "pareto_k"]
+  out$mm_info <- matrix(r$info, N, 6, byrow = TRUE,
+                        dimnames = list(NULL, c("accepted_t1", "accepted_t2", "rounds", "split_done", "stop", "reserved")))
+  out
+}
+
 # loo::loo_compare: rows sorted by elpd_loo, elpd_diff against the best and se_diff = sqrt(N) sd(pointwise differences).  The fits must be
 # of the same polls (e.g. potus_loo_compare(full = potus_loo(fit_full), no_mode = potus_loo(fit_no_mode))).
 potus_loo_compare <- function(...) {

@@ -612,6 +612,48 @@ int potus_loo_device(int device, const void *log_lik, int n_polls, int n_chains,
  * temporaries stay within 256 MB; r_eff as loo::relative_eff (not split) when NULL. */
 int potus_loo(const int *handles, int n_handles, int integrate, const double *r_eff, double *pointwise_out, double *estimates_out);
 
+/* ---- moment matching for PSIS-LOO (Paananen, Piironen, Buerkner, Vehtari 2021): loo(..., moment_match = TRUE) ----
+ * For the polls whose k-hat is above k_threshold, a diagonal affine map T(theta) = a + b * theta of the pooled draws is adapted step by step
+ * (T1: match the mean under the PSIS weights; T2: mean and marginal variance), each candidate accepted iff its k-hat falls; the log density
+ * and the poll's log-likelihood are evaluated at the mapped draws by the model pass.  With split = 1 the map is then applied to the draws
+ * at even iterations of every chain only and the mixture of the posterior and its push-forward is the proposal.  Departures from loo: the
+ * split halves (loo: the first half of the rows), the exact inverse (x - a) / b, no covariance step (cov = 1 is refused with
+ * POTUS_ERR_UNSUPPORTED: with S < D the weighted covariance is singular), the fit and the model handle on one device.
+ *   model_handle  supplies the model of the pass: one workgroup per chain (cus_per_chain = 1, twin = 0), diagonal metric, no data sets, the
+ *                 data of the fit.  It may be one of `handles`.
+ *   handles       the fit, pooled as potus_loo pools (any layout), on the model handle's device.
+ *   polls         [n_polls] poll numbers as potus_loo numbers them, or NULL: every poll.  Only polls above the threshold are worked on.
+ *   pointwise     in: potus_loo's [N][5] of these handles with the same integrate; out: the rows of the polls with an accepted step updated
+ *                 (elpd_loo, p_loo = lpd - elpd_loo with the old lpd, looic, pareto_k; r_eff stays); every other row keeps its bytes.
+ *                 The call recomputes each worked poll's k from the draws and refuses rows it cannot reproduce to 1e-12 (rows of the other
+ *                 form or of another fit).  A call that fails leaves pointwise and estimates_out as they were (the optional outputs not).
+ *   info_out      optional [N][6]: accepted T1 steps, accepted T2 steps, candidates evaluated, split done, stop reason (1: k <= threshold,
+ *                 2: max_iters accepted, 3: both candidates rejected; 0: the poll was not listed), reserved.
+ *   k_path_out    optional [N][max_iters + 2]: k of plain PSIS, k after every accepted step, k after the split; NaN beyond.
+ *   map_out       optional, needs polls: [n_polls][2][D], a then b of every listed poll (0 and 1 where no step was accepted).
+ * A poll's outputs depend on neither the other polls of the call nor the grid.  Refused before any kernel runs: cov = 1, a model handle that
+ * is not one workgroup per chain with the diagonal metric (POTUS_ERR_UNSUPPORTED), handles with data sets (POTUS_ERR_STATE), a model
+ * handle with other data than the fit (POTUS_ERR_ARG), handles on another device (POTUS_ERR_UNSUPPORTED). */
+typedef struct potus_loo_mm_opts { int32_t integrate, max_iters, split, cov; double k_threshold; } potus_loo_mm_opts;   /* 24 bytes */
+void potus_default_loo_mm_opts(potus_loo_mm_opts *o);   /* 1, 30, 1, 0, 0 (k_threshold = 0: min(1 - 1 / log10 S, 0.7)) */
+int potus_loo_moment_match(int model_handle, const int *handles, int n_handles, const potus_loo_mm_opts *opts, const int32_t *polls, int n_polls,
+                           double *pointwise /*[N][5]*/, double *estimates_out /*[3][2]*/, int32_t *info_out, double *k_path_out, double *map_out);
+int potus_loo_mm_timing(double *ms /*[4]: passes, moments, PSIS, final; HIP events, calling thread's last potus_loo_moment_match*/);
+/* The stages on device blocks.  draws [n_chains][n_draws][7 + D] are rows as potus_get_draws returns them (canonical order).
+ * ratios: lp_out, ll_out [n_polls][n_chains][n_draws] = the log density and poll polls[k]'s log-likelihood at theta (sel[k] = 0), a_k + b_k *
+ * theta (1), (theta - a_k) / b_k (2), or (3) the first at even and the second at odd iterations; a, b host [n_polls][D]; lp0_out optional
+ * [n_chains][n_draws]: the log density at theta by the same kernel.
+ * moments: mu_out[k][j] = sum_s w[k][s] theta[s][j], q_out[k][j] = sum_s w[k][s] (theta[s][j] - m0[j])^2 (m0 NULL: 0); weights [n_polls][S]
+ * on the device, log weights when is_log.
+ * psis: PSIS of general log ratios [n_polls][n_chains][n_draws] (-inf: weight 0; a NaN or +inf entry, or no finite one: k = NaN and NaN
+ * weights): normalised log weights to log_weights_out (device, same shape), k-hat to khat_out (host). */
+int potus_loo_mm_ratios_device(int model_handle, const void *draws, int n_chains, int n_draws, const double *a, const double *b, const int32_t *polls,
+                               const int32_t *sel, int n_polls, int integrate, void *lp_out, void *ll_out, void *lp0_out);
+int potus_loo_mm_moments_device(int device, const void *draws, int n_chains, int n_draws, int D, const void *weights, int n_polls, int is_log,
+                                const double *m0, double *mu_out /*[n_polls][D]*/, double *q_out);
+int potus_psis_device(int device, const void *log_ratios, int n_polls, int n_chains, long long n_draws, const double *r_eff /*[n_polls]*/,
+                      void *log_weights_out, double *khat_out);
+
 /* ---- joint election outcomes: what the run scripts compute from the JOINT outcome of a draw ----
  * final_2016.R:904-920 (final_2012.R, final_2008.R, README.Rmd "Final electoral college histogram") the distribution of Democratic electoral
  * votes; final_2012.R:809-839, final_2008.R:813-843 the tipping-point state; README.Rmd:481-502, :1638-1672 the p-value of the certified
@@ -733,6 +775,9 @@ void potus_R_simulate_prior(int *handle, double *seed, int *dims /*[2]: n_sims, 
                             int *n_democrat_national_out, int *status);
 void potus_R_sbc_ranks(int *handle, double *truth, int *cols /*[3]: col_begin, col_end, thin*/, int *less, int *equal, int *L, int *status);
 void potus_R_constrain(int *handle, double *q, int *n, int *cols /*[2]: col_begin, col_end*/, double *out, int *status);
+void potus_R_loo_moment_match(int *model_handle, int *handles, int *n_handles, int *iopts /*[5]: integrate, max_iters, split, cov, n_polls (0: every poll)*/,
+                              double *k_threshold, int *polls, double *pointwise /*[n_polls of the data][5], in and out*/, double *estimates_out,
+                              int *info_out /*[n_polls of the data][6]*/, int *status);
 void potus_R_loo(int *handles, int *n_handles, int *iopts /*[2]: integrate, r_eff given*/, double *r_eff, double *pointwise_out /*[n_polls][5]*/,
                  double *estimates_out /*[3][2]*/, int *status);
 void potus_R_outcomes(int *handles, int *n_handles, int *iopts /*[4]: day_begin, day_end, ev_to_win, actual given*/, int *ev, double *actual,

@@ -72,6 +72,13 @@ class PotusLaplaceOpts(C.Structure):
     ]
 
 
+class PotusLooMmOpts(C.Structure):
+    """potus_loo_mm_opts (24 bytes); start from potus_default_loo_mm_opts()."""
+    _fields_ = [
+        ("integrate", C.c_int32), ("max_iters", C.c_int32), ("split", C.c_int32), ("cov", C.c_int32), ("k_threshold", C.c_double),
+    ]
+
+
 class PotusPathfinderOpts(C.Structure):
     """potus_pathfinder_opts (88 bytes); start from potus_default_pathfinder_opts()."""
     _fields_ = [
@@ -93,6 +100,8 @@ class PotusAdviOpts(C.Structure):
 ADVI_ALGORITHMS = {"meanfield": 0, "fullrank": 1}
 ADVI_CODES = {1: "MEAN_CONVERGED", 2: "MEDIAN_CONVERGED", 3: "MAXIT", 4: "NONFINITE", 5: "INIT", 6: "ADAPT_FAILED"}
 ADVI_ETAS = (100.0, 10.0, 1.0, 0.1, 0.01)
+LOO_MM_STOPS = {0: "NOT_LISTED", 1: "BELOW_THRESHOLD", 2: "MAX_ITERS", 3: "REJECTED"}
+LOO_MM_INFO = ("accepted_t1", "accepted_t2", "rounds", "split_done", "stop", "reserved")
 LAPLACE_CODES = {0: "OK", 1: "NOT_PD", 2: "NOT_FINITE"}
 PATHFINDER_CODES = {0: "OK", 1: "NO_ELBO"}
 OPTIMIZE_CODES = {1: "ABSF", 2: "RELF", 3: "ABSGRAD", 4: "RELGRAD", 5: "ABSX", 6: "MAXIT", 7: "LSFAIL", 8: "INIT"}

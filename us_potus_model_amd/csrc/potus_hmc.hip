@@ -760,6 +760,8 @@ __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, c
 #include "potus_scenario.hpp"   // conditional forecasts and the covariance of the state scores
 #include "potus_timeline.hpp"   // run dates as the data sets of one handle: their rows, scores and summaries
 #include "potus_crossval.hpp"   // exact cross-validation: held-out polls under the draws of the data set that did not see them
+#include "potus_loo_mm.hpp"     // moment matching for PSIS-LOO: the pass under an affine map, weighted moments, PSIS of general ratios
+#include "potus_loo_mm_rules.hpp"
 #include "potus_optimize.hpp"   // the posterior mode: batched L-BFGS, one workgroup per path
 #include "potus_laplace.hpp"    // the Laplace approximation at a mode: Hessian, factor, draws
 #include "potus_pathfinder.hpp" // Pathfinder: a normal around every iterate of an L-BFGS path, the best ELBO, draws
@@ -3445,6 +3447,499 @@ int potus_loo(const int *handles, int n_handles, int integrate, const double *r_
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------- moment matching (potus_loo_mm.hpp)
+extern "C++" {   // (a template and a function that returns a vector)
+namespace {
+constexpr size_t MM_PART_BUDGET = 128ull << 20;   // the chunk partials of one k_mm_moments launch
+thread_local double g_mm_ms[4] = {0.0, 0.0, 0.0, 0.0};   // the calling thread's last call: passes, moments, PSIS, final (HIP events)
+
+// What the stages work with: the model (a handle of one workgroup per chain), the pooled chains on its device, the scratch of the kernels.
+struct MmCtx {
+  const char *what = "";
+  Sampler *mp = nullptr;
+  hipStream_t st = nullptr;
+  int C = 0, n = 0, D = 0, Dpad = 0, row = 0, ncols = 0, S = 0, pass_grid = 1, psis_grid = 1, psis_mmax = 0, maxB = 1;
+  DevBufs keep;
+  const double **dchain = nullptr;
+  double *lc = nullptr, *scratch = nullptr, *part = nullptr, *mom = nullptr, *wsd = nullptr, *dre = nullptr, *dk = nullptr, *da = nullptr, *db = nullptr, *dm0 = nullptr;
+  int *dpoll = nullptr, *dsel = nullptr, *wsi = nullptr;
+  unsigned long long *rkey = nullptr;
+  unsigned *ridx = nullptr;
+  MmPassParams *dP = nullptr;
+  std::vector<int> model_index;   // poll as the output row numbers it -> the model's (day-sorted) index
+  double ms[4] = {0.0, 0.0, 0.0, 0.0};
+  int nchunk() const { return (S + MM_CHUNK - 1) / MM_CHUNK; }
+};
+
+// the wording of potus_optimize / potus_cv_lpd for a handle that cannot run the one-workgroup pass
+int mm_check_model(const char *what, const Sampler *mp) {
+  if (mp->dense) return fail(POTUS_ERR_UNSUPPORTED, "%s: the dense metric is not supported (metric = POTUS_METRIC_DIAG only)", what);
+  if (mp->K != 1 || mp->twin) return fail(POTUS_ERR_UNSUPPORTED, "%s: needs one workgroup per chain (cus_per_chain = 1, twin = 0); this handle runs %d x %d", what, mp->K, mp->sides());
+  if (!mp->k1_unsupported.empty()) return fail(POTUS_ERR_UNSUPPORTED, "%s: %s", what, mp->k1_unsupported.c_str());
+  if (mp->lds_bytes + sizeof(RowLds) > 160 * 1024) return fail(POTUS_ERR_UNSUPPORTED, "%s: the pass and the row builder need %zu bytes of LDS (> 160 KiB)", what, mp->lds_bytes + sizeof(RowLds));
+  return refuse_many_datasets(mp, what);
+}
+int mm_check_sizes(const char *what, long long C, long long n, long long maxB) {
+  if (C < 1 || n < 4) return fail(POTUS_ERR_ARG, "%s: %lld chains of %lld draws (at least one chain, four draws per chain)", what, C, n);
+  if (2 * C > DG_MAXCH) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld chains pooled (at most %d)", what, C, DG_MAXCH / 2);
+  // (k_mm_pass walks its items with an int that a stride of up to 2^16 workgroups must not overflow; k_mm_moments has one grid row per chunk of draws)
+  if (C * n * std::max<long long>(maxB, 1) > 0x7fffffffll - 65536) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld polls x %lld draws in one launch (at most 2^31 - 2^16 items)", what, maxB, C * n);
+  if ((C * n + MM_CHUNK - 1) / MM_CHUNK > 65535) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld pooled draws (at most %d: one grid row per %d draws)", what, C * n, 65535 * MM_CHUNK, MM_CHUNK);
+  return 0;
+}
+
+// under the device lock, the model's device current: chains = the first post-warm-up row of every pooled chain (device pointers)
+int mm_setup(MmCtx &x, const char *what, Sampler *mp, const std::vector<const double *> &chains, int n, int maxB) {
+  x.what = what; x.mp = mp; x.st = mp->stream;
+  x.C = (int)chains.size(); x.n = n; x.S = x.C * n; x.D = mp->L.D; x.Dpad = (x.D + 7) & ~7; x.row = POTUS_N_SAMPLER_COLS + x.D; x.ncols = mp->L.ncols;
+  x.maxB = std::max(maxB, 1);
+  int rc;
+  LooRows lr;
+  if ((rc = loo_rows_setup(mp, 1, x.keep, lr, what))) return rc;
+  x.lc = lr.lc;
+  const int Np = mp->M.Npoll, Npad = mp->M.Npad;
+  std::vector<int> pi((size_t)6 * Npad);
+  HIP_TRY(hipMemcpy(pi.data(), mp->M.pi, pi.size() * 4, hipMemcpyDeviceToHost));
+  x.model_index.assign(Np, -1);
+  for (int i = 0; i < Np; i++) {
+    const int s = pi[i], qi = pi[(size_t)5 * Npad + i];
+    const int k = s == mp->M.S ? mp->M.Ns + (qi - mp->M.o_nn) : qi - mp->M.o_ns;
+    if (k >= 0 && k < Np) x.model_index[k] = i;
+  }
+  int ncu = 256;
+  hipDeviceProp_t prop;
+  if (hipGetDeviceProperties(&prop, mp->device) == hipSuccess) ncu = std::max(1, prop.multiProcessorCount);
+  x.pass_grid = (int)std::max<long long>(1, std::min<long long>((long long)x.maxB * x.S, 2ll * ncu));
+  x.psis_mmax = 32 + (int)std::sqrt(0.2 * (double)x.S + 1.0);
+  const size_t wsd_n = 2 * (size_t)x.S + 2 * (size_t)x.psis_mmax;
+  x.psis_grid = std::min(x.maxB, 1024);
+  const size_t BD = (size_t)x.maxB * x.D;
+  if ((rc = x.keep.get(&x.dchain, chains.size() * sizeof(double *), what)) || (rc = x.keep.get(&x.scratch, (size_t)x.pass_grid * mm_scratch_doubles(x.Dpad, x.ncols) * 8, what)) ||
+      (rc = x.keep.get(&x.dP, sizeof(MmPassParams), what)) || (rc = x.keep.get(&x.da, BD * 8, what)) || (rc = x.keep.get(&x.db, BD * 8, what)) ||
+      (rc = x.keep.get(&x.dm0, (size_t)x.D * 8, what)) || (rc = x.keep.get(&x.dpoll, (size_t)x.maxB * 4, what)) || (rc = x.keep.get(&x.dsel, (size_t)x.maxB * 4, what)) ||
+      (rc = x.keep.get(&x.part, (size_t)x.nchunk() * BD * 2 * 8, what)) || (rc = x.keep.get(&x.mom, BD * 2 * 8, what)) ||
+      (rc = x.keep.get(&x.wsd, (size_t)x.psis_grid * wsd_n * 8, what)) || (rc = x.keep.get(&x.wsi, (size_t)x.psis_grid * x.S * 4, what)) ||
+      (rc = x.keep.get(&x.dre, (size_t)x.maxB * 8, what)) || (rc = x.keep.get(&x.dk, (size_t)x.maxB * 8, what)))
+    return rc;
+  if (x.S > DG_RUN && ((rc = x.keep.get(&x.rkey, (size_t)x.psis_grid * x.S * 8, what)) || (rc = x.keep.get(&x.ridx, (size_t)x.psis_grid * x.S * 4, what)))) return rc;
+  HIP_TRY(hipMemcpy(x.dchain, chains.data(), chains.size() * sizeof(double *), hipMemcpyHostToDevice));
+  HIP_TRY(hipMemset(x.scratch, 0, (size_t)x.pass_grid * mm_scratch_doubles(x.Dpad, x.ncols) * 8));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mm_pass), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(mp->M.lds_doubles * 8 + sizeof(RowLds))));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mm_psis), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sorted_run_lds(x.S)));
+  return 0;
+}
+
+// one stage's launches between two events; the stream is idle on return
+template <class Launch>
+int mm_timed(MmCtx &x, int stage, Launch launch) {
+  EventTimer t;
+  HIP_TRY(t.made);
+  HIP_TRY(t.start(x.st));
+  if (const int rc = launch()) return rc;
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(t.stop(x.st));
+  HIP_TRY(hipStreamSynchronize(x.st));
+  double ms = 0.0;
+  if (t.elapsed(&ms)) x.ms[stage] += ms;
+  return 0;
+}
+
+// lp, ll [B][S] (device) of the polls (output numbering) at theta, T theta or T^-1 theta; a, b host [B][D]
+int mm_pass(MmCtx &x, int B, const double *a, const double *b, const int *polls, const int *sel, int integrate, double *lp, double *ll) {
+  std::vector<int> mi(B);
+  for (int k = 0; k < B; k++) mi[k] = x.model_index[polls[k]];
+  HIP_TRY(hipMemcpyAsync(x.da, a, (size_t)B * x.D * 8, hipMemcpyHostToDevice, x.st));
+  HIP_TRY(hipMemcpyAsync(x.db, b, (size_t)B * x.D * 8, hipMemcpyHostToDevice, x.st));
+  HIP_TRY(hipMemcpyAsync(x.dpoll, mi.data(), (size_t)B * 4, hipMemcpyHostToDevice, x.st));
+  HIP_TRY(hipMemcpyAsync(x.dsel, sel, (size_t)B * 4, hipMemcpyHostToDevice, x.st));
+  const MmPassParams P{x.dchain, x.da, x.db, x.dpoll, x.dsel, x.lc, x.scratch, lp, ll, x.n, x.C, B, x.row, x.Dpad, x.ncols, integrate};
+  HIP_TRY(hipMemcpyAsync(x.dP, &P, sizeof P, hipMemcpyHostToDevice, x.st));
+  HIP_TRY(hipStreamSynchronize(x.st));   // (the host arrays above are the caller's stack)
+  const int grid = (int)std::min<long long>(x.pass_grid, (long long)B * x.S);
+  return mm_timed(x, 0, [&] {
+    hipLaunchKernelGGL(k_mm_pass, dim3(grid), dim3(PT_THREADS), x.mp->M.lds_doubles * 8 + sizeof(RowLds), x.st, (const DevModel *)x.mp->dM, (const MmPassParams *)x.dP);
+    return 0;
+  });
+}
+
+// mu~, q~ -> host mu, q [B][D]; w device [B][S] (log weights when is_log); m0 host [D] or null
+int mm_moments(MmCtx &x, int B, const double *w, int is_log, const double *m0, double *mu, double *q) {
+  if (m0) HIP_TRY(hipMemcpyAsync(x.dm0, m0, (size_t)x.D * 8, hipMemcpyHostToDevice, x.st));
+  const MmMomParams P{x.dchain, w, m0 ? x.dm0 : nullptr, x.part, x.n, x.C, B, x.row, x.D, is_log};
+  const long long BD2 = (long long)B * 2 * x.D;
+  if (const int rc = mm_timed(x, 1, [&] {
+        hipLaunchKernelGGL(k_mm_moments, dim3((x.D + 255) / 256, x.nchunk(), (B + MM_BT - 1) / MM_BT), dim3(256), 0, x.st, P);
+        hipLaunchKernelGGL(k_mm_moments_sum, dim3((unsigned)std::min<long long>((BD2 + 255) / 256, 65535)), dim3(256), 0, x.st, (const double *)x.part, x.mom, x.nchunk(), BD2);
+        return 0;
+      })) return rc;
+  std::vector<double> h((size_t)BD2);
+  HIP_TRY(hipMemcpy(h.data(), x.mom, h.size() * 8, hipMemcpyDeviceToHost));
+  for (int k = 0; k < B; k++) {
+    std::copy(h.begin() + (size_t)k * 2 * x.D, h.begin() + (size_t)k * 2 * x.D + x.D, mu + (size_t)k * x.D);
+    std::copy(h.begin() + (size_t)k * 2 * x.D + x.D, h.begin() + (size_t)(k + 1) * 2 * x.D, q + (size_t)k * x.D);
+  }
+  return 0;
+}
+
+// PSIS of r [B][S] (device) -> lw [B][S] (device), k (host [B]); r_eff host [B]
+int mm_psis(MmCtx &x, int B, const double *r, const double *r_eff, double *lw, double *k) {
+  HIP_TRY(hipMemcpyAsync(x.dre, r_eff, (size_t)B * 8, hipMemcpyHostToDevice, x.st));
+  const PsisGenParams P{r, x.dre, x.wsd, x.wsi, x.rkey, x.ridx, lw, x.dk, (long long)x.S, B, x.psis_mmax};
+  if (const int rc = mm_timed(x, 2, [&] {
+        hipLaunchKernelGGL(k_mm_psis, dim3(std::min(B, x.psis_grid)), dim3(DG_THREADS), sorted_run_lds(x.S), x.st, P);
+        return 0;
+      })) return rc;
+  HIP_TRY(hipMemcpy(k, x.dk, (size_t)B * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int mm_ratio(MmCtx &x, int B, int mode, const double *lp, const double *ll, const double *lp0, const double *ll0, const double *slb, double *r, double *llx) {
+  const MmRatioParams P{lp, ll, lp0, ll0, slb, r, llx, x.n, x.S, B, mode};
+  hipLaunchKernelGGL(k_mm_ratio, dim3((unsigned)std::min<long long>(((long long)B * x.S + 255) / 256, 65535)), dim3(256), 0, x.st, P);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+int mm_check_r_eff(const char *what, const double *r_eff, int n) {
+  if (!r_eff) return fail(POTUS_ERR_ARG, "%s: null r_eff", what);
+  return loo_check_r_eff(r_eff, n, what);
+}
+
+// a further block of an entry point whose DeviceBlock is open on `device`
+int mm_also_device(const char *what, int device, const void *ptr, const char *ptr_name) {
+  hipPointerAttribute_t at;
+  if (hipPointerGetAttributes(&at, ptr) != hipSuccess || at.type != hipMemoryTypeDevice || at.device != device) {
+    (void)hipGetLastError();
+    return fail(POTUS_ERR_ARG, "%s: the %s is not device memory of GPU %d", what, ptr_name, device);
+  }
+  return 0;
+}
+
+// the chains of a device block [C][n][row]
+std::vector<const double *> mm_block_chains(const void *draws, int C, int n, int row) {
+  std::vector<const double *> ch(C);
+  for (int c = 0; c < C; c++) ch[c] = (const double *)draws + (size_t)c * n * row;
+  return ch;
+}
+} // namespace
+} // extern "C++"
+
+void potus_default_loo_mm_opts(potus_loo_mm_opts *o) {
+  if (!o) return;
+  o->integrate = 1; o->max_iters = 30; o->split = 1; o->cov = 0; o->k_threshold = 0.0;
+}
+
+int potus_loo_mm_timing(double *ms) {
+  return timing_out("potus_loo_mm_timing", g_mm_ms, 4, ms);
+}
+
+int potus_psis_device(int device, const void *log_ratios, int n_polls, int n_chains, long long n_draws, const double *r_eff, void *log_weights_out, double *khat_out) {
+  const char *what = "potus_psis_device";
+  if (!log_ratios || !log_weights_out || !khat_out || n_polls < 1) return fail(POTUS_ERR_ARG, "%s: bad argument", what);
+  if (const int rc_ = mm_check_sizes(what, n_chains, n_draws, 1)) return rc_;
+  if (const int rc_ = mm_check_r_eff(what, r_eff, n_polls)) return rc_;
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, device, log_ratios)) return rc_;
+  if (const int rc_ = mm_also_device(what, device, log_weights_out, "output")) return rc_;
+  // (no model: the PSIS scratch alone)
+  const long long S = (long long)n_chains * n_draws;
+  const int mmax = 32 + (int)std::sqrt(0.2 * (double)S + 1.0), grid = std::min(n_polls, 1024);
+  const size_t wsd_n = 2 * (size_t)S + 2 * (size_t)mmax;
+  DevBufs tmp;
+  double *wsd = nullptr, *dre = nullptr, *dk = nullptr;
+  int *wsi = nullptr;
+  unsigned long long *rkey = nullptr;
+  unsigned *ridx = nullptr;
+  int rc;
+  if ((rc = tmp.get(&wsd, (size_t)grid * wsd_n * 8, what)) || (rc = tmp.get(&wsi, (size_t)grid * S * 4, what)) || (rc = tmp.get(&dre, (size_t)n_polls * 8, what)) ||
+      (rc = tmp.get(&dk, (size_t)n_polls * 8, what)))
+    return rc;
+  if (S > DG_RUN && ((rc = tmp.get(&rkey, (size_t)grid * S * 8, what)) || (rc = tmp.get(&ridx, (size_t)grid * S * 4, what)))) return rc;
+  HIP_TRY(hipMemcpy(dre, r_eff, (size_t)n_polls * 8, hipMemcpyHostToDevice));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mm_psis), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sorted_run_lds(S)));
+  const PsisGenParams P{(const double *)log_ratios, dre, wsd, wsi, rkey, ridx, (double *)log_weights_out, dk, S, n_polls, mmax};
+  hipLaunchKernelGGL(k_mm_psis, dim3(grid), dim3(DG_THREADS), sorted_run_lds(S), 0, P);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(hipMemcpy(khat_out, dk, (size_t)n_polls * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int potus_loo_mm_moments_device(int device, const void *draws, int n_chains, int n_draws, int D, const void *weights, int n_polls, int is_log, const double *m0,
+                                double *mu_out, double *q_out) {
+  const char *what = "potus_loo_mm_moments_device";
+  if (!draws || !weights || !mu_out || !q_out || n_polls < 1 || D < 1) return fail(POTUS_ERR_ARG, "%s: bad argument", what);
+  if (n_polls > 65535 * MM_BT) return fail(POTUS_ERR_UNSUPPORTED, "%s: %d polls (at most %d)", what, n_polls, 65535 * MM_BT);
+  if (const int rc_ = mm_check_sizes(what, n_chains, n_draws, 1)) return rc_;
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, device, draws, "block of draws")) return rc_;
+  if (const int rc_ = mm_also_device(what, device, weights, "block of weights")) return rc_;
+  const int row = POTUS_N_SAMPLER_COLS + D, S = n_chains * n_draws, nchunk = (S + MM_CHUNK - 1) / MM_CHUNK;
+  const std::vector<const double *> ch = mm_block_chains(draws, n_chains, n_draws, row);
+  DevBufs tmp;
+  const double **dchain = nullptr;
+  double *part = nullptr, *mom = nullptr, *dm0 = nullptr;
+  const long long BD2 = (long long)n_polls * 2 * D;
+  int rc;
+  if ((rc = tmp.get(&dchain, ch.size() * sizeof(double *), what)) || (rc = tmp.get(&part, (size_t)nchunk * BD2 * 8, what)) || (rc = tmp.get(&mom, (size_t)BD2 * 8, what)) ||
+      (rc = tmp.get(&dm0, (size_t)D * 8, what)))
+    return rc;
+  HIP_TRY(hipMemcpy(dchain, ch.data(), ch.size() * sizeof(double *), hipMemcpyHostToDevice));
+  if (m0) HIP_TRY(hipMemcpy(dm0, m0, (size_t)D * 8, hipMemcpyHostToDevice));
+  const MmMomParams P{dchain, (const double *)weights, m0 ? dm0 : nullptr, part, n_draws, n_chains, n_polls, row, D, is_log ? 1 : 0};
+  hipLaunchKernelGGL(k_mm_moments, dim3((D + 255) / 256, nchunk, (n_polls + MM_BT - 1) / MM_BT), dim3(256), 0, 0, P);
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_mm_moments_sum, dim3((unsigned)std::min<long long>((BD2 + 255) / 256, 65535)), dim3(256), 0, 0, (const double *)part, mom, nchunk, BD2);
+  HIP_TRY(hipGetLastError());
+  std::vector<double> h((size_t)BD2);
+  HIP_TRY(hipMemcpy(h.data(), mom, h.size() * 8, hipMemcpyDeviceToHost));
+  for (int k = 0; k < n_polls; k++) {
+    std::copy(h.begin() + (size_t)k * 2 * D, h.begin() + (size_t)k * 2 * D + D, mu_out + (size_t)k * D);
+    std::copy(h.begin() + (size_t)k * 2 * D + D, h.begin() + (size_t)(k + 1) * 2 * D, q_out + (size_t)k * D);
+  }
+  return 0;
+}
+
+int potus_loo_mm_ratios_device(int model_handle, const void *draws, int n_chains, int n_draws, const double *a, const double *b, const int32_t *polls, const int32_t *sel,
+                               int n_polls, int integrate, void *lp_out, void *ll_out, void *lp0_out) {
+  const char *what = "potus_loo_mm_ratios_device";
+  Sampler *mp = get(model_handle);
+  if (!mp) return fail(POTUS_ERR_STATE, "%s: bad handle %d", what, model_handle);
+  if (!draws || !a || !b || !polls || !sel || !lp_out || !ll_out || n_polls < 1) return fail(POTUS_ERR_ARG, "%s: bad argument", what);
+  if (integrate != 0 && integrate != 1) return fail(POTUS_ERR_ARG, "%s: integrate = %d (0: plain, 1: noise coordinate integrated out)", what, integrate);
+  if (const int rc_ = mm_check_model(what, mp)) return rc_;
+  if (const int rc_ = mm_check_sizes(what, n_chains, n_draws, n_polls)) return rc_;
+  for (int k = 0; k < n_polls; k++) {
+    if (polls[k] < 0 || polls[k] >= mp->M.Npoll) return fail(POTUS_ERR_ARG, "%s: polls[%d] = %d of %d polls", what, k, polls[k], mp->M.Npoll);
+    if (sel[k] < MM_SEL_ID || sel[k] > MM_SEL_SPLIT) return fail(POTUS_ERR_ARG, "%s: sel[%d] = %d (0: theta, 1: T theta, 2: T^-1 theta, 3: split)", what, k, sel[k]);
+  }
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, mp->device, draws, "block of draws")) return rc_;
+  if (const int rc_ = mm_also_device(what, mp->device, lp_out, "lp output")) return rc_;
+  if (const int rc_ = mm_also_device(what, mp->device, ll_out, "ll output")) return rc_;
+  if (lp0_out) if (const int rc_ = mm_also_device(what, mp->device, lp0_out, "lp0 output")) return rc_;
+  MmCtx x;
+  int rc;
+  if ((rc = mm_setup(x, what, mp, mm_block_chains(draws, n_chains, n_draws, POTUS_N_SAMPLER_COLS + mp->L.D), n_draws, n_polls))) return rc;
+  std::vector<int> pl(polls, polls + n_polls), sl(sel, sel + n_polls);
+  if (lp0_out) {
+    DevBufs tmp;
+    double *ll_tmp = nullptr;
+    if ((rc = tmp.get(&ll_tmp, (size_t)x.S * 8, what))) return rc;
+    const int id = MM_SEL_ID;
+    if ((rc = mm_pass(x, 1, a, b, pl.data(), &id, integrate, (double *)lp0_out, ll_tmp))) return rc;
+  }
+  return mm_pass(x, n_polls, a, b, pl.data(), sl.data(), integrate, (double *)lp_out, (double *)ll_out);
+}
+
+int potus_loo_moment_match(int model_handle, const int *handles, int n_handles, const potus_loo_mm_opts *opts, const int32_t *polls, int n_polls, double *pointwise,
+                           double *estimates_out, int32_t *info_out, double *k_path_out, double *map_out) {
+  const char *what = "potus_loo_moment_match";
+  potus_loo_mm_opts o;
+  potus_default_loo_mm_opts(&o);
+  if (opts) o = *opts;
+  if (!handles || n_handles < 1 || !pointwise || !estimates_out) return fail(POTUS_ERR_ARG, "%s: null argument", what);
+  if (o.cov) return fail(POTUS_ERR_UNSUPPORTED, "%s: cov = 1 (loo's third step, a D x D weighted covariance) is not supported: with fewer pooled draws than the D "
+                                                "coordinates the weighted covariance is singular; the maps stay diagonal", what);
+  if (o.integrate != 0 && o.integrate != 1) return fail(POTUS_ERR_ARG, "%s: integrate = %d (0: plain, 1: noise coordinate integrated out)", what, o.integrate);
+  if (o.max_iters < 0 || o.max_iters > 10000) return fail(POTUS_ERR_ARG, "%s: max_iters = %d (0 to 10000)", what, o.max_iters);
+  if (std::isnan(o.k_threshold)) return fail(POTUS_ERR_ARG, "%s: k_threshold is NaN", what);
+  if (map_out && !polls) return fail(POTUS_ERR_ARG, "%s: map_out [n_polls][2][D] follows the order of polls, which is null", what);
+  Sampler *mp = get(model_handle);
+  if (!mp) return fail(POTUS_ERR_STATE, "%s: bad model handle %d", what, model_handle);
+  if (const int rc_ = mm_check_model(what, mp)) return rc_;
+  Pool P;
+  if (const int rc_ = P.resolve(handles, n_handles, what)) return rc_;
+  if (const int rc_ = P.same_posterior("moment matching pools the chains of one")) return rc_;
+  Sampler *s0 = P.s0;
+  if (mp->L.D != s0->L.D || mp->L.ncols != s0->L.ncols || mp->M.full != s0->M.full || mp->data_hash != s0->data_hash)
+    return fail(POTUS_ERR_ARG, "%s: model handle %d holds another model than handle %d (D, the polls or other data differ): the log density must be the fit's", what, model_handle, handles[0]);
+  for (size_t i = 0; i < P.sps.size(); i++)
+    if (P.sps[i]->device != mp->device) return fail(POTUS_ERR_UNSUPPORTED, "%s: handle %d is on GPU %d, the model handle on GPU %d (one device in this version)", what, handles[i], P.sps[i]->device, mp->device);
+  const int Np = mp->M.Npoll, D = mp->L.D;
+  if (Np < 1) return fail(POTUS_ERR_ARG, "%s: the data hold no polls", what);
+  if (polls) {
+    if (n_polls < 1) return fail(POTUS_ERR_ARG, "%s: n_polls = %d", what, n_polls);
+    for (int k = 0; k < n_polls; k++) {
+      if (polls[k] < 0 || polls[k] >= Np) return fail(POTUS_ERR_ARG, "%s: polls[%d] = %d of %d polls", what, k, polls[k], Np);
+      for (int j = 0; j < k; j++) if (polls[j] == polls[k]) return fail(POTUS_ERR_ARG, "%s: poll %d listed twice", what, polls[k]);
+    }
+  }
+  for (int i = 0; i < Np; i++) {
+    const double re = pointwise[(size_t)i * LOO_NPW + 4];
+    if (!(std::isfinite(re) && re > 0)) return fail(POTUS_ERR_ARG, "%s: pointwise[%d] holds r_eff = %g (the rows of potus_loo expected)", what, i, re);
+  }
+  std::vector<int> devs = P.devs;
+  devs.push_back(mp->device);
+  DeviceGuard guard;
+  DeviceLocks lock(devs);
+  if (const int rc_ = P.count()) return rc_;
+  if (const int rc_ = P.equal_counts()) return rc_;
+  int first = 0, n_post = 0;
+  if (const int rc_ = P.post_warmup(&first, &n_post)) return rc_;
+  const int Ctot = P.chains;
+  const long long S = (long long)Ctot * n_post;
+  const double thr = o.k_threshold == 0.0 ? lmm_default_threshold(S) : o.k_threshold;
+  const int kp = o.max_iters + 2;
+  std::fill(g_mm_ms, g_mm_ms + 4, 0.0);
+  // the rules decide who enters the loop, before any kernel runs
+  std::vector<int> cand;
+  if (polls) cand.assign(polls, polls + n_polls);
+  else for (int i = 0; i < Np; i++) cand.push_back(i);
+  std::vector<LmmPoll> ru(Np);
+  std::vector<int> work;
+  if (info_out) std::fill(info_out, info_out + (size_t)Np * LMM_NINFO, 0);
+  if (k_path_out) std::fill(k_path_out, k_path_out + (size_t)Np * kp, std::numeric_limits<double>::quiet_NaN());
+  if (map_out) for (int k = 0; k < n_polls; k++) { std::fill(map_out + (size_t)k * 2 * D, map_out + (size_t)k * 2 * D + D, 0.0); std::fill(map_out + (size_t)k * 2 * D + D, map_out + (size_t)(k + 1) * 2 * D, 1.0); }
+  for (int i : cand) {
+    if (ru[i].start(pointwise[(size_t)i * LOO_NPW + 3], thr, o.max_iters) != LMM_NONE) work.push_back(i);
+    if (info_out) info_out[(size_t)i * LMM_NINFO + 4] = ru[i].stop;
+  }
+  std::sort(work.begin(), work.end());
+  if (work.empty()) { loo_estimates(pointwise, Np, estimates_out); return 0; }
+  if (const int rc_ = mm_check_sizes(what, Ctot, n_post, 1)) return rc_;
+  const int nchunk = (int)((S + MM_CHUNK - 1) / MM_CHUNK);
+  int maxB = (int)std::max<size_t>(1, std::min<size_t>(64, MM_PART_BUDGET / ((size_t)nchunk * 2 * D * 8)));
+  if (maxB >= MM_BT) maxB -= maxB % MM_BT;
+  maxB = std::min<int>(maxB, (int)work.size());
+  maxB = (int)std::min<long long>(maxB, std::max<long long>(1, 0x7fffffffll / S));
+
+  HIP_TRY(hipSetDevice(mp->device));
+  std::vector<const double *> chains;
+  for (Sampler *sp : P.sps) {
+    HIP_TRY(hipStreamSynchronize(sp->stream));
+    for (int c = 0; c < sp->R.chains; c++) chains.push_back(sp->R.draws + ((size_t)c * sp->R.n_save_max + first) * sp->R.row);
+  }
+  MmCtx x;
+  int rc;
+  if ((rc = mm_setup(x, what, mp, chains, n_post, maxB))) return rc;
+  const size_t BS = (size_t)maxB * S;
+  double *lp = nullptr, *ll = nullptr, *ll0 = nullptr, *llc = nullptr, *r = nullptr, *lwc = nullptr, *lwn = nullptr, *lp0 = nullptr, *wuni = nullptr, *gA = nullptr, *gB = nullptr, *dslb = nullptr, *delpd = nullptr;
+  if ((rc = x.keep.get(&lp, BS * 8, what)) || (rc = x.keep.get(&ll, BS * 8, what)) || (rc = x.keep.get(&ll0, BS * 8, what)) || (rc = x.keep.get(&llc, BS * 8, what)) ||
+      (rc = x.keep.get(&r, BS * 8, what)) || (rc = x.keep.get(&lwc, BS * 8, what)) || (rc = x.keep.get(&lwn, BS * 8, what)) || (rc = x.keep.get(&lp0, (size_t)S * 8, what)) ||
+      (rc = x.keep.get(&wuni, (size_t)S * 8, what)) || (rc = x.keep.get(&gA, BS * 8, what)) || (rc = x.keep.get(&gB, BS * 8, what)) || (rc = x.keep.get(&dslb, (size_t)maxB * 8, what)) ||
+      (rc = x.keep.get(&delpd, (size_t)maxB * 8, what)))
+    return rc;
+  auto finish = [&](int code) { std::copy(x.ms, x.ms + 4, g_mm_ms); return code; };
+  const size_t rowS = (size_t)S * 8;
+  // base moments: m0 = mean, v0 = variance (S - 1), two passes of the moments kernel under uniform weights
+  std::vector<double> m0(D), v0(D), tmpq(D);
+  {
+    std::vector<double> wu((size_t)S, 1.0 / (double)S);
+    HIP_TRY(hipMemcpy(wuni, wu.data(), rowS, hipMemcpyHostToDevice));
+    if ((rc = mm_moments(x, 1, wuni, 0, nullptr, m0.data(), tmpq.data()))) return finish(rc);
+    if ((rc = mm_moments(x, 1, wuni, 0, m0.data(), tmpq.data(), v0.data()))) return finish(rc);
+    for (int j = 0; j < D; j++) v0[j] *= (double)S / (double)(S - 1);
+  }
+  bool have_lp0 = false;
+  std::vector<double> rows_new(pointwise, pointwise + (size_t)Np * LOO_NPW);   // the caller's rows change once, when every batch is through: a call that fails leaves them alone
+  for (size_t w0 = 0; w0 < work.size(); w0 += maxB) {
+    const int B = (int)std::min<size_t>(maxB, work.size() - w0);
+    const int *pb = work.data() + w0;
+    std::vector<double> a((size_t)B * D, 0.0), b((size_t)B * D, 1.0), a1((size_t)B * D), b1((size_t)B * D), mu((size_t)B * D), q((size_t)B * D), reff(B), kk(B);
+    std::vector<int> sel(B, MM_SEL_ID), idx(B), pa(B);
+    std::vector<std::vector<double>> path(B);
+    for (int k = 0; k < B; k++) reff[k] = pointwise[(size_t)pb[k] * LOO_NPW + 4];
+    // ---- start: lp0 and ll0 by the kernel of the candidates, PSIS of -ll0
+    if ((rc = mm_pass(x, B, a.data(), b.data(), pb, sel.data(), o.integrate, lp, ll0))) return finish(rc);
+    if (!have_lp0) { HIP_TRY(hipMemcpy(lp0, lp, rowS, hipMemcpyDeviceToDevice)); have_lp0 = true; }
+    HIP_TRY(hipMemcpy(llc, ll0, (size_t)B * rowS, hipMemcpyDeviceToDevice));
+    if ((rc = mm_ratio(x, B, 0, lp, ll0, lp0, nullptr, nullptr, r, nullptr)) || (rc = mm_psis(x, B, r, reff.data(), lwc, kk.data()))) return finish(rc);
+    for (int k = 0; k < B; k++) {
+      const double kpw = pointwise[(size_t)pb[k] * LOO_NPW + 3];
+      const bool same = kk[k] == kpw || std::fabs(kk[k] - kpw) <= 1e-12 * std::max(1.0, std::fabs(kpw));   // (both NaN never enters: the rules stop there)
+      if (!same) return finish(fail(POTUS_ERR_ARG, "%s: poll %d: PSIS of the fit's draws gives k = %.17g, pointwise holds %.17g: the rows are not potus_loo's of these handles with integrate = %d",
+                                    what, pb[k], kk[k], kpw, o.integrate));
+      ru[pb[k]].start(kk[k], thr, o.max_iters);
+      path[k].push_back(kk[k]);
+    }
+    // ---- rounds: one candidate per active poll
+    for (;;) {
+      int nA = 0;
+      for (int k = 0; k < B; k++) if (ru[pb[k]].next != LMM_NONE) idx[nA++] = k;
+      if (nA == 0) break;
+      for (int u = 0; u < nA; u++) HIP_TRY(hipMemcpyAsync(gA + (size_t)u * S, lwc + (size_t)idx[u] * S, rowS, hipMemcpyDeviceToDevice, x.st));
+      if ((rc = mm_moments(x, nA, gA, 1, m0.data(), mu.data(), q.data()))) return finish(rc);
+      for (int u = 0; u < nA; u++) {
+        const int k = idx[u];
+        const double *ak = a.data() + (size_t)k * D, *bk = b.data() + (size_t)k * D, *mk = mu.data() + (size_t)u * D, *qk = q.data() + (size_t)u * D;
+        double *an = a1.data() + (size_t)u * D, *bn = b1.data() + (size_t)u * D;
+        const bool t1 = ru[pb[k]].next == LMM_T1;
+        for (int j = 0; j < D; j++) {
+          const double m = ak[j] + bk[j] * m0[j], muw = ak[j] + bk[j] * mk[j];
+          if (t1) { an[j] = ak[j] + (muw - m); bn[j] = bk[j]; continue; }
+          const double dm = mk[j] - m0[j], s2w = bk[j] * bk[j] * (qk[j] - dm * dm) * (double)S / (double)(S - 1);
+          double rho = std::sqrt(s2w / (bk[j] * bk[j] * v0[j]));
+          if (!(std::isfinite(rho) && rho > 0.0)) rho = 1.0;
+          bn[j] = rho * bk[j];
+          an[j] = muw - rho * bk[j] * m0[j];
+        }
+        pa[u] = pb[k]; sel[u] = MM_SEL_T;
+      }
+      if ((rc = mm_pass(x, nA, a1.data(), b1.data(), pa.data(), sel.data(), o.integrate, lp, ll))) return finish(rc);
+      std::vector<double> re(nA), kn(nA);
+      for (int u = 0; u < nA; u++) re[u] = reff[idx[u]];
+      if ((rc = mm_ratio(x, nA, 1, lp, ll, lp0, nullptr, nullptr, r, nullptr)) || (rc = mm_psis(x, nA, r, re.data(), lwn, kn.data()))) return finish(rc);
+      for (int u = 0; u < nA; u++) {
+        const int k = idx[u];
+        if (!ru[pb[k]].feed(kn[u], thr, o.max_iters)) continue;
+        std::copy(a1.begin() + (size_t)u * D, a1.begin() + (size_t)(u + 1) * D, a.begin() + (size_t)k * D);
+        std::copy(b1.begin() + (size_t)u * D, b1.begin() + (size_t)(u + 1) * D, b.begin() + (size_t)k * D);
+        HIP_TRY(hipMemcpyAsync(lwc + (size_t)k * S, lwn + (size_t)u * S, rowS, hipMemcpyDeviceToDevice, x.st));
+        HIP_TRY(hipMemcpyAsync(llc + (size_t)k * S, ll + (size_t)u * S, rowS, hipMemcpyDeviceToDevice, x.st));
+        path[k].push_back(kn[u]);
+      }
+      HIP_TRY(hipStreamSynchronize(x.st));
+    }
+    // ---- split: half of every chain's draws transformed, the mixture of the posterior and its push-forward as the proposal
+    int nS = 0;
+    for (int k = 0; k < B; k++) if (o.split && ru[pb[k]].accepted() > 0) idx[nS++] = k;
+    if (nS > 0) {
+      std::vector<double> slb(nS), re(nS), kn(nS);
+      for (int u = 0; u < nS; u++) {
+        const int k = idx[u];
+        std::copy(a.begin() + (size_t)k * D, a.begin() + (size_t)(k + 1) * D, a1.begin() + (size_t)u * D);
+        std::copy(b.begin() + (size_t)k * D, b.begin() + (size_t)(k + 1) * D, b1.begin() + (size_t)u * D);
+        double s = 0.0;
+        for (int j = 0; j < D; j++) s += std::log(b[(size_t)k * D + j]);
+        slb[u] = s; re[u] = reff[k]; pa[u] = pb[k]; sel[u] = MM_SEL_SPLIT;
+        HIP_TRY(hipMemcpyAsync(gA + (size_t)u * S, ll0 + (size_t)k * S, rowS, hipMemcpyDeviceToDevice, x.st));
+      }
+      HIP_TRY(hipMemcpyAsync(dslb, slb.data(), (size_t)nS * 8, hipMemcpyHostToDevice, x.st));
+      if ((rc = mm_pass(x, nS, a1.data(), b1.data(), pa.data(), sel.data(), o.integrate, lp, ll))) return finish(rc);
+      if ((rc = mm_ratio(x, nS, 2, lp, ll, lp0, gA, dslb, r, gB)) || (rc = mm_psis(x, nS, r, re.data(), lwn, kn.data()))) return finish(rc);
+      for (int u = 0; u < nS; u++) {
+        const int k = idx[u];
+        HIP_TRY(hipMemcpyAsync(lwc + (size_t)k * S, lwn + (size_t)u * S, rowS, hipMemcpyDeviceToDevice, x.st));
+        HIP_TRY(hipMemcpyAsync(llc + (size_t)k * S, gB + (size_t)u * S, rowS, hipMemcpyDeviceToDevice, x.st));
+        ru[pb[k]].k = kn[u];
+        path[k].push_back(kn[u]);
+      }
+      HIP_TRY(hipStreamSynchronize(x.st));
+    }
+    // ---- the result rows
+    std::vector<double> elpd(B);
+    if ((rc = mm_timed(x, 3, [&] { hipLaunchKernelGGL(k_mm_final, dim3(B), dim3(DG_THREADS), 0, x.st, (const double *)llc, (const double *)lwc, delpd, S, B); return 0; }))) return finish(rc);
+    HIP_TRY(hipMemcpy(elpd.data(), delpd, (size_t)B * 8, hipMemcpyDeviceToHost));
+    for (int k = 0; k < B; k++) {
+      const int i = pb[k];
+      const LmmPoll &u = ru[i];
+      const bool split_done = o.split && u.accepted() > 0;
+      if (info_out) { int32_t *io = info_out + (size_t)i * LMM_NINFO; io[0] = u.n_t1; io[1] = u.n_t2; io[2] = u.rounds; io[3] = split_done; io[4] = u.stop; io[5] = 0; }
+      if (k_path_out) for (size_t t = 0; t < path[k].size() && t < (size_t)kp; t++) k_path_out[(size_t)i * kp + t] = path[k][t];
+      if (map_out)
+        for (int t = 0; t < n_polls; t++)
+          if (polls[t] == i) { std::copy(a.begin() + (size_t)k * D, a.begin() + (size_t)(k + 1) * D, map_out + (size_t)t * 2 * D); std::copy(b.begin() + (size_t)k * D, b.begin() + (size_t)(k + 1) * D, map_out + (size_t)t * 2 * D + D); }
+      if (u.accepted() == 0) continue;                       // the row keeps its bytes
+      double *pw = rows_new.data() + (size_t)i * LOO_NPW;
+      const double lpd = pw[0] + pw[1];
+      pw[0] = elpd[k]; pw[1] = lpd - elpd[k]; pw[2] = -2.0 * elpd[k]; pw[3] = u.k;
+    }
+  }
+  std::copy(rows_new.begin(), rows_new.end(), pointwise);
+  loo_estimates(pointwise, Np, estimates_out);
+  return finish(0);
+}
+
 // ---------------------------------------------------------------------------------------------- summary table (potus_monitor.hpp)
 namespace {
 // the gathered rows of one handle plus the transposed columns of one block of a potus_monitor call (POTUS_MONITOR_BLOCK_BUDGET, bytes: tests)
@@ -5764,6 +6259,11 @@ void potus_R_monitor(int *handles, int *n_handles, int *cols /*[2]: col_begin, c
 void potus_R_loo(int *handles, int *n_handles, int *iopts /*[2]: integrate, r_eff given*/, double *r_eff, double *pointwise_out, double *estimates_out,
                  int *status) {
   *status = potus_loo(handles, *n_handles, iopts[0], iopts[1] ? r_eff : nullptr, pointwise_out, estimates_out);
+}
+void potus_R_loo_moment_match(int *model_handle, int *handles, int *n_handles, int *iopts /*[5]: integrate, max_iters, split, cov, n_polls (0: every poll)*/,
+                              double *k_threshold, int *polls, double *pointwise, double *estimates_out, int *info_out, int *status) {
+  const potus_loo_mm_opts o{iopts[0], iopts[1], iopts[2], iopts[3], *k_threshold};
+  *status = potus_loo_moment_match(*model_handle, handles, *n_handles, &o, iopts[4] > 0 ? polls : nullptr, iopts[4], pointwise, estimates_out, info_out, nullptr, nullptr);
 }
 // counts come back as doubles (exact below 2^53); below_actual is written only when actual is given
 void potus_R_outcomes(int *handles, int *n_handles, int *iopts /*[4]: day_begin, day_end, ev_to_win, actual given*/, int *ev, double *actual,

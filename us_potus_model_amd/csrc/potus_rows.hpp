@@ -37,12 +37,13 @@ __device__ __forceinline__ double row_poll_eta(const DevModel &M, const RowCols 
 }
 
 // One full CmdStan output row (ncols doubles) from a draw's sampler columns and unconstrained point src[0 .. 7 + D); src must not
-// alias row.  Called by every thread of a 256-thread workgroup.
+// alias row.  Called by every thread of a workgroup of NT threads (256 in the row kernels; k_mm_pass shares its workgroup with the model pass).
+template <int NT = 256>
 __device__ __forceinline__ void wa_build_row(const DevModel &M, const double *src, double *row, RowLds &lds) {
   const int tid = threadIdx.x, S = M.S, T = M.T, D = M.D;
   const RowCols c = row_cols(M);
   const double *q = src + POTUS_N_SAMPLER_COLS;
-  for (int i = tid; i < POTUS_N_SAMPLER_COLS + D; i += 256) row[i] = src[i];
+  for (int i = tid; i < POTUS_N_SAMPLER_COLS + D; i += NT) row[i] = src[i];
   __syncthreads();
   double *Ct = row + c.predicted_score; // suffix sums, staged where predicted_score will go
   if (tid < S) {
@@ -60,13 +61,13 @@ __device__ __forceinline__ void wa_build_row(const DevModel &M, const double *sr
     row[c.e_bias] = e;
     for (int t = 1; t < T; t++) { e = mue + rho * (e - mue) + q[M.o_ze + t] * srho; row[c.e_bias + t] = e; }
   }
-  for (int i = tid; i < M.P; i += 256) row[c.mu_c + i] = q[M.o_c + i] * M.sigma_c;
+  for (int i = tid; i < M.P; i += NT) row[c.mu_c + i] = q[M.o_c + i] * M.sigma_c;
   if (M.full) {
-    for (int i = tid; i < M.M; i += 256) row[c.mu_m + i] = q[M.o_m + i] * M.sigma_m;
-    for (int i = tid; i < M.Pop; i += 256) row[c.mu_pop + i] = q[M.o_pop + i] * M.sigma_pop;
+    for (int i = tid; i < M.M; i += NT) row[c.mu_m + i] = q[M.o_m + i] * M.sigma_m;
+    for (int i = tid; i < M.Pop; i += NT) row[c.mu_pop + i] = q[M.o_pop + i] * M.sigma_pop;
   }
   __syncthreads();
-  for (int idx = tid; idx < S * T; idx += 256) {
+  for (int idx = tid; idx < S * T; idx += NT) {
     const int s = idx % S, t = idx / S;
     double a = lds.bT[s];
     const double *Lrow = M.mat + s * M.SP, *Cc = Ct + S * t;
@@ -75,13 +76,13 @@ __device__ __forceinline__ void wa_build_row(const DevModel &M, const double *sr
   }
   if (tid == 0) { double a = 0.0; for (int s = 0; s < S; s++) a += lds.pb[s] * M.mat[M.m_w + s]; lds.misc[0] = a; row[c.nat_polling_bias] = a; }
   __syncthreads();
-  for (int t = tid; t < T; t += 256) {
+  for (int t = tid; t < T; t += NT) {
     double a = 0.0;
     for (int s = 0; s < S; s++) a += row[c.mu_b + s + S * t] * M.mat[M.m_w + s];
     row[c.nat_mu_b + t] = a;
   }
   __syncthreads();
-  for (int i = tid; i < M.Npoll; i += 256) {
+  for (int i = tid; i < M.Npoll; i += NT) {
     const int s = M.pi[i], qi = M.pi[5 * M.Npad + i];
     const bool nat = s == S;
     double eta = row_poll_eta(M, c, row, M.pd + 2 * M.Npad, i);
@@ -89,7 +90,7 @@ __device__ __forceinline__ void wa_build_row(const DevModel &M, const double *sr
     if (nat) row[c.logit_pi_national + (qi - M.o_nn)] = eta; else row[c.logit_pi_state + (qi - M.o_ns)] = eta;
   }
   __syncthreads();
-  for (int idx = tid; idx < S * T; idx += 256) { // predicted_score[t,s] = inv_logit(mu_b[s,t]) (stan:135-139)
+  for (int idx = tid; idx < S * T; idx += NT) { // predicted_score[t,s] = inv_logit(mu_b[s,t]) (stan:135-139)
     const int t = idx % T, s = idx / T;
     row[c.predicted_score + idx] = d_inv_logit(row[c.mu_b + s + S * t]);
   }

@@ -4,6 +4,7 @@
     1. per-poll log-likelihood       potus_log_lik_device (k_loo_loglik: rows rebuilt per draw, no draws x columns block)
     2. PSIS per poll                 potus_loo / potus_loo_device (k_loo_psis: r_eff, generalized-Pareto tail, weights, elpd_loo_i)
     3. comparison                    loo_compare (host: the pointwise differences)
+    4. moment matching               moment_match (potus_loo_moment_match: the polls with a high Pareto k)
 
 integrate=True (the default) integrates each poll's own noise coordinate raw_measure_noise_* out of its likelihood (integrated
 importance sampling, Vehtari et al. 2016): every poll has a parameter of its own, so leaving it out moves that parameter from posterior
@@ -15,7 +16,8 @@ import ctypes as C
 
 import numpy as np
 
-from .sampler import _check, _device_block, _dp, _handle_ids, load_library
+from . import _abi
+from .sampler import _check, _device_block, _dp, _handle_ids, _ip, load_library
 
 POINTWISE = ("elpd_loo", "p_loo", "looic", "pareto_k", "r_eff")
 ESTIMATES = ("elpd_loo", "p_loo", "looic")
@@ -90,6 +92,55 @@ def loo(handles, integrate=True, r_eff=None, name=None):
     y, n = poll_vectors(h0.data)
     S = h0.post_warmup_saved() * sum(h.opts.chains for h in hs)
     return Loo(pw, est, S, name if name is not None else h0.variant, y, n, bool(integrate))
+
+
+def _runs_one_workgroup_per_chain(h):
+    return h.cus_per_chain == 1 and not h.opts.twin and h.opts.metric == _abi.METRIC_DIAG and h.n_datasets == 1
+
+
+def moment_match(handles, loo, polls=None, model_handle=None, **opts):
+    """loo::loo_moment_match (Paananen et al. 2021) for the polls of `loo` whose Pareto k is above the threshold: potus_loo_moment_match.
+    handles: the fit `loo` was computed from (with the same `integrate`).  polls: poll numbers, or None for every poll.  model_handle: a
+    handle of one workgroup per chain (cus_per_chain = 1, twin = 0, diagonal metric) with the fit's data, whose model evaluates the log
+    density; None takes the first such handle of the fit, or creates (and closes) a one-chain handle of the same data.  opts: max_iters
+    (30), split (True), k_threshold (0: min(1 - 1 / log10 S, 0.7)), cov (False; True is refused).  Returns a Loo that loo_compare takes,
+    with .k_before (the Pareto k of `loo`), .mm_info [N, 6] (_abi.LOO_MM_INFO), .mm_k_path [N, max_iters + 2], .mm_map (a, b of the listed
+    polls when polls is given) and .mm_ms (passes, moments, PSIS, final: milliseconds of the device stages)."""
+    from .sampler import Handle
+    hs, ids = _handle_ids(handles)
+    h0 = hs[0]
+    L = h0.L
+    o = _abi.PotusLooMmOpts()
+    L.potus_default_loo_mm_opts(C.byref(o))
+    o.integrate = int(bool(loo.integrate if loo.integrate is not None else True))
+    for k, v in opts.items():
+        if k not in ("max_iters", "split", "cov", "k_threshold", "integrate"):
+            raise TypeError(f"unknown moment-matching option {k!r}")
+        setattr(o, k, float(v) if k == "k_threshold" else int(v))
+    N = h0.n_polls
+    if loo.pointwise.shape != (N, 5):
+        raise ValueError(f"the Loo holds {loo.pointwise.shape[0]} polls, the fit {N}")
+    own = None
+    if model_handle is None:
+        model_handle = next((h for h in hs if _runs_one_workgroup_per_chain(h)), None)
+    if model_handle is None:
+        own = model_handle = Handle(h0.data, h0.variant, chains=1, num_warmup=0, num_samples=0, seed=1, device=int(h0.opts.device),
+                                    cus_per_chain=1, twin=0)
+    try:
+        pw, est = np.array(loo.pointwise, dtype=np.float64, order="C"), np.zeros((3, 2))
+        info, kpath = np.zeros((N, 6), np.int32), np.full((N, o.max_iters + 2), np.nan)
+        pl = None if polls is None else np.ascontiguousarray(np.asarray(polls).reshape(-1), dtype=np.int32)
+        mp = None if pl is None else np.zeros((pl.size, 2, h0.D))
+        _check(L, L.potus_loo_moment_match(model_handle.h, ids, len(hs), C.byref(o), None if pl is None else _ip(pl), 0 if pl is None else pl.size,
+                                           _dp(pw), _dp(est), _ip(info), _dp(kpath), None if mp is None else _dp(mp)))
+        ms = np.zeros(4)
+        _check(L, L.potus_loo_mm_timing(_dp(ms)))
+    finally:
+        if own is not None:
+            own.close()
+    out = Loo(pw, est, loo.n_draws, loo.name, loo.y, loo.n, loo.integrate)
+    out.k_before, out.mm_info, out.mm_k_path, out.mm_map, out.mm_ms = loo.pareto_k.copy(), info, kpath, mp, ms
+    return out
 
 
 def loo_of_block(block, r_eff=None, name=None, y=None, n=None):

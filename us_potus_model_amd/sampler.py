@@ -100,6 +100,17 @@ def load_library():
         L.potus_log_lik_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.potus_loo_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_longlong, dp, dp, dp]
         L.potus_loo.argtypes = [ip, C.c_int, C.c_int, dp, dp, dp]
+    if hasattr(L, "potus_loo_moment_match"):            # moment matching for PSIS-LOO (loo.moment_match)
+        i32p, mop = C.POINTER(C.c_int32), C.POINTER(_abi.PotusLooMmOpts)
+        L.potus_default_loo_mm_opts.argtypes = [mop]
+        L.potus_default_loo_mm_opts.restype = None
+        L.potus_loo_moment_match.argtypes = [C.c_int, ip, C.c_int, mop, i32p, C.c_int, dp, dp, i32p, dp, dp]
+        L.potus_loo_mm_timing.argtypes = [dp]
+        L.potus_loo_mm_ratios_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, dp, dp, i32p, i32p, C.c_int, C.c_int, C.c_void_p, C.c_void_p, C.c_void_p]
+        L.potus_loo_mm_moments_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_int, C.c_int, dp, dp, dp]
+        L.potus_psis_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_longlong, dp, C.c_void_p, dp]
+        L.potus_R_loo_moment_match.argtypes = [ip, ip, ip, ip, dp, ip, dp, dp, ip, ip]
+        L.potus_R_loo_moment_match.restype = None
     if hasattr(L, "potus_outcomes"):                    # joint election outcomes (outcomes.py)
         i32p, llp = C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
         L.potus_outcomes.argtypes = [ip, C.c_int, C.c_int, C.c_int, i32p, C.c_int, dp, llp, llp, llp, llp, llp]
@@ -183,6 +194,8 @@ EXPORTS = [
     "potus_set_datasets", "potus_simulate_prior", "potus_constrain", "potus_sbc_ranks",
     "potus_set_datasets_ex", "potus_timeline", "potus_timeline_scores_device", "potus_timeline_timing",
     "potus_log_lik_device", "potus_loo_device", "potus_loo",
+    "potus_default_loo_mm_opts", "potus_loo_moment_match", "potus_loo_mm_timing", "potus_loo_mm_ratios_device", "potus_loo_mm_moments_device",
+    "potus_psis_device", "potus_R_loo_moment_match",
     "potus_cv_log_lik_device", "potus_cv_lpd", "potus_cv_timing",
     "potus_default_optimize_opts", "potus_optimize", "potus_optimize_timing",
     "potus_default_laplace_opts", "potus_laplace", "potus_laplace_write_array_device", "potus_laplace_scores_device", "potus_laplace_summary",
@@ -873,6 +886,11 @@ class Handle:
             raise ValueError(f"tensor has {out.numel()} elements, {want} expected")
         _check(self.L, self.L.potus_log_lik_device(self.h, int(poll_begin), int(poll_end), int(bool(integrate)), C.c_void_p(out.data_ptr())))
         return out
+
+    def loo_moment_match(self, loo, polls=None, model_handle=None, **opts):
+        """loo.moment_match on this handle's draws: the Loo with the rows of the polls above the k-hat threshold moment-matched."""
+        from .loo import moment_match
+        return moment_match(self, loo, polls=polls, model_handle=model_handle, **opts)
 
     def _cv_masks(self, held_state, held_national):
         """The two masks as contiguous int32 [n_datasets, polls] arrays (None where the data have no such polls)."""
