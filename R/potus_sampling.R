@@ -356,6 +356,40 @@ potus_loo <- function(fit, integrate = TRUE, r_eff = NULL) {
             class = "potus_loo")
 }
 
+# Which polls move the forecast (DESIGN.md section 4r; us_potus_model_amd/loo.py influence is the same in Python): for every poll the
+# leave-one-out expectation of the forecast of `day` (1-based; NULL: election day) minus its posterior mean, from one fit: potus_e_loo.  ev:
+# electoral votes per state.  Columns: the S state scores, the national vote, the S indicators score > 0.5, electoral college won, electoral
+# votes.  Returns delta, loo_mean, sd [polls, 2 S + 3], post_mean, pareto_k (potus_loo's; read it first: the weights are the plain PSIS
+# weights), khat (the k of every mean, when diag), ess.  The fit must run one workgroup per chain.  Like the rest of this file: not run under R here.
+potus_loo_influence <- function(fit, ev, day = NULL, ev_to_win = 270, integrate = TRUE, diag = TRUE) {
+  N <- as.integer(fit$data$N_state_polls) + as.integer(fit$data$N_national_polls)
+  S <- as.integer(fit$data$S)
+  NC <- 2L * S + 3L
+  r <- .C("potus_R_loo_influence", as.integer(fit$handles), length(fit$handles),
+          as.integer(c(isTRUE(integrate), ev_to_win, if (is.null(day)) -1L else as.integer(day) - 1L, isTRUE(diag))), as.double(ev),
+          loo_mean = double(N * NC), var = double(N * NC), post = double(NC), pareto_k = double(N), ess = double(N), khat = double(N * NC),
+          status = integer(1))
+  .potus_check(r$status)
+  cols <- c(paste0("score_", seq_len(S)), "national", paste0("win_", seq_len(S)), "ec_win", "ev")
+  m <- function(v) matrix(v, N, NC, byrow = TRUE, dimnames = list(NULL, cols))
+  loo_mean <- m(r$loo_mean)
+  list(delta = sweep(loo_mean, 2, r$post), loo_mean = loo_mean, sd = sqrt(pmax(m(r$var), 0)), post_mean = setNames(r$post, cols),
+       pareto_k = r$pareto_k, khat = if (isTRUE(diag)) m(r$khat) else NULL, ess = r$ess)
+}
+
+# What the model expected of each poll before it saw it: the leave-one-out predictive mean and sd of its share y / n (potus_e_loo, predict),
+# with the k of the mean, the in-sample mean, residual = y / n - mean and z = residual / sd.  Plain PSIS weights.  Not run under R here.
+potus_loo_predict <- function(fit, integrate = TRUE) {
+  N <- as.integer(fit$data$N_state_polls) + as.integer(fit$data$N_national_polls)
+  r <- .C("potus_R_loo_predict", as.integer(fit$handles), length(fit$handles), as.integer(isTRUE(integrate)), out = double(N * 5),
+          pareto_k = double(N), status = integer(1))
+  .potus_check(r$status)
+  o <- matrix(r$out, N, 5, byrow = TRUE, dimnames = list(NULL, c("mean", "variance", "sd", "pareto_k", "in_sample_mean")))
+  share <- c(fit$data$n_democrat_state, fit$data$n_democrat_national) / c(fit$data$n_two_share_state, fit$data$n_two_share_national)
+  data.frame(o, share = share, residual = share - o[, "mean"], z = (share - o[, "mean"]) / o[, "sd"],
+             pollster = c(fit$data$poll_state, fit$data$poll_national))
+}
+
 # loo::loo_moment_match for the polls of `loo` (a potus_loo of this fit with the same `integrate`) whose Pareto k is above k_threshold
 # (0: min(1 - 1 / log10 S, 0.7)): potus_loo_moment_match (DESIGN.md section 4q; us_potus_model_amd/loo.py moment_match is the same in Python).
 # polls: poll numbers from 1 (state polls first, then national polls), or NULL for every poll.  model_handle: a handle of the fit's data that

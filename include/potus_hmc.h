@@ -654,6 +654,54 @@ int potus_loo_mm_moments_device(int device, const void *draws, int n_chains, int
 int potus_psis_device(int device, const void *log_ratios, int n_polls, int n_chains, long long n_draws, const double *r_eff /*[n_polls]*/,
                       void *log_weights_out, double *khat_out);
 
+/* ---- E_loo (loo::E_loo): expectations under the posterior that has not seen poll i, from the PSIS weights ----
+ * For poll i: r = the raw log ratios (from a fit: -log_lik_i), lw = the normalised log weights potus_psis_device gives for r, w = exp(lw) (a
+ * weight of -inf is 0), rho = exp(r - max r).  For a quantity x[s]:
+ *   mean = sum w x;  variance = sum w (x - mean)^2;  sd = its square root;
+ *   quantile(p): type 7 when all weights are equal; otherwise x sorted ascending (ties by draw index) with w carried along, ww = cumsum(w) /
+ *     sum w, j the first index with ww[j] >= p: x[0] when j = 0, else x[j-1] + (x[j] - x[j-1]) (p - ww[j-1]) / (ww[j] - ww[j-1]);
+ *   Pareto k of the estimate: mean: h = x, variance and sd: h = x^2: max(k_r, k_hr); quantile: k_r; also k_r when h is constant, takes exactly
+ *     two values or is not finite somewhere.  k_r = the k-hat of the right tail of rho (potus_loo's pareto_k of the poll), k_hr = the larger of
+ *     the k-hats of the right tails of h rho and -h rho; a tail = the M largest values, M = ceil(min(0.2 S, 3 sqrt(S / r_eff))), minus the value
+ *     just below them, fitted by gpdfit with loo's prior; M < 5 or a tail spread below DBL_EPSILON / 100: +inf.
+ * pointwise form: x and log_ratios [n_polls][n_chains][n_draws] on `device` (x has its own values per poll); r_eff [n_polls] or NULL (computed
+ * from -log_ratios as potus_loo computes it); probs [n_probs] inside (0, 1), at most 16.  out [n_polls][3 + n_probs] = mean, variance, sd,
+ * quantiles; khat_out [n_polls][3] = k of the mean, of variance and sd, of the quantiles.  A poll whose ratios hold a NaN or +inf, no finite
+ * value, or a -inf while r_eff is NULL gets NaN.  A poll's bytes depend on its own rows alone.
+ * shared form: X [n_cols][n_chains][n_draws] quantities common to all polls, log_weights [n_polls][n_chains][n_draws] normalised log weights,
+ * both on `device`: mean_out, var_out [n_polls][n_cols], ess_out [n_polls] = 1 / sum w^2 (host).  The products run on the fp64 matrix cores
+ * about c[j] = the equal-weight mean of column j: mean = c + sum w (x - c), variance = sum w (x - c)^2 - (sum w (x - c))^2; the draws are summed
+ * in chunks of 1024, the chunks added in order: an entry's bytes depend on its poll's weights and its column alone.  log_ratios (optional, device,
+ * the shape of log_weights) and r_eff ([n_polls] or NULL: computed) give the diagnostic: diag = 0: khat_out [n_polls] = k_r; diag = 1: khat_out
+ * [n_polls][n_cols] = the k of every mean.
+ * Refused before any kernel runs (POTUS_ERR_ARG): fewer than four draws per chain, probs outside (0, 1), r_eff not finite and positive, blocks that
+ * are not memory of `device`. */
+int potus_e_loo_device(int device, const void *x, const void *log_ratios, int n_polls, int n_chains, long long n_draws, const double *r_eff,
+                       const double *probs, int n_probs, double *out, double *khat_out);
+int potus_e_loo_shared_device(int device, const void *X, int n_cols, const void *log_weights, int n_polls, int n_chains, long long n_draws,
+                              const void *log_ratios, const double *r_eff, int diag, double *mean_out, double *var_out, double *ess_out, double *khat_out);
+/* What the model expects of each poll at every post-warm-up draw (k_el_poll_share, the sibling of potus_log_lik_device: same polls, same
+ * eta): a1 = E_z[p], a2 = E_z[p^2], p = inv_logit(eta + sigma z); integrate = 0: at the draw's own noise coordinate (a2 = a1^2); integrate = 1:
+ * over z ~ N(0, 1), 16 Gauss-Hermite nodes centred at 0.  a1_out, a2_out: device [poll_end - poll_begin][chains][n_post].  With E_loo of a1 and
+ * a2 the leave-one-out predictive mean of the observed share y / n is E[a1], its variance E[a1] / n + (1 - 1 / n) E[a2] - E[a1]^2. */
+int potus_poll_share_device(int handle, int poll_begin, int poll_end, int integrate, void *a1_out_device, void *a2_out_device);
+/* E_loo on a fit's handles, pooled as potus_loo pools (one posterior; polls in blocks whose temporaries stay within 256 MB; blocks of other GPUs
+ * brought to the first handle's by peer copies): log-likelihood -> potus_loo's k-hat and r_eff -> ratios -> PSIS weights -> the forms above.
+ * The weights are the plain PSIS weights, not moment-matched ones.  pareto_k_out [N] is potus_loo's pareto_k.
+ *   what = POTUS_ELOO_PREDICT: out [N][5] = the leave-one-out predictive mean of the poll's share y / n (E_loo[a1]), its variance E_loo[a1] / n +
+ *     (1 - 1 / n) E_loo[a2] - E_loo[a1]^2, its sd, the k of the a1 mean, the in-sample (equal-weight) mean of a1.  The other arguments are ignored.
+ *   what = POTUS_ELOO_INFLUENCE: the 2 S + 3 forecast columns of `day` (0-based; negative: election day): the S state scores, the national vote
+ *     (normalised state_weights . scores), the S indicators score > 0.5, electoral college won (sum ev won >= ev_to_win), electoral votes.
+ *     out, var_out [N][2 S + 3] = leave-one-out mean and variance, post_out [2 S + 3] the posterior means (influence = out - post_out), ess_out
+ *     [N], khat_out [N][2 S + 3] the k of every mean when diag = 1.  With day_begin < day_end also the score and national columns of those days:
+ *     days_out [N][days][S + 1], days_post_out [days][S + 1].  Needs handles of one workgroup per chain with the diagonal metric.
+ * Refused before any kernel runs: handles with data sets (POTUS_ERR_STATE), handles of another posterior or listed twice (POTUS_ERR_ARG), fewer
+ * than four post-warm-up draws per chain (POTUS_ERR_STATE, potus_loo's refusal), bad integrate / what / day.  potus_e_loo_timing: the stages summed. */
+enum { POTUS_ELOO_PREDICT = 0, POTUS_ELOO_INFLUENCE = 1 };
+int potus_e_loo(const int *handles, int n_handles, int integrate, int what, const double *ev /*[S]*/, int ev_to_win, int day, int day_begin, int day_end, int diag,
+                double *out, double *var_out, double *post_out, double *pareto_k_out, double *ess_out, double *khat_out, double *days_out, double *days_post_out);
+int potus_e_loo_timing(double *ms /*[4]: pointwise form; column means and products; chunk sums and ess; diagnostic.  HIP events, calling thread's last call*/);
+
 /* ---- joint election outcomes: what the run scripts compute from the JOINT outcome of a draw ----
  * final_2016.R:904-920 (final_2012.R, final_2008.R, README.Rmd "Final electoral college histogram") the distribution of Democratic electoral
  * votes; final_2012.R:809-839, final_2008.R:813-843 the tipping-point state; README.Rmd:481-502, :1638-1672 the p-value of the certified
@@ -775,6 +823,10 @@ void potus_R_simulate_prior(int *handle, double *seed, int *dims /*[2]: n_sims, 
                             int *n_democrat_national_out, int *status);
 void potus_R_sbc_ranks(int *handle, double *truth, int *cols /*[3]: col_begin, col_end, thin*/, int *less, int *equal, int *L, int *status);
 void potus_R_constrain(int *handle, double *q, int *n, int *cols /*[2]: col_begin, col_end*/, double *out, int *status);
+void potus_R_loo_influence(int *handles, int *n_handles, int *iopts /*[4]: integrate, ev_to_win, day (0-based; -1: election day), diag*/, double *ev,
+                           double *loo_mean /*[N][2S+3]*/, double *var_out, double *post_out /*[2S+3]*/, double *pareto_k /*[N]*/, double *ess, double *khat,
+                           int *status);
+void potus_R_loo_predict(int *handles, int *n_handles, int *integrate, double *out /*[N][5]*/, double *pareto_k /*[N]*/, int *status);
 void potus_R_loo_moment_match(int *model_handle, int *handles, int *n_handles, int *iopts /*[5]: integrate, max_iters, split, cov, n_polls (0: every poll)*/,
                               double *k_threshold, int *polls, double *pointwise /*[n_polls of the data][5], in and out*/, double *estimates_out,
                               int *info_out /*[n_polls of the data][6]*/, int *status);

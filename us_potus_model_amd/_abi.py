@@ -183,3 +183,6 @@ def column_layout(data: dict, variant: str | int = "full"):
         out[name] = (col, col + n, dims)
         col += n
     return out, col
+
+
+ELOO_PREDICT, ELOO_INFLUENCE = 0, 1      # potus_e_loo's `what`

@@ -766,6 +766,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, c
 #include "potus_laplace.hpp"    // the Laplace approximation at a mode: Hessian, factor, draws
 #include "potus_pathfinder.hpp" // Pathfinder: a normal around every iterate of an L-BFGS path, the best ELBO, draws
 #include "potus_advi.hpp"       // mean-field ADVI: stochastic-gradient tracks, the ELBO on a chip-wide grid, draws
+#include "potus_eloo.hpp"       // E_loo: expectations under the leave-one-out posteriors, pointwise and as a product on the matrix cores (included last: potus_loo_mm.hpp's reason)
 
 // ======================================================================== host
 namespace {
@@ -3940,6 +3941,192 @@ int potus_loo_moment_match(int model_handle, const int *handles, int n_handles, 
   return finish(0);
 }
 
+// ---------------------------------------------------------------------------------------------- E_loo (potus_eloo.hpp)
+namespace {
+constexpr size_t EL_PART_BUDGET = 128ull << 20;   // the chunk partials of one k_el_shared launch
+thread_local double g_el_ms[4] = {0.0, 0.0, 0.0, 0.0};   // the calling thread's last call: pointwise form, column means and product, chunk sum and ess, diagnostic
+
+// the sort kernels' scratch for `grid` workgroups of S draws
+int el_work(DevBufs &tmp, int grid, long long S, ElWork &W, const char *what) {
+  W.mmax = 32 + (int)std::sqrt(0.2 * (double)S + 1.0);
+  W.rkey = nullptr; W.ridx = nullptr;
+  int rc;
+  if ((rc = tmp.get(&W.wsd, (size_t)grid * el_ws_doubles(S, W.mmax) * 8, what)) || (rc = tmp.get(&W.wsi, (size_t)grid * S * 4, what))) return rc;
+  if (S > DG_RUN && ((rc = tmp.get(&W.rkey, (size_t)grid * S * 8, what)) || (rc = tmp.get(&W.ridx, (size_t)grid * S * 4, what)))) return rc;
+  return 0;
+}
+size_t el_work_bytes(long long S) {
+  const int mmax = 32 + (int)std::sqrt(0.2 * (double)S + 1.0);
+  return el_ws_doubles(S, mmax) * 8 + (size_t)S * 4 + (S > DG_RUN ? (size_t)S * 12 : 0);
+}
+int el_check_sizes(const char *what, long long C, long long n) {
+  if (C < 1 || n < 4) return fail(POTUS_ERR_ARG, "%s: %lld chains of %lld draws (at least one chain, four draws per chain)", what, C, n);
+  if (2 * C > DG_MAXCH) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld chains pooled (at most %d)", what, C, DG_MAXCH / 2);
+  if (C * n > 0x7fffffffll) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld draws per poll (at most 2^31 - 1)", what, C * n);
+  if ((C * n + EL_CHUNK - 1) / EL_CHUNK > 65535) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld pooled draws (at most %d: one grid plane per %d draws)", what, C * n, 65535 * EL_CHUNK, EL_CHUNK);
+  return 0;
+}
+// the span between two recorded events of an idle stream, added to ms[stage]
+int el_span(EventTimer &t, hipStream_t st, double *ms, int stage) {
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(t.stop(st));
+  HIP_TRY(hipStreamSynchronize(st));
+  double v = 0.0;
+  if (t.elapsed(&v)) ms[stage] += v;
+  return 0;
+}
+} // namespace
+
+int potus_e_loo_timing(double *ms) {
+  return timing_out("potus_e_loo_timing", g_el_ms, 4, ms);
+}
+
+int potus_poll_share_device(int handle, int poll_begin, int poll_end, int integrate, void *a1_out_device, void *a2_out_device) {
+  const char *what = "potus_poll_share_device";
+  Sampler *sp = get(handle);
+  if (!sp || !a1_out_device || !a2_out_device) return fail(POTUS_ERR_STATE, "bad handle or null output");
+  if (const int rc_ = refuse_many_datasets(sp, what)) return rc_;
+  if (integrate != 0 && integrate != 1) return fail(POTUS_ERR_ARG, "%s: integrate = %d (0: at the draw's noise coordinate, 1: noise coordinate integrated out)", what, integrate);
+  const int Np = sp->M.Npoll;
+  if (poll_begin < 0 || poll_end > Np || poll_begin >= poll_end) return fail(POTUS_ERR_ARG, "%s: polls [%d, %d) of %d", what, poll_begin, poll_end, Np);
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, sp->device, a1_out_device, "a1 output")) return rc_;
+  if (const int rc_ = mm_also_device(what, sp->device, a2_out_device, "a2 output")) return rc_;
+  int n_saved = 0, rc = saved_count(sp, &n_saved);
+  if (rc) return rc;
+  const int first = warm_rows(sp, n_saved), n_post = n_saved - first, C = sp->R.chains;
+  if (n_post < 1) return fail(POTUS_ERR_STATE, "%s: no post-warm-up draws saved (%d saved, %d of them warm-up)", what, n_saved, first);
+  DevBufs keep;
+  LooRows r;
+  if ((rc = loo_rows_setup(sp, (long long)n_post * C, keep, r, what))) return rc;
+  const int nb = loo_block_polls((size_t)n_post * C * 16, poll_end - poll_begin);
+  double *b1 = nullptr, *b2 = nullptr;
+  if ((rc = keep.get(&b1, (size_t)n_post * C * nb * 8, what)) || (rc = keep.get(&b2, (size_t)n_post * C * nb * 8, what))) return rc;
+  for (int b0 = poll_begin; b0 < poll_end; b0 += nb) {
+    const int e1 = std::min(b0 + nb, poll_end);
+    ElShareParams P{row_src(sp, first), sp->L.ncols, n_post, b0, e1, integrate, r.scratch, b1, b2};
+    hipLaunchKernelGGL(k_el_poll_share, dim3(r.grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, P);
+    HIP_TRY(hipGetLastError());
+    if ((rc = transpose_block(sp->stream, b1, (double *)a1_out_device + (size_t)(b0 - poll_begin) * C * n_post, n_post, C, e1 - b0, C, 0))) return rc;
+    if ((rc = transpose_block(sp->stream, b2, (double *)a2_out_device + (size_t)(b0 - poll_begin) * C * n_post, n_post, C, e1 - b0, C, 0))) return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  return 0;
+}
+
+int potus_e_loo_device(int device, const void *x, const void *log_ratios, int n_polls, int n_chains, long long n_draws, const double *r_eff, const double *probs,
+                       int n_probs, double *out, double *khat_out) {
+  const char *what = "potus_e_loo_device";
+  if (!x || !log_ratios || !out || !khat_out || n_polls < 1 || n_probs < 0 || (n_probs > 0 && !probs)) return fail(POTUS_ERR_ARG, "%s: bad argument", what);
+  if (n_probs > EL_MAXP) return fail(POTUS_ERR_UNSUPPORTED, "%s: %d quantile probabilities (at most %d per call)", what, n_probs, EL_MAXP);
+  for (int i = 0; i < n_probs; i++)
+    if (!(probs[i] > 0.0 && probs[i] < 1.0)) return fail(POTUS_ERR_ARG, "%s: probs[%d] = %g (inside (0, 1) expected)", what, i, probs[i]);
+  if (const int rc_ = el_check_sizes(what, n_chains, n_draws)) return rc_;
+  if (const int rc_ = loo_check_r_eff(r_eff, n_polls, what)) return rc_;
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, device, x, "block of x")) return rc_;
+  if (const int rc_ = mm_also_device(what, device, log_ratios, "block of log ratios")) return rc_;
+  std::fill(g_el_ms, g_el_ms + 4, 0.0);
+  const long long S = (long long)n_chains * n_draws;
+  const int grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(n_polls, 1024), LOO_BLOCK_BUDGET / 2 / el_work_bytes(S)));
+  DevBufs tmp;
+  ElPwParams P{};
+  double *dre = nullptr, *dout = nullptr, *dk = nullptr;
+  int rc;
+  if ((rc = el_work(tmp, grid, S, P.W, what)) || (rc = tmp.get(&dout, (size_t)n_polls * (3 + n_probs) * 8, what)) || (rc = tmp.get(&dk, (size_t)n_polls * EL_NK * 8, what))) return rc;
+  if (r_eff) {
+    if ((rc = tmp.get(&dre, (size_t)n_polls * 8, what))) return rc;
+    HIP_TRY(hipMemcpy(dre, r_eff, (size_t)n_polls * 8, hipMemcpyHostToDevice));
+  }
+  P.x = (const double *)x; P.r = (const double *)log_ratios; P.r_eff = dre; P.out = dout; P.khat = dk;
+  for (int i = 0; i < n_probs; i++) P.probs[i] = probs[i];
+  P.n = n_draws; P.C = n_chains; P.NP = n_polls; P.np = n_probs;
+  const size_t lds = sorted_run_lds(S);
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_el_pointwise), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  EventTimer t;
+  HIP_TRY(t.made);
+  HIP_TRY(t.start(0));
+  hipLaunchKernelGGL(k_el_pointwise, dim3(grid), dim3(DG_THREADS), lds, 0, P);
+  if ((rc = el_span(t, 0, g_el_ms, 0))) return rc;
+  HIP_TRY(hipMemcpy(out, dout, (size_t)n_polls * (3 + n_probs) * 8, hipMemcpyDeviceToHost));
+  HIP_TRY(hipMemcpy(khat_out, dk, (size_t)n_polls * EL_NK * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int potus_e_loo_shared_device(int device, const void *X, int n_cols, const void *log_weights, int n_polls, int n_chains, long long n_draws, const void *log_ratios,
+                              const double *r_eff, int diag, double *mean_out, double *var_out, double *ess_out, double *khat_out) {
+  const char *what = "potus_e_loo_shared_device";
+  if (!X || !log_weights || !mean_out || !var_out || !ess_out || n_polls < 1 || n_cols < 1) return fail(POTUS_ERR_ARG, "%s: bad argument", what);
+  if (diag != 0 && diag != 1) return fail(POTUS_ERR_ARG, "%s: diag = %d (0: k of the ratios per poll, 1: k of every mean)", what, diag);
+  if (diag && !log_ratios) return fail(POTUS_ERR_ARG, "%s: diag = 1 needs the raw log ratios", what);
+  if (log_ratios && !khat_out) return fail(POTUS_ERR_ARG, "%s: log ratios without an output for their k", what);
+  if (const int rc_ = el_check_sizes(what, n_chains, n_draws)) return rc_;
+  if (const int rc_ = loo_check_r_eff(r_eff, n_polls, what)) return rc_;
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, device, X, "block of columns")) return rc_;
+  if (const int rc_ = mm_also_device(what, device, log_weights, "block of log weights")) return rc_;
+  if (log_ratios) if (const int rc_ = mm_also_device(what, device, log_ratios, "block of log ratios")) return rc_;
+  std::fill(g_el_ms, g_el_ms + 4, 0.0);
+  const long long S = (long long)n_chains * n_draws;
+  const int nchunk = (int)((S + EL_CHUNK - 1) / EL_CHUNK);
+  // polls per launch: whole tiles whose chunk partials stay within the budget (at least one tile)
+  const size_t per_tile = (size_t)nchunk * 2 * EL_TM * (size_t)n_cols * 8;
+  const int pb = (int)std::min<size_t>((size_t)(n_polls + EL_TM - 1) / EL_TM, std::max<size_t>(1, EL_PART_BUDGET / per_tile)) * EL_TM;
+  const int pmax = std::min(pb, n_polls);
+  DevBufs tmp;
+  double *cm = nullptr, *part = nullptr, *dmean = nullptr, *dvar = nullptr, *dess = nullptr;
+  int rc;
+  if ((rc = tmp.get(&cm, (size_t)n_cols * 8, what)) || (rc = tmp.get(&part, (size_t)nchunk * 2 * pmax * (size_t)n_cols * 8, what)) ||
+      (rc = tmp.get(&dmean, (size_t)pmax * n_cols * 8, what)) || (rc = tmp.get(&dvar, (size_t)pmax * n_cols * 8, what)) || (rc = tmp.get(&dess, (size_t)n_polls * 8, what)))
+    return rc;
+  EventTimer t;
+  HIP_TRY(t.made);
+  const double *Xd = (const double *)X, *lw = (const double *)log_weights;
+  HIP_TRY(t.start(0));
+  hipLaunchKernelGGL(k_el_colmean, dim3(std::min(n_cols, 65535)), dim3(DG_THREADS), 0, 0, Xd, cm, S, n_cols);
+  if ((rc = el_span(t, 0, g_el_ms, 1))) return rc;
+  for (int p0 = 0; p0 < n_polls; p0 += pb) {
+    const int np = std::min(pb, n_polls - p0);
+    const ElShParams P{Xd, lw + (size_t)p0 * S, cm, part, S, np, n_cols};
+    HIP_TRY(t.start(0));
+    hipLaunchKernelGGL(k_el_shared, dim3((n_cols + EL_TN - 1) / EL_TN, (np + EL_TM - 1) / EL_TM, nchunk), dim3(EL_THREADS), 0, 0, P);
+    if ((rc = el_span(t, 0, g_el_ms, 1))) return rc;
+    const long long PC = (long long)np * n_cols;
+    HIP_TRY(t.start(0));
+    hipLaunchKernelGGL(k_el_shared_sum, dim3((unsigned)std::min<long long>((PC + 255) / 256, 65535)), dim3(256), 0, 0, (const double *)part, (const double *)cm, dmean, dvar, nchunk, np, n_cols);
+    if ((rc = el_span(t, 0, g_el_ms, 2))) return rc;
+    HIP_TRY(hipMemcpy(mean_out + (size_t)p0 * n_cols, dmean, (size_t)PC * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(var_out + (size_t)p0 * n_cols, dvar, (size_t)PC * 8, hipMemcpyDeviceToHost));
+  }
+  HIP_TRY(t.start(0));
+  hipLaunchKernelGGL(k_el_ess, dim3(std::min(n_polls, 65535)), dim3(DG_THREADS), 0, 0, lw, dess, S, n_polls);
+  if ((rc = el_span(t, 0, g_el_ms, 2))) return rc;
+  HIP_TRY(hipMemcpy(ess_out, dess, (size_t)n_polls * 8, hipMemcpyDeviceToHost));
+  if (!log_ratios) return 0;
+  // ---- the diagnostic: k_r (and r_eff) per poll, then with diag = 1 the k of every mean
+  const long long items = diag ? (long long)n_polls * n_cols : n_polls;
+  const int grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min<long long>(items, 1024), LOO_BLOCK_BUDGET / 2 / el_work_bytes(S)));
+  ElKParams K{};
+  double *dre = nullptr, *dkr = nullptr, *dreff = nullptr, *dkh = nullptr;
+  if ((rc = el_work(tmp, grid, S, K.W, what)) || (rc = tmp.get(&dkr, (size_t)n_polls * 8, what)) || (rc = tmp.get(&dreff, (size_t)n_polls * 8, what))) return rc;
+  if (r_eff) {
+    if ((rc = tmp.get(&dre, (size_t)n_polls * 8, what))) return rc;
+    HIP_TRY(hipMemcpy(dre, r_eff, (size_t)n_polls * 8, hipMemcpyHostToDevice));
+  }
+  if (diag && (rc = tmp.get(&dkh, (size_t)items * 8, what))) return rc;
+  K.X = Xd; K.r = (const double *)log_ratios; K.r_eff = dre; K.kr = dkr; K.reff = dreff; K.khat = dkh;
+  K.n = n_draws; K.C = n_chains; K.NP = n_polls; K.NC = n_cols;
+  const size_t lds = sorted_run_lds(S);
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_el_kr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_el_khat), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(t.start(0));
+  hipLaunchKernelGGL(k_el_kr, dim3(std::min(n_polls, grid)), dim3(DG_THREADS), lds, 0, K);
+  if (diag) hipLaunchKernelGGL(k_el_khat, dim3(grid), dim3(DG_THREADS), lds, 0, K);
+  if ((rc = el_span(t, 0, g_el_ms, 3))) return rc;
+  HIP_TRY(hipMemcpy(khat_out, diag ? dkh : dkr, (size_t)items * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
 // ---------------------------------------------------------------------------------------------- summary table (potus_monitor.hpp)
 namespace {
 // the gathered rows of one handle plus the transposed columns of one block of a potus_monitor call (POTUS_MONITOR_BLOCK_BUDGET, bytes: tests)
@@ -6137,6 +6324,196 @@ int potus_debug_state(int handle, int which, double *out, unsigned char *scal) {
   return 1;
 }
 
+// ---------------------------------------------------------------------------------------------- E_loo on a fit's handles (potus_eloo.hpp)
+// Pools as potus_loo pools: the polls in blocks whose temporaries stay within LOO_BLOCK_BUDGET, every handle's block made on its own GPU and
+// brought to the first handle's (gather_block).  Per block: log-likelihoods -> potus_loo's k-hat and r_eff (loo_psis) -> ratios -> under no
+// lock of its own the device forms (potus_psis_device, potus_e_loo_shared_device / potus_e_loo_device take the device's lock themselves).
+// The scores (k_tl_scores) and the log-likelihoods (k_loo_loglik) both walk a handle's draws chain after chain, iterations within, and the
+// handles are placed at their chain offset in the order listed: column s of X and weight s of a poll are the same draw.
+int potus_e_loo(const int *handles, int n_handles, int integrate, int what, const double *ev, int ev_to_win, int day, int day_begin, int day_end, int diag,
+                double *out, double *var_out, double *post_out, double *pareto_k_out, double *ess_out, double *khat_out, double *days_out, double *days_post_out) {
+  const char *nm = "potus_e_loo";
+  if (!out || !pareto_k_out) return fail(POTUS_ERR_ARG, "%s: null output", nm);
+  if (what != POTUS_ELOO_PREDICT && what != POTUS_ELOO_INFLUENCE) return fail(POTUS_ERR_ARG, "%s: what = %d (0: predict, 1: influence)", nm, what);
+  if (integrate != 0 && integrate != 1) return fail(POTUS_ERR_ARG, "%s: integrate = %d (0: plain, 1: noise coordinate integrated out)", nm, integrate);
+  if (diag != 0 && diag != 1) return fail(POTUS_ERR_ARG, "%s: diag = %d", nm, diag);
+  Pool P;
+  if (const int rc_ = P.resolve(handles, n_handles, nm)) return rc_;
+  if (const int rc_ = P.same_posterior("E_loo pools the chains of one")) return rc_;
+  const std::vector<Sampler *> &sps = P.sps;
+  Sampler *s0 = P.s0;
+  const int Np = s0->M.Npoll, S = s0->M.S, T = s0->M.T;
+  if (Np < 1) return fail(POTUS_ERR_ARG, "%s: the data hold no polls", nm);
+  const bool infl = what == POTUS_ELOO_INFLUENCE;
+  const int t = day < 0 ? T - 1 : day, nday = infl && day_end > day_begin ? day_end - day_begin : 0, NC = 2 * S + 3;
+  std::vector<TlPlan> plans(sps.size());
+  if (infl) {
+    if (!ev || !var_out || !post_out || !ess_out || (diag && !khat_out)) return fail(POTUS_ERR_ARG, "%s: influence needs ev and the outputs var, post, ess (and khat with diag)", nm);
+    if (nday && (!days_out || !days_post_out)) return fail(POTUS_ERR_ARG, "%s: a day range without its outputs", nm);
+    for (size_t i = 0; i < sps.size(); i++) {
+      if (const int rc_ = tl_check_args(nm, sps[i], t, t + 1, plans[i])) return rc_;
+      if (nday) if (const int rc_ = tl_check_args(nm, sps[i], day_begin, day_end, plans[i])) return rc_;
+    }
+  }
+  double acc[4] = {0.0, 0.0, 0.0, 0.0};
+  DevBufs keep;
+  double *cols = nullptr, *rr = nullptr, *lw = nullptr, *b1 = nullptr, *b2 = nullptr, *X = nullptr, *Xd = nullptr, *cm = nullptr;
+  int Ctot = 0, n_post = 0, first = 0, nb = 0;
+  long long Stot = 0;
+  std::vector<LooRows> rows(sps.size());
+  {
+    DeviceGuard guard;
+    DeviceLocks lock(P.devs);
+    if (const int rc_ = P.count()) return rc_;
+    if (const int rc_ = P.equal_counts()) return rc_;
+    Ctot = P.chains;
+    if (2 * Ctot > DG_MAXCH) return fail(POTUS_ERR_UNSUPPORTED, "%s: %d chains pooled (at most %d)", nm, Ctot, DG_MAXCH / 2);
+    if (const int rc_ = P.post_warmup(&first, &n_post)) return rc_;
+    Stot = (long long)n_post * Ctot;
+    if (const int rc_ = el_check_sizes(nm, Ctot, n_post)) return rc_;
+    int rc;
+    for (size_t i = 0; i < sps.size(); i++)
+      if ((rc = loo_rows_setup(sps[i], (long long)n_post * sps[i]->R.chains, keep, rows[i], nm))) return rc;
+    nb = loo_block_polls((size_t)Stot * 8 * (infl ? 4 : 6), Np);
+    if (const char *e = getenv("POTUS_ELOO_BLOCK_POLLS")) nb = std::max(1, std::min(nb, atoi(e)));   // (tests: several blocks on a small fit)
+    HIP_TRY(hipSetDevice(s0->device));
+    if ((rc = keep.get(&cols, (size_t)Stot * nb * 8, nm)) || (rc = keep.get(&rr, (size_t)Stot * nb * 8, nm)) || (rc = keep.get(&lw, (size_t)Stot * nb * 8, nm))) return rc;
+    if (!infl && ((rc = keep.get(&b1, (size_t)Stot * nb * 8, nm)) || (rc = keep.get(&b2, (size_t)Stot * nb * 8, nm)) || (rc = keep.get(&cm, (size_t)nb * 8, nm)))) return rc;
+    if (infl) {
+      // ---- the forecast columns, shared by all polls
+      const int ncd = nday * (S + 1);
+      double *dw = nullptr, *dev_ev = nullptr;
+      if ((rc = keep.get(&X, (size_t)NC * Stot * 8, nm)) || (rc = keep.get(&cm, (size_t)std::max(NC, ncd) * 8, nm)) || (rc = keep.get(&dw, (size_t)S * 8, nm)) ||
+          (rc = keep.get(&dev_ev, (size_t)S * 8, nm)) || (nday && (rc = keep.get(&Xd, (size_t)ncd * Stot * 8, nm))))
+        return rc;
+      HIP_TRY(hipMemcpy(dw, s0->h_w.data(), (size_t)S * 8, hipMemcpyHostToDevice));
+      HIP_TRY(hipMemcpy(dev_ev, ev, (size_t)S * 8, hipMemcpyHostToDevice));
+      for (int pass = 0; pass < (nday ? 2 : 1); pass++) {
+        const int d0 = pass ? day_begin : t, d1 = pass ? day_end : t + 1, nd = d1 - d0;
+        long long off = 0;
+        for (size_t i = 0; i < sps.size(); i++) {
+          Sampler *sp = sps[i];
+          const long long n_h = (long long)sp->R.chains * n_post;
+          const size_t bytes = (size_t)n_h * nd * S * 8;
+          DevBufs blkbuf;
+          double *blk = nullptr;
+          if ((rc = blkbuf.get(&blk, bytes, nm))) return rc;
+          TlPlan &pl = plans[i];
+          if ((rc = gather_block(s0, sp, bytes, blk, [&](double *o) {
+                 if (const int r_ = ds_plan(nm, sp, pl)) return r_;
+                 DevBufs tmp;
+                 int *dskip = nullptr;
+                 if (const int r_ = tmp.get(&dskip, 4, nm)) return r_;
+                 const int zero = 0;
+                 HIP_TRY(hipMemcpyAsync(dskip, &zero, 4, hipMemcpyHostToDevice, sp->stream));
+                 if (const int r_ = tl_scores(sp, pl, d0, d1, dskip, o)) return r_;
+                 HIP_TRY(hipStreamSynchronize(sp->stream));
+                 return 0;
+               }))) return rc;
+          const ElColParams Q{blk, dw, dev_ev, pass ? Xd : X, n_h, Stot, off, nd, S, pass ? 0 : 1, (double)ev_to_win};
+          hipLaunchKernelGGL(k_el_columns, dim3((unsigned)std::min<long long>((n_h * nd + 255) / 256, 65535)), dim3(256), 0, s0->stream, Q);
+          HIP_TRY(hipGetLastError());
+          HIP_TRY(hipStreamSynchronize(s0->stream));
+          off += n_h;
+        }
+        const int nc = pass ? ncd : NC;
+        hipLaunchKernelGGL(k_el_colmean, dim3(std::min(nc, 65535)), dim3(DG_THREADS), 0, s0->stream, (const double *)(pass ? Xd : X), cm, Stot, nc);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(pass ? days_post_out : post_out, cm, (size_t)nc * 8, hipMemcpyDeviceToHost, s0->stream));
+        HIP_TRY(hipStreamSynchronize(s0->stream));
+      }
+    }
+  }
+  std::vector<double> pw((size_t)nb * LOO_NPW), re(nb), kk(nb), o3((size_t)nb * 3), k3((size_t)nb * EL_NK), e2(nb), ins(nb);
+  for (int b0 = 0; b0 < Np; b0 += nb) {
+    const int e1 = std::min(b0 + nb, Np), nbk = e1 - b0;
+    {
+      DeviceGuard guard;
+      DeviceLocks lock(P.devs);
+      int rc, coff = 0;
+      HIP_TRY(hipSetDevice(s0->device));
+      for (size_t i = 0; i < sps.size(); i++) {
+        Sampler *sp = sps[i];
+        const int C = sp->R.chains;
+        const size_t bytes = (size_t)n_post * C * nbk * 8;
+        DevBufs blkbuf;
+        double *blk = nullptr, *blk2 = nullptr;
+        if ((rc = blkbuf.get(&blk, bytes, nm))) return rc;
+        if ((rc = gather_block(s0, sp, bytes, blk, [&](double *o) { return loo_loglik(sp, rows[i], first, n_post, b0, e1, integrate, o); }))) return rc;
+        if ((rc = pool_transpose(s0, blk, cols, n_post, C, nbk, Ctot, coff))) return rc;
+        if (!infl) {
+          // (a1 and a2 come from one launch: both blocks are made on the handle's GPU, then brought over one after the other)
+          HIP_TRY(hipSetDevice(sp->device));
+          DevBufs far;
+          double *f1 = nullptr, *f2 = nullptr;
+          if ((rc = far.get(&f1, bytes, nm)) || (rc = far.get(&f2, bytes, nm))) return rc;
+          ElShareParams Q{row_src(sp, first), sp->L.ncols, n_post, b0, e1, integrate, rows[i].scratch, f1, f2};
+          hipLaunchKernelGGL(k_el_poll_share, dim3(rows[i].grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, Q);
+          HIP_TRY(hipGetLastError());
+          HIP_TRY(hipStreamSynchronize(sp->stream));
+          HIP_TRY(hipSetDevice(s0->device));
+          const double *g1 = f1, *g2 = f2;
+          if (sp->device != s0->device) {      // (on one device the transposes read the blocks where they are: a copy there is not ordered with s0's stream)
+            if ((rc = blkbuf.get(&blk2, bytes, nm))) return rc;
+            HIP_TRY(hipMemcpyPeer(blk, s0->device, f1, sp->device, bytes));
+            HIP_TRY(hipMemcpyPeer(blk2, s0->device, f2, sp->device, bytes));
+            HIP_TRY(hipDeviceSynchronize());
+            g1 = blk; g2 = blk2;
+          }
+          if ((rc = pool_transpose(s0, g1, b1, n_post, C, nbk, Ctot, coff)) || (rc = pool_transpose(s0, g2, b2, n_post, C, nbk, Ctot, coff))) return rc;
+        }
+        coff += C;
+      }
+      if ((rc = loo_psis(s0->stream, cols, nbk, Ctot, n_post, nullptr, pw.data(), nm))) return rc;
+      const MmRatioParams R{nullptr, cols, nullptr, nullptr, nullptr, rr, nullptr, n_post, (int)Stot, nbk, 0};
+      hipLaunchKernelGGL(k_mm_ratio, dim3((unsigned)std::min<long long>(((long long)nbk * Stot + 255) / 256, 65535)), dim3(256), 0, s0->stream, R);
+      HIP_TRY(hipGetLastError());
+      if (!infl) {
+        hipLaunchKernelGGL(k_el_colmean, dim3(std::min(nbk, 65535)), dim3(DG_THREADS), 0, s0->stream, (const double *)b1, cm, Stot, nbk);
+        HIP_TRY(hipGetLastError());
+        HIP_TRY(hipMemcpyAsync(ins.data(), cm, (size_t)nbk * 8, hipMemcpyDeviceToHost, s0->stream));
+      }
+      HIP_TRY(hipStreamSynchronize(s0->stream));
+    }
+    for (int k = 0; k < nbk; k++) { pareto_k_out[b0 + k] = pw[(size_t)k * LOO_NPW + 3]; re[k] = pw[(size_t)k * LOO_NPW + 4]; }
+    // a poll with identical log-likelihoods has no r_eff (NaN): any value gives its flat tail no fit
+    for (int k = 0; k < nbk; k++) if (!(std::isfinite(re[k]) && re[k] > 0)) re[k] = 1.0;
+    int rc;
+    if (infl) {
+      if ((rc = potus_psis_device(s0->device, rr, nbk, Ctot, n_post, re.data(), lw, kk.data()))) return rc;
+      if ((rc = potus_e_loo_shared_device(s0->device, X, NC, lw, nbk, Ctot, n_post, rr, re.data(), diag, out + (size_t)b0 * NC, var_out + (size_t)b0 * NC, ess_out + b0,
+                                          diag ? khat_out + (size_t)b0 * NC : kk.data())))
+        return rc;
+      for (int k = 0; k < 4; k++) acc[k] += g_el_ms[k];
+      if (nday) {
+        const int ncd = nday * (S + 1);
+        std::vector<double> dvar((size_t)nbk * ncd);
+        if ((rc = potus_e_loo_shared_device(s0->device, Xd, ncd, lw, nbk, Ctot, n_post, nullptr, nullptr, 0, days_out + (size_t)b0 * ncd, dvar.data(), e2.data(), nullptr))) return rc;
+        for (int k = 0; k < 4; k++) acc[k] += g_el_ms[k];
+      }
+    } else {
+      if ((rc = potus_e_loo_device(s0->device, b2, rr, nbk, Ctot, n_post, re.data(), nullptr, 0, o3.data(), k3.data()))) return rc;
+      for (int k = 0; k < nbk; k++) e2[k] = o3[(size_t)k * 3];
+      for (int k = 0; k < 4; k++) acc[k] += g_el_ms[k];
+      if ((rc = potus_e_loo_device(s0->device, b1, rr, nbk, Ctot, n_post, re.data(), nullptr, 0, o3.data(), k3.data()))) return rc;
+      for (int k = 0; k < 4; k++) acc[k] += g_el_ms[k];
+      std::vector<double> nn((size_t)2 * s0->M.Npad);
+      { DeviceGuard guard; HIP_TRY(hipSetDevice(s0->device)); HIP_TRY(hipMemcpy(nn.data(), s0->M.pd, nn.size() * 8, hipMemcpyDeviceToHost)); }
+      std::vector<int> pi((size_t)6 * s0->M.Npad);
+      { DeviceGuard guard; HIP_TRY(hipSetDevice(s0->device)); HIP_TRY(hipMemcpy(pi.data(), s0->M.pi, pi.size() * 4, hipMemcpyDeviceToHost)); }
+      for (int i = 0; i < Np; i++) {          // the model's (day-sorted) poll i is poll k of the output numbering
+        const int st = pi[i], qi = pi[(size_t)5 * s0->M.Npad + i], k = (st == S ? s0->M.Ns + (qi - s0->M.o_nn) : qi - s0->M.o_ns) - b0;
+        if (k < 0 || k >= nbk) continue;
+        const double n = nn[(size_t)s0->M.Npad + i], m1 = o3[(size_t)k * 3], var = m1 / n + (1.0 - 1.0 / n) * e2[k] - m1 * m1;
+        double *o = out + (size_t)(b0 + k) * 5;
+        o[0] = m1; o[1] = var; o[2] = std::sqrt(std::max(var, 0.0)); o[3] = k3[(size_t)k * EL_NK]; o[4] = ins[k];
+      }
+    }
+  }
+  std::copy(acc, acc + 4, g_el_ms);
+  return 0;
+}
+
 // ---------------------------------------------------------------- .C() wrappers
 void potus_R_create(int *dims, int *state, int *day_state, int *day_national, int *poll_state, int *poll_national,
                     int *poll_mode_state, int *poll_mode_national, int *poll_pop_state, int *poll_pop_national,
@@ -6259,6 +6636,14 @@ void potus_R_monitor(int *handles, int *n_handles, int *cols /*[2]: col_begin, c
 void potus_R_loo(int *handles, int *n_handles, int *iopts /*[2]: integrate, r_eff given*/, double *r_eff, double *pointwise_out, double *estimates_out,
                  int *status) {
   *status = potus_loo(handles, *n_handles, iopts[0], iopts[1] ? r_eff : nullptr, pointwise_out, estimates_out);
+}
+// E_loo on a fit: influence (iopts: integrate, ev_to_win, day (-1: election day), diag) and predict; the outputs of potus_e_loo
+void potus_R_loo_influence(int *handles, int *n_handles, int *iopts /*[4]*/, double *ev, double *loo_mean, double *var_out, double *post_out, double *pareto_k,
+                           double *ess, double *khat, int *status) {
+  *status = potus_e_loo(handles, *n_handles, iopts[0], POTUS_ELOO_INFLUENCE, ev, iopts[1], iopts[2], 0, 0, iopts[3], loo_mean, var_out, post_out, pareto_k, ess, khat, nullptr, nullptr);
+}
+void potus_R_loo_predict(int *handles, int *n_handles, int *integrate, double *out /*[N][5]*/, double *pareto_k, int *status) {
+  *status = potus_e_loo(handles, *n_handles, *integrate, POTUS_ELOO_PREDICT, nullptr, 0, -1, 0, 0, 0, out, nullptr, nullptr, pareto_k, nullptr, nullptr, nullptr, nullptr);
 }
 void potus_R_loo_moment_match(int *model_handle, int *handles, int *n_handles, int *iopts /*[5]: integrate, max_iters, split, cov, n_polls (0: every poll)*/,
                               double *k_threshold, int *polls, double *pointwise, double *estimates_out, int *info_out, int *status) {

@@ -5,6 +5,8 @@
     2. PSIS per poll                 potus_loo / potus_loo_device (k_loo_psis: r_eff, generalized-Pareto tail, weights, elpd_loo_i)
     3. comparison                    loo_compare (host: the pointwise differences)
     4. moment matching               moment_match (potus_loo_moment_match: the polls with a high Pareto k)
+    5. E_loo                         e_loo, e_loo_shared, influence (potus_e_loo_device, potus_e_loo_shared_device: expectations under the
+                                     leave-one-out posteriors and what every poll does to the forecast)
 
 integrate=True (the default) integrates each poll's own noise coordinate raw_measure_noise_* out of its likelihood (integrated
 importance sampling, Vehtari et al. 2016): every poll has a parameter of its own, so leaving it out moves that parameter from posterior
@@ -153,6 +155,232 @@ def loo_of_block(block, r_eff=None, name=None, y=None, n=None):
     _check(L, L.potus_loo_device(int(block.device.index or 0), C.c_void_p(block.data_ptr()), N, ch, nd, None if re is None else _dp(re),
                                  _dp(pw), _dp(est)))
     return Loo(pw, est, ch * nd, name, y, n)
+
+
+E_LOO_TYPES = ("mean", "variance", "sd", "quantile")
+
+
+class ELoo:
+    """loo::E_loo of a block: .value and .pareto_k of the requested type ([polls], quantiles [polls, len(probs)]), and every estimate the
+    kernel computed beside it: .mean, .variance, .sd, .quantiles [polls, len(probs)], .khat [polls, 3] (k of the mean, of variance and sd,
+    of the quantiles)."""
+
+    def __init__(self, out, khat, type, probs):
+        self.type, self.probs = type, probs
+        self.mean, self.variance, self.sd, self.quantiles, self.khat = out[:, 0], out[:, 1], out[:, 2], out[:, 3:], khat
+        self.value = {"mean": self.mean, "variance": self.variance, "sd": self.sd, "quantile": self.quantiles}[type]
+        self.pareto_k = khat[:, {"mean": 0, "variance": 1, "sd": 1, "quantile": 2}[type]]
+
+
+def e_loo(block_x, block_ratios, type="mean", probs=None, r_eff=None):
+    """potus_e_loo_device: loo::E_loo of x under the PSIS weights of the raw log ratios (from a fit: -log_lik), both torch tensors [polls,
+    chains, draws] (float64, contiguous, on one GPU), x with its own values per poll.  type: "mean", "variance", "sd" or "quantile" (with
+    probs inside (0, 1), at most 16).  r_eff: [polls], or None (computed as loo::relative_eff of -ratios).  The weights are the plain PSIS
+    weights, not moment-matched ones.  DESIGN.md section 4r states the definitions."""
+    if type not in E_LOO_TYPES:
+        raise ValueError(f"type = {type!r}: one of {E_LOO_TYPES}")
+    if type == "quantile" and probs is None:
+        raise ValueError("type = 'quantile' needs probs")
+    _device_block(block_x, "e_loo", ("polls", "chains", "draws"))
+    _device_block(block_ratios, "e_loo", ("polls", "chains", "draws"))
+    if tuple(block_x.shape) != tuple(block_ratios.shape):
+        raise ValueError(f"e_loo: x is {tuple(block_x.shape)}, the log ratios {tuple(block_ratios.shape)}")
+    L = load_library()
+    N, ch, nd = (int(v) for v in block_x.shape)
+    pr = np.zeros(0) if probs is None else np.ascontiguousarray(np.atleast_1d(probs), dtype=np.float64)
+    out, kh = np.zeros((N, 3 + pr.size)), np.zeros((N, 3))
+    re = None if r_eff is None else np.ascontiguousarray(r_eff, dtype=np.float64).reshape(N)
+    _check(L, L.potus_e_loo_device(int(block_x.device.index or 0), C.c_void_p(block_x.data_ptr()), C.c_void_p(block_ratios.data_ptr()), N, ch, nd,
+                                   None if re is None else _dp(re), _dp(pr) if pr.size else None, int(pr.size), _dp(out), _dp(kh)))
+    return ELoo(out, kh, type, pr)
+
+
+class ELooShared:
+    """E_loo of quantities shared by all polls: .mean, .variance, .sd [polls, columns], .ess [polls] = 1 / sum w^2, .pareto_k ([polls]: the k
+    of the ratios; [polls, columns] with diag: the k of every mean; None without ratios) and .ms (potus_e_loo_timing)."""
+
+    def __init__(self, mean, var, ess, khat, ms):
+        self.mean, self.variance, self.ess, self.pareto_k, self.ms = mean, var, ess, khat, ms
+        self.sd = np.sqrt(np.maximum(var, 0.0))     # (.variance itself is not clamped: see e_loo_shared)
+
+
+def e_loo_shared(block_x, block_log_weights, block_ratios=None, r_eff=None, diag=False):
+    """potus_e_loo_shared_device: mean and variance of every column of block_x [columns, chains, draws] under every poll's normalised log
+    weights block_log_weights [polls, chains, draws] (what potus_psis_device writes; plain PSIS weights, not moment-matched ones), as tiled
+    products on the fp64 matrix cores.  block_ratios (the raw log ratios, same shape as the weights) and r_eff give the Pareto k.
+    The product is centred per column on the column's equal-weight mean c: variance = sum w (x - c)^2 - (sum w (x - c))^2, so its absolute
+    error is about eps * (variance + shift^2), shift = the leave-one-out mean minus c.  Where one draw carries nearly all the weight (a high
+    k: the estimate is unusable anyway) the true variance is near 0 and the result is rounding noise of that size, possibly slightly negative;
+    .variance is returned as computed, .sd clamps at 0.  e_loo (the pointwise form) has the exactly centred second pass."""
+    _device_block(block_x, "e_loo_shared", ("columns", "chains", "draws"))
+    _device_block(block_log_weights, "e_loo_shared", ("polls", "chains", "draws"))
+    if tuple(block_x.shape[1:]) != tuple(block_log_weights.shape[1:]):
+        raise ValueError(f"e_loo_shared: the columns hold {tuple(block_x.shape[1:])} chains x draws, the weights {tuple(block_log_weights.shape[1:])}")
+    if block_ratios is not None:
+        _device_block(block_ratios, "e_loo_shared", ("polls", "chains", "draws"))
+        if tuple(block_ratios.shape) != tuple(block_log_weights.shape):
+            raise ValueError(f"e_loo_shared: the log ratios are {tuple(block_ratios.shape)}, the weights {tuple(block_log_weights.shape)}")
+    elif diag:
+        raise ValueError("e_loo_shared: diag needs the raw log ratios")
+    L = load_library()
+    nc, ch, nd = (int(v) for v in block_x.shape)
+    N = int(block_log_weights.shape[0])
+    mean, var, ess = np.zeros((N, nc)), np.zeros((N, nc)), np.zeros(N)
+    kh = None if block_ratios is None else (np.zeros((N, nc)) if diag else np.zeros(N))
+    re = None if r_eff is None else np.ascontiguousarray(r_eff, dtype=np.float64).reshape(N)
+    _check(L, L.potus_e_loo_shared_device(int(block_x.device.index or 0), C.c_void_p(block_x.data_ptr()), nc, C.c_void_p(block_log_weights.data_ptr()), N, ch, nd,
+                                          None if block_ratios is None else C.c_void_p(block_ratios.data_ptr()), None if re is None else _dp(re),
+                                          int(bool(diag)), _dp(mean), _dp(var), _dp(ess), None if kh is None else _dp(kh)))
+    ms = np.zeros(4)
+    _check(L, L.potus_e_loo_timing(_dp(ms)))
+    return ELooShared(mean, var, ess, kh, ms)
+
+
+def psis_weights(block_ratios, r_eff):
+    """potus_psis_device: (normalised log weights as a torch tensor of the block's shape and device, k-hat [polls]) of raw log ratios."""
+    import torch
+    _device_block(block_ratios, "psis_weights", ("polls", "chains", "draws"))
+    L = load_library()
+    N, ch, nd = (int(v) for v in block_ratios.shape)
+    lw, k = torch.empty_like(block_ratios), np.zeros(N)
+    re = np.ascontiguousarray(r_eff, dtype=np.float64).reshape(N)
+    _check(L, L.potus_psis_device(int(block_ratios.device.index or 0), C.c_void_p(block_ratios.data_ptr()), N, ch, nd, _dp(re), C.c_void_p(lw.data_ptr()), _dp(k)))
+    return lw, k
+
+
+class Influence:
+    """What every poll does to the forecast: .delta [N, 2 S + 3] = the leave-one-out expectation of each column minus its posterior mean,
+    .loo_mean, .sd (leave-one-out) [N, 2 S + 3], .post_mean [2 S + 3], .columns (names: score_s, national, win_s, ec_win, ev), .pareto_k [N]
+    (potus_loo's), .khat [N, 2 S + 3] (the k of every mean; None without diag), .ess [N], .n_draws, .ms (potus_e_loo_timing of the product).
+    With days: .days = (begin, end), .delta_days, .loo_mean_days [N, days, S + 1] and .post_mean_days [days, S + 1] (scores, national)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def k_threshold(self):
+        return min(1.0 - 1.0 / np.log10(self.n_draws), 0.7)
+
+    def top(self, column, n=10):
+        """The n polls with the largest |delta| of `column` (a name or an index) among those whose Pareto k is at most the threshold:
+        a list of (poll, delta, pareto_k)."""
+        c = self.columns.index(column) if isinstance(column, str) else int(column)
+        ok = np.flatnonzero(self.pareto_k <= self.k_threshold())
+        order = ok[np.argsort(-np.abs(self.delta[ok, c]), kind="stable")][:n]
+        return [(int(i), float(self.delta[i, c]), float(self.pareto_k[i])) for i in order]
+
+
+def influence_columns(scores, state_weights, ev, ev_to_win=270):
+    """The 2 S + 3 forecast columns of one day from scores [draws, S] (torch): the S state scores, the national vote (normalised
+    state_weights . scores), the S indicators score > 0.5, electoral college won (sum ev won >= ev_to_win), electoral votes: [2 S + 3, draws]."""
+    import torch
+    w = torch.as_tensor(np.asarray(state_weights, dtype=np.float64) / np.sum(state_weights), device=scores.device)
+    e = torch.as_tensor(np.asarray(ev, dtype=np.float64), device=scores.device)
+    won = (scores > 0.5).to(torch.float64)
+    evs = won @ e
+    return torch.cat([scores.T, (scores @ w)[None], won.T, (evs >= ev_to_win).to(torch.float64)[None], evs[None]]).contiguous()
+
+
+POOL_BLOCK_BUDGET = 256 << 20     # bytes of the pooled per-poll blocks (log-likelihoods, ratios, weights, shares) alive at a time
+
+
+def _pooled_ratio_blocks(hs, integrate, blocks_alive=3, shares=False):
+    """The polls of a fit in blocks whose pooled [polls, chains, draws] tensors stay within POOL_BLOCK_BUDGET, as potus_loo blocks them: yields
+    (b0, b1, r, pointwise, a1, a2) with r = -log_lik of polls [b0, b1) over the chains of every handle (those of other GPUs brought to the
+    first handle's by torch), pointwise = potus_loo_device's rows of the block (k-hat, r_eff), and with shares potus_poll_share_device's blocks.
+    A handle with data sets, or with fewer than four post-warm-up draws per chain, is refused by the library before any kernel runs."""
+    import torch
+    h0 = hs[0]
+    N = h0.n_polls
+    dev0 = torch.device(f"cuda:{h0.opts.device}")
+    if len({id(h) for h in hs}) != len(hs):
+        raise ValueError("a handle is listed twice")
+    nd = h0.post_warmup_saved()
+    if any(h.n_polls != N or h.post_warmup_saved() != nd for h in hs):
+        raise ValueError("the handles do not hold the same polls and the same number of post-warm-up draws")
+    if nd < 4:
+        raise ValueError(f"{nd} post-warm-up draws per chain (at least 4)")
+    per_poll = 8 * nd * sum(h.opts.chains for h in hs) * (blocks_alive + (2 if shares else 0))
+    nb = max(1, min(N, POOL_BLOCK_BUDGET // max(per_poll, 1)))
+    for b0 in range(0, N, nb):
+        b1 = min(b0 + nb, N)
+        lls, s1, s2 = [], [], []
+        for h in hs:
+            ll = torch.empty((b1 - b0, h.opts.chains, nd), dtype=torch.float64, device=f"cuda:{h.opts.device}")
+            lls.append(h.log_lik_device(b0, b1, ll, integrate=integrate).to(dev0))
+            if shares:
+                a1, a2 = h.poll_share_device(b0, b1, integrate=integrate)
+                s1.append(a1.to(dev0))
+                s2.append(a2.to(dev0))
+        ll = torch.cat(lls, dim=1).contiguous()
+        del lls
+        pw = loo_of_block(ll).pointwise
+        yield b0, b1, (-ll).contiguous(), pw, (torch.cat(s1, dim=1).contiguous() if shares else None), (torch.cat(s2, dim=1).contiguous() if shares else None)
+
+
+def influence(handles, ev, day=-1, days=None, ev_to_win=270, integrate=True, diag=True):
+    """Which polls move the forecast (potus_e_loo, what = influence): for every poll the leave-one-out expectation of the forecast of one day
+    (default: election day) minus its posterior mean, from one fit: log-likelihood -> potus_loo's k-hat and r_eff -> PSIS weights -> the
+    product on the matrix cores, on the pooled post-warm-up draws of the handles (one posterior; blocks of other GPUs are brought to the first
+    handle's), the polls in blocks whose temporaries stay within 256 MB.  days = (begin, end) adds the score and national columns of every
+    day of the range.  The weights are the plain PSIS weights of `loo`, not moment-matched ones: read .pareto_k first.  Handles of one
+    workgroup per chain with the diagonal metric; handles with data sets and fewer than four post-warm-up draws are refused by the library."""
+    hs, ids = _handle_ids(handles)
+    h0 = hs[0]
+    L = h0.L
+    S, T, N = int(h0.data["S"]), int(h0.data["T"]), h0.n_polls
+    t = T - 1 if day in (-1, None) else int(day)
+    if not 0 <= t < T:
+        raise ValueError(f"influence: day {day} of {T}")
+    NC = 2 * S + 3
+    evv = np.ascontiguousarray(ev, dtype=np.float64).reshape(S)
+    mean, var, post, k, ess = np.zeros((N, NC)), np.zeros((N, NC)), np.zeros(NC), np.zeros(N), np.zeros(N)
+    kh = np.zeros((N, NC)) if diag else None
+    d0, d1 = (0, 0) if days is None else (int(days[0]), int(days[1]))
+    nday = max(d1 - d0, 0)
+    dm, dp_ = (np.zeros((N, nday, S + 1)), np.zeros((nday, S + 1))) if nday else (None, None)
+    _check(L, L.potus_e_loo(ids, len(hs), int(bool(integrate)), _abi.ELOO_INFLUENCE, _dp(evv), int(ev_to_win), t, d0, d1, int(bool(diag)), _dp(mean), _dp(var),
+                            _dp(post), _dp(k), _dp(ess), None if kh is None else _dp(kh), None if dm is None else _dp(dm), None if dp_ is None else _dp(dp_)))
+    ms = np.zeros(4)
+    _check(L, L.potus_e_loo_timing(_dp(ms)))
+    out = Influence(delta=mean - post[None], loo_mean=mean, variance=var, sd=np.sqrt(np.maximum(var, 0.0)), post_mean=post, pareto_k=k, khat=kh, ess=ess,
+                    n_draws=h0.post_warmup_saved() * sum(h.opts.chains for h in hs), day=t, ms=ms,
+                    columns=[f"score_{s}" for s in range(S)] + ["national"] + [f"win_{s}" for s in range(S)] + ["ec_win", "ev"])
+    if nday:
+        out.days, out.loo_mean_days, out.post_mean_days, out.delta_days = (d0, d1), dm, dp_, dm - dp_[None]
+    return out
+
+
+class Predict:
+    """What the model expected of each poll before it saw it: .mean, .sd of the leave-one-out predictive distribution of the observed share
+    y / n, .pareto_k (of the mean of a1), .in_sample_mean (equal weights), .share = y / n, .residual = share - mean, .z = residual / sd."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def by_pollster(self):
+        """(mean z, count) per pollster index [P] (state and national polls together; NaN for a pollster without polls)."""
+        P = int(max(self.pollster.max(), 0)) + 1
+        cnt = np.bincount(self.pollster, minlength=P)
+        tot = np.bincount(self.pollster, weights=self.z, minlength=P)
+        with np.errstate(invalid="ignore", divide="ignore"):
+            return tot / cnt, cnt
+
+
+def predict(handles, integrate=True):
+    """For every poll the leave-one-out predictive mean and sd of its observed share y / n (potus_e_loo, what = predict): k_el_poll_share
+    gives a1 = E_z[p] and a2 = E_z[p^2] per draw, the pointwise form their expectations under the poll's PSIS weights; mean = E[a1],
+    variance = E[a1] / n + (1 - 1 / n) E[a2] - E[a1]^2.  Pooled as `influence` pools.  Plain PSIS weights, not moment-matched ones."""
+    hs, ids = _handle_ids(handles)
+    h0 = hs[0]
+    y, n = (a.astype(np.float64) for a in poll_vectors(h0.data))
+    N = h0.n_polls
+    o, k = np.zeros((N, 5)), np.zeros(N)
+    _check(h0.L, h0.L.potus_e_loo(ids, len(hs), int(bool(integrate)), _abi.ELOO_PREDICT, None, 0, -1, 0, 0, 0, _dp(o), None, None, _dp(k), None, None, None, None))
+    share = y / n
+    d = h0.data
+    pollster = np.concatenate([np.asarray(d["poll_state"]), np.asarray(d["poll_national"])]).astype(np.int64) - 1
+    return Predict(mean=o[:, 0], variance=o[:, 1], sd=o[:, 2], pareto_k=o[:, 3], in_sample_mean=o[:, 4], k_ratios=k, share=share,
+                   residual=share - o[:, 0], z=(share - o[:, 0]) / o[:, 2], pollster=pollster, n=n, y=y)
 
 
 def loo_compare(*loos):

@@ -111,6 +111,16 @@ def load_library():
         L.potus_psis_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_longlong, dp, C.c_void_p, dp]
         L.potus_R_loo_moment_match.argtypes = [ip, ip, ip, ip, dp, ip, dp, dp, ip, ip]
         L.potus_R_loo_moment_match.restype = None
+    if hasattr(L, "potus_e_loo_device"):                # E_loo (loo.e_loo, loo.e_loo_shared)
+        L.potus_e_loo_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_int, C.c_int, C.c_longlong, dp, dp, C.c_int, dp, dp]
+        L.potus_e_loo_shared_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, C.c_longlong, C.c_void_p, dp, C.c_int, dp, dp, dp, dp]
+        L.potus_e_loo_timing.argtypes = [dp]
+        L.potus_poll_share_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p, C.c_void_p]
+        L.potus_e_loo.argtypes = [ip, C.c_int, C.c_int, C.c_int, dp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, dp, dp, dp, dp, dp, dp, dp, dp]
+        L.potus_R_loo_influence.argtypes = [ip, ip, ip, dp, dp, dp, dp, dp, dp, dp, ip]
+        L.potus_R_loo_influence.restype = None
+        L.potus_R_loo_predict.argtypes = [ip, ip, ip, dp, dp, ip]
+        L.potus_R_loo_predict.restype = None
     if hasattr(L, "potus_outcomes"):                    # joint election outcomes (outcomes.py)
         i32p, llp = C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
         L.potus_outcomes.argtypes = [ip, C.c_int, C.c_int, C.c_int, i32p, C.c_int, dp, llp, llp, llp, llp, llp]
@@ -196,6 +206,7 @@ EXPORTS = [
     "potus_log_lik_device", "potus_loo_device", "potus_loo",
     "potus_default_loo_mm_opts", "potus_loo_moment_match", "potus_loo_mm_timing", "potus_loo_mm_ratios_device", "potus_loo_mm_moments_device",
     "potus_psis_device", "potus_R_loo_moment_match",
+    "potus_e_loo_device", "potus_e_loo_shared_device", "potus_e_loo_timing", "potus_poll_share_device", "potus_e_loo", "potus_R_loo_influence", "potus_R_loo_predict",
     "potus_cv_log_lik_device", "potus_cv_lpd", "potus_cv_timing",
     "potus_default_optimize_opts", "potus_optimize", "potus_optimize_timing",
     "potus_default_laplace_opts", "potus_laplace", "potus_laplace_write_array_device", "potus_laplace_scores_device", "potus_laplace_summary",
@@ -891,6 +902,27 @@ class Handle:
         """loo.moment_match on this handle's draws: the Loo with the rows of the polls above the k-hat threshold moment-matched."""
         from .loo import moment_match
         return moment_match(self, loo, polls=polls, model_handle=model_handle, **opts)
+
+    def poll_share_device(self, poll_begin, poll_end, integrate=True):
+        """potus_poll_share_device: (a1, a2) = E_z[p], E_z[p^2] of the polls at the post-warm-up draws, two torch tensors [polls, chains,
+        draws] on this handle's GPU; p = inv_logit(eta + sigma z), z the draw's own noise coordinate or (integrate) integrated out."""
+        import torch
+        shape = (int(poll_end) - int(poll_begin), self.opts.chains, self.post_warmup_saved())
+        a1 = torch.empty(shape, dtype=torch.float64, device=f"cuda:{self.opts.device}")
+        a2 = torch.empty_like(a1)
+        torch.cuda.current_stream(a1.device).synchronize()
+        _check(self.L, self.L.potus_poll_share_device(self.h, int(poll_begin), int(poll_end), int(bool(integrate)), C.c_void_p(a1.data_ptr()), C.c_void_p(a2.data_ptr())))
+        return a1, a2
+
+    def loo_predict(self, **kw):
+        """loo.predict on this handle's draws: the leave-one-out predictive mean and sd of every poll's share (plain PSIS weights)."""
+        from .loo import predict
+        return predict(self, **kw)
+
+    def loo_influence(self, ev, **kw):
+        """loo.influence on this handle's draws: what leaving each poll out does to the forecast (plain PSIS weights)."""
+        from .loo import influence
+        return influence(self, ev, **kw)
 
     def _cv_masks(self, held_state, held_national):
         """The two masks as contiguous int32 [n_datasets, polls] arrays (None where the data have no such polls)."""
