@@ -47,6 +47,11 @@ int potus_dense_pool_matvec_probe(int device, int chains, int D, int nrhs, const
                                   double *ms, long long *pass_bytes);
 int potus_dense_pool_factor_probe(int device, int chains, int D, int n, const double *draws_host, const double *u_host, double *Minv_host, double *L_host,
                                   double *p_host, double *ms);
+/* The environment variable POTUS_PROBE_F32=1 runs all four probes with potus_opts.metric_storage = f32, on caller data as on generated matrices.
+ * Per chain: potus_dense_matvec_probe rounds Minv_host to fp32 on the way in -- element (i, j), j > i, becomes the float in the free half of row i
+ * (dn_f32_row), the diagonal vector the rounded values as doubles, the caller's lower triangle stays there as doubles -- and runs k_dn_symv<NRHS, true>;
+ * potus_dense_factor_probe takes the fp32 branch of k_dn_cov and returns Minv_host from those floats as they are AFTER the factorisation.  Pooled: the
+ * matrix is rounded into DnParams::A32.  The product and the factor are those of the rounded matrix, in fp64. */
 /* The per-poll scalar arithmetic, without a sampler (tests/test_gpu_poll_terms.py).  potus_poll_ll_probe: out[i] = loo_poll_ll(y[i], n[i],
  * eta[i], sigma[i], z[i], integrate) -- the log-likelihood term of k_loo_loglik / k_cv_loglik without log C(n, y) -- one thread per item and
  * nothing else.  potus_binomial_draw_probe: out[item][draw] = binomial_logit_draw(n[item], eta[item]) of k_simulate_prior with the Philox key

@@ -130,17 +130,20 @@ def test_draws_with_the_callers_u(small, variant, jacobian):
     check_draws(s["h"], oref.small_reference(variant, bool(jacobian))["q"], s["res"][jacobian], s["u"][0], f"{variant} jacobian={jacobian}")
 
 
-@pytest.mark.parametrize("shape", ["tiny", "mid"])
+@pytest.mark.parametrize("shape", ["tiny", "mid", "panel", "panel_and_a_row"])
 def test_draws_on_other_block_counts(shape):
-    """Tiny: D = 78, two blocks of 64, one ragged.  Mid: D = 598, ten blocks, three panels of the factorisation.  Draw counts 1, 17 and 65."""
-    kw = dict(tiny=dict(S=3, T=8, N_state=20, N_national=8, P=4), mid=dict(S=9, T=40, N_state=120, N_national=40, P=12))[shape]
+    """Tiny: D = 78, two blocks of 64, one ragged.  Mid: D = 598, ten blocks, three panels of the factorisation.  Draw counts 1, 17 and 65.
+    Panel: D = 256 exactly, one full panel of four blocks and no ragged one.  Panel and a row: D = 257, the one-row block is the first that
+    k_lap_solve_diag solves.  Their draw counts are 63, 64, 65 and 128: a workgroup of k_lap_solve_update owns 64 draws."""
+    kw = dict(tiny=dict(S=3, T=8, N_state=20, N_national=8, P=4), mid=dict(S=9, T=40, N_state=120, N_national=40, P=12),
+              panel=dict(S=5, T=20, N_state=90, N_national=22, P=6), panel_and_a_row=dict(S=5, T=20, N_state=91, N_national=22, P=6))[shape]
     data = synthetic.make(**kw)
     h = Handle(data, "full", chains=1, **OPTS)
-    assert h.D == dict(tiny=78, mid=598)[shape]
+    assert h.D == dict(tiny=78, mid=598, panel=256, panel_and_a_row=257)[shape]
     opt = h.optimize(np.zeros((1, h.D)), jacobian=1, tol_obj=0.0, tol_rel_obj=0.0, tol_grad=1e-4, tol_rel_grad=0.0, tol_param=0.0, iter=5000)
     assert opt["return_code"][0] == 3
     mode = opt["q"][0]
-    for n in (1, 17, 65):
+    for n in ((63, 64, 65, 128) if shape.startswith("panel") else (1, 17, 65)):
         u = np.random.default_rng(n).standard_normal((n, h.D))
         res = h.laplace(mode, n, u=u, precision=True)
         assert res["return_code"][0] == 0

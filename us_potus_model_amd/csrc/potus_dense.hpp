@@ -211,12 +211,13 @@ __global__ __launch_bounds__(DN_THREADS) void k_dn_symv(const DnParams P, const 
 #pragma unroll
           for (int e = 0; e < NE; e++) { xc[u][e][r] = xs[r * DN_CT + NE * (lane + 64 * u) + e]; t_acc[u][e][r] = 0.0; }
       }
-      // The tile overlaps the block's own rows (only j > i counts) or the matrix's right edge (fp32 storage: beyond column D a row's
-      // float half runs into the next row's doubles, whose halves may read as NaN): elements are masked one by one.  Every other tile
-      // -- 79 of 81 per row block at D = 41 610 -- takes the loop without the two compares and the select per element (
-      // same products in the same order: same bytes).
+      // The tile overlaps the block's own rows (only j > i counts) or the matrix's right edge (beyond column LD a row runs into the next
+      // row's doubles -- the factor's, which are not the metric's and need not even be finite; fp32 storage: a row's float half does so
+      // from column D on, and their halves may read as NaN): elements are masked one by one, selected and not multiplied by a zero of x.
+      // Every other tile -- 79 of 81 per row block at D = 41 610 -- takes the loop without the two compares and the select per element
+      // (same products in the same order: same bytes).
       const bool band = c0 < r0 + RB;
-      const bool masked = band || (F32 && c0 + DN_CT > D);
+      const bool masked = band || c0 + DN_CT > D;
       auto rows = [&](auto masked_c) {
         constexpr bool MASKED = decltype(masked_c)::value;
         // one group of GR rows: the loads ...
@@ -245,7 +246,7 @@ __global__ __launch_bounds__(DN_THREADS) void k_dn_symv(const DnParams P, const 
                 // (through a scalar: __builtin_bit_cast applied to a vector ELEMENT reads element 0 whatever the index, hipcc 7.2)
                 if constexpr (F32) { const unsigned wv = buf[k][u][e]; av = (double)__uint_as_float(wv); }
                 else av = __hiloint2double((int)buf[k][u][2 * e + 1], (int)buf[k][u][2 * e]);   // (constexpr: the other branch would index past the vector)
-                const double ae = (!MASKED || (col > lim && (!F32 || col < D))) ? av : 0.0;
+                const double ae = (!MASKED || (col > lim && col < D)) ? av : 0.0;
 #pragma unroll
                 for (int r = 0; r < NRHS; r++) { sp[r] += ae * xc[u][e][r]; t_acc[u][e][r] += ae * xrow[r]; }
               }

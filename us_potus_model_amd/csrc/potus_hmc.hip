@@ -6116,8 +6116,8 @@ struct DenseProbe {   // a DnParams with every chain active, owned buffers
     const size_t mat = (size_t)(pooled ? 1 : chains) * D * P.LD * 8;
     HIP_TRY(bufs.alloc(&P.state, (size_t)chains * DV_COUNT * P.LD * 8)); HIP_TRY(bufs.alloc(&P.A, mat)); HIP_TRY(bufs.alloc(&P.dg, (size_t)chains * P.LD * 8));
     P.pool_split = 1; P.pool_rows = D;
-    // development: POTUS_PROBE_F32 = 1 -- the pooled pieces with metric_storage = f32 (the per-chain pass reads the variable itself, below)
-    P.f32 = pooled && getenv("POTUS_PROBE_F32") && atoi(getenv("POTUS_PROBE_F32")) ? 1 : 0;
+    // development: POTUS_PROBE_F32 = 1 -- every piece with metric_storage = f32 (per chain: the floats in the rows' free halves, dn_f32_row; pooled: A32)
+    P.f32 = getenv("POTUS_PROBE_F32") && atoi(getenv("POTUS_PROBE_F32")) ? 1 : 0;
     if (pooled) {   // (as dense_alloc)
       const int panels = (D + DNP_COLS_OF(P.f32) - 1) / DNP_COLS_OF(P.f32);
       int s = std::max(1, std::min(DNP_SPLIT_MAX, (2 * 256) / panels));   // at most two workgroups per compute unit, all resident at once (measured: profiles/r06_dense_pooled.txt)
@@ -6140,6 +6140,8 @@ struct DenseProbe {   // a DnParams with every chain active, owned buffers
     HIP_TRY(hipMemset(P.fail, 0, 4));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dn_symv<1>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DN_SYMV_LDS(1)));
     HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dn_symv<2>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DN_SYMV_LDS(2)));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dn_symv<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DN_SYMV_LDS(1)));
+    HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dn_symv<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DN_SYMV_LDS(2)));
     return 0;
   }
   int set_rounds(const std::vector<DnRound> &r) { HIP_TRY(hipMemcpy(P.rd, r.data(), r.size() * sizeof(DnRound), hipMemcpyHostToDevice)); return 0; }
@@ -6150,7 +6152,8 @@ struct DenseProbe {   // a DnParams with every chain active, owned buffers
 // upper triangle and the diagonal).  Minv_host == NULL: the matrices are generated on the device (k_dn_fill) -- for rates
 // at sizes whose matrices would take seconds to upload.  Runs the product `reps` times; x_host / y_host are
 // [chains][nrhs][D]; dot_host [chains] receives x_0 . M^-1 x_0; *ms the average time of a pass (HIP events); *pass_bytes
-// the bytes of matrix one pass loads per chain.
+// the bytes of matrix one pass loads per chain.  POTUS_PROBE_F32 = 1: metric_storage = f32 -- the caller's matrix is rounded to fp32 on the way in
+// (upper triangle as floats in the rows' free halves, the diagonal vector as doubles) and k_dn_symv<NRHS, true> runs.
 static int dense_matvec_probe_impl(bool pooled, int device, int chains, int D, int nrhs, const double *Minv_host, const double *x_host, double *y_host, double *dot_host, int reps,
                                    double *ms, long long *pass_bytes) {
   if (chains < 1 || D < 1 || nrhs < 1 || nrhs > 3 || !x_host || !y_host || reps < 1) return fail(POTUS_ERR_ARG, "potus_dense_matvec_probe: bad arguments");
@@ -6164,19 +6167,28 @@ static int dense_matvec_probe_impl(bool pooled, int device, int chains, int D, i
       if (P.f32) hipLaunchKernelGGL(k_dn_pool_round32, dim3(4096), dim3(256), 0, 0, P);
     } else hipLaunchKernelGGL(k_dn_pool_fill, dim3(4096), dim3(256), 0, 0, P);
   } else if (Minv_host) {
-    HIP_TRY(hipMemcpy2D(P.A, (size_t)P.LD * 8, Minv_host, (size_t)D * 8, (size_t)D * 8, (size_t)chains * D, hipMemcpyHostToDevice));   // the lower half is ignored
     std::vector<double> dg((size_t)chains * P.LD, 0.0);
-    for (int c = 0; c < chains; c++) for (int i = 0; i < D; i++) dg[(size_t)c * P.LD + i] = Minv_host[((size_t)c * D + i) * D + i];
-    HIP_TRY(hipMemcpy(P.dg, dg.data(), dg.size() * 8, hipMemcpyHostToDevice));
-  } else {
-    // development: POTUS_PROBE_F32 = 1 times the pass over fp32 storage (generated matrices only)
-    if (getenv("POTUS_PROBE_F32") && atoi(getenv("POTUS_PROBE_F32"))) {
-      P.f32 = 1;
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dn_symv<1, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DN_SYMV_LDS(1)));
-      HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dn_symv<2, true>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)DN_SYMV_LDS(2)));
+    if (P.f32) {
+      // fp32 storage as the sampler keeps it: row i holds the caller's lower triangle as doubles [0, i] (not the metric's: the factor's place) and
+      // element (i, j), j > i, rounded to fp32 in its free half (dn_f32_row); the diagonal vector holds the rounded values as doubles
+      std::vector<double> rows((size_t)D * P.LD);
+      for (int c = 0; c < chains; c++) {
+        std::fill(rows.begin(), rows.end(), 0.0);
+        const double *Mc = Minv_host + (size_t)c * D * D;
+        for (int i = 0; i < D; i++) {
+          for (int j = 0; j <= i; j++) rows[(size_t)i * P.LD + j] = Mc[(size_t)i * D + j];
+          float *f = dn_f32_row(rows.data(), P.LD, i);
+          for (int j = i + 1; j < D; j++) f[j] = (float)Mc[(size_t)i * D + j];
+          dg[(size_t)c * P.LD + i] = (double)(float)Mc[(size_t)i * D + i];
+        }
+        HIP_TRY(hipMemcpy(P.A + (size_t)c * D * P.LD, rows.data(), rows.size() * 8, hipMemcpyHostToDevice));
+      }
+    } else {
+      HIP_TRY(hipMemcpy2D(P.A, (size_t)P.LD * 8, Minv_host, (size_t)D * 8, (size_t)D * 8, (size_t)chains * D, hipMemcpyHostToDevice));   // the lower half is ignored
+      for (int c = 0; c < chains; c++) for (int i = 0; i < D; i++) dg[(size_t)c * P.LD + i] = Minv_host[((size_t)c * D + i) * D + i];
     }
-    hipLaunchKernelGGL(k_dn_fill, dim3(4096), dim3(256), 0, 0, P);
-  }
+    HIP_TRY(hipMemcpy(P.dg, dg.data(), dg.size() * 8, hipMemcpyHostToDevice));
+  } else hipLaunchKernelGGL(k_dn_fill, dim3(4096), dim3(256), 0, 0, P);   // (POTUS_PROBE_F32 = 1: the floats of the generated matrix)
   std::vector<DnRound> rds(chains);
   // development: a launch with idle companions (POTUS_PROBE_ACTIVE = n: the first n chains take part; or a list "2,7,11")
   std::vector<int> act_flag(chains, 1);
@@ -6240,6 +6252,7 @@ int potus_dense_pool_matvec_probe(int device, int chains, int D, int nrhs, const
 // Cholesky factor (in place, in the lower triangle of the same matrix), and p = L^-T u for u [chains][D] (the momentum
 // draw's triangular solve).  Outputs [chains][D][D] (M^-1 rebuilt from the upper triangle and the diagonal vector; L the
 // lower triangle, zeros above) / [chains][D]; ms[3] = covariance, factorisation, solve (milliseconds).
+// POTUS_PROBE_F32 = 1: metric_storage = f32 -- M^-1 comes back from the floats in the rows' free halves (dn_f32_row), read AFTER the factorisation.
 static int dense_factor_probe_impl(bool pooled, int device, int chains, int D, int n, const double *draws_host, const double *u_host, double *Minv_host, double *L_host,
                                    double *p_host, double *ms) {
   if (chains < 1 || D < 1 || n < 2 || !draws_host) return fail(POTUS_ERR_ARG, "potus_dense_factor_probe: bad arguments");
@@ -6283,15 +6296,18 @@ static int dense_factor_probe_impl(bool pooled, int device, int chains, int D, i
   HIP_TRY(hipMemcpy(&failed, P.fail, 4, hipMemcpyDeviceToHost));
   if (failed) return fail(POTUS_ERR_STATE, "covariance not positive definite");
   if (Minv_host || L_host) {
-    std::vector<double> buf((size_t)D * D), dg(D), lbuf;
+    std::vector<double> buf((size_t)D * D), dg(D), lbuf, rows;
+    const bool halves = !pooled && P.f32;               // per chain with fp32 storage: the metric above the diagonal is the floats in the rows' free halves
     for (int c = 0; c < (pooled ? 1 : chains); c++) {   // (pooled: ONE matrix and ONE factor come back)
       HIP_TRY(hipMemcpy2D(buf.data(), (size_t)D * 8, dn_mat(P, c), (size_t)P.LD * 8, (size_t)D * 8, (size_t)D, hipMemcpyDeviceToHost));
+      if (halves) { rows.resize((size_t)D * P.LD); HIP_TRY(hipMemcpy(rows.data(), dn_mat(P, c), rows.size() * 8, hipMemcpyDeviceToHost)); }
+      auto upper = [&](size_t i, size_t j) { return halves ? (double)dn_f32_row(rows.data(), P.LD, (int)i)[j] : buf[i * D + j]; };   // i < j
       HIP_TRY(hipMemcpy(dg.data(), dn_diag(P, c), (size_t)D * 8, hipMemcpyDeviceToHost));
       if (pooled) { lbuf.resize((size_t)D * D); HIP_TRY(hipMemcpy2D(lbuf.data(), (size_t)D * 8, P.Lf, (size_t)P.LD * 8, (size_t)D * 8, (size_t)D, hipMemcpyDeviceToHost)); }
       const std::vector<double> &lb = pooled ? lbuf : buf;
       for (size_t i = 0; i < (size_t)D; i++)
         for (size_t j = 0; j < (size_t)D; j++) {
-          if (Minv_host) Minv_host[((size_t)c * D + i) * D + j] = pooled ? buf[i * D + j] : (i == j ? dg[i] : (i < j ? buf[i * D + j] : buf[j * D + i]));
+          if (Minv_host) Minv_host[((size_t)c * D + i) * D + j] = pooled ? buf[i * D + j] : (i == j ? dg[i] : (i < j ? upper(i, j) : upper(j, i)));
           if (L_host) L_host[((size_t)c * D + i) * D + j] = j <= i ? lb[i * D + j] : 0.0;
         }
     }
