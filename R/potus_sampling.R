@@ -390,6 +390,39 @@ potus_loo_predict <- function(fit, integrate = TRUE) {
              pollster = c(fit$data$poll_state, fit$data$poll_national))
 }
 
+# Posterior predictive checks (DESIGN.md section 4s; us_potus_model_amd/ppc.py check is the same in Python): could the fitted model have
+# produced its polls?  Per poll the PIT and LOO-PIT sums lo = P(y_rep < y), eq = P(y_rep = y) (randomised PIT: lo + runif(N) * eq) with
+# potus_loo's pareto_k; per group of `by` the realised and replicated bias, dispersion and count with their posterior predictive p-values
+# (gt + eq / 2) / draws.  integrate = TRUE replicates a new poll of the same pollster, mode, population, state and day.  National polls get
+# state S + 1; the no-mode variant has no mode and no population.  Plain PSIS weights.  Like the rest of this file: not run under R here.
+potus_ppc <- function(fit, by = c("pollster", "mode", "population", "state"), integrate = TRUE, rep = 0L) {
+  d <- fit$data
+  N <- as.integer(d$N_state_polls) + as.integer(d$N_national_polls)
+  full <- !is.null(d$poll_mode_state)
+  if (!full) by <- setdiff(by, c("mode", "population"))
+  labels <- list(pollster = c(d$poll_state, d$poll_national), mode = c(d$poll_mode_state, d$poll_mode_national),
+                 population = c(d$poll_pop_state, d$poll_pop_national), state = c(d$state, rep.int(as.integer(d$S) + 1L, as.integer(d$N_national_polls))))
+  sizes <- c(pollster = as.integer(d$P), mode = as.integer(d$M), population = as.integer(d$Pop), state = as.integer(d$S) + 1L)
+  groups <- unlist(lapply(by, function(b) as.integer(labels[[b]]) - 1L))
+  ng <- as.integer(sizes[by])
+  tot <- sum(ng)
+  r <- .C("potus_R_ppc", as.integer(fit$handles), length(fit$handles), as.integer(c(isTRUE(integrate), rep, length(by))), as.integer(groups), ng,
+          pit = double(N * 4), pareto_k = double(N), group = double(tot * 18), n_in_group = double(tot), status = integer(1))
+  .potus_check(r$status)
+  pit <- matrix(r$pit, N, 4, byrow = TRUE, dimnames = list(NULL, c("lo", "eq", "loo_lo", "loo_eq")))
+  g <- aperm(array(r$group, c(6, 3, tot)), c(3, 2, 1))
+  dimnames(g) <- list(NULL, c("bias", "dispersion", "count"), c("T_obs", "T_rep", "gt", "eq", "lt", "p"))
+  tabs <- list()
+  o <- 0L
+  for (k in seq_along(by)) {
+    i <- o + seq_len(ng[k])
+    tabs[[by[k]]] <- data.frame(label = seq_len(ng[k]), n_polls = r$n_in_group[i], T_obs = g[i, , "T_obs"], T_rep = g[i, , "T_rep"],
+                                p_bias = g[i, "bias", "p"], p_dispersion = g[i, "dispersion", "p"], p_count = g[i, "count", "p"])
+    o <- o + ng[k]
+  }
+  list(pit = pit, pareto_k = r$pareto_k, groups = tabs)
+}
+
 # loo::loo_moment_match for the polls of `loo` (a potus_loo of this fit with the same `integrate`) whose Pareto k is above k_threshold
 # (0: min(1 - 1 / log10 S, 0.7)): potus_loo_moment_match (DESIGN.md section 4q; us_potus_model_amd/loo.py moment_match is the same in Python).
 # polls: poll numbers from 1 (state polls first, then national polls), or NULL for every poll.  model_handle: a handle of the fit's data that

@@ -702,6 +702,56 @@ int potus_e_loo(const int *handles, int n_handles, int integrate, int what, cons
                 double *out, double *var_out, double *post_out, double *pareto_k_out, double *ess_out, double *khat_out, double *days_out, double *days_post_out);
 int potus_e_loo_timing(double *ms /*[4]: pointwise form; column means and products; chunk sums and ess; diagnostic.  HIP events, calling thread's last call*/);
 
+/* ---- posterior predictive checks: could the fitted model have produced the polls it was fitted to? ----
+ * Polls are numbered as potus_loo numbers them: state polls in data order, then national polls.  For poll i (outcome y_i of n_i) and post-warm-up
+ * draw s (S of them over all chains): eta_is = the predictor without the poll's noise term, exactly as potus_log_lik_device forms it, sigma_i the
+ * poll's noise scale, z_is the draw's own noise coordinate.
+ *   replicate   integrate = 0: x = eta_is + sigma_i z_is (the same poll repeated);  integrate = 1: x = eta_is + sigma_i z', z' ~ N(0, 1) fresh (a new
+ *               poll of the same pollster, mode, population, state and day: the replicate that belongs with the integrated log-likelihood, since
+ *               under leave-one-out the poll's noise coordinate has its prior);  sigma_i = 0: as integrate = 0.
+ *               y_rep_is ~ Binomial(n_i, inv_logit(x)) by the prior simulator's exact sampler: inversion below n min(p, 1 - p) = 10, BTRS above.
+ *               n_i = 0: y_rep = 0, NaN PIT values, and the poll is in no group sum.
+ *   randomness  Philox4x32-10, purpose RNG_PPC = 11.  Key = the handle's seed; counter words
+ *                 c0 = poll number;  c1 = 11 | kind << 8 | attempt << 10 | rep << 22;  c2 = post-warm-up iteration (0-based);
+ *                 c3 = the chain's global id, chain_id_offset + c + 1
+ *               kind 1 = the fresh normal z' (attempt 0; the first normal of the Box-Muller pair of the block), kind 2 = u and kind 3 = v of the
+ *               sampler's attempt (< 4096, 12 bits); rep in [0, 1023], rep + 1 an independent second replicate.  A cell's y_rep depends on seed,
+ *               chain id, iteration, poll and rep, and on nothing else: not on the poll block, the grid, or how the chains are split over handles
+ *               or GPUs.
+ *   moments     a1, a2 = potus_poll_share_device's blocks with the same integrate;  m = n a1;  v = n a1 (1 - a1) + n (n - 1) max(a2 - a1^2, 0);
+ *               r(k) = (k - m) / sqrt(v) for v > 0, else 0.  Every operation is rounded on its own (no fused multiply-adds), evaluated as
+ *               ((n a1) (1 - a1)) + ((n (n - 1)) max(a2 - (a1 a1), 0)).
+ *   groups      for group g and draw s, over the group's polls with n > 0 in ascending poll number, added one after the other from 0:
+ *               bias B = sum r(.), dispersion X = sum r(.)^2, count N = sum (.), each at y_i (realised, T_obs) and at y_rep_is (replicated, T_rep).
+ *               Per (group, statistic) six numbers: mean_s T_obs, mean_s T_rep, the exact counts #{T_rep > T_obs}, #{=}, #{<} (whole numbers),
+ *               p = (gt + eq / 2) / S.  A group without polls: NaN, NaN, 0, 0, 0, NaN.
+ *   PIT         lo_i = sum_s w_is 1[y_rep_is < y_i], eq_i = sum_s w_is 1[y_rep_is = y_i], summed in a fixed order.  Without weights (w = 1 / S, the
+ *               posterior PIT) the exact counts divided by S; with log_weights w = exp(lw), lw = the normalised PSIS log weights potus_psis_device
+ *               gives for r = -log_lik_i with the same integrate (the LOO-PIT); a weight of -inf counts as 0, NaN weights give NaN.  The
+ *               randomised PIT lo + v eq, the non-randomised histogram (Czado, Gneiting, Held 2009) and the coverage are formed on the host.
+ * potus_poll_rep_device: the sibling of potus_log_lik_device / potus_poll_share_device (same polls, same eta): y_rep of polls [poll_begin, poll_end)
+ *   as doubles, device [polls][chains][n_post]: it feeds potus_e_loo_device unchanged.
+ * potus_ppc_pit_device: yrep (and log_weights, or NULL) device [n_polls][n_chains][n_draws], y host [n_polls]; out host [n_polls][2] = lo, eq.
+ * potus_ppc_groups_device: yrep, a1, a2 device [n_polls][n_chains][n_draws]; y, n, groups host [n_polls] (a label in [0, n_groups), or -1: in no
+ *   group).  acc_device [n_groups][3][2][n_chains][n_draws] (statistic, then realised / replicated) holds T per draw; flags: POTUS_PPC_BEGIN zeroes
+ *   it and n_in_group first, POTUS_PPC_FINISH writes group_out [n_groups][3][6] afterwards; between them the poll blocks of one fit are added in
+ *   ascending order, and the bytes do not depend on where the blocks are cut.  acc_device may be NULL when both flags are set.
+ *   n_in_group [n_groups] (host) counts the polls with n > 0 added so far.
+ * potus_ppc: the whole check on a fit's handles, pooled as potus_e_loo pools (and refusing what it refuses).  Per poll block: log-likelihood ->
+ *   potus_loo's k-hat and r_eff -> PSIS weights -> shares -> replicate -> PIT -> group accumulation.  groups [n_groupings][N] labels, n_groups
+ *   [n_groupings]; pit_out [N][4] = lo, eq, loo_lo, loo_eq; pareto_k_out [N] = potus_loo's pareto_k; group_out [sum n_groups][3][6];
+ *   n_in_group_out [sum n_groups].  n_groupings may be 0.  The poll blocks stay within 256 MB (POTUS_PPC_BLOCK_BUDGET, bytes, overrides it: tests).
+ * Refused before any kernel runs: handles with data sets (POTUS_ERR_STATE), fewer than four post-warm-up draws per chain, integrate not 0 or 1,
+ * rep outside [0, 1023], a label >= its n_groups or < -1, NULL outputs, blocks that are not memory of `device`. */
+enum { POTUS_PPC_BEGIN = 1, POTUS_PPC_FINISH = 2 };
+int potus_poll_rep_device(int handle, int poll_begin, int poll_end, int integrate, int rep, void *yrep_out_device);
+int potus_ppc_pit_device(int device, const void *yrep, const double *y, const void *log_weights, int n_polls, int n_chains, long long n_draws, double *out);
+int potus_ppc_groups_device(int device, const void *yrep, const void *a1, const void *a2, const double *y, const double *n, const int32_t *groups, int n_groups,
+                            int n_polls, int n_chains, long long n_draws, void *acc_device, int flags, double *group_out, long long *n_in_group);
+int potus_ppc(const int *handles, int n_handles, int integrate, int rep, const int32_t *groups, int n_groupings, const int32_t *n_groups, double *pit_out,
+              double *pareto_k_out, double *group_out, long long *n_in_group_out);
+int potus_ppc_timing(double *ms /*[4]: log-likelihood and PSIS; shares and replicate; PIT; groups.  HIP events, calling thread's last call*/);
+
 /* ---- joint election outcomes: what the run scripts compute from the JOINT outcome of a draw ----
  * final_2016.R:904-920 (final_2012.R, final_2008.R, README.Rmd "Final electoral college histogram") the distribution of Democratic electoral
  * votes; final_2012.R:809-839, final_2008.R:813-843 the tipping-point state; README.Rmd:481-502, :1638-1672 the p-value of the certified
@@ -827,6 +877,9 @@ void potus_R_loo_influence(int *handles, int *n_handles, int *iopts /*[4]: integ
                            double *loo_mean /*[N][2S+3]*/, double *var_out, double *post_out /*[2S+3]*/, double *pareto_k /*[N]*/, double *ess, double *khat,
                            int *status);
 void potus_R_loo_predict(int *handles, int *n_handles, int *integrate, double *out /*[N][5]*/, double *pareto_k /*[N]*/, int *status);
+/* potus_ppc; the counts of n_in_group as doubles */
+void potus_R_ppc(int *handles, int *n_handles, int *iopts /*[3]: integrate, rep, n_groupings*/, int *groups /*[n_groupings][N]*/, int *n_groups /*[n_groupings]*/,
+                 double *pit_out /*[N][4]*/, double *pareto_k /*[N]*/, double *group_out /*[sum n_groups][3][6]*/, double *n_in_group /*[sum n_groups]*/, int *status);
 void potus_R_loo_moment_match(int *model_handle, int *handles, int *n_handles, int *iopts /*[5]: integrate, max_iters, split, cov, n_polls (0: every poll)*/,
                               double *k_threshold, int *polls, double *pointwise /*[n_polls of the data][5], in and out*/, double *estimates_out,
                               int *info_out /*[n_polls of the data][6]*/, int *status);

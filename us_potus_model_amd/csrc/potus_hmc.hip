@@ -767,6 +767,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, c
 #include "potus_pathfinder.hpp" // Pathfinder: a normal around every iterate of an L-BFGS path, the best ELBO, draws
 #include "potus_advi.hpp"       // mean-field ADVI: stochastic-gradient tracks, the ELBO on a chip-wide grid, draws
 #include "potus_eloo.hpp"       // E_loo: expectations under the leave-one-out posteriors, pointwise and as a product on the matrix cores (included last: potus_loo_mm.hpp's reason)
+#include "potus_ppc.hpp"        // posterior predictive checks: replicated polls, PIT and LOO-PIT sums, group statistics (after potus_eloo.hpp: it adds kernels only)
 
 // ======================================================================== host
 namespace {
@@ -6530,6 +6531,341 @@ int potus_e_loo(const int *handles, int n_handles, int integrate, int what, cons
   return 0;
 }
 
+// ---------------------------------------------------------------------------------------------- posterior predictive checks (potus_ppc.hpp)
+namespace {
+constexpr size_t PPC_BLOCK_BUDGET = 256ull << 20;   // the pooled per-poll blocks of one round of potus_ppc (POTUS_PPC_BLOCK_BUDGET, bytes: tests)
+thread_local double g_ppc_ms[4] = {0.0, 0.0, 0.0, 0.0};   // the calling thread's last call: log-likelihood and PSIS, shares and replicate, PIT, groups
+
+// y_rep of polls [b0, b1) of the handle's post-warm-up draws -> out [n_post][chains][b1 - b0], on the handle's device and stream
+int ppc_rep(Sampler *sp, const LooRows &r, int first, int n_post, int b0, int b1, int integrate, int rep, double *out) {
+  PpcRepParams P{row_src(sp, first), sp->L.ncols, n_post, b0, b1, integrate, rep, sp->R.chain_id_offset, sp->R.seed_lo, sp->R.seed_hi, r.scratch, out};
+  hipLaunchKernelGGL(k_ppc_rep, dim3(r.grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, P);
+  HIP_TRY(hipGetLastError());
+  return 0;
+}
+
+// lo, eq of NP polls (blocks on the current device, whose lock the caller holds) -> out [NP] rows of `stride` doubles on the host; ms += the kernel's time
+int ppc_pit(hipStream_t st, const double *yrep, const double *y, const double *lw, int NP, long long S, double *out, int stride, double *ms, const char *what) {
+  DevBufs tmp;
+  double *dy = nullptr, *dout = nullptr;
+  int rc;
+  if ((rc = tmp.get(&dy, (size_t)NP * 8, what)) || (rc = tmp.get(&dout, (size_t)NP * 16, what))) return rc;
+  HIP_TRY(hipMemcpyAsync(dy, y, (size_t)NP * 8, hipMemcpyHostToDevice, st));
+  EventTimer t;
+  HIP_TRY(t.made);
+  HIP_TRY(t.start(st));
+  hipLaunchKernelGGL(k_ppc_pit, dim3(std::min(NP, 65535)), dim3(DG_THREADS), 0, st, yrep, (const double *)dy, lw, dout, S, NP);
+  if ((rc = el_span(t, st, ms, 2))) return rc;
+  std::vector<double> h((size_t)NP * 2);
+  HIP_TRY(hipMemcpy(h.data(), dout, h.size() * 8, hipMemcpyDeviceToHost));
+  for (int k = 0; k < NP; k++) { out[(size_t)k * stride] = h[2 * k]; out[(size_t)k * stride + 1] = h[2 * k + 1]; }
+  return 0;
+}
+
+// the polls of a block join their groups' sums: acc [G][3][2][S] on the current device, count [G] on the host (polls with n > 0 so far)
+int ppc_groups_add(hipStream_t st, const double *yrep, const double *a1, const double *a2, const double *y, const double *n, const int32_t *labels, int G, int NP, long long S,
+                   double *acc, long long *count, double *ms, const char *what) {
+  std::vector<int> goff(G + 1, 0), gpoll;
+  for (int k = 0; k < NP; k++) if (labels[k] >= 0 && n[k] > 0) goff[labels[k] + 1]++;
+  for (int g = 0; g < G; g++) { count[g] += goff[g + 1]; goff[g + 1] += goff[g]; }
+  gpoll.assign(std::max(goff[G], 1), 0);
+  {
+    std::vector<int> at(goff.begin(), goff.end() - 1);
+    for (int k = 0; k < NP; k++) if (labels[k] >= 0 && n[k] > 0) gpoll[at[labels[k]]++] = k;   // ascending poll number within a group
+  }
+  if (goff[G] == 0) return 0;
+  DevBufs tmp;
+  double *dy = nullptr, *dn = nullptr;
+  int *doff = nullptr, *dpoll = nullptr;
+  int rc;
+  if ((rc = tmp.get(&dy, (size_t)NP * 8, what)) || (rc = tmp.get(&dn, (size_t)NP * 8, what)) || (rc = tmp.get(&doff, goff.size() * 4, what)) ||
+      (rc = tmp.get(&dpoll, gpoll.size() * 4, what)))
+    return rc;
+  HIP_TRY(hipMemcpyAsync(dy, y, (size_t)NP * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dn, n, (size_t)NP * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(doff, goff.data(), goff.size() * 4, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dpoll, gpoll.data(), gpoll.size() * 4, hipMemcpyHostToDevice, st));
+  const PpcGroupParams P{yrep, a1, a2, dy, dn, doff, dpoll, acc, S, G};
+  EventTimer t;
+  HIP_TRY(t.made);
+  HIP_TRY(t.start(st));
+  hipLaunchKernelGGL(k_ppc_groups, dim3((unsigned)std::min<long long>(((long long)G * S + 255) / 256, 65535)), dim3(256), 0, st, P);
+  return el_span(t, st, ms, 3);
+}
+
+// out [G][3][6] on the host from acc
+int ppc_groups_finish(hipStream_t st, const double *acc, const long long *count, int G, long long S, double *out, double *ms, const char *what) {
+  DevBufs tmp;
+  long long *dc = nullptr;
+  double *dout = nullptr;
+  int rc;
+  if ((rc = tmp.get(&dc, (size_t)G * 8, what)) || (rc = tmp.get(&dout, (size_t)G * PPC_NSTAT * PPC_NOUT * 8, what))) return rc;
+  HIP_TRY(hipMemcpyAsync(dc, count, (size_t)G * 8, hipMemcpyHostToDevice, st));
+  EventTimer t;
+  HIP_TRY(t.made);
+  HIP_TRY(t.start(st));
+  hipLaunchKernelGGL(k_ppc_group_stats, dim3(std::min(G * PPC_NSTAT, 65535)), dim3(DG_THREADS), 0, st, acc, (const long long *)dc, dout, S, G);
+  if ((rc = el_span(t, st, ms, 3))) return rc;
+  HIP_TRY(hipMemcpy(out, dout, (size_t)G * PPC_NSTAT * PPC_NOUT * 8, hipMemcpyDeviceToHost));
+  return 0;
+}
+
+int ppc_check_labels(const char *what, const int32_t *labels, long long N, int G, int grouping) {
+  if (G < 1) return fail(POTUS_ERR_ARG, "%s: grouping %d has %d groups", what, grouping, G);
+  for (long long k = 0; k < N; k++)
+    if (labels[k] < -1 || labels[k] >= G) return fail(POTUS_ERR_ARG, "%s: poll %lld of grouping %d has label %d (-1: in no group, or 0 .. %d)", what, k, grouping, labels[k], G - 1);
+  return 0;
+}
+int ppc_check_modes(const char *what, int integrate, int rep) {
+  if (integrate != 0 && integrate != 1) return fail(POTUS_ERR_ARG, "%s: integrate = %d (0: the draw's noise coordinate, 1: a fresh one)", what, integrate);
+  if (rep < 0 || rep > PPC_MAX_REP) return fail(POTUS_ERR_ARG, "%s: rep = %d (0 .. %d)", what, rep, PPC_MAX_REP);
+  return 0;
+}
+} // namespace
+
+int potus_ppc_timing(double *ms) {
+  return timing_out("potus_ppc_timing", g_ppc_ms, 4, ms);
+}
+
+int potus_poll_rep_device(int handle, int poll_begin, int poll_end, int integrate, int rep, void *yrep_out_device) {
+  const char *what = "potus_poll_rep_device";
+  Sampler *sp = get(handle);
+  if (!sp || !yrep_out_device) return fail(POTUS_ERR_STATE, "bad handle or null output");
+  if (const int rc_ = refuse_many_datasets(sp, what)) return rc_;
+  if (const int rc_ = ppc_check_modes(what, integrate, rep)) return rc_;
+  const int Np = sp->M.Npoll;
+  if (poll_begin < 0 || poll_end > Np || poll_begin >= poll_end) return fail(POTUS_ERR_ARG, "%s: polls [%d, %d) of %d", what, poll_begin, poll_end, Np);
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, sp->device, yrep_out_device, "output")) return rc_;
+  int n_saved = 0, rc = saved_count(sp, &n_saved);
+  if (rc) return rc;
+  const int first = warm_rows(sp, n_saved), n_post = n_saved - first, C = sp->R.chains;
+  if (n_post < 1) return fail(POTUS_ERR_STATE, "%s: no post-warm-up draws saved (%d saved, %d of them warm-up)", what, n_saved, first);
+  std::fill(g_ppc_ms, g_ppc_ms + 4, 0.0);
+  DevBufs keep;
+  LooRows r;
+  if ((rc = loo_rows_setup(sp, (long long)n_post * C, keep, r, what))) return rc;
+  const int nb = loo_block_polls((size_t)n_post * C * 8, poll_end - poll_begin);
+  double *blk = nullptr, *out = (double *)yrep_out_device;
+  if ((rc = keep.get(&blk, (size_t)n_post * C * nb * 8, what))) return rc;
+  EventTimer t;
+  HIP_TRY(t.made);
+  for (int b0 = poll_begin; b0 < poll_end; b0 += nb) {
+    const int b1 = std::min(b0 + nb, poll_end);
+    HIP_TRY(t.start(sp->stream));
+    if ((rc = ppc_rep(sp, r, first, n_post, b0, b1, integrate, rep, blk))) return rc;
+    if ((rc = el_span(t, sp->stream, g_ppc_ms, 1))) return rc;
+    if ((rc = transpose_block(sp->stream, blk, out + (size_t)(b0 - poll_begin) * C * n_post, n_post, C, b1 - b0, C, 0))) return rc;
+  }
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  return 0;
+}
+
+int potus_ppc_pit_device(int device, const void *yrep, const double *y, const void *log_weights, int n_polls, int n_chains, long long n_draws, double *out) {
+  const char *what = "potus_ppc_pit_device";
+  if (!yrep || !y || !out || n_polls < 1) return fail(POTUS_ERR_ARG, "%s: bad argument", what);
+  if (const int rc_ = el_check_sizes(what, n_chains, n_draws)) return rc_;
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, device, yrep, "block of y_rep")) return rc_;
+  if (log_weights) if (const int rc_ = mm_also_device(what, device, log_weights, "block of log weights")) return rc_;
+  std::fill(g_ppc_ms, g_ppc_ms + 4, 0.0);
+  return ppc_pit(0, (const double *)yrep, y, (const double *)log_weights, n_polls, (long long)n_chains * n_draws, out, 2, g_ppc_ms, what);
+}
+
+int potus_ppc_groups_device(int device, const void *yrep, const void *a1, const void *a2, const double *y, const double *n, const int32_t *groups, int n_groups,
+                            int n_polls, int n_chains, long long n_draws, void *acc_device, int flags, double *group_out, long long *n_in_group) {
+  const char *what = "potus_ppc_groups_device";
+  if (!yrep || !a1 || !a2 || !y || !n || !groups || !n_in_group || n_polls < 1) return fail(POTUS_ERR_ARG, "%s: bad argument", what);
+  if (flags < 0 || flags > (POTUS_PPC_BEGIN | POTUS_PPC_FINISH)) return fail(POTUS_ERR_ARG, "%s: flags = %d", what, flags);
+  const bool begin = flags & POTUS_PPC_BEGIN, finish = flags & POTUS_PPC_FINISH;
+  if (finish && !group_out) return fail(POTUS_ERR_ARG, "%s: POTUS_PPC_FINISH without group_out", what);
+  if (!acc_device && !(begin && finish)) return fail(POTUS_ERR_ARG, "%s: without acc_device the call is the first and the last block (flags = 3)", what);
+  if (const int rc_ = ppc_check_labels(what, groups, n_polls, n_groups, 0)) return rc_;
+  if (const int rc_ = el_check_sizes(what, n_chains, n_draws)) return rc_;
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, device, yrep, "block of y_rep")) return rc_;
+  if (const int rc_ = mm_also_device(what, device, a1, "block of a1")) return rc_;
+  if (const int rc_ = mm_also_device(what, device, a2, "block of a2")) return rc_;
+  if (acc_device) if (const int rc_ = mm_also_device(what, device, acc_device, "block of accumulators")) return rc_;
+  std::fill(g_ppc_ms, g_ppc_ms + 4, 0.0);
+  const long long S = (long long)n_chains * n_draws;
+  const size_t acc_bytes = (size_t)n_groups * PPC_NSTAT * 2 * S * 8;
+  DevBufs tmp;
+  double *acc = (double *)acc_device;
+  int rc;
+  if (!acc && (rc = tmp.get(&acc, acc_bytes, what))) return rc;
+  if (begin) {
+    HIP_TRY(hipMemset(acc, 0, acc_bytes));
+    std::fill(n_in_group, n_in_group + n_groups, 0ll);
+  }
+  if ((rc = ppc_groups_add(0, (const double *)yrep, (const double *)a1, (const double *)a2, y, n, groups, n_groups, n_polls, S, acc, n_in_group, g_ppc_ms, what))) return rc;
+  if (finish && (rc = ppc_groups_finish(0, acc, n_in_group, n_groups, S, group_out, g_ppc_ms, what))) return rc;
+  HIP_TRY(hipDeviceSynchronize());
+  return 0;
+}
+
+// Pools as potus_e_loo pools.  Per poll block: every handle's log-likelihoods, shares and replicates made on its own GPU and brought to the first
+// handle's; there potus_loo's k-hat and r_eff (loo_psis), the ratios, the PSIS weights (potus_psis_device, under its own lock), the PIT and
+// LOO-PIT sums and the groups' accumulators, which stay on the device from the first block to the last.
+int potus_ppc(const int *handles, int n_handles, int integrate, int rep, const int32_t *groups, int n_groupings, const int32_t *n_groups, double *pit_out,
+              double *pareto_k_out, double *group_out, long long *n_in_group_out) {
+  const char *nm = "potus_ppc";
+  if (!pit_out || !pareto_k_out) return fail(POTUS_ERR_ARG, "%s: null output", nm);
+  if (n_groupings < 0 || (n_groupings > 0 && (!groups || !n_groups || !group_out || !n_in_group_out))) return fail(POTUS_ERR_ARG, "%s: %d groupings without their labels or outputs", nm, n_groupings);
+  if (const int rc_ = ppc_check_modes(nm, integrate, rep)) return rc_;
+  Pool P;
+  if (const int rc_ = P.resolve(handles, n_handles, nm)) return rc_;
+  if (const int rc_ = P.same_posterior("a posterior predictive check pools the chains of one")) return rc_;
+  const std::vector<Sampler *> &sps = P.sps;
+  Sampler *s0 = P.s0;
+  const int Np = s0->M.Npoll, Sst = s0->M.S, Npad = s0->M.Npad;
+  if (Np < 1) return fail(POTUS_ERR_ARG, "%s: the data hold no polls", nm);
+  std::vector<size_t> goff(n_groupings + 1, 0);
+  for (int j = 0; j < n_groupings; j++) {
+    if (const int rc_ = ppc_check_labels(nm, groups + (size_t)j * Np, Np, n_groups[j], j)) return rc_;
+    goff[j + 1] = goff[j] + (size_t)n_groups[j];
+  }
+  size_t budget = PPC_BLOCK_BUDGET;
+  if (const char *e = getenv("POTUS_PPC_BLOCK_BUDGET")) budget = std::max<size_t>(1, (size_t)atoll(e));
+  double ms[4] = {0.0, 0.0, 0.0, 0.0};
+  DevBufs keep;
+  double *cols = nullptr, *rr = nullptr, *lw = nullptr, *b1 = nullptr, *b2 = nullptr, *yr = nullptr, *acc = nullptr;
+  int Ctot = 0, n_post = 0, first = 0, nb = 0;
+  long long Stot = 0;
+  std::vector<LooRows> rows(sps.size());
+  std::vector<double> y(Np), n(Np);
+  {
+    DeviceGuard guard;
+    DeviceLocks lock(P.devs);
+    if (const int rc_ = P.count()) return rc_;
+    if (const int rc_ = P.equal_counts()) return rc_;
+    Ctot = P.chains;
+    if (const int rc_ = P.post_warmup(&first, &n_post)) return rc_;
+    Stot = (long long)n_post * Ctot;
+    if (const int rc_ = el_check_sizes(nm, Ctot, n_post)) return rc_;
+    int rc;
+    for (size_t i = 0; i < sps.size(); i++)
+      if ((rc = loo_rows_setup(sps[i], (long long)n_post * sps[i]->R.chains, keep, rows[i], nm))) return rc;
+    // six pooled blocks (log-likelihoods, ratios, weights, a1, a2, y_rep) and a handle's block before its transpose
+    nb = (int)std::max<size_t>(1, std::min<size_t>((size_t)Np, budget / ((size_t)Stot * 8 * 7)));
+    HIP_TRY(hipSetDevice(s0->device));
+    const size_t blk_bytes = (size_t)Stot * nb * 8;
+    if ((rc = keep.get(&cols, blk_bytes, nm)) || (rc = keep.get(&rr, blk_bytes, nm)) || (rc = keep.get(&lw, blk_bytes, nm)) || (rc = keep.get(&b1, blk_bytes, nm)) ||
+        (rc = keep.get(&b2, blk_bytes, nm)) || (rc = keep.get(&yr, blk_bytes, nm)))
+      return rc;
+    if (n_groupings) {
+      const size_t acc_bytes = goff[n_groupings] * PPC_NSTAT * 2 * (size_t)Stot * 8;
+      if ((rc = keep.get(&acc, acc_bytes, nm))) return rc;
+      HIP_TRY(hipMemset(acc, 0, acc_bytes));
+      std::fill(n_in_group_out, n_in_group_out + goff[n_groupings], 0ll);
+    }
+    std::vector<double> pd((size_t)2 * Npad);
+    std::vector<int> pi((size_t)6 * Npad);
+    HIP_TRY(hipMemcpy(pd.data(), s0->M.pd, pd.size() * 8, hipMemcpyDeviceToHost));
+    HIP_TRY(hipMemcpy(pi.data(), s0->M.pi, pi.size() * 4, hipMemcpyDeviceToHost));
+    for (int i = 0; i < Np; i++) {          // the model's (day-sorted) poll i is poll k of the output numbering
+      const int st = pi[i], qi = pi[(size_t)5 * Npad + i], k = st == Sst ? s0->M.Ns + (qi - s0->M.o_nn) : qi - s0->M.o_ns;
+      y[k] = pd[i]; n[k] = pd[(size_t)Npad + i];
+    }
+  }
+  std::vector<double> pw((size_t)nb * LOO_NPW), re(nb), kk(nb);
+  for (int b0 = 0; b0 < Np; b0 += nb) {
+    const int e1 = std::min(b0 + nb, Np), nbk = e1 - b0;
+    {
+      DeviceGuard guard;
+      DeviceLocks lock(P.devs);
+      int rc, coff = 0;
+      HIP_TRY(hipSetDevice(s0->device));
+      for (size_t i = 0; i < sps.size(); i++) {
+        Sampler *sp = sps[i];
+        const int C = sp->R.chains;
+        const size_t bytes = (size_t)n_post * C * nbk * 8;
+        DevBufs blkbuf;
+        double *blk = nullptr;
+        if ((rc = blkbuf.get(&blk, bytes, nm))) return rc;
+        // (one block at a time: made on the handle's GPU, brought over, transposed into its chains' places)
+        for (int which = 0; which < 3; which++) {          // log-likelihoods; a1 (a2 comes from the same launch, into a block of its own: f2); y_rep
+          double *dst = which == 0 ? cols : which == 1 ? b1 : yr;
+          DevBufs far2;
+          double *f2 = nullptr, *g2 = nullptr;
+          if (which == 1) {
+            HIP_TRY(hipSetDevice(sp->device));
+            if ((rc = far2.get(&f2, bytes, nm))) return rc;
+            HIP_TRY(hipSetDevice(s0->device));
+          }
+          if ((rc = gather_block(s0, sp, bytes, blk, [&](double *o) {
+                 EventTimer t;
+                 HIP_TRY(t.made);
+                 HIP_TRY(t.start(sp->stream));
+                 if (which == 0) { if (const int r_ = loo_loglik(sp, rows[i], first, n_post, b0, e1, integrate, o)) return r_; }
+                 else if (which == 1) {
+                   ElShareParams Q{row_src(sp, first), sp->L.ncols, n_post, b0, e1, integrate, rows[i].scratch, o, f2};
+                   hipLaunchKernelGGL(k_el_poll_share, dim3(rows[i].grid), dim3(256), 0, sp->stream, (const DevModel *)sp->dM, Q);
+                 } else if (const int r_ = ppc_rep(sp, rows[i], first, n_post, b0, e1, integrate, rep, o)) return r_;
+                 return el_span(t, sp->stream, ms, which == 0 ? 0 : 1);
+               }))) return rc;
+          if ((rc = pool_transpose(s0, blk, dst, n_post, C, nbk, Ctot, coff))) return rc;
+          if (which == 1) {
+            const double *src2 = f2;
+            DevBufs near2;
+            if (sp->device != s0->device) {
+              if ((rc = near2.get(&g2, bytes, nm))) return rc;
+              HIP_TRY(hipMemcpyPeer(g2, s0->device, f2, sp->device, bytes));
+              HIP_TRY(hipDeviceSynchronize());
+              src2 = g2;
+            }
+            if ((rc = pool_transpose(s0, src2, b2, n_post, C, nbk, Ctot, coff))) return rc;
+          }
+        }
+        coff += C;
+      }
+      EventTimer t;
+      HIP_TRY(t.made);
+      HIP_TRY(t.start(s0->stream));
+      if ((rc = loo_psis(s0->stream, cols, nbk, Ctot, n_post, nullptr, pw.data(), nm))) return rc;
+      const MmRatioParams R{nullptr, cols, nullptr, nullptr, nullptr, rr, nullptr, n_post, (int)Stot, nbk, 0};
+      hipLaunchKernelGGL(k_mm_ratio, dim3((unsigned)std::min<long long>(((long long)nbk * Stot + 255) / 256, 65535)), dim3(256), 0, s0->stream, R);
+      if ((rc = el_span(t, s0->stream, ms, 0))) return rc;
+    }
+    for (int k = 0; k < nbk; k++) { pareto_k_out[b0 + k] = pw[(size_t)k * LOO_NPW + 3]; re[k] = pw[(size_t)k * LOO_NPW + 4]; }
+    // a poll with identical log-likelihoods has no r_eff (NaN): any value gives its flat tail no fit (potus_e_loo's rule)
+    for (int k = 0; k < nbk; k++) if (!(std::isfinite(re[k]) && re[k] > 0)) re[k] = 1.0;
+    {
+      DeviceGuard guard;
+      HIP_TRY(hipSetDevice(s0->device));
+      EventTimer t;
+      HIP_TRY(t.made);
+      HIP_TRY(t.start(0));
+      if (const int rc = potus_psis_device(s0->device, rr, nbk, Ctot, n_post, re.data(), lw, kk.data())) return rc;
+      if (const int rc = el_span(t, 0, ms, 0)) return rc;
+    }
+    {
+      DeviceGuard guard;
+      DeviceLocks lock(P.devs);
+      int rc;
+      HIP_TRY(hipSetDevice(s0->device));
+      if ((rc = ppc_pit(s0->stream, yr, y.data() + b0, nullptr, nbk, Stot, pit_out + (size_t)b0 * 4, 4, ms, nm))) return rc;
+      if ((rc = ppc_pit(s0->stream, yr, y.data() + b0, lw, nbk, Stot, pit_out + (size_t)b0 * 4 + 2, 4, ms, nm))) return rc;
+      for (int k = b0; k < e1; k++) if (!(n[k] > 0)) for (int c = 0; c < 4; c++) pit_out[(size_t)k * 4 + c] = NAN;
+      for (int j = 0; j < n_groupings; j++)
+        if ((rc = ppc_groups_add(s0->stream, yr, b1, b2, y.data() + b0, n.data() + b0, groups + (size_t)j * Np + b0, n_groups[j], nbk, Stot,
+                                 acc + goff[j] * PPC_NSTAT * 2 * (size_t)Stot, n_in_group_out + goff[j], ms, nm)))
+          return rc;
+    }
+  }
+  {
+    DeviceGuard guard;
+    DeviceLocks lock(P.devs);
+    HIP_TRY(hipSetDevice(s0->device));
+    for (int j = 0; j < n_groupings; j++)
+      if (const int rc = ppc_groups_finish(s0->stream, acc + goff[j] * PPC_NSTAT * 2 * (size_t)Stot, n_in_group_out + goff[j], n_groups[j], Stot,
+                                           group_out + goff[j] * PPC_NSTAT * PPC_NOUT, ms, nm))
+        return rc;
+  }
+  std::copy(ms, ms + 4, g_ppc_ms);
+  return 0;
+}
+
 // ---------------------------------------------------------------- .C() wrappers
 void potus_R_create(int *dims, int *state, int *day_state, int *day_national, int *poll_state, int *poll_national,
                     int *poll_mode_state, int *poll_mode_national, int *poll_pop_state, int *poll_pop_national,
@@ -6660,6 +6996,14 @@ void potus_R_loo_influence(int *handles, int *n_handles, int *iopts /*[4]*/, dou
 }
 void potus_R_loo_predict(int *handles, int *n_handles, int *integrate, double *out /*[N][5]*/, double *pareto_k, int *status) {
   *status = potus_e_loo(handles, *n_handles, *integrate, POTUS_ELOO_PREDICT, nullptr, 0, -1, 0, 0, 0, out, nullptr, nullptr, pareto_k, nullptr, nullptr, nullptr, nullptr);
+}
+void potus_R_ppc(int *handles, int *n_handles, int *iopts /*[3]: integrate, rep, n_groupings*/, int *groups, int *n_groups, double *pit_out, double *pareto_k,
+                 double *group_out, double *n_in_group, int *status) {
+  size_t tot = 0;
+  for (int j = 0; j < iopts[2]; j++) tot += (size_t)std::max(n_groups[j], 0);
+  std::vector<long long> cnt(std::max<size_t>(tot, 1), 0);
+  *status = potus_ppc(handles, *n_handles, iopts[0], iopts[1], groups, iopts[2], n_groups, pit_out, pareto_k, group_out, cnt.data());
+  if (*status == 0) for (size_t g = 0; g < tot; g++) n_in_group[g] = (double)cnt[g];
 }
 void potus_R_loo_moment_match(int *model_handle, int *handles, int *n_handles, int *iopts /*[5]: integrate, max_iters, split, cov, n_polls (0: every poll)*/,
                               double *k_threshold, int *polls, double *pointwise, double *estimates_out, int *info_out, int *status) {

@@ -132,8 +132,13 @@ __global__ __launch_bounds__(256) void k_write_array_ds(const DevModel *Mg, WAPa
 // ------------------------------------------------------------------------ prior predictive simulation and SBC ranks
 // y ~ binomial(n, p) with p = inv_logit(eta), exactly: inversion (sequential search from 0) when n min(p, 1 - p) < 10, else BTRS (Hoermann
 // 1993, "The generation of binomial random variates", with the exact log-ratio lgamma form of its acceptance bound).  Uniforms of attempt a
-// come from Philox counter (iter a, RNG_PRIOR, aux 2 / 3, index idx).
-__device__ int binomial_logit_draw(const RngKey &key, uint32_t idx, int n, double eta) {
+// come from Philox counter (iter a, RNG_PRIOR, aux 2 / 3, index idx): BinomCtrPrior, the default.  Another caller gives the uniforms a purpose and a
+// counter of its own as Ctr: ctr(key, attempt, kind, idx), kind 2 = u, 3 = v (potus_ppc.hpp).
+struct BinomCtrPrior {
+  __device__ __forceinline__ double operator()(const RngKey &key, uint32_t att, uint32_t kind, uint32_t idx) const { return rng_uniform(key, att, RNG_PRIOR, kind, idx); }
+};
+template <class Ctr = BinomCtrPrior>
+__device__ int binomial_logit_draw(const RngKey &key, uint32_t idx, int n, double eta, const Ctr ctr = Ctr()) {
   if (n <= 0) return 0;
   const double e = exp(-fabs(eta));
   const double p = e / (1.0 + e), q = 1.0 / (1.0 + e);          // p = min(pi, 1 - pi), computed without cancellation
@@ -142,7 +147,7 @@ __device__ int binomial_logit_draw(const RngKey &key, uint32_t idx, int n, doubl
   if ((double)n * p < 10.0) {
     const double s = p / q, a = (n + 1) * s, r0 = pow(q, (double)n);
     for (uint32_t att = 0; att < 64; att++) {
-      double u = rng_uniform(key, att, RNG_PRIOR, 2, idx), r = r0;
+      double u = ctr(key, att, 2, idx), r = r0;
       int x = 0;
       while (u > r && x <= n) { u -= r; x++; r *= a / x - s; }
       k = x;
@@ -154,7 +159,7 @@ __device__ int binomial_logit_draw(const RngKey &key, uint32_t idx, int n, doubl
     const double vr = 0.92 - 4.2 / b, alpha = (2.83 + 5.1 / b) * spq, lpq = log(p / q), m = floor((n + 1) * p);
     const double h = lgamma(m + 1.0) + lgamma(n - m + 1.0);
     for (uint32_t att = 0; att < 4096; att++) {
-      const double u = rng_uniform(key, att, RNG_PRIOR, 2, idx) - 0.5, v0 = rng_uniform(key, att, RNG_PRIOR, 3, idx);
+      const double u = ctr(key, att, 2, idx) - 0.5, v0 = ctr(key, att, 3, idx);
       const double us = 0.5 - fabs(u), kk = floor((2.0 * a / us + b) * u + c);
       if (kk < 0.0 || kk > (double)n) continue;
       k = (int)kk;

@@ -121,6 +121,16 @@ def load_library():
         L.potus_R_loo_influence.restype = None
         L.potus_R_loo_predict.argtypes = [ip, ip, ip, dp, dp, ip]
         L.potus_R_loo_predict.restype = None
+    if hasattr(L, "potus_ppc"):                         # posterior predictive checks (ppc.py)
+        i32p, llp = C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
+        L.potus_poll_rep_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_void_p]
+        L.potus_ppc_pit_device.argtypes = [C.c_int, C.c_void_p, dp, C.c_void_p, C.c_int, C.c_int, C.c_longlong, dp]
+        L.potus_ppc_groups_device.argtypes = [C.c_int, C.c_void_p, C.c_void_p, C.c_void_p, dp, dp, i32p, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_void_p, C.c_int,
+                                              dp, llp]
+        L.potus_ppc.argtypes = [ip, C.c_int, C.c_int, C.c_int, i32p, C.c_int, i32p, dp, dp, dp, llp]
+        L.potus_ppc_timing.argtypes = [dp]
+        L.potus_R_ppc.argtypes = [ip, ip, ip, ip, ip, dp, dp, dp, dp, ip]
+        L.potus_R_ppc.restype = None
     if hasattr(L, "potus_outcomes"):                    # joint election outcomes (outcomes.py)
         i32p, llp = C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
         L.potus_outcomes.argtypes = [ip, C.c_int, C.c_int, C.c_int, i32p, C.c_int, dp, llp, llp, llp, llp, llp]
@@ -207,6 +217,7 @@ EXPORTS = [
     "potus_default_loo_mm_opts", "potus_loo_moment_match", "potus_loo_mm_timing", "potus_loo_mm_ratios_device", "potus_loo_mm_moments_device",
     "potus_psis_device", "potus_R_loo_moment_match",
     "potus_e_loo_device", "potus_e_loo_shared_device", "potus_e_loo_timing", "potus_poll_share_device", "potus_e_loo", "potus_R_loo_influence", "potus_R_loo_predict",
+    "potus_poll_rep_device", "potus_ppc_pit_device", "potus_ppc_groups_device", "potus_ppc", "potus_ppc_timing", "potus_R_ppc",
     "potus_cv_log_lik_device", "potus_cv_lpd", "potus_cv_timing",
     "potus_default_optimize_opts", "potus_optimize", "potus_optimize_timing",
     "potus_default_laplace_opts", "potus_laplace", "potus_laplace_write_array_device", "potus_laplace_scores_device", "potus_laplace_summary",
@@ -914,6 +925,21 @@ class Handle:
         _check(self.L, self.L.potus_poll_share_device(self.h, int(poll_begin), int(poll_end), int(bool(integrate)), C.c_void_p(a1.data_ptr()), C.c_void_p(a2.data_ptr())))
         return a1, a2
 
+    def poll_rep_device(self, poll_begin, poll_end, integrate=True, rep=0):
+        """potus_poll_rep_device: replicated outcomes y_rep of the polls at the post-warm-up draws, a torch tensor [polls, chains, draws]
+        (float64) on this handle's GPU; integrate: a fresh noise coordinate per cell (a new poll), else the draw's own (the same poll again)."""
+        import torch
+        shape = (int(poll_end) - int(poll_begin), self.opts.chains, self.post_warmup_saved())
+        yr = torch.empty(shape, dtype=torch.float64, device=f"cuda:{self.opts.device}")
+        torch.cuda.current_stream(yr.device).synchronize()
+        _check(self.L, self.L.potus_poll_rep_device(self.h, int(poll_begin), int(poll_end), int(bool(integrate)), int(rep), C.c_void_p(yr.data_ptr())))
+        return yr
+
+    def ppc(self, **kw):
+        """ppc.check on this handle's draws: PIT, LOO-PIT and the grouped posterior predictive p-values."""
+        from .ppc import check
+        return check(self, **kw)
+
     def loo_predict(self, **kw):
         """loo.predict on this handle's draws: the leave-one-out predictive mean and sd of every poll's share (plain PSIS weights)."""
         from .loo import predict
@@ -1163,6 +1189,11 @@ class StanFit:
         """fit$loo(): PSIS-LOO of the polls over every chain of the fit, on the device (us_potus_model_amd.loo)."""
         from .loo import loo
         return loo(self._hs, integrate=integrate, r_eff=r_eff, name=self.model_name)
+
+    def ppc(self, **kw):
+        """Posterior predictive checks over every chain of the fit, on the device (us_potus_model_amd.ppc.check)."""
+        from .ppc import check
+        return check(self._hs, **kw)
 
     def outcomes(self, ev, actual=None, days=None, ev_to_win=270):
         """EV histogram, tipping point, joint win counts and p-values over every chain of the fit, on the device (us_potus_model_amd.outcomes)."""
