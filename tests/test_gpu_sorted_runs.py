@@ -204,6 +204,36 @@ def test_leg_d_psis_of_general_ratios_at_the_edges_of_a_run(chains, draws):
     _close(k, k_ref)
 
 
+def _entry_case(which):
+    """(log-likelihoods, x, given r_eff) of test_leg_d_the_psis_entries_agree_in_bytes"""
+    if which == "many_ratios":       # the tied tails and the polls without a finite ratio (all -inf) among the early exits
+        sel = [j for j in range(cases.N_EARLY) if _early_kind(j) in ("tied tail", "no finite ratio")]
+        return -cases.many_ratios()[sel], cases.many_quantities()[sel], np.array(cases.GENERAL_R_EFF)[np.arange(len(sel)) % 3]
+    chains, draws = which
+    return cases.log_lik_block(chains, draws), cases.quantity_block(chains, draws, "continuous"), np.array(cases.GENERAL_R_EFF)
+
+
+@pytest.mark.parametrize("which", [(1, 25), (2, 10), (3, 2731), (8, 1024), "many_ratios"], ids=str)
+def test_leg_d_the_psis_entries_agree_in_bytes(which):
+    """PSIS is stated once (potus_psis.hpp), so for the same ratios and the same given r_eff the k-hat of loo_of_block (k_loo_psis), of
+    psis_weights on -ll (k_mm_psis) and e_loo(...).khat[:, 2] (k_el_pointwise) are the same bytes, NaN and inf included: S = 25 (Mt = 5, the
+    smallest fitted tail), 20 (Mt = 4: nothing fitted), 8193 (a last run of one) and 8192, and the tied tails and all -inf ratios of many_ratios.
+    r_eff: e_loo does not return the r_eff it computes, so what is compared is e_loo under loo_of_block's computed r_eff with e_loo under its
+    own -- every output, in bytes."""
+    ll, x, re = _entry_case(which)
+    pw, _ = _loo(ll, re)
+    _, k = _psis(-ll, re)
+    out, khat = _e_loo(x, -ll, r_eff=re)
+    print(f"leg D entries {which}: max |k psis_weights - k loo| = {_rel(k, pw[:, 3]):.2e}, max |k e_loo - k loo| = {_rel(khat[:, 2], pw[:, 3]):.2e}")
+    assert k.tobytes() == np.ascontiguousarray(pw[:, 3]).tobytes()
+    assert np.ascontiguousarray(khat[:, 2]).tobytes() == np.ascontiguousarray(pw[:, 3]).tobytes()
+    pw_c, _ = _loo(ll)
+    fin = np.isfinite(pw_c[:, 4])               # (no finite ratio: loo_of_block reports a NaN r_eff, which e_loo would refuse as a given one)
+    assert fin.any() and (which != "many_ratios" or not fin.all())
+    own, under = _e_loo(x[fin], -ll[fin]), _e_loo(x[fin], -ll[fin], r_eff=pw_c[fin, 4])
+    assert own[0].tobytes() == under[0].tobytes() and own[1].tobytes() == under[1].tobytes()
+
+
 @pytest.mark.parametrize("kind", ["continuous", "rounded"])
 @pytest.mark.parametrize("chains,draws", cases.PSIS_SHAPES)
 def test_leg_e_e_loo_at_the_edges_of_a_run(chains, draws, kind):

@@ -79,9 +79,25 @@ __device__ __forceinline__ int dg_count_less(const K *keys, const I *idx, int n,
   while (lo < hi) { const int mid = (lo + hi) >> 1; if (dg_less(keys[mid], idx[mid], key, id)) lo = mid + 1; else hi = mid; }
   return lo;
 }
+// One workgroup's view of its sorted runs: xk / xi = the keys and the indices of one run in the kernel's dynamic LDS (min(npad, DG_RUN) keys, then
+// as many indices), rkey / ridx = the workgroup's rows of the runs in global memory (null up to DG_RUN items: the one run stays in LDS).
+struct DgRuns {
+  unsigned long long *xk;
+  unsigned *xi;
+  unsigned long long *rkey;
+  unsigned *ridx;
+};
+// dyn = the kernel's own extern __shared__ symbol, N = the most items it sorts, rkey / ridx = [gridDim.x][N] or null
+__device__ __forceinline__ DgRuns dg_runs(unsigned long long *dyn, long long N, unsigned long long *rkey, unsigned *ridx) {
+  int npad = 1;
+  while (npad < N && npad < DG_RUN) npad <<= 1;
+  return DgRuns{dyn, (unsigned *)(dyn + npad), rkey ? rkey + (size_t)blockIdx.x * (size_t)N : nullptr, ridx ? ridx + (size_t)blockIdx.x * (size_t)N : nullptr};
+}
 template <class F>
-__device__ __forceinline__ void dg_sort_runs(F val, long long N, unsigned long long *xk, unsigned *xi, unsigned long long *rkey, unsigned *ridx) {
+__device__ __forceinline__ void dg_sort_runs(F val, long long N, const DgRuns &R) {
   const int tid = threadIdx.x;
+  unsigned long long *const xk = R.xk, *const rkey = R.rkey;
+  unsigned *const xi = R.xi, *const ridx = R.ridx;
   const bool multi = N > DG_RUN;
   for (long long r0 = 0; r0 < N; r0 += DG_RUN) {
     const int nn = (int)(N - r0 < DG_RUN ? N - r0 : DG_RUN);
@@ -109,11 +125,11 @@ __device__ __forceinline__ void dg_sort_runs(F val, long long N, unsigned long l
   }
   if (multi) __threadfence_block();
 }
-__device__ __forceinline__ long long dg_rank(double v, long long j, long long N, const unsigned long long *xk, const unsigned *xi, const unsigned long long *rkey, const unsigned *ridx) {
+__device__ __forceinline__ long long dg_rank(double v, long long j, long long N, const DgRuns &R) {
   const unsigned long long key = ps_key(v);
-  if (N <= DG_RUN) return 1 + dg_count_less(xk, xi, (int)N, key, (unsigned)j);
+  if (N <= DG_RUN) return 1 + dg_count_less(R.xk, R.xi, (int)N, key, (unsigned)j);
   long long r = 1;
-  for (long long r0 = 0; r0 < N; r0 += DG_RUN) r += dg_count_less(rkey + r0, ridx + r0, (int)(N - r0 < DG_RUN ? N - r0 : DG_RUN), key, (unsigned)j);
+  for (long long r0 = 0; r0 < N; r0 += DG_RUN) r += dg_count_less(R.rkey + r0, R.ridx + r0, (int)(N - r0 < DG_RUN ? N - r0 : DG_RUN), key, (unsigned)j);
   return r;
 }
 // k-th smallest key (0-based) of the union of the sorted runs in global memory
@@ -133,14 +149,39 @@ __device__ __forceinline__ unsigned long long dg_select(const unsigned long long
   return lo;
 }
 
+// k-th smallest (0-based) of the M values the last dg_sort_runs sorted
+__device__ __forceinline__ double dg_order(long long M, long long k, const DgRuns &R) {
+  return ps_unkey(M <= DG_RUN ? R.xk[k] : dg_select(R.rkey, M, k));
+}
+
 // normal scores of the ranks of val(0 .. N-1) into zout, in the order of the split array: sorts the runs, then ranks every draw in them
 template <class F>
-__device__ __forceinline__ void dg_scores(F val, long long N, unsigned long long *xk, unsigned *xi, unsigned long long *rkey, unsigned *ridx, double *zout) {
+__device__ __forceinline__ void dg_scores(F val, long long N, const DgRuns &R, double *zout) {
   for (long long j = threadIdx.x; j < N; j += DG_THREADS) {
     const double v = val(j);
-    const long long r = dg_rank(v, j, N, xk, xi, rkey, ridx);
+    const long long r = dg_rank(v, j, N, R);
     zout[j] = dg_normal_score(((double)r - 0.375) / ((double)N + 0.25));
   }
+}
+
+// sum and maximum over the DG_THREADS threads of a workgroup in a fixed order (a DPP tree per wave, then the waves in order), returned in every thread
+__device__ __forceinline__ double dg_block_sum(double v, double *red) {
+  const double s = dpp_wave_sum(v);
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
+  __syncthreads();
+  double t = 0.0;
+  for (int w = 0; w < DG_THREADS / 64; w++) t += red[w];
+  __syncthreads();
+  return t;
+}
+__device__ __forceinline__ double dg_block_max(double v, double *red) {
+  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
+  __syncthreads();
+  double t = -INFINITY;
+  for (int w = 0; w < DG_THREADS / 64; w++) t = fmax(t, red[w]);
+  __syncthreads();
+  return t;
 }
 
 // classic R-hat (rhat_basic) of the split chains zz [C2][h]: one wave per split chain, two passes (mean, then variance).  The chain means and
@@ -235,11 +276,7 @@ __global__ __launch_bounds__(DG_THREADS) void k_dg_column(DgParams P) {
   const int C = P.C, C2 = 2 * C;
   const long long N = (long long)C2 * h;
   double *z = P.zbuf + (size_t)blockIdx.x * 2 * (size_t)N, *zf = z + N;
-  unsigned long long *rkey = P.rkey ? P.rkey + (size_t)blockIdx.x * (size_t)N : nullptr;
-  unsigned *ridx = P.ridx ? P.ridx + (size_t)blockIdx.x * (size_t)N : nullptr;
-  int npad_all = 1;
-  while (npad_all < N && npad_all < DG_RUN) npad_all <<= 1;
-  unsigned *xi = (unsigned *)(xk + npad_all);
+  const DgRuns R = dg_runs(xk, N, P.rkey, P.ridx);
   for (int col = blockIdx.x; col < P.NC; col += gridDim.x) {
     const double *x = P.cols + (size_t)col * C * n;
     if (h < 2) { if (tid == 0) { P.rhat[col] = NAN; P.ess[col] = NAN; } continue; }
@@ -252,20 +289,20 @@ __global__ __launch_bounds__(DG_THREADS) void k_dg_column(DgParams P) {
       if (__syncthreads_or(bad)) { if (tid == 0) { P.rhat[col] = NAN; P.ess[col] = NAN; } continue; }
     }
     // ---- bulk: ranks of the split draws
-    dg_sort_runs(val, N, xk, xi, rkey, ridx);
+    dg_sort_runs(val, N, R);
     if (tid == 0) {                                    // the median of the split draws (numpy: mean of the two middle ones)
       const long long k1 = (N - 1) / 2, k2 = N / 2;
-      const double a = ps_unkey(N <= DG_RUN ? xk[k1] : dg_select(rkey, N, k1)), b = ps_unkey(N <= DG_RUN ? xk[k2] : dg_select(rkey, N, k2));
+      const double a = dg_order(N, k1, R), b = dg_order(N, k2, R);
       sc[0] = 0.5 * (a + b);
     }
-    dg_scores(val, N, xk, xi, rkey, ridx, z);
+    dg_scores(val, N, R, z);
     __syncthreads();
     const double med = sc[0];
     __syncthreads();
     // ---- folded: ranks of |x - median|
     auto fval = [&](long long j) { return fabs(dg_split_value(x, n, C, h, j) - med) + 0.0; };
-    dg_sort_runs(fval, N, xk, xi, rkey, ridx);
-    dg_scores(fval, N, xk, xi, rkey, ridx, zf);
+    dg_sort_runs(fval, N, R);
+    dg_scores(fval, N, R, zf);
     __threadfence_block();
     __syncthreads();
     // ---- classic R-hat of both, bulk last: its chain means and variances stay for the ESS

@@ -11,10 +11,9 @@
 //             a tail = the M largest values, M = ceil(min(0.2 S, 3 sqrt(S / r_eff))), minus the value just below them, through gpdfit with
 //             loo's prior; M < 5 or a spread below DBL_EPSILON / 100: +inf.
 // Kernels:
-//   k_el_pointwise    x with its own values per poll.  One workgroup of DG_THREADS per poll: r_eff (when not given) and PSIS of r RESTATED from
-//                     k_loo_psis / k_mm_psis (restated, not shared, for potus_loo_mm.hpp's reason: factoring them would change their code), the
-//                     moments, four sorts on potus_diag.hpp's runs (r, x, x rho, x^2 rho: one sort of h rho gives both of its tails), the
-//                     weighted quantiles by a segmented scan in a fixed order.  Every sum is loo_block_sum's: a poll's bytes depend on its own row alone.
+//   k_el_pointwise    x with its own values per poll.  One workgroup of DG_THREADS per poll: r_eff (when not given) and PSIS of r by potus_psis.hpp
+//                     (what k_loo_psis and k_mm_psis call), the moments, four sorts on potus_diag.hpp's runs (r, x, x rho, x^2 rho: one sort of
+//                     h rho gives both of its tails), the weighted quantiles by a segmented scan in a fixed order.  Every sum is dg_block_sum's: a poll's bytes depend on its own row alone.
 //   k_el_colmean      c[j] = the equal-weight mean of column j of X (the posterior mean), one workgroup per column.
 //   k_el_shared       X shared by all polls: D1 = W (X - c), D2 = W (X - c)^2 as tiled products on v_mfma_f64_16x16x4_f64.  A workgroup of four
 //                     waves owns EL_TM polls x EL_TN columns of one chunk of EL_CHUNK draws; EL_KB draws at a time are staged in LDS, the weights
@@ -37,217 +36,18 @@
 #define EL_CHUNK 1024    // draws per partial sum
 #define EL_THREADS 256
 
-// a workgroup's scratch in global memory: doubles xc [S] | tail [S] | th [mmax] | lth [mmax] | lwn [S] | xs [S] | ws [S], then ranks and sorted runs
-__host__ __device__ inline size_t el_ws_doubles(long long S, int mmax) { return 5 * (size_t)S + 2 * (size_t)mmax; }
-struct ElWork {
-  double *wsd;                // [gridDim.x][el_ws_doubles]
-  int *wsi;                   // [gridDim.x][S]
-  unsigned long long *rkey;   // [gridDim.x][S] sorted runs when S > DG_RUN
-  unsigned *ridx;
-  int mmax;
-};
-struct ElLds {
-  double red[DG_THREADS / 64], sc[8], cmean[DG_MAXCH / 2], cvar[DG_MAXCH / 2], rho[DG_LAGS], seg[DG_THREADS + 1];
-};
-struct ElPtrs {               // one workgroup's views of ElWork and of the dynamic LDS
-  double *xc, *tail, *th, *lth, *lwn, *xs, *ws;
-  int *rnk;
-  unsigned long long *xk, *rkey;
-  unsigned *xi, *ridx;
-};
-__device__ __forceinline__ ElPtrs el_ptrs(const ElWork &W, long long S, unsigned long long *dyn) {
-  ElPtrs p;
-  p.xc = W.wsd + (size_t)blockIdx.x * el_ws_doubles(S, W.mmax);
-  p.tail = p.xc + S; p.th = p.tail + S; p.lth = p.th + W.mmax; p.lwn = p.lth + W.mmax; p.xs = p.lwn + S; p.ws = p.xs + S;
-  p.rnk = W.wsi + (size_t)blockIdx.x * (size_t)S;
-  p.rkey = W.rkey ? W.rkey + (size_t)blockIdx.x * (size_t)S : nullptr;
-  p.ridx = W.ridx ? W.ridx + (size_t)blockIdx.x * (size_t)S : nullptr;
-  int npad = 1;
-  while (npad < S && npad < DG_RUN) npad <<= 1;
-  p.xk = dyn;
-  p.xi = (unsigned *)(dyn + npad);
-  return p;
-}
-
-// r_eff = ESS / S of exp(ll - max ll), ll = -r, chains not split: k_loo_psis's block, restated on r (rmin = min r)
-__device__ double el_reff(const double *r, double rmin, int C, long long n, double *xc, ElLds &L) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const long long S = (long long)C * n;
-  double *sc = L.sc;
-  for (long long j = tid; j < S; j += DG_THREADS) xc[j] = exp(-r[j] + rmin);
-  __threadfence_block();
-  __syncthreads();
-  for (int c = w; c < C; c += DG_THREADS / 64) {
-    double s = 0.0;
-    for (long long i = lane; i < n; i += 64) s += xc[(size_t)c * n + i];
-    const double m = dpp_wave_sum(s) / (double)n;
-    double q = 0.0;
-    for (long long i = lane; i < n; i += 64) { const double d = xc[(size_t)c * n + i] - m; q += d * d; }
-    const double v = dpp_wave_sum(q) / (double)n;
-    if (lane == 0) { L.cmean[c] = m; L.cvar[c] = v; }
-  }
-  __syncthreads();
-  for (long long j = tid; j < S; j += DG_THREADS) xc[j] -= L.cmean[j / n];
-  if (tid == 0) {
-    double a = 0.0, mm = 0.0;
-    for (int c = 0; c < C; c++) { a += L.cvar[c]; mm += L.cmean[c]; }
-    const double mean_var = a / C * (double)n / (double)(n - 1);
-    double var_plus = mean_var * (double)(n - 1) / (double)n;
-    if (C > 1) {
-      mm /= C;
-      double b = 0.0;
-      for (int c = 0; c < C; c++) b += (L.cmean[c] - mm) * (L.cmean[c] - mm);
-      var_plus += b / (C - 1);
-    }
-    sc[0] = mean_var; sc[1] = var_plus;
-    sc[2] = 0.0; sc[3] = 0.0; sc[4] = 0.0; sc[5] = 0.0;   // sum of rho over lags < max_t, previous pair, rho(max_t), done
-  }
-  __threadfence_block();
-  __syncthreads();
-  const double mean_var = sc[0], var_plus = sc[1];
-  for (long long t0 = 0; t0 < n; t0 += DG_LAGS) {
-    for (int lg = w; lg < DG_LAGS; lg += DG_THREADS / 64) {
-      const long long t = t0 + lg;
-      double s = 0.0;
-      if (t < n)
-        for (int c = 0; c < C; c++) {
-          const double *xcc = xc + (size_t)c * n;
-          double a = 0.0;
-          for (long long i = lane; i + t < n; i += 64) a += xcc[i] * xcc[i + t];
-          s += dpp_wave_sum(a) / (double)n;
-        }
-      if (lane == 0) L.rho[lg] = t < n ? 1.0 - (mean_var - s / C) / var_plus : NAN;
-    }
-    __syncthreads();
-    if (tid == 0) {
-      double tsum = sc[2], prev = sc[3];
-      for (int lg = 0; lg < DG_LAGS; lg += 2) {
-        const long long t = t0 + lg;
-        const double even = t == 0 ? 1.0 : L.rho[lg], odd = L.rho[lg + 1], pair = even + odd;
-        if (t < n - 5 && pair > 0) {
-          double e = even, od = odd;
-          if (t >= 2 && pair > prev) { e = prev / 2; od = e; }
-          tsum += e; tsum += od;
-          prev = e + od;
-        } else {
-          sc[4] = (t == 0 || pair >= 0 || even > 0) ? even : 0.0;
-          sc[5] = 1.0;
-          break;
-        }
-      }
-      sc[2] = tsum; sc[3] = prev;
-    }
-    __syncthreads();
-    if (sc[5] != 0.0) break;
-  }
-  if (tid == 0) {
-    double tau = -1.0 + 2.0 * sc[2] + sc[4];
-    tau = fmax(tau, 1.0 / log10((double)S));
-    sc[6] = ((double)S / tau) / (double)S;
-  }
-  __syncthreads();
-  const double reff = sc[6];
-  __syncthreads();
-  return reff;
-}
-
-// gpdfit (Zhang & Stephens 2009 with loo's prior) of the ascending sample xs [N], already visible to the workgroup: k (NaN: +inf), sigma
-__device__ double el_gpdfit(const double *xs, int N, double *th, double *lth, ElLds &L, double *sigma_out) {
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
-  const int m = 30 + (int)floor(sqrt((double)N));
-  const double xstar = xs[(int)floor(N / 4.0 + 0.5) - 1];
-  for (int jj = w; jj < m; jj += DG_THREADS / 64) {      // one wave per grid point theta_j
-    const double theta = 1.0 / xs[N - 1] + (1.0 - sqrt((double)m / (jj + 0.5))) / 3.0 / xstar;
-    double a = 0.0;
-    for (int i = lane; i < N; i += 64) a += log1p(-theta * xs[i]);
-    const double kj = dpp_wave_sum(a) / N;
-    if (lane == 0) { th[jj] = theta; lth[jj] = N * (log(-theta / kj) - kj - 1.0); }
-  }
-  __threadfence_block();
-  __syncthreads();
-  if (tid == 0) {                                        // theta-hat = sum_j softmax(l)_j theta_j
-    double lm = -INFINITY;
-    for (int jj = 0; jj < m; jj++) lm = fmax(lm, lth[jj]);
-    double s = 0.0;
-    for (int jj = 0; jj < m; jj++) s += exp(lth[jj] - lm);
-    const double lse = lm + log(s);
-    double thh = 0.0;
-    for (int jj = 0; jj < m; jj++) thh += th[jj] * exp(lth[jj] - lse);
-    L.sc[7] = thh;
-  }
-  __syncthreads();
-  const double thh = L.sc[7];
-  double a = 0.0;
-  for (int j = tid; j < N; j += DG_THREADS) a += log1p(-thh * xs[j]);
-  double k = loo_block_sum(a, L.red) / N;
-  *sigma_out = -k / thh;
-  k = k * N / (N + 10) + 10 * 0.5 / (N + 10);          // loo's weakly informative prior
-  if (isnan(k)) k = INFINITY;
-  return k;
-}
-
-// PSIS of the ratios r [S] (max rmax, finite): the normalised log weights into lwo, k_r returned: k_mm_psis's steps in its order
-__device__ double el_psis(const double *r, double rmax, double reff, long long S, const ElPtrs &Q, ElLds &L, double *lwo) {
-  const int tid = threadIdx.x;
-  auto lwv = [&](long long j) { return r[j] - rmax + 0.0; };
-  const long long Mt = (long long)ceil(fmin(0.2 * (double)S, 3.0 * sqrt((double)S / reff)));
-  double khat = INFINITY;
-  bool smooth = false;
-  double *tail = Q.tail, *tl = tail + 1;                  // tail[0] = the cutoff, tail[1 .. M] = the M largest lw, ascending
-  if (Mt >= 5) {
-    dg_sort_runs(lwv, S, Q.xk, Q.xi, Q.rkey, Q.ridx);
-    for (long long j = tid; j < S; j += DG_THREADS) {
-      const double v = lwv(j);
-      const long long r0 = dg_rank(v, j, S, Q.xk, Q.xi, Q.rkey, Q.ridx) - 1;
-      Q.rnk[j] = (int)r0;
-      if (r0 >= S - Mt - 1) tail[r0 - (S - Mt - 1)] = v;
-    }
-    __threadfence_block();
-    __syncthreads();
-    if (tl[Mt - 1] - tl[0] >= DBL_EPSILON / 100) {
-      smooth = true;
-      const int N = (int)Mt;
-      const double ec = exp(tail[0]);
-      double *xs = Q.xc;                                  // gpdfit's sample exp(tail) - exp(cutoff), ascending
-      for (int j = tid; j < N; j += DG_THREADS) xs[j] = exp(tl[j]) - ec;
-      __threadfence_block();
-      __syncthreads();
-      double sigma;
-      const double k = el_gpdfit(xs, N, Q.th, Q.lth, L, &sigma);
-      khat = k;
-      if (isfinite(k))
-        for (int j = tid; j < N; j += DG_THREADS) tl[j] = log(sigma * expm1(-k * log1p(-(j + 0.5) / N)) / k + ec);
-      __threadfence_block();
-      __syncthreads();
-    }
-  }
-  auto lwf = [&](long long j) {                           // smoothed, then truncated at max lw = 0
-    double v = lwv(j);
-    if (smooth && Q.rnk[j] >= S - Mt) v = tl[Q.rnk[j] - (S - Mt)];
-    return fmin(v, 0.0);
-  };
-  double m1 = -INFINITY;
-  for (long long j = tid; j < S; j += DG_THREADS) m1 = fmax(m1, lwf(j));
-  m1 = loo_block_max(m1, L.red);
-  double s1 = 0.0;
-  for (long long j = tid; j < S; j += DG_THREADS) s1 += exp(lwf(j) - m1);
-  const double lse_w = m1 + log(loo_block_sum(s1, L.red));
-  for (long long j = tid; j < S; j += DG_THREADS) lwo[j] = lwf(j) - lse_w;
-  __threadfence_block();
-  __syncthreads();
-  return khat;
-}
+#define EL_ROWS 3         // a workgroup's rows of S doubles behind the PSIS scratch (PsisPtrs::end): lwn | xs | ws
 
 // h constant, two-valued or not finite somewhere: its k is k_r
 template <class H>
-__device__ bool el_plain(H h, long long S, ElLds &L) {
+__device__ bool el_plain(H h, long long S, PsisLds &L) {
   const int tid = threadIdx.x;
   int bad = 0;
   double mx = -INFINITY, mn = INFINITY;
   for (long long j = tid; j < S; j += DG_THREADS) { const double v = h(j); bad |= !isfinite(v); mx = fmax(mx, v); mn = fmin(mn, v); }
   if (__syncthreads_or(bad)) return true;
-  mx = loo_block_max(mx, L.red);
-  mn = -loo_block_max(-mn, L.red);
+  mx = dg_block_max(mx, L.red);
+  mn = -dg_block_max(-mn, L.red);
   int other = 0;
   for (long long j = tid; j < S; j += DG_THREADS) { const double v = h(j); other |= (v != mn && v != mx); }
   return !__syncthreads_or(other);
@@ -255,14 +55,14 @@ __device__ bool el_plain(H h, long long S, ElLds &L) {
 
 // the larger k-hat of the right tails of v and of -v (v finite): one sort; the right tail of -v is the left tail of v, negated
 template <class F>
-__device__ double el_khat_both(F val, long long S, long long Mt, const ElPtrs &Q, ElLds &L) {
+__device__ double el_khat_both(F val, long long S, long long Mt, const PsisPtrs &Q, PsisLds &L) {
   if (Mt < 5) return INFINITY;
   const int tid = threadIdx.x;
   double *tr = Q.tail, *tn = Q.tail + S / 2;              // [0] = the cutoff, [1 .. M] the tail ascending (M + 1 <= 0.2 S + 2 <= S / 2 from S = 7)
-  dg_sort_runs(val, S, Q.xk, Q.xi, Q.rkey, Q.ridx);
+  dg_sort_runs(val, S, Q.R);
   for (long long j = tid; j < S; j += DG_THREADS) {
     const double v = val(j);
-    const long long r0 = dg_rank(v, j, S, Q.xk, Q.xi, Q.rkey, Q.ridx) - 1;
+    const long long r0 = dg_rank(v, j, S, Q.R) - 1;
     if (r0 >= S - Mt - 1) tr[r0 - (S - Mt - 1)] = v;
     if (r0 <= Mt) tn[Mt - r0] = -v + 0.0;
   }
@@ -272,13 +72,13 @@ __device__ double el_khat_both(F val, long long S, long long Mt, const ElPtrs &Q
   for (int side = 0; side < 2; side++) {
     const double *t = side ? tn : tr;
     double ks = INFINITY;
-    if (t[Mt] - t[1] >= DBL_EPSILON / 100) {
+    if (psis_tail_varies(t + 1, Mt)) {
       const int N = (int)Mt;
       for (int j = tid; j < N; j += DG_THREADS) Q.xc[j] = t[1 + j] - t[0];
       __threadfence_block();
       __syncthreads();
       double sigma;
-      ks = el_gpdfit(Q.xc, N, Q.th, Q.lth, L, &sigma);
+      ks = psis_gpdfit(Q.xc, N, Q.th, Q.lth, L, &sigma);
     }
     k = fmax(k, ks);
     __syncthreads();
@@ -287,22 +87,34 @@ __device__ double el_khat_both(F val, long long S, long long Mt, const ElPtrs &Q
 }
 
 // the ratios of a poll: false (and NaN to report) when they hold a NaN or +inf, no finite value, or a -inf without a given r_eff
-__device__ bool el_ratio_range(const double *r, long long S, bool given, ElLds &L, double *rmax_, double *rmin_) {
+__device__ bool el_ratio_range(const double *r, long long S, bool given, PsisLds &L, double *rmax_, double *rmin_) {
   int bad = 0, low = 0;
   double rmax = -INFINITY, rmin = INFINITY;
   for (long long j = threadIdx.x; j < S; j += DG_THREADS) { const double v = r[j]; bad |= (isnan(v) || v == INFINITY); low |= (v == -INFINITY); rmax = fmax(rmax, v); rmin = fmin(rmin, v); }
-  *rmax_ = rmax = loo_block_max(rmax, L.red);
-  *rmin_ = -loo_block_max(-rmin, L.red);
+  *rmax_ = rmax = dg_block_max(rmax, L.red);
+  *rmin_ = -dg_block_max(-rmin, L.red);
   bad = __syncthreads_or(bad);
   low = __syncthreads_or(low);
   return !(bad || rmax == -INFINITY || (low && !given));
+}
+
+// r_eff (the given one, or that of exp(-r + min r) = exp(ll - max ll)) and PSIS of the finite-maximum ratios r [C][n]: the normalised log weights
+// into lwo, k_r returned
+__device__ __forceinline__ double el_psis(const double *r, double rmax, double rmin, const double *r_eff, int C, long long n, const PsisPtrs &Q, PsisLds &L,
+                                          PsisReffLds &G, double *lwo, double *reff_out) {
+  const double reff = r_eff ? *r_eff : psis_reff([&](long long j) { return exp(-r[j] + rmin); }, C, n, Q.xc, L, G);
+  auto lwv = [&](long long j) { return r[j] - rmax + 0.0; };
+  const PsisTail T = psis_tail(lwv, (long long)C * n, reff, Q, L);
+  psis_normalise(lwv, T, L, lwo);
+  *reff_out = reff;
+  return T.khat;
 }
 
 // ---- the pointwise form
 struct ElPwParams {
   const double *x, *r;        // [NP][C][n]
   const double *r_eff;        // [NP], or null: computed
-  ElWork W;
+  PsisWork W;                 // stride: psis_ws_doubles(S, EL_ROWS)
   double *out;                // [NP][3 + np]: mean, variance, sd, quantiles
   double *khat;               // [NP][EL_NK]
   double probs[EL_MAXP];
@@ -312,10 +124,13 @@ struct ElPwParams {
 
 __global__ __launch_bounds__(DG_THREADS) void k_el_pointwise(ElPwParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long el_dyn[];   // min(npad, DG_RUN) keys, then the indices (a symbol of its own, as k_mm_psis's)
-  __shared__ ElLds L;
+  __shared__ PsisLds L;
+  __shared__ PsisReffLds G;
+  __shared__ double seg[DG_THREADS + 1];
   const int tid = threadIdx.x, np = P.np;
   const long long n = P.n, S = (long long)P.C * n;
-  const ElPtrs Q = el_ptrs(P.W, S, el_dyn);
+  const PsisPtrs Q = psis_ptrs(P.W, S, el_dyn);
+  double *const lwn = Q.end, *const xs = lwn + S, *const ws = xs + S;
   for (int p = blockIdx.x; p < P.NP; p += gridDim.x) {
     const double *x = P.x + (size_t)p * S, *r = P.r + (size_t)p * S;
     double *o = P.out + (size_t)p * (3 + np), *ko = P.khat + (size_t)p * EL_NK;
@@ -326,20 +141,20 @@ __global__ __launch_bounds__(DG_THREADS) void k_el_pointwise(ElPwParams P) {
       if (tid < EL_NK) ko[tid] = NAN;
       continue;
     }
-    const double reff = P.r_eff ? P.r_eff[p] : el_reff(r, rmin, P.C, n, Q.xc, L);
-    const double k_r = el_psis(r, rmax, reff, S, Q, L, Q.lwn);
-    const double *lw = Q.lwn;
+    double reff;
+    const double k_r = el_psis(r, rmax, rmin, P.r_eff ? P.r_eff + p : nullptr, P.C, n, Q, L, G, lwn, &reff);
+    const double *lw = lwn;
     // ---- mean, then the variance about it
     double a = 0.0, lmx = -INFINITY, lmn = INFINITY;
     for (long long j = tid; j < S; j += DG_THREADS) { const double l = lw[j]; a += exp(l) * x[j]; lmx = fmax(lmx, l); lmn = fmin(lmn, l); }
-    const double mean = loo_block_sum(a, L.red);
-    lmx = loo_block_max(lmx, L.red);
-    lmn = -loo_block_max(-lmn, L.red);
+    const double mean = dg_block_sum(a, L.red);
+    lmx = dg_block_max(lmx, L.red);
+    lmn = -dg_block_max(-lmn, L.red);
     double q = 0.0;
     for (long long j = tid; j < S; j += DG_THREADS) { const double d = x[j] - mean; q += exp(lw[j]) * (d * d); }
-    const double var = loo_block_sum(q, L.red);
+    const double var = dg_block_sum(q, L.red);
     // ---- k of the mean (h = x) and of variance and sd (h = x^2)
-    const long long Mt = (long long)ceil(fmin(0.2 * (double)S, 3.0 * sqrt((double)S / reff)));
+    const long long Mt = psis_tail_len(S, reff);
     auto h1 = [&](long long j) { return x[j]; };
     auto h2 = [&](long long j) { return x[j] * x[j]; };
     auto v1 = [&](long long j) { return x[j] * exp(r[j] - rmax) + 0.0; };
@@ -350,11 +165,11 @@ __global__ __launch_bounds__(DG_THREADS) void k_el_pointwise(ElPwParams P) {
     // ---- quantiles: x sorted (ties by draw index), the weights carried along
     if (np > 0) {
       auto xv = [&](long long j) { return x[j] + 0.0; };
-      dg_sort_runs(xv, S, Q.xk, Q.xi, Q.rkey, Q.ridx);
+      dg_sort_runs(xv, S, Q.R);
       for (long long j = tid; j < S; j += DG_THREADS) {
         const double v = xv(j);
-        const long long r0 = dg_rank(v, j, S, Q.xk, Q.xi, Q.rkey, Q.ridx) - 1;
-        Q.xs[r0] = v; Q.ws[r0] = exp(lw[j]);
+        const long long r0 = dg_rank(v, j, S, Q.R) - 1;
+        xs[r0] = v; ws[r0] = exp(lw[j]);
       }
       __threadfence_block();
       __syncthreads();
@@ -362,30 +177,30 @@ __global__ __launch_bounds__(DG_THREADS) void k_el_pointwise(ElPwParams P) {
         if (tid < np) {
           const double hh = (double)(S - 1) * P.probs[tid], fl = floor(hh), g = hh - fl;
           const long long lo = (long long)fl, hi = lo + 1 < S ? lo + 1 : S - 1;
-          const double xa = Q.xs[lo], xb = Q.xs[hi], d = xb - xa;
+          const double xa = xs[lo], xb = xs[hi], d = xb - xa;
           o[3 + tid] = g >= 0.5 ? xb - d * (1.0 - g) : xa + d * g;
         }
       } else {
         // cum[j] = (the sum of the segments before j's) + (the sum within j's segment up to j), each added in index order
-        const long long seg = (S + DG_THREADS - 1) / DG_THREADS, j0 = (long long)tid * seg, j1 = j0 + seg < S ? j0 + seg : S;
+        const long long len = (S + DG_THREADS - 1) / DG_THREADS, j0 = (long long)tid * len, j1 = j0 + len < S ? j0 + len : S;
         double s = 0.0;
-        for (long long j = j0; j < j1; j++) s += Q.ws[j];
-        L.seg[tid + 1] = s;
+        for (long long j = j0; j < j1; j++) s += ws[j];
+        seg[tid + 1] = s;
         __syncthreads();
         if (tid == 0) {
-          L.seg[0] = 0.0;
-          for (int t = 1; t <= DG_THREADS; t++) L.seg[t] += L.seg[t - 1];
+          seg[0] = 0.0;
+          for (int t = 1; t <= DG_THREADS; t++) seg[t] += seg[t - 1];
         }
         __syncthreads();
-        const double pre = L.seg[tid], tot = L.seg[DG_THREADS];
+        const double pre = seg[tid], tot = seg[DG_THREADS];
         double loc = 0.0, wprev = pre / tot;
         for (long long j = j0; j < j1; j++) {
-          loc += Q.ws[j];
+          loc += ws[j];
           const double wj = (pre + loc) / tot;
           for (int i = 0; i < np; i++) {
             const double pr = P.probs[i];
             if (wj >= pr && (j == 0 || wprev < pr))
-              o[3 + i] = j == 0 ? Q.xs[0] : Q.xs[j - 1] + (Q.xs[j] - Q.xs[j - 1]) * (pr - wprev) / (wj - wprev);
+              o[3 + i] = j == 0 ? xs[0] : xs[j - 1] + (xs[j] - xs[j - 1]) * (pr - wprev) / (wj - wprev);
           }
           wprev = wj;
         }
@@ -446,14 +261,14 @@ __global__ __launch_bounds__(256) void k_el_poll_share(const DevModel *Mg, ElSha
 }
 
 // ---- the shared form
-// c[j] = sum_s X[j][s] / S, one workgroup per column, loo_block_sum's order
+// c[j] = sum_s X[j][s] / S, one workgroup per column, dg_block_sum's order
 __global__ __launch_bounds__(DG_THREADS) void k_el_colmean(const double *X, double *c, long long S, int NC) {
   __shared__ double red[DG_THREADS / 64];
   for (int j = blockIdx.x; j < NC; j += gridDim.x) {
     const double *x = X + (size_t)j * S;
     double a = 0.0;
     for (long long s = threadIdx.x; s < S; s += DG_THREADS) a += x[s];
-    const double t = loo_block_sum(a, red);
+    const double t = dg_block_sum(a, red);
     if (threadIdx.x == 0) c[j] = t / (double)S;
   }
 }
@@ -569,7 +384,7 @@ __global__ __launch_bounds__(DG_THREADS) void k_el_ess(const double *lw, double 
     const double *l = lw + (size_t)p * S;
     double a = 0.0;
     for (long long s = threadIdx.x; s < S; s += DG_THREADS) { const double wv = exp(l[s]); a += wv * wv; }
-    const double t = loo_block_sum(a, red);
+    const double t = dg_block_sum(a, red);
     if (threadIdx.x == 0) ess[p] = 1.0 / t;
   }
 }
@@ -578,7 +393,7 @@ struct ElKParams {
   const double *X;            // [NC][S] (k_el_khat)
   const double *r;            // [NP][S] raw log ratios
   const double *r_eff;        // [NP] given, or null: computed
-  ElWork W;
+  PsisWork W;                 // stride: psis_ws_doubles(S, EL_ROWS)
   double *kr, *reff;          // [NP]
   double *khat;               // [NP][NC] (k_el_khat)
   long long n;
@@ -586,9 +401,10 @@ struct ElKParams {
 };
 __global__ __launch_bounds__(DG_THREADS) void k_el_kr(ElKParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long el_dyn[];
-  __shared__ ElLds L;
+  __shared__ PsisLds L;
+  __shared__ PsisReffLds G;
   const long long S = (long long)P.C * P.n;
-  const ElPtrs Q = el_ptrs(P.W, S, el_dyn);
+  const PsisPtrs Q = psis_ptrs(P.W, S, el_dyn);
   for (int p = blockIdx.x; p < P.NP; p += gridDim.x) {
     const double *r = P.r + (size_t)p * S;
     double rmax, rmin;
@@ -596,8 +412,8 @@ __global__ __launch_bounds__(DG_THREADS) void k_el_kr(ElKParams P) {
       if (threadIdx.x == 0) { P.kr[p] = NAN; P.reff[p] = NAN; }
       continue;
     }
-    const double reff = P.r_eff ? P.r_eff[p] : el_reff(r, rmin, P.C, P.n, Q.xc, L);
-    const double k = el_psis(r, rmax, reff, S, Q, L, Q.lwn);
+    double reff;
+    const double k = el_psis(r, rmax, rmin, P.r_eff ? P.r_eff + p : nullptr, P.C, P.n, Q, L, G, Q.end, &reff);
     if (threadIdx.x == 0) { P.kr[p] = k; P.reff[p] = reff; }
     __syncthreads();
   }
@@ -605,9 +421,9 @@ __global__ __launch_bounds__(DG_THREADS) void k_el_kr(ElKParams P) {
 // khat[p][j] = k of the mean of column j under poll p's weights, after k_el_kr
 __global__ __launch_bounds__(DG_THREADS) void k_el_khat(ElKParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long el_dyn[];
-  __shared__ ElLds L;
+  __shared__ PsisLds L;
   const long long S = (long long)P.C * P.n, items = (long long)P.NP * P.NC;
-  const ElPtrs Q = el_ptrs(P.W, S, el_dyn);
+  const PsisPtrs Q = psis_ptrs(P.W, S, el_dyn);
   for (long long e = blockIdx.x; e < items; e += gridDim.x) {
     const int p = (int)(e / P.NC), j = (int)(e % P.NC);
     const double *r = P.r + (size_t)p * S, *x = P.X + (size_t)j * S;
@@ -616,8 +432,8 @@ __global__ __launch_bounds__(DG_THREADS) void k_el_khat(ElKParams P) {
     if (!isnan(k_r)) {
       double rmax = -INFINITY;
       for (long long s = threadIdx.x; s < S; s += DG_THREADS) rmax = fmax(rmax, r[s]);
-      rmax = loo_block_max(rmax, L.red);
-      const long long Mt = (long long)ceil(fmin(0.2 * (double)S, 3.0 * sqrt((double)S / reff)));
+      rmax = dg_block_max(rmax, L.red);
+      const long long Mt = psis_tail_len(S, reff);
       auto h1 = [&](long long s) { return x[s]; };
       auto v1 = [&](long long s) { return x[s] * exp(r[s] - rmax) + 0.0; };
       if (!el_plain(h1, S, L)) k = fmax(k_r, el_khat_both(v1, S, Mt, Q, L));

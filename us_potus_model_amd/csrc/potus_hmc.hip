@@ -2185,6 +2185,29 @@ size_t sorted_run_lds(long long n) {
   while (npad < n && npad < DG_RUN) npad <<= 1;
   return (size_t)npad * 12;
 }
+// ... and their runs in global memory, for `grid` workgroups of N items each: above DG_RUN items only (one run stays in LDS)
+size_t sorted_run_bytes(long long N) { return N > DG_RUN ? (size_t)N * 12 : 0; }
+int sorted_run_scratch(DevBufs &bufs, int grid, long long N, unsigned long long **rkey, unsigned **ridx, const char *what) {
+  *rkey = nullptr; *ridx = nullptr;
+  if (N <= DG_RUN) return 0;
+  if (const int rc = bufs.get(rkey, (size_t)grid * (size_t)N * 8, what)) return rc;
+  return bufs.get(ridx, (size_t)grid * (size_t)N * 4, what);
+}
+
+// The PSIS workspace (potus_psis.hpp) of `grid` workgroups over S pooled draws, each with extra_rows rows of S doubles of the kernel's own behind
+// the PSIS rows: the bytes one workgroup needs (what a budget-capped grid divides by); the buffers out of `bufs`, and the dynamic LDS of the
+// kernels that will be launched on them.
+size_t psis_work_bytes(long long S, int extra_rows) { return psis_ws_doubles(S, extra_rows) * 8 + (size_t)S * 4 + sorted_run_bytes(S); }
+int psis_work(DevBufs &bufs, int grid, long long S, int extra_rows, PsisWork &W, const char *what, std::initializer_list<const void *> kernels) {
+  W.mmax = psis_mmax(S);
+  W.stride = psis_ws_doubles(S, extra_rows);
+  int rc;
+  if ((rc = bufs.get(&W.wsd, (size_t)grid * W.stride * 8, what)) || (rc = bufs.get(&W.wsi, (size_t)grid * S * 4, what)) ||
+      (rc = sorted_run_scratch(bufs, grid, S, &W.rkey, &W.ridx, what)))
+    return rc;
+  for (const void *k : kernels) HIP_TRY(hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, (int)sorted_run_lds(S)));
+  return 0;
+}
 
 } // namespace
 
@@ -3132,16 +3155,15 @@ int diagnostics_of_columns(hipStream_t stream, const double *cols, long long n, 
   const long long N = 2ll * C * (n / 2);
   DevBufs tmp;
   double *zbuf = nullptr, *dout = nullptr;
-  unsigned long long *rkey = nullptr;
-  unsigned *ridx = nullptr;
+  unsigned long long *rkey;
+  unsigned *ridx;
   // a workgroup's scratch: two rank-normalised copies of the column, and the sorted runs when they do not fit LDS; the grid is
   // capped so that the scratch of a call stays within 768 MB whatever the number of pooled draws (a workgroup loops over columns)
-  const long long per_wg = std::max<long long>(N, 1) * (16 + (N > DG_RUN ? 12 : 0));
+  const long long per_wg = std::max<long long>(N, 1) * 16 + (long long)sorted_run_bytes(N);
   const int grid = (int)std::max<long long>(1, std::min<long long>(std::min(NC, 1024), (768ll << 20) / per_wg));
   int rc;
   if ((rc = tmp.get(&zbuf, (size_t)grid * 2 * (size_t)std::max<long long>(N, 1) * 8, what))) return rc;
-  if (N > DG_RUN && ((rc = tmp.get(&rkey, (size_t)grid * (size_t)N * 8, what)) || (rc = tmp.get(&ridx, (size_t)grid * (size_t)N * 4, what)))) return rc;
-  if ((rc = tmp.get(&dout, (size_t)NC * 2 * 8, what))) return rc;
+  if ((rc = sorted_run_scratch(tmp, grid, N, &rkey, &ridx, what)) || (rc = tmp.get(&dout, (size_t)NC * 2 * 8, what))) return rc;
   const size_t lds = sorted_run_lds(N);                // keys + split indices
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_dg_column), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   DgParams P{cols, zbuf, rkey, ridx, dout, dout + NC, n, C, NC};
@@ -3310,28 +3332,18 @@ int loo_block_polls(size_t bytes_per_poll, int n) {
 // PSIS-LOO of ll [NP][C][n] on the current device -> pointwise [NP][LOO_NPW] on the host (r_eff: host [NP] or null)
 int loo_psis(hipStream_t st, const double *ll, int NP, int C, long long n, const double *r_eff, double *pw, const char *what) {
   const long long S = (long long)C * n;
-  const int mmax = 32 + (int)std::sqrt(0.2 * (double)S + 1.0);
-  const size_t wsd_n = 2 * (size_t)S + 2 * (size_t)mmax;
-  const size_t per_wg = wsd_n * 8 + (size_t)S * 4 + (S > DG_RUN ? (size_t)S * 12 : 0);
-  const int grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(NP, 1024), LOO_BLOCK_BUDGET / 2 / per_wg));
+  const int grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(NP, 1024), LOO_BLOCK_BUDGET / 2 / psis_work_bytes(S, 0)));
   DevBufs tmp;
-  double *wsd = nullptr, *dre = nullptr, *dout = nullptr;
-  int *wsi = nullptr;
-  unsigned long long *rkey = nullptr;
-  unsigned *ridx = nullptr;
+  PsisWork W;
+  double *dre = nullptr, *dout = nullptr;
   int rc;
-  if ((rc = tmp.get(&wsd, (size_t)grid * wsd_n * 8, what)) || (rc = tmp.get(&wsi, (size_t)grid * S * 4, what)) ||
-      (rc = tmp.get(&dout, (size_t)NP * LOO_NPW * 8, what)))
-    return rc;
-  if (S > DG_RUN && ((rc = tmp.get(&rkey, (size_t)grid * S * 8, what)) || (rc = tmp.get(&ridx, (size_t)grid * S * 4, what)))) return rc;
+  if ((rc = psis_work(tmp, grid, S, 0, W, what, {reinterpret_cast<const void *>(k_loo_psis)})) || (rc = tmp.get(&dout, (size_t)NP * LOO_NPW * 8, what))) return rc;
   if (r_eff) {
     if ((rc = tmp.get(&dre, (size_t)NP * 8, what))) return rc;
     HIP_TRY(hipMemcpyAsync(dre, r_eff, (size_t)NP * 8, hipMemcpyHostToDevice, st));
   }
-  const size_t lds = sorted_run_lds(S);                // keys + indices of one sorted run
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_loo_psis), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  PsisParams P{ll, dre, wsd, wsi, rkey, ridx, dout, n, C, NP, mmax};
-  hipLaunchKernelGGL(k_loo_psis, dim3(grid), dim3(DG_THREADS), lds, st, P);
+  PsisParams P{ll, dre, W, dout, n, C, NP};
+  hipLaunchKernelGGL(k_loo_psis, dim3(grid), dim3(DG_THREADS), sorted_run_lds(S), st, P);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpyAsync(pw, dout, (size_t)NP * LOO_NPW * 8, hipMemcpyDeviceToHost, st));
   HIP_TRY(hipStreamSynchronize(st));
@@ -3460,13 +3472,12 @@ struct MmCtx {
   const char *what = "";
   Sampler *mp = nullptr;
   hipStream_t st = nullptr;
-  int C = 0, n = 0, D = 0, Dpad = 0, row = 0, ncols = 0, S = 0, pass_grid = 1, psis_grid = 1, psis_mmax = 0, maxB = 1;
+  int C = 0, n = 0, D = 0, Dpad = 0, row = 0, ncols = 0, S = 0, pass_grid = 1, psis_grid = 1, maxB = 1;
   DevBufs keep;
   const double **dchain = nullptr;
-  double *lc = nullptr, *scratch = nullptr, *part = nullptr, *mom = nullptr, *wsd = nullptr, *dre = nullptr, *dk = nullptr, *da = nullptr, *db = nullptr, *dm0 = nullptr;
-  int *dpoll = nullptr, *dsel = nullptr, *wsi = nullptr;
-  unsigned long long *rkey = nullptr;
-  unsigned *ridx = nullptr;
+  double *lc = nullptr, *scratch = nullptr, *part = nullptr, *mom = nullptr, *dre = nullptr, *dk = nullptr, *da = nullptr, *db = nullptr, *dm0 = nullptr;
+  int *dpoll = nullptr, *dsel = nullptr;
+  PsisWork psis{};
   MmPassParams *dP = nullptr;
   std::vector<int> model_index;   // poll as the output row numbers it -> the model's (day-sorted) index
   double ms[4] = {0.0, 0.0, 0.0, 0.0};
@@ -3512,22 +3523,17 @@ int mm_setup(MmCtx &x, const char *what, Sampler *mp, const std::vector<const do
   hipDeviceProp_t prop;
   if (hipGetDeviceProperties(&prop, mp->device) == hipSuccess) ncu = std::max(1, prop.multiProcessorCount);
   x.pass_grid = (int)std::max<long long>(1, std::min<long long>((long long)x.maxB * x.S, 2ll * ncu));
-  x.psis_mmax = 32 + (int)std::sqrt(0.2 * (double)x.S + 1.0);
-  const size_t wsd_n = 2 * (size_t)x.S + 2 * (size_t)x.psis_mmax;
   x.psis_grid = std::min(x.maxB, 1024);
   const size_t BD = (size_t)x.maxB * x.D;
   if ((rc = x.keep.get(&x.dchain, chains.size() * sizeof(double *), what)) || (rc = x.keep.get(&x.scratch, (size_t)x.pass_grid * mm_scratch_doubles(x.Dpad, x.ncols) * 8, what)) ||
       (rc = x.keep.get(&x.dP, sizeof(MmPassParams), what)) || (rc = x.keep.get(&x.da, BD * 8, what)) || (rc = x.keep.get(&x.db, BD * 8, what)) ||
       (rc = x.keep.get(&x.dm0, (size_t)x.D * 8, what)) || (rc = x.keep.get(&x.dpoll, (size_t)x.maxB * 4, what)) || (rc = x.keep.get(&x.dsel, (size_t)x.maxB * 4, what)) ||
       (rc = x.keep.get(&x.part, (size_t)x.nchunk() * BD * 2 * 8, what)) || (rc = x.keep.get(&x.mom, BD * 2 * 8, what)) ||
-      (rc = x.keep.get(&x.wsd, (size_t)x.psis_grid * wsd_n * 8, what)) || (rc = x.keep.get(&x.wsi, (size_t)x.psis_grid * x.S * 4, what)) ||
-      (rc = x.keep.get(&x.dre, (size_t)x.maxB * 8, what)) || (rc = x.keep.get(&x.dk, (size_t)x.maxB * 8, what)))
+      (rc = psis_work(x.keep, x.psis_grid, x.S, 0, x.psis, what, {reinterpret_cast<const void *>(k_mm_psis)})) || (rc = x.keep.get(&x.dre, (size_t)x.maxB * 8, what)) || (rc = x.keep.get(&x.dk, (size_t)x.maxB * 8, what)))
     return rc;
-  if (x.S > DG_RUN && ((rc = x.keep.get(&x.rkey, (size_t)x.psis_grid * x.S * 8, what)) || (rc = x.keep.get(&x.ridx, (size_t)x.psis_grid * x.S * 4, what)))) return rc;
   HIP_TRY(hipMemcpy(x.dchain, chains.data(), chains.size() * sizeof(double *), hipMemcpyHostToDevice));
   HIP_TRY(hipMemset(x.scratch, 0, (size_t)x.pass_grid * mm_scratch_doubles(x.Dpad, x.ncols) * 8));
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mm_pass), hipFuncAttributeMaxDynamicSharedMemorySize, (int)(mp->M.lds_doubles * 8 + sizeof(RowLds))));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mm_psis), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sorted_run_lds(x.S)));
   return 0;
 }
 
@@ -3586,7 +3592,7 @@ int mm_moments(MmCtx &x, int B, const double *w, int is_log, const double *m0, d
 // PSIS of r [B][S] (device) -> lw [B][S] (device), k (host [B]); r_eff host [B]
 int mm_psis(MmCtx &x, int B, const double *r, const double *r_eff, double *lw, double *k) {
   HIP_TRY(hipMemcpyAsync(x.dre, r_eff, (size_t)B * 8, hipMemcpyHostToDevice, x.st));
-  const PsisGenParams P{r, x.dre, x.wsd, x.wsi, x.rkey, x.ridx, lw, x.dk, (long long)x.S, B, x.psis_mmax};
+  const PsisGenParams P{r, x.dre, x.psis, lw, x.dk, (long long)x.S, B};
   if (const int rc = mm_timed(x, 2, [&] {
         hipLaunchKernelGGL(k_mm_psis, dim3(std::min(B, x.psis_grid)), dim3(DG_THREADS), sorted_run_lds(x.S), x.st, P);
         return 0;
@@ -3645,21 +3651,16 @@ int potus_psis_device(int device, const void *log_ratios, int n_polls, int n_cha
   if (const int rc_ = mm_also_device(what, device, log_weights_out, "output")) return rc_;
   // (no model: the PSIS scratch alone)
   const long long S = (long long)n_chains * n_draws;
-  const int mmax = 32 + (int)std::sqrt(0.2 * (double)S + 1.0), grid = std::min(n_polls, 1024);
-  const size_t wsd_n = 2 * (size_t)S + 2 * (size_t)mmax;
+  const int grid = std::min(n_polls, 1024);
   DevBufs tmp;
-  double *wsd = nullptr, *dre = nullptr, *dk = nullptr;
-  int *wsi = nullptr;
-  unsigned long long *rkey = nullptr;
-  unsigned *ridx = nullptr;
+  PsisWork W;
+  double *dre = nullptr, *dk = nullptr;
   int rc;
-  if ((rc = tmp.get(&wsd, (size_t)grid * wsd_n * 8, what)) || (rc = tmp.get(&wsi, (size_t)grid * S * 4, what)) || (rc = tmp.get(&dre, (size_t)n_polls * 8, what)) ||
+  if ((rc = psis_work(tmp, grid, S, 0, W, what, {reinterpret_cast<const void *>(k_mm_psis)})) || (rc = tmp.get(&dre, (size_t)n_polls * 8, what)) ||
       (rc = tmp.get(&dk, (size_t)n_polls * 8, what)))
     return rc;
-  if (S > DG_RUN && ((rc = tmp.get(&rkey, (size_t)grid * S * 8, what)) || (rc = tmp.get(&ridx, (size_t)grid * S * 4, what)))) return rc;
   HIP_TRY(hipMemcpy(dre, r_eff, (size_t)n_polls * 8, hipMemcpyHostToDevice));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mm_psis), hipFuncAttributeMaxDynamicSharedMemorySize, (int)sorted_run_lds(S)));
-  const PsisGenParams P{(const double *)log_ratios, dre, wsd, wsi, rkey, ridx, (double *)log_weights_out, dk, S, n_polls, mmax};
+  const PsisGenParams P{(const double *)log_ratios, dre, W, (double *)log_weights_out, dk, S, n_polls};
   hipLaunchKernelGGL(k_mm_psis, dim3(grid), dim3(DG_THREADS), sorted_run_lds(S), 0, P);
   HIP_TRY(hipGetLastError());
   HIP_TRY(hipMemcpy(khat_out, dk, (size_t)n_polls * 8, hipMemcpyDeviceToHost));
@@ -3947,19 +3948,6 @@ namespace {
 constexpr size_t EL_PART_BUDGET = 128ull << 20;   // the chunk partials of one k_el_shared launch
 thread_local double g_el_ms[4] = {0.0, 0.0, 0.0, 0.0};   // the calling thread's last call: pointwise form, column means and product, chunk sum and ess, diagnostic
 
-// the sort kernels' scratch for `grid` workgroups of S draws
-int el_work(DevBufs &tmp, int grid, long long S, ElWork &W, const char *what) {
-  W.mmax = 32 + (int)std::sqrt(0.2 * (double)S + 1.0);
-  W.rkey = nullptr; W.ridx = nullptr;
-  int rc;
-  if ((rc = tmp.get(&W.wsd, (size_t)grid * el_ws_doubles(S, W.mmax) * 8, what)) || (rc = tmp.get(&W.wsi, (size_t)grid * S * 4, what))) return rc;
-  if (S > DG_RUN && ((rc = tmp.get(&W.rkey, (size_t)grid * S * 8, what)) || (rc = tmp.get(&W.ridx, (size_t)grid * S * 4, what)))) return rc;
-  return 0;
-}
-size_t el_work_bytes(long long S) {
-  const int mmax = 32 + (int)std::sqrt(0.2 * (double)S + 1.0);
-  return el_ws_doubles(S, mmax) * 8 + (size_t)S * 4 + (S > DG_RUN ? (size_t)S * 12 : 0);
-}
 int el_check_sizes(const char *what, long long C, long long n) {
   if (C < 1 || n < 4) return fail(POTUS_ERR_ARG, "%s: %lld chains of %lld draws (at least one chain, four draws per chain)", what, C, n);
   if (2 * C > DG_MAXCH) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld chains pooled (at most %d)", what, C, DG_MAXCH / 2);
@@ -4029,12 +4017,12 @@ int potus_e_loo_device(int device, const void *x, const void *log_ratios, int n_
   if (const int rc_ = mm_also_device(what, device, log_ratios, "block of log ratios")) return rc_;
   std::fill(g_el_ms, g_el_ms + 4, 0.0);
   const long long S = (long long)n_chains * n_draws;
-  const int grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(n_polls, 1024), LOO_BLOCK_BUDGET / 2 / el_work_bytes(S)));
+  const int grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min(n_polls, 1024), LOO_BLOCK_BUDGET / 2 / psis_work_bytes(S, EL_ROWS)));
   DevBufs tmp;
   ElPwParams P{};
   double *dre = nullptr, *dout = nullptr, *dk = nullptr;
   int rc;
-  if ((rc = el_work(tmp, grid, S, P.W, what)) || (rc = tmp.get(&dout, (size_t)n_polls * (3 + n_probs) * 8, what)) || (rc = tmp.get(&dk, (size_t)n_polls * EL_NK * 8, what))) return rc;
+  if ((rc = psis_work(tmp, grid, S, EL_ROWS, P.W, what, {reinterpret_cast<const void *>(k_el_pointwise)})) || (rc = tmp.get(&dout, (size_t)n_polls * (3 + n_probs) * 8, what)) || (rc = tmp.get(&dk, (size_t)n_polls * EL_NK * 8, what))) return rc;
   if (r_eff) {
     if ((rc = tmp.get(&dre, (size_t)n_polls * 8, what))) return rc;
     HIP_TRY(hipMemcpy(dre, r_eff, (size_t)n_polls * 8, hipMemcpyHostToDevice));
@@ -4043,7 +4031,6 @@ int potus_e_loo_device(int device, const void *x, const void *log_ratios, int n_
   for (int i = 0; i < n_probs; i++) P.probs[i] = probs[i];
   P.n = n_draws; P.C = n_chains; P.NP = n_polls; P.np = n_probs;
   const size_t lds = sorted_run_lds(S);
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_el_pointwise), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   EventTimer t;
   HIP_TRY(t.made);
   HIP_TRY(t.start(0));
@@ -4106,10 +4093,10 @@ int potus_e_loo_shared_device(int device, const void *X, int n_cols, const void 
   if (!log_ratios) return 0;
   // ---- the diagnostic: k_r (and r_eff) per poll, then with diag = 1 the k of every mean
   const long long items = diag ? (long long)n_polls * n_cols : n_polls;
-  const int grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min<long long>(items, 1024), LOO_BLOCK_BUDGET / 2 / el_work_bytes(S)));
+  const int grid = (int)std::max<size_t>(1, std::min<size_t>((size_t)std::min<long long>(items, 1024), LOO_BLOCK_BUDGET / 2 / psis_work_bytes(S, EL_ROWS)));
   ElKParams K{};
   double *dre = nullptr, *dkr = nullptr, *dreff = nullptr, *dkh = nullptr;
-  if ((rc = el_work(tmp, grid, S, K.W, what)) || (rc = tmp.get(&dkr, (size_t)n_polls * 8, what)) || (rc = tmp.get(&dreff, (size_t)n_polls * 8, what))) return rc;
+  if ((rc = psis_work(tmp, grid, S, EL_ROWS, K.W, what, {reinterpret_cast<const void *>(k_el_kr), reinterpret_cast<const void *>(k_el_khat)})) || (rc = tmp.get(&dkr, (size_t)n_polls * 8, what)) || (rc = tmp.get(&dreff, (size_t)n_polls * 8, what))) return rc;
   if (r_eff) {
     if ((rc = tmp.get(&dre, (size_t)n_polls * 8, what))) return rc;
     HIP_TRY(hipMemcpy(dre, r_eff, (size_t)n_polls * 8, hipMemcpyHostToDevice));
@@ -4118,8 +4105,6 @@ int potus_e_loo_shared_device(int device, const void *X, int n_cols, const void 
   K.X = Xd; K.r = (const double *)log_ratios; K.r_eff = dre; K.kr = dkr; K.reff = dreff; K.khat = dkh;
   K.n = n_draws; K.C = n_chains; K.NP = n_polls; K.NC = n_cols;
   const size_t lds = sorted_run_lds(S);
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_el_kr), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_el_khat), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   HIP_TRY(t.start(0));
   hipLaunchKernelGGL(k_el_kr, dim3(std::min(n_polls, grid)), dim3(DG_THREADS), lds, 0, K);
   if (diag) hipLaunchKernelGGL(k_el_khat, dim3(grid), dim3(DG_THREADS), lds, 0, K);
@@ -4152,14 +4137,10 @@ int monitor_of_columns(hipStream_t stream, const double *cols, long long n, int 
   MnParams P{};
   int rc;
   // k_dg_column's scratch per workgroup (its runs hold the C middle draws too when n is odd) and its cap on the grid
-  const long long per_wg = N * 16 + (M > DG_RUN ? M * 12 : 0);
+  const long long per_wg = N * 16 + (long long)sorted_run_bytes(M);
   const int grid = (int)std::max<long long>(1, std::min<long long>(std::min(NC, 1024), (768ll << 20) / per_wg));
   if ((rc = tmp.get(&P.zbuf, (size_t)grid * 2 * (size_t)N * 8, what))) return rc;
-  if (M > DG_RUN) {
-    if ((rc = tmp.get(&P.rkey, (size_t)grid * (size_t)M * 8, what))) return rc;
-    if ((rc = tmp.get(&P.ridx, (size_t)grid * (size_t)M * 4, what))) return rc;
-  }
-  if ((rc = tmp.get(&P.out, (size_t)NC * W * 8, what))) return rc;
+  if ((rc = sorted_run_scratch(tmp, grid, M, &P.rkey, &P.ridx, what)) || (rc = tmp.get(&P.out, (size_t)NC * W * 8, what))) return rc;
   const size_t lds = sorted_run_lds(M);                // keys + indices
   HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_mn_column), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
   P.cols = cols; P.n = n; P.C = C; P.NC = NC; P.n_probs = n_probs;

@@ -11,15 +11,12 @@
 //   1. k_loo_loglik: one 256-thread workgroup per saved draw rebuilds the output row (wa_build_row, as k_sbc_ranks does) and writes the
 //      log-likelihoods of a block of polls as one row [draw][chain][poll]; k_dg_transpose turns the block into [poll][chain][draw]
 //      (coalesced stores on both sides);
-//   2. k_loo_psis: one workgroup per poll over its S pooled draws: r_eff (loo::relative_eff: Geyer's initial positive, then monotone
-//      sequence of the chain-averaged autocorrelations of exp(ll - max ll), lag by lag as far as the sequence reads them), the tail of the
-//      largest importance ratios by the order statistics of potus_diag.hpp (sorted runs, ranks by binary search: any S up to 512 pooled
-//      chains), gpdfit (Zhang & Stephens 2009 with loo's prior), the smoothed and truncated tail, self-normalised weights and
+//   2. k_loo_psis: one workgroup per poll over its S pooled draws: r_eff of exp(ll - max ll), the smoothed and truncated tail of the
+//      ratios -ll (potus_psis.hpp: psis_reff, psis_tail; any S up to 512 pooled chains), then here the self-normalised weights and
 //      elpd_loo_i, p_loo_i, looic_i, k-hat_i.  Every sum runs in a fixed order (lane-strided, then a DPP tree, then the waves in order):
 //      same block, same bytes.
 #pragma once
-#include <float.h>
-#include "potus_diag.hpp"
+#include "potus_psis.hpp"
 
 #define LOO_GH 16             // Gauss-Hermite nodes of the integrated form (the error against scipy.integrate.quad)
 #define LOO_MODE_CAP 100      // most trips of the safeguarded mode search (it stops when a step no longer moves the mode: 3 - 60 trips)
@@ -109,51 +106,22 @@ __global__ __launch_bounds__(256) void k_loo_loglik(const DevModel *Mg, LlParams
   }
 }
 
-// ---- reductions over the DG_THREADS threads of a workgroup in a fixed order (every thread gets the result)
-__device__ __forceinline__ double loo_block_sum(double v, double *red) {
-  const double s = dpp_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  double t = 0.0;
-  for (int w = 0; w < DG_THREADS / 64; w++) t += red[w];
-  __syncthreads();
-  return t;
-}
-__device__ __forceinline__ double loo_block_max(double v, double *red) {
-  for (int o = 32; o > 0; o >>= 1) v = fmax(v, __shfl_xor(v, o));
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-  __syncthreads();
-  double t = -INFINITY;
-  for (int w = 0; w < DG_THREADS / 64; w++) t = fmax(t, red[w]);
-  __syncthreads();
-  return t;
-}
-
 struct PsisParams {
   const double *ll;           // [NP][C][n]
   const double *r_eff;        // [NP], or null: computed
-  double *wsd;                // [gridDim.x][2 S + 2 mmax]: centred weights, then gpdfit's sample | tail | grid of theta | profile log-likelihoods
-  int *wsi;                   // [gridDim.x][S] ranks of the draws among the ratios
-  unsigned long long *rkey;   // [gridDim.x][S] sorted runs when S > DG_RUN
-  unsigned *ridx;
+  PsisWork W;
   double *out;                // [NP][LOO_NPW]
   long long n;                // draws per chain
-  int C, NP, mmax;
+  int C, NP;
 };
 
 __global__ __launch_bounds__(DG_THREADS) void k_loo_psis(PsisParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long xk[];   // as k_dg_column: min(npad, DG_RUN) keys, then the indices
-  __shared__ double cmean[DG_MAXCH / 2], cvar[DG_MAXCH / 2], rho[DG_LAGS];
-  __shared__ double red[DG_THREADS / 64], sc[8];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, C = P.C;
+  __shared__ PsisLds L;
+  __shared__ PsisReffLds G;
+  const int tid = threadIdx.x, C = P.C;
   const long long n = P.n, S = (long long)C * n;
-  double *xc = P.wsd + (size_t)blockIdx.x * (2 * (size_t)S + 2 * (size_t)P.mmax), *tail = xc + S, *th = tail + S, *lth = th + P.mmax;
-  int *rnk = P.wsi + (size_t)blockIdx.x * (size_t)S;
-  unsigned long long *rkey = P.rkey ? P.rkey + (size_t)blockIdx.x * (size_t)S : nullptr;
-  unsigned *ridx = P.ridx ? P.ridx + (size_t)blockIdx.x * (size_t)S : nullptr;
-  int npad_all = 1;
-  while (npad_all < S && npad_all < DG_RUN) npad_all <<= 1;
-  unsigned *xi = (unsigned *)(xk + npad_all);
+  const PsisPtrs Q = psis_ptrs(P.W, S, xk);
   for (int p = blockIdx.x; p < P.NP; p += gridDim.x) {
     const double *ll = P.ll + (size_t)p * S;
     double *o = P.out + (size_t)p * LOO_NPW;
@@ -167,167 +135,29 @@ __global__ __launch_bounds__(DG_THREADS) void k_loo_psis(PsisParams P) {
     }
     double mx = -INFINITY, mn = INFINITY;
     for (long long j = tid; j < S; j += DG_THREADS) { mx = fmax(mx, ll[j]); mn = fmin(mn, ll[j]); }
-    mx = loo_block_max(mx, red);
-    mn = -loo_block_max(-mn, red);
-    // ---- r_eff = ESS / S of x = exp(ll - max ll), chains not split
-    double reff;
-    if (P.r_eff) reff = P.r_eff[p];
-    else {
-      for (long long j = tid; j < S; j += DG_THREADS) xc[j] = exp(ll[j] - mx);
-      __threadfence_block();
-      __syncthreads();
-      for (int c = w; c < C; c += DG_THREADS / 64) {       // one wave per chain: mean, biased autocovariance at lag 0
-        double s = 0.0;
-        for (long long i = lane; i < n; i += 64) s += xc[(size_t)c * n + i];
-        const double m = dpp_wave_sum(s) / (double)n;
-        double q = 0.0;
-        for (long long i = lane; i < n; i += 64) { const double d = xc[(size_t)c * n + i] - m; q += d * d; }
-        const double v = dpp_wave_sum(q) / (double)n;
-        if (lane == 0) { cmean[c] = m; cvar[c] = v; }
-      }
-      __syncthreads();
-      for (long long j = tid; j < S; j += DG_THREADS) xc[j] -= cmean[j / n];
-      if (tid == 0) {
-        double a = 0.0, mm = 0.0;
-        for (int c = 0; c < C; c++) { a += cvar[c]; mm += cmean[c]; }
-        const double mean_var = a / C * (double)n / (double)(n - 1);
-        double var_plus = mean_var * (double)(n - 1) / (double)n;
-        if (C > 1) {
-          mm /= C;
-          double b = 0.0;
-          for (int c = 0; c < C; c++) b += (cmean[c] - mm) * (cmean[c] - mm);
-          var_plus += b / (C - 1);
-        }
-        sc[0] = mean_var; sc[1] = var_plus;
-        sc[2] = 0.0; sc[3] = 0.0; sc[4] = 0.0; sc[5] = 0.0;   // sum of rho over lags < max_t, previous pair, rho(max_t), done
-      }
-      __threadfence_block();
-      __syncthreads();
-      const double mean_var = sc[0], var_plus = sc[1];
-      for (long long t0 = 0; t0 < n; t0 += DG_LAGS) {
-        for (int lg = w; lg < DG_LAGS; lg += DG_THREADS / 64) {
-          const long long t = t0 + lg;
-          double s = 0.0;
-          if (t < n)
-            for (int c = 0; c < C; c++) {
-              const double *xcc = xc + (size_t)c * n;
-              double a = 0.0;
-              for (long long i = lane; i + t < n; i += 64) a += xcc[i] * xcc[i + t];
-              s += dpp_wave_sum(a) / (double)n;                // biased autocovariance of chain c at lag t
-            }
-          if (lane == 0) rho[lg] = t < n ? 1.0 - (mean_var - s / C) / var_plus : NAN;
-        }
-        __syncthreads();
-        if (tid == 0) {
-          double tsum = sc[2], prev = sc[3];
-          for (int lg = 0; lg < DG_LAGS; lg += 2) {
-            const long long t = t0 + lg;
-            const double even = t == 0 ? 1.0 : rho[lg], odd = rho[lg + 1], pair = even + odd;
-            if (t < n - 5 && pair > 0) {                   // not the last pair: kept, then made monotone
-              double e = even, od = odd;
-              if (t >= 2 && pair > prev) { e = prev / 2; od = e; }
-              tsum += e; tsum += od;
-              prev = e + od;
-            } else {                                       // the last pair: max_t = t
-              sc[4] = (t == 0 || pair >= 0 || even > 0) ? even : 0.0;
-              sc[5] = 1.0;
-              break;
-            }
-          }
-          sc[2] = tsum; sc[3] = prev;
-        }
-        __syncthreads();
-        if (sc[5] != 0.0) break;
-      }
-      if (tid == 0) {
-        double tau = -1.0 + 2.0 * sc[2] + sc[4];
-        tau = fmax(tau, 1.0 / log10((double)S));
-        sc[6] = ((double)S / tau) / (double)S;
-      }
-      __syncthreads();
-      reff = sc[6];
-      __syncthreads();
-    }
+    mx = dg_block_max(mx, L.red);
+    mn = -dg_block_max(-mn, L.red);
+    const double reff = P.r_eff ? P.r_eff[p] : psis_reff([&](long long j) { return exp(ll[j] - mx); }, C, n, Q.xc, L, G);
     // ---- PSIS of the ratios r = -ll: lw = r - max r
     const double rmax = -mn;
     auto lwv = [&](long long j) { return -ll[j] - rmax + 0.0; };
-    const long long Mt = (long long)ceil(fmin(0.2 * (double)S, 3.0 * sqrt((double)S / reff)));
-    double khat = INFINITY;
-    bool smooth = false;
-    double *tl = tail + 1;                                  // tail[0] = the cutoff, tail[1 .. M] = the M largest lw, ascending
-    if (Mt >= 5) {
-      dg_sort_runs(lwv, S, xk, xi, rkey, ridx);
-      for (long long j = tid; j < S; j += DG_THREADS) {
-        const double v = lwv(j);
-        const long long r0 = dg_rank(v, j, S, xk, xi, rkey, ridx) - 1;
-        rnk[j] = (int)r0;
-        if (r0 >= S - Mt - 1) tail[r0 - (S - Mt - 1)] = v;
-      }
-      __threadfence_block();
-      __syncthreads();
-      if (tl[Mt - 1] - tl[0] >= DBL_EPSILON / 100) {
-        smooth = true;
-        const int N = (int)Mt, m = 30 + (int)floor(sqrt((double)N));
-        const double ec = exp(tail[0]);
-        double *xs = xc;                                   // gpdfit's sample exp(tail) - exp(cutoff), ascending
-        for (int j = tid; j < N; j += DG_THREADS) xs[j] = exp(tl[j]) - ec;
-        __threadfence_block();
-        __syncthreads();
-        const double xstar = xs[(int)floor(N / 4.0 + 0.5) - 1];
-        for (int jj = w; jj < m; jj += DG_THREADS / 64) {  // one wave per grid point theta_j
-          const double theta = 1.0 / xs[N - 1] + (1.0 - sqrt((double)m / (jj + 0.5))) / 3.0 / xstar;
-          double a = 0.0;
-          for (int i = lane; i < N; i += 64) a += log1p(-theta * xs[i]);
-          const double kj = dpp_wave_sum(a) / N;
-          if (lane == 0) { th[jj] = theta; lth[jj] = N * (log(-theta / kj) - kj - 1.0); }
-        }
-        __threadfence_block();
-        __syncthreads();
-        if (tid == 0) {                                    // theta-hat = sum_j softmax(l)_j theta_j
-          double lm = -INFINITY;
-          for (int jj = 0; jj < m; jj++) lm = fmax(lm, lth[jj]);
-          double s = 0.0;
-          for (int jj = 0; jj < m; jj++) s += exp(lth[jj] - lm);
-          const double lse = lm + log(s);
-          double thh = 0.0;
-          for (int jj = 0; jj < m; jj++) thh += th[jj] * exp(lth[jj] - lse);
-          sc[7] = thh;
-        }
-        __syncthreads();
-        const double thh = sc[7];
-        double a = 0.0;
-        for (int j = tid; j < N; j += DG_THREADS) a += log1p(-thh * xs[j]);
-        double k = loo_block_sum(a, red) / N;
-        const double sigma = -k / thh;
-        k = k * N / (N + 10) + 10 * 0.5 / (N + 10);     // loo's weakly informative prior
-        if (isnan(k)) k = INFINITY;
-        khat = k;
-        if (isfinite(k))
-          for (int j = tid; j < N; j += DG_THREADS) tl[j] = log(sigma * expm1(-k * log1p(-(j + 0.5) / N)) / k + ec);
-        __threadfence_block();
-        __syncthreads();
-      }
-    }
-    auto lwf = [&](long long j) {                          // smoothed, then truncated at max lw = 0
-      double v = lwv(j);
-      if (smooth && rnk[j] >= S - Mt) v = tl[rnk[j] - (S - Mt)];
-      return fmin(v, 0.0);
-    };
-    // ---- self-normalised weights; elpd_loo_i = logsumexp(ll + lw), lpd_i = logsumexp(ll) - log S
+    const PsisTail T = psis_tail(lwv, S, reff, Q, L);
+    auto lwf = [&](long long j) { return T.lw(lwv(j), j); };
+    // ---- self-normalised weights; elpd_loo_i = logsumexp(ll + lw), lpd_i = logsumexp(ll) - log S (one pass for both sums, no weights stored)
     double m1 = -INFINITY;
     for (long long j = tid; j < S; j += DG_THREADS) m1 = fmax(m1, lwf(j));
-    m1 = loo_block_max(m1, red);
+    m1 = dg_block_max(m1, L.red);
     double s1 = 0.0, s3 = 0.0;
     for (long long j = tid; j < S; j += DG_THREADS) { s1 += exp(lwf(j) - m1); s3 += exp(ll[j] - mx); }
-    const double lse_w = m1 + log(loo_block_sum(s1, red));
-    const double lpd = mx + log(loo_block_sum(s3, red)) - log((double)S);
+    const double lse_w = m1 + log(dg_block_sum(s1, L.red));
+    const double lpd = mx + log(dg_block_sum(s3, L.red)) - log((double)S);
     double m2 = -INFINITY;
     for (long long j = tid; j < S; j += DG_THREADS) m2 = fmax(m2, ll[j] + (lwf(j) - lse_w));
-    m2 = loo_block_max(m2, red);
+    m2 = dg_block_max(m2, L.red);
     double s2 = 0.0;
     for (long long j = tid; j < S; j += DG_THREADS) s2 += exp(ll[j] + (lwf(j) - lse_w) - m2);
-    const double elpd = m2 + log(loo_block_sum(s2, red));
-    if (tid == 0) { o[0] = elpd; o[1] = lpd - elpd; o[2] = -2.0 * elpd; o[3] = khat; o[4] = reff; }
+    const double elpd = m2 + log(dg_block_sum(s2, L.red));
+    if (tid == 0) { o[0] = elpd; o[1] = lpd - elpd; o[2] = -2.0 * elpd; o[3] = T.khat; o[4] = reff; }
     __syncthreads();
   }
 }

@@ -16,9 +16,8 @@
 //                  Partials [chunk][b][2][D]; k_mm_moments_sum adds the chunks in order.  The chunk is a constant, the draws of a
 //                  chunk are summed in order: an entry's bytes depend on (w[b], theta[:, j], m0[j]) alone, not on the other polls or the grid.
 //   k_mm_ratio     the log ratios of a round from lp, ll and lp0: start, candidate or split (see MmRatioParams).
-//   k_mm_psis      PSIS of general log ratios, one workgroup per poll: k_loo_psis's tail, gpdfit, smoothing and truncation RESTATED on
-//                  r instead of -ll, with the normalised log weights written out.  Restated, not shared: k_loo_psis holds its ratios as
-//                  a lambda over ll and interleaves r_eff and lpd with the PSIS steps; factoring it would have changed its code.
+//   k_mm_psis      PSIS of general log ratios, one workgroup per poll: potus_psis.hpp's tail step and normalisation (k_loo_psis's, on r
+//                  instead of -ll), with the normalised log weights written out.
 //   k_mm_final     elpd[b] = logsumexp_s(ll[b][s] + lw[b][s]), fixed order.
 #pragma once
 #include "potus_loo.hpp"
@@ -194,112 +193,35 @@ __global__ __launch_bounds__(256) void k_mm_ratio(MmRatioParams P) {
 struct PsisGenParams {
   const double *r;            // [NP][S]
   const double *r_eff;        // [NP]
-  double *wsd;                // [gridDim.x][2 S + 2 mmax], as PsisParams
-  int *wsi;                   // [gridDim.x][S]
-  unsigned long long *rkey;   // [gridDim.x][S] sorted runs when S > DG_RUN
-  unsigned *ridx;
+  PsisWork W;
   double *lw;                 // [NP][S] normalised log weights
   double *khat;               // [NP]
   long long S;
-  int NP, mmax;
+  int NP;
 };
 // A NaN or +inf ratio, or no finite ratio at all: k = NaN and NaN weights (the rules reject a NaN k).
 __global__ __launch_bounds__(DG_THREADS) void k_mm_psis(PsisGenParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long mk[];   // min(npad, DG_RUN) keys, then the indices (its own symbol: see DESIGN.md 4q)
-  __shared__ double red[DG_THREADS / 64], sc[8];
-  const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6;
+  __shared__ PsisLds L;
+  const int tid = threadIdx.x;
   const long long S = P.S;
-  double *xc = P.wsd + (size_t)blockIdx.x * (2 * (size_t)S + 2 * (size_t)P.mmax), *tail = xc + S, *th = tail + S, *lth = th + P.mmax;
-  int *rnk = P.wsi + (size_t)blockIdx.x * (size_t)S;
-  unsigned long long *rkey = P.rkey ? P.rkey + (size_t)blockIdx.x * (size_t)S : nullptr;
-  unsigned *ridx = P.ridx ? P.ridx + (size_t)blockIdx.x * (size_t)S : nullptr;
-  int npad_all = 1;
-  while (npad_all < S && npad_all < DG_RUN) npad_all <<= 1;
-  unsigned *xi = (unsigned *)(mk + npad_all);
+  const PsisPtrs Q = psis_ptrs(P.W, S, mk);
   for (int p = blockIdx.x; p < P.NP; p += gridDim.x) {
     const double *r = P.r + (size_t)p * S;
     double *lwo = P.lw + (size_t)p * S;
     int bad = 0;
     double rmax = -INFINITY;
     for (long long j = tid; j < S; j += DG_THREADS) { const double v = r[j]; bad |= (isnan(v) || v == INFINITY); rmax = fmax(rmax, v); }
-    rmax = loo_block_max(rmax, red);
+    rmax = dg_block_max(rmax, L.red);
     if (__syncthreads_or(bad) || rmax == -INFINITY) {
       for (long long j = tid; j < S; j += DG_THREADS) lwo[j] = NAN;
       if (tid == 0) P.khat[p] = NAN;
       continue;
     }
-    const double reff = P.r_eff[p];
     auto lwv = [&](long long j) { return r[j] - rmax + 0.0; };
-    const long long Mt = (long long)ceil(fmin(0.2 * (double)S, 3.0 * sqrt((double)S / reff)));
-    double khat = INFINITY;
-    bool smooth = false;
-    double *tl = tail + 1;                                  // tail[0] = the cutoff, tail[1 .. M] = the M largest lw, ascending
-    if (Mt >= 5) {
-      dg_sort_runs(lwv, S, mk, xi, rkey, ridx);
-      for (long long j = tid; j < S; j += DG_THREADS) {
-        const double v = lwv(j);
-        const long long r0 = dg_rank(v, j, S, mk, xi, rkey, ridx) - 1;
-        rnk[j] = (int)r0;
-        if (r0 >= S - Mt - 1) tail[r0 - (S - Mt - 1)] = v;
-      }
-      __threadfence_block();
-      __syncthreads();
-      if (tl[Mt - 1] - tl[0] >= DBL_EPSILON / 100) {
-        smooth = true;
-        const int N = (int)Mt, m = 30 + (int)floor(sqrt((double)N));
-        const double ec = exp(tail[0]);
-        double *xs = xc;                                   // gpdfit's sample exp(tail) - exp(cutoff), ascending
-        for (int j = tid; j < N; j += DG_THREADS) xs[j] = exp(tl[j]) - ec;
-        __threadfence_block();
-        __syncthreads();
-        const double xstar = xs[(int)floor(N / 4.0 + 0.5) - 1];
-        for (int jj = w; jj < m; jj += DG_THREADS / 64) {  // one wave per grid point theta_j
-          const double theta = 1.0 / xs[N - 1] + (1.0 - sqrt((double)m / (jj + 0.5))) / 3.0 / xstar;
-          double a = 0.0;
-          for (int i = lane; i < N; i += 64) a += log1p(-theta * xs[i]);
-          const double kj = dpp_wave_sum(a) / N;
-          if (lane == 0) { th[jj] = theta; lth[jj] = N * (log(-theta / kj) - kj - 1.0); }
-        }
-        __threadfence_block();
-        __syncthreads();
-        if (tid == 0) {                                    // theta-hat = sum_j softmax(l)_j theta_j
-          double lm = -INFINITY;
-          for (int jj = 0; jj < m; jj++) lm = fmax(lm, lth[jj]);
-          double s = 0.0;
-          for (int jj = 0; jj < m; jj++) s += exp(lth[jj] - lm);
-          const double lse = lm + log(s);
-          double thh = 0.0;
-          for (int jj = 0; jj < m; jj++) thh += th[jj] * exp(lth[jj] - lse);
-          sc[7] = thh;
-        }
-        __syncthreads();
-        const double thh = sc[7];
-        double a = 0.0;
-        for (int j = tid; j < N; j += DG_THREADS) a += log1p(-thh * xs[j]);
-        double k = loo_block_sum(a, red) / N;
-        const double sigma = -k / thh;
-        k = k * N / (N + 10) + 10 * 0.5 / (N + 10);     // loo's weakly informative prior
-        if (isnan(k)) k = INFINITY;
-        khat = k;
-        if (isfinite(k))
-          for (int j = tid; j < N; j += DG_THREADS) tl[j] = log(sigma * expm1(-k * log1p(-(j + 0.5) / N)) / k + ec);
-        __threadfence_block();
-        __syncthreads();
-      }
-    }
-    auto lwf = [&](long long j) {                          // smoothed, then truncated at max lw = 0
-      double v = lwv(j);
-      if (smooth && rnk[j] >= S - Mt) v = tl[rnk[j] - (S - Mt)];
-      return fmin(v, 0.0);
-    };
-    double m1 = -INFINITY;
-    for (long long j = tid; j < S; j += DG_THREADS) m1 = fmax(m1, lwf(j));
-    m1 = loo_block_max(m1, red);
-    double s1 = 0.0;
-    for (long long j = tid; j < S; j += DG_THREADS) s1 += exp(lwf(j) - m1);
-    const double lse_w = m1 + log(loo_block_sum(s1, red));
-    for (long long j = tid; j < S; j += DG_THREADS) lwo[j] = lwf(j) - lse_w;
-    if (tid == 0) P.khat[p] = khat;
+    const PsisTail T = psis_tail(lwv, S, P.r_eff[p], Q, L);
+    psis_normalise(lwv, T, L, lwo);
+    if (tid == 0) P.khat[p] = T.khat;
     __syncthreads();
   }
 }
@@ -312,10 +234,10 @@ __global__ __launch_bounds__(DG_THREADS) void k_mm_final(const double *ll, const
     const double *l = ll + (size_t)p * S, *v = lw + (size_t)p * S;
     double m2 = -INFINITY;
     for (long long j = tid; j < S; j += DG_THREADS) m2 = fmax(m2, l[j] + v[j]);
-    m2 = loo_block_max(m2, red);
+    m2 = dg_block_max(m2, red);
     double s2 = 0.0;
     for (long long j = tid; j < S; j += DG_THREADS) s2 += exp(l[j] + v[j] - m2);
-    const double e = m2 + log(loo_block_sum(s2, red));
+    const double e = m2 + log(dg_block_sum(s2, red));
     if (tid == 0) elpd[p] = e;
   }
 }

@@ -38,20 +38,6 @@ struct MnParams {
 __device__ __forceinline__ double mn_all_value(const double *x, long long n, int C, long long h, long long N, long long j) {
   return j < N ? dg_split_value(x, n, C, h, j) : x[(size_t)(j - N) * n + h] + 0.0;
 }
-// k-th smallest (0-based) of the M values the last dg_sort_runs sorted
-__device__ __forceinline__ double mn_order(long long M, long long k, const unsigned long long *xk, const unsigned long long *rkey) {
-  return ps_unkey(M <= DG_RUN ? xk[k] : dg_select(rkey, M, k));
-}
-// sum over the workgroup in a fixed order (a DPP tree per wave, then the waves in order), returned in every thread
-__device__ __forceinline__ double mn_block_sum(double v, double *red) {
-  const double s = dpp_wave_sum(v);
-  if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = s;
-  __syncthreads();
-  double t = 0.0;
-  for (int i = 0; i < DG_THREADS / 64; i++) t += red[i];
-  __syncthreads();
-  return t;
-}
 
 __global__ __launch_bounds__(DG_THREADS) void k_mn_column(MnParams P) {
   extern __shared__ __attribute__((aligned(16))) unsigned long long xk[];   // min(npad, DG_RUN) keys, then as many indices
@@ -66,11 +52,7 @@ __global__ __launch_bounds__(DG_THREADS) void k_mn_column(MnParams P) {
   const long long N = (long long)C2 * h, M = (long long)C * n;   // split draws, all draws
   const bool odd = (n & 1) != 0, ranked = h >= 2;                // below two draws per half there is no R-hat and no ESS
   double *z = P.zbuf + (size_t)blockIdx.x * 2 * (size_t)(N > 0 ? N : 1), *zf = z + N;
-  unsigned long long *rkey = P.rkey ? P.rkey + (size_t)blockIdx.x * (size_t)M : nullptr;
-  unsigned *ridx = P.ridx ? P.ridx + (size_t)blockIdx.x * (size_t)M : nullptr;
-  int npad_all = 1;
-  while (npad_all < M && npad_all < DG_RUN) npad_all <<= 1;
-  unsigned *xi = (unsigned *)(xk + npad_all);
+  const DgRuns R = dg_runs(xk, M, P.rkey, P.ridx);
   for (int col = blockIdx.x; col < P.NC; col += gridDim.x) {
     const double *x = P.cols + (size_t)col * C * n;
     double *o = P.out + (size_t)col * W;
@@ -84,12 +66,12 @@ __global__ __launch_bounds__(DG_THREADS) void k_mn_column(MnParams P) {
     // ---- moments over all draws
     double s = 0.0;
     for (long long j = tid; j < M; j += DG_THREADS) s += aval(j);
-    const double mean = mn_block_sum(s, red) / (double)M;
+    const double mean = dg_block_sum(s, red) / (double)M;
     double q = 0.0;
     for (long long j = tid; j < M; j += DG_THREADS) { const double d = aval(j) - mean; q += d * d; }
-    const double sd = sqrt(mn_block_sum(q, red) / (double)(M - 1));
+    const double sd = sqrt(dg_block_sum(q, red) / (double)(M - 1));
     // ---- sort 1: all draws
-    dg_sort_runs(aval, M, xk, xi, rkey, ridx);
+    dg_sort_runs(aval, M, R);
     if (tid < MN_NORD) {
       long long k = -1;
       if (tid < 2 * P.n_probs) k = ps_q7_index(M, prob[tid >> 1], tid & 1);
@@ -98,7 +80,7 @@ __global__ __launch_bounds__(DG_THREADS) void k_mn_column(MnParams P) {
       else if (tid == 2 * MN_MAXPROBS + 5) k = M / 2;
       else if (tid == 2 * MN_MAXPROBS + 6) k = 0;
       else if (tid == 2 * MN_MAXPROBS + 7) k = M - 1;
-      if (k >= 0) ord[tid] = mn_order(M, k, xk, rkey);
+      if (k >= 0) ord[tid] = dg_order(M, k, R);
     }
     __syncthreads();
     const double *tl = ord + 2 * MN_MAXPROBS;
@@ -109,25 +91,25 @@ __global__ __launch_bounds__(DG_THREADS) void k_mn_column(MnParams P) {
       if (tid == 0) { o[0] = tl[6]; o[1] = 0.0; o[2] = 0.0; for (int i = 3; i < MN_NSTATS; i++) o[i] = NAN; }
       continue;
     }
-    if (ranked && !odd) dg_scores(aval, N, xk, xi, rkey, ridx, z);
+    if (ranked && !odd) dg_scores(aval, N, R, z);
     __syncthreads();
     // ---- sort 2: |x - median| of all draws
     auto afold = [&](long long j) { return fabs(aval(j) - med) + 0.0; };
-    dg_sort_runs(afold, M, xk, xi, rkey, ridx);
-    if (tid < 2) ord[tid] = mn_order(M, tid == 0 ? (M - 1) / 2 : M / 2, xk, rkey);
-    if (ranked && !odd) dg_scores(afold, N, xk, xi, rkey, ridx, zf);
+    dg_sort_runs(afold, M, R);
+    if (tid < 2) ord[tid] = dg_order(M, tid == 0 ? (M - 1) / 2 : M / 2, R);
+    if (ranked && !odd) dg_scores(afold, N, R, zf);
     __syncthreads();
     const double mad = 1.4826 * (0.5 * (ord[0] + ord[1]));
     if (ranked && odd) {                               // the split draws on their own, with their own median: k_dg_column's two sorts
-      dg_sort_runs(val, N, xk, xi, rkey, ridx);
-      if (tid == 0) sc[0] = 0.5 * (mn_order(N, (N - 1) / 2, xk, rkey) + mn_order(N, N / 2, xk, rkey));
-      dg_scores(val, N, xk, xi, rkey, ridx, z);
+      dg_sort_runs(val, N, R);
+      if (tid == 0) sc[0] = 0.5 * (dg_order(N, (N - 1) / 2, R) + dg_order(N, N / 2, R));
+      dg_scores(val, N, R, z);
       __syncthreads();
       const double smed = sc[0];
       __syncthreads();
       auto fval = [&](long long j) { return fabs(dg_split_value(x, n, C, h, j) - smed) + 0.0; };
-      dg_sort_runs(fval, N, xk, xi, rkey, ridx);
-      dg_scores(fval, N, xk, xi, rkey, ridx, zf);
+      dg_sort_runs(fval, N, R);
+      dg_scores(fval, N, R, zf);
     }
     __threadfence_block();
     __syncthreads();

@@ -14,7 +14,7 @@
 //   groups      per (group, draw) B = sum r, X = sum r^2, N = sum k over the group's polls with n > 0 in ascending poll number, one after the
 //               other, at k = y_i (realised) and k = y_rep_is (replicated); compiled without contraction into fused multiply-adds.
 //   PIT         lo_i = sum_s w_is [y_rep_is < y_i], eq_i = sum_s w_is [y_rep_is = y_i]: w = exp(lw) (a weight of -inf is 0, NaN gives NaN) in
-//               loo_block_sum's order, or without weights the exact counts divided by S.
+//               dg_block_sum's order, or without weights the exact counts divided by S.
 // Kernels:
 //   k_ppc_rep          k_loo_loglik's sibling: one 256-thread workgroup per draw rebuilds the row, one thread per poll draws y_rep -> [draw][chain][poll]
 //   k_ppc_groups       one thread per (group, draw), draws fastest (every load and store coalesced): the six accumulators of the cell are loaded,
@@ -148,8 +148,8 @@ __global__ __launch_bounds__(DG_THREADS) void k_ppc_group_stats(const double *ac
       so += a; sr += b;
       gt += b > a ? 1.0 : 0.0; eq += b == a ? 1.0 : 0.0; lt += b < a ? 1.0 : 0.0;
     }
-    so = loo_block_sum(so, red); sr = loo_block_sum(sr, red);
-    gt = loo_block_sum(gt, red); eq = loo_block_sum(eq, red); lt = loo_block_sum(lt, red);
+    so = dg_block_sum(so, red); sr = dg_block_sum(sr, red);
+    gt = dg_block_sum(gt, red); eq = dg_block_sum(eq, red); lt = dg_block_sum(lt, red);
     if (threadIdx.x == 0) {
       o[0] = so / (double)S; o[1] = sr / (double)S;
       o[2] = (double)(unsigned long long)gt; o[3] = (double)(unsigned long long)eq; o[4] = (double)(unsigned long long)lt;
@@ -170,8 +170,8 @@ __global__ __launch_bounds__(DG_THREADS) void k_ppc_pit(const double *yrep, cons
       a += w * (v < yi ? 1.0 : 0.0);
       b += w * (v == yi ? 1.0 : 0.0);
     }
-    a = loo_block_sum(a, red);
-    b = loo_block_sum(b, red);
+    a = dg_block_sum(a, red);
+    b = dg_block_sum(b, red);
     if (threadIdx.x == 0) { out[2 * p] = l ? a : a / (double)S; out[2 * p + 1] = l ? b : b / (double)S; }
   }
 }
