@@ -43,8 +43,9 @@ WAVES, CW_DAY, CW_POLL, DW4_MAXAVG = 8, 30, 45, 26      # waves per member; the 
 
 
 # ------------------------------------------------------------------------------------------------------------ designs
-def design(S, T, K, variant, per_day, expect, seed=SEED, P=5, extra=()):
-    """per_day: (p, n) for every day, or a function of the 1-based day; extra: [(day, state, count)] more polls of one state on one day (1-based)."""
+def design(S, T, K, variant, per_day, expect, seed=SEED, P=5, extra=(), pollsters=None):
+    """per_day: (p, n) for every day, or a function of the 1-based day; extra: [(day, state, count)] more polls of one state on one day (1-based);
+    pollsters: a function of (state polls, national polls) that returns the 1-based poll_state and poll_national to overwrite synthetic.make's with."""
     pn = [per_day(t) if callable(per_day) else per_day for t in range(1, T + 1)]
     day_state = [t for t, (p, _) in enumerate(pn, 1) for _ in range(p)]
     state = [i % S + 1 for p, _ in pn for i in range(p)]
@@ -55,6 +56,10 @@ def design(S, T, K, variant, per_day, expect, seed=SEED, P=5, extra=()):
     data = synthetic.make(S=S, T=T, N_state=len(day_state), N_national=len(day_national), P=P, seed=seed, variant=variant)
     i32 = lambda a: np.asarray(a, dtype=np.int32)
     data.update(day_state=i32(day_state), state=i32(state), day_national=i32(day_national))
+    if pollsters is not None:
+        of_state, of_national = pollsters(len(day_state), len(day_national))
+        assert len(of_state) == len(day_state) and len(of_national) == len(day_national)
+        data.update(poll_state=i32(of_state), poll_national=i32(of_national))
     return dict(data=data, variant=variant, K=K, seed=seed, **expect)
 
 

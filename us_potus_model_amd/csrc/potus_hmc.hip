@@ -1149,7 +1149,7 @@ int build_model(Sampler *sp, const potus_data *d) {
   }
   for (int t = 0; t < T; t++) day_ptr[t + 1] += day_ptr[t];
 
-  // per-day gathers: days balanced over the 16 waves (longest-processing-time first); each wave gets
+  // per-day gathers: days balanced over the 8 waves (PT_NW; longest-processing-time first); each wave gets
   // the polls of its days as one contiguous entry list (index, day, state)
   std::vector<int> order, load(PT_NW, 0), npolls_w(PT_NW, 0);
   for (int t = 0; t < T; t++) if (day_ptr[t + 1] > day_ptr[t]) order.push_back(t);
@@ -4987,9 +4987,10 @@ void potus_default_optimize_opts(potus_optimize_opts *o) {
 namespace {
 // what every call that deals paths to a handle's data sets refuses first: the handle's layout, then the number of paths
 int paths_check(const Sampler *sp, const char *what, int n_paths, const char *noun = "n_paths") {
+  // a model beyond the one-workgroup kernels first: "cus_per_chain = 1" is no advice for it, that handle cannot be created
+  if (!sp->k1_unsupported.empty()) return fail(POTUS_ERR_UNSUPPORTED, "%s: %s", what, sp->k1_unsupported.c_str());
   if (sp->K != 1) return fail(POTUS_ERR_UNSUPPORTED, "%s: needs one workgroup per chain (cus_per_chain = 1); this handle runs %d per chain", what, sp->K);
   if (sp->dense) return fail(POTUS_ERR_UNSUPPORTED, "%s: the dense metric is not supported (metric = POTUS_METRIC_DIAG only)", what);
-  if (!sp->k1_unsupported.empty()) return fail(POTUS_ERR_UNSUPPORTED, "%s: %s", what, sp->k1_unsupported.c_str());
   if (n_paths <= 0) return fail(POTUS_ERR_ARG, "%s: %s = %d, at least 1", what, noun, n_paths);
   if (sp->n_ds && n_paths % sp->n_ds) return fail(POTUS_ERR_ARG, "%s: %s = %d is not a multiple of the handle's %d data sets", what, noun, n_paths, sp->n_ds);
   return 0;

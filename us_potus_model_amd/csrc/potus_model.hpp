@@ -586,7 +586,7 @@ __device__ __forceinline__ double model_pass(CMp M_in, ldp lds, const PassStatic
     if (sg_kind == 0) { const double qv = s_mid[sg_index - o_c]; pol.g_fin(sg_vg, sg_scale * sum - qv, qv, sg_gt); }
     else if (tid < M->nseg) { if (sg_kind == 1) s_gs[sg_index] = sum; else s_ge[sg_index] = sum; }
     const int nseg = M->nseg;
-    for (int seg = tid + PT_THREADS; seg < nseg; seg += PT_THREADS) {   // only with more than 1024 segments
+    for (int seg = tid + PT_THREADS; seg < nseg; seg += PT_THREADS) {   // only with more than 512 (PT_THREADS) segments
       const int AS_C *sc = as_c(M->sched);
       const int a = sc[M->c_segptr + seg], b = sc[M->c_segptr + seg + 1], kind = sc[M->c_segkind + seg], index = sc[M->c_segidx + seg];
       double s2 = 0.0;
