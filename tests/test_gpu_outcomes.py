@@ -15,6 +15,9 @@ from us_potus_model_amd.sampler import Handle, PotusError, run_many
 pytestmark = pytest.mark.gpu
 DP, I32 = C.POINTER(C.c_double), C.POINTER(C.c_int32)
 KEYS = ("ev_hist", "tipping", "joint", "below_actual")
+# day ranges of the 254 days of the 2016 design for k_oc_days, which cuts them in tiles of 64: one tile less a day, exactly, and a day; the
+# same from day 1; the last 65 and 64 days; two days across the edge of the second tile
+DAY_RANGES_254 = ((0, 63), (0, 64), (0, 65), (1, 65), (189, 254), (190, 254), (127, 129))
 
 
 @pytest.fixture(scope="module", autouse=True)
@@ -157,6 +160,12 @@ def test_fitted_draws_equal_the_restatement(fitted, name):
         assert np.array_equal(getattr(sub, k), want[k][3:9]), k
     last = h.outcomes(ev, days=(int(h.data["T"]) - 1, int(h.data["T"])))
     assert np.array_equal(last.joint[0], want["joint"][-1]) and last.below_actual is None
+    if int(h.data["T"]) == 254:                          # k_oc_days at the edges of its tiles of 64 days
+        for d0, d1 in DAY_RANGES_254:
+            sub = oc.outcomes([h], ev, actual=actual, days=(d0, d1))
+            assert sub.days == (d0, d1) and sub.n_draws == got.n_draws
+            for k in KEYS:
+                assert np.array_equal(getattr(sub, k), want[k][d0:d1]), (d0, d1, k)
 
 
 # 6. consistency with potus_posterior_summary on the same handle (save_warmup = 0: both pool the same rows)

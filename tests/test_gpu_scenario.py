@@ -12,6 +12,7 @@ import pytest
 import outcomes_ref
 import scenario_ref as ref
 from conftest import second_device
+from test_gpu_outcomes import DAY_RANGES_254
 from us_potus_model_amd import outcomes as oc, scenario as sc
 from us_potus_model_amd.sampler import Handle, PotusError, run_many
 
@@ -251,6 +252,22 @@ def test_fitted_draws_equal_the_restatement(fitted, name):
         assert sub.n_kept == n and sub.mean.tobytes() == got.mean[d0:d1].tobytes() and sub.cov.tobytes() == got.cov[d0:d1].tobytes(), (d0, d1)
         for k in COUNTS:
             assert np.array_equal(getattr(sub.outcomes, k), getattr(got.outcomes, k)[d0:d1]), (d0, d1, k)
+    if T == 254:
+        # k_oc_days at the edges of its tiles of 64 days, the condition day outside the range every time (cut as a one-day block of its own):
+        # election day for the ranges that end before it, day 0 -- state i above its median there -- for the two that hold it
+        first = {i: (float(np.median(ps[:, 0, i])), None)}
+        want0 = ref.scenario(ps, w, 0, *_bounds(first, S), ev=ev)
+        full0 = sc.scenario([h], ev, given=first, day=0)
+        assert 0 < want0["n_kept"] < nd
+        _assert_counts(full0, want0, "2016, condition on day 0")
+        for d0, d1 in DAY_RANGES_254:
+            g, cd, full = (given, T - 1, got) if d1 < T else (first, 0, full0)
+            assert not d0 <= cd < d1
+            sub = sc.scenario([h], ev, given=g, day=cd, days=(d0, d1))
+            assert sub.n_kept == full.n_kept and sub.days == (d0, d1) and sub.cond_day == cd
+            assert sub.mean.tobytes() == full.mean[d0:d1].tobytes() and sub.cov.tobytes() == full.cov[d0:d1].tobytes(), (d0, d1)
+            for k in COUNTS:
+                assert np.array_equal(getattr(sub.outcomes, k), getattr(full.outcomes, k)[d0:d1]), (d0, d1, k)
 
 
 @pytest.mark.parametrize("name", ["small_full", "2016"])

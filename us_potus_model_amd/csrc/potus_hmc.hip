@@ -4310,7 +4310,7 @@ int potus_outcomes_timing(double *ms) {
 // ---------------------------------------------------------------------------------------------- conditional forecasts (potus_scenario.hpp)
 namespace {
 thread_local double g_sc_ms[5] = {0.0, 0.0, 0.0, 0.0, 0.0};   // the last call of this thread (potus_scenario_timing)
-constexpr size_t SC_SCRATCH_BUDGET = (size_t)256 << 20;        // nat and the chunk partials of one block of days
+constexpr size_t SC_SCRATCH_BUDGET = (size_t)256 << 20;        // nat and the chunk partials of one block of days (POTUS_SCENARIO_SCRATCH_BUDGET, bytes: tests)
 
 struct ScOut { long long *n_kept; double *mean, *cov; long long *ev_hist, *tipping, *joint; };
 
@@ -4388,7 +4388,9 @@ int sc_compute(const char *what, hipStream_t st, const double *items, long long 
     if (n > 65535ll * SC_CHUNK) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld kept draws (the moments take at most %lld)", what, n, 65535ll * SC_CHUNK);
     const int nchunks = (int)((n + SC_CHUNK - 1) / SC_CHUNK);
     const size_t per_day = ((size_t)n + (size_t)nchunks * (C + (want_cov ? (size_t)C * C : 0))) * 8;
-    const int dblk = (int)std::min<size_t>((size_t)n_days, std::max<size_t>(1, SC_SCRATCH_BUDGET / per_day));
+    size_t budget = SC_SCRATCH_BUDGET;
+    if (const char *e = getenv("POTUS_SCENARIO_SCRATCH_BUDGET")) budget = std::max<size_t>(1, (size_t)atoll(e));
+    const int dblk = (int)std::min<size_t>((size_t)n_days, std::max<size_t>(1, budget / per_day));
     double *scratch = nullptr, *dmean = nullptr, *dcov = nullptr;
     if (const int rc_ = tmp.get(&scratch, per_day * dblk, what)) return rc_;
     if (const int rc_ = tmp.get(&dmean, n_mean * 8, what)) return rc_;
