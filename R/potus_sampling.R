@@ -338,6 +338,56 @@ potus_timeline <- function(data, keep_state, keep_national, ev, mu_b_prior = NUL
        electoral_votes = aperm(array(r$ev, c(5, nd, n)), 3:1), n_draws = r$n_draws)
 }
 
+# ---- prior sensitivity by refit (us_potus_model_amd/sensitivity.py is the same in Python; DESIGN.md section 4t) ----
+# A grid of prior scales fitted as chains of ONE handle and compared with the baseline on the device.  scales: a named list of factor vectors,
+# list(sigma_c = c(0.5, 2), mu_b_T_scale = 3): the data list's own value of the scale times each factor.  Setting 1 is the data as given; with
+# null = TRUE setting 2 is a second copy of it with other chains (its distance to setting 1 is the Monte-Carlo floor); then one setting per
+# (scale, factor), or with product = TRUE the full factorial of the factor vectors.  days: c(first, last), 1-based, default election day alone.
+# Returns list(labels, scales = [n, 9], factors = [n, 9], distance = [n, days, S + 2, 3] (w1, ks, cjs of the S state scores, the national vote
+# and the electoral votes of a draw, against setting 1), n_draws = [n], and potus_timeline's state, national and electoral_votes per setting).
+.potus_scale_names <- c("sigma_c", "sigma_m", "sigma_pop", "sigma_measure_noise_national", "sigma_measure_noise_state", "sigma_e_bias",
+                        "random_walk_scale", "mu_b_T_scale", "polling_bias_scale")
+potus_prior_grid <- function(data, scales, ev, product = FALSE, null = TRUE, variant = c("full", "no_mode_adjustment"), chains_per_setting = 4,
+                             iter_warmup = 1000, iter_sampling = 1000, days = NULL, ev_to_win = 270L, seed = 1843, device = 0) {
+  variant <- match.arg(variant)
+  stopifnot(all(names(scales) %in% .potus_scale_names), all(is.finite(unlist(scales))), all(unlist(scales) > 0))
+  base <- vapply(.potus_scale_names, function(nm) if (is.null(data[[nm]])) 0 else as.double(data[[nm]]), double(1))
+  rows <- list(rep(1, 9)); labels <- "baseline"
+  if (null) { rows <- c(rows, list(rep(1, 9))); labels <- c(labels, "null copy") }
+  one <- function(nms, vals) { f <- rep(1, 9); f[match(nms, .potus_scale_names)] <- vals; f }
+  if (product) {
+    combos <- expand.grid(rev(scales))[, rev(seq_along(scales)), drop = FALSE]      # the first scale varies slowest
+    for (i in seq_len(nrow(combos))) {
+      rows <- c(rows, list(one(names(scales), as.double(combos[i, ]))))
+      labels <- c(labels, paste(sprintf("%s x %g", names(scales), as.double(combos[i, ])), collapse = ", "))
+    }
+  } else for (nm in names(scales)) for (v in scales[[nm]]) { rows <- c(rows, list(one(nm, v))); labels <- c(labels, sprintf("%s x %g", nm, v)) }
+  factors <- do.call(rbind, rows); n <- nrow(factors)
+  sc <- sweep(factors, 2, base, `*`)
+  S <- as.integer(data$S); T <- as.integer(data$T)
+  days <- if (is.null(days)) c(T, T) else as.integer(days)
+  nd <- days[2] - days[1] + 1L
+  counts <- function(v) as.integer(rep(as.integer(v), n))                            # [n][polls], row-major: every setting sees every poll
+  res <- .potus_create(data, variant, c(n * chains_per_setting, 0L, iter_warmup, iter_sampling, 10L, as.integer(device), 0L, 1L, 0L, 0L, 0L, 0L),
+                       c(0.8, 0.05, 0.75, 10, 1, 2, seed))
+  .potus_check(res$status)
+  on.exit(.C("potus_R_destroy", res$handle, status = integer(1)))
+  .potus_check(.C("potus_R_set_datasets_grid", res$handle, n, counts(data$n_democrat_state), counts(data$n_democrat_national),
+                  counts(data$n_two_share_state), counts(data$n_two_share_national), c(0L, 0L, 1L), double(1), double(1), as.double(t(sc)),
+                  status = integer(1))$status)
+  .potus_check(.C("potus_R_init", res$handle, status = integer(1))$status)
+  .potus_check(.C("potus_R_run", res$handle, as.integer(iter_warmup + iter_sampling), status = integer(1))$status)
+  g <- .C("potus_R_grid_compare", res$handle, c(0L, days[1] - 1L, days[2], as.integer(ev_to_win)), as.double(ev), out = double(n * nd * (S + 2) * 3),
+          n_draws = integer(n), status = integer(1))
+  .potus_check(g$status)
+  r <- .C("potus_R_timeline", res$handle, days[1] - 1L, days[2], as.double(ev), as.integer(ev_to_win), state = double(n * nd * S * 4),
+          national = double(n * nd * 4), ev = double(n * nd * 5), n_draws = integer(n), status = integer(1))
+  .potus_check(r$status)
+  list(labels = labels, scales = sc, factors = factors, distance = aperm(array(g$out, c(3, S + 2, nd, n)), 4:1), n_draws = g$n_draws,
+       state = aperm(array(r$state, c(4, S, nd, n)), 4:1), national = aperm(array(r$national, c(4, nd, n)), 3:1),
+       electoral_votes = aperm(array(r$ev, c(5, nd, n)), 3:1))
+}
+
 # ---- PSIS-LOO (us_potus_model_amd/loo.py is the same in Python; DESIGN.md section 4e) ----
 # What fit$loo() gives a cmdstanr user with a log_lik generated quantity, computed on the device over every chain of the fit (post-warm-up
 # draws).  integrate = TRUE integrates each poll's own noise coordinate out of its likelihood (plain PSIS-LOO meets high Pareto k there, since

@@ -365,6 +365,54 @@ int potus_set_datasets(int handle, int n_datasets, const int32_t *n_democrat_sta
 int potus_set_datasets_ex(int handle, int n_datasets, const int32_t *n_democrat_state, const int32_t *n_democrat_national,
                           const int32_t *n_two_share_state, const int32_t *n_two_share_national,
                           const double *mu_b_prior /*[n][S] or NULL*/, const double *mu_b_T_scale /*[n] or NULL*/);
+/* ---- prior sensitivity by refit: the settings of a grid of prior scales as the data sets of one handle ----
+ * potus_set_datasets_ex with one more thing that may differ between the data sets: the nine hand-set scales of potus_data, scales
+ * [n][POTUS_N_SCALES] in the order sigma_c, sigma_m, sigma_pop, sigma_measure_noise_national, sigma_measure_noise_state, sigma_e_bias,
+ * random_walk_scale, mu_b_T_scale, polling_bias_scale; NULL = potus_set_datasets_ex.  It is a superset of that call, so one handle can hold
+ * run dates x settings.  Giving both mu_b_T_scale[] and scales is refused (POTUS_ERR_ARG): scales[][7] is that scale.  Every scale must be
+ * positive and finite (POTUS_ERR_ARG, naming the data set and the scale), and the covariance scaled by it must factor, as for potus_create;
+ * for the no-mode variant sigma_m, sigma_pop and sigma_e_bias are ignored, as potus_create ignores them.  Preconditions and refusals are
+ * potus_set_datasets_ex's.  With scales every data set gets, besides what potus_set_datasets_ex gives it, its own sigma fields, the sigma
+ * of every poll, the scales of the pollster / mode / population segments, L_W with its row L_W' w, L_T, L_B and the ratios of the three
+ * factors, all built by the code potus_create uses; sizes, offsets, the LDS layout and the schedule do not depend on a scale and stay the
+ * handle's (checked, not assumed).  The contract is the timeline's: chain c of the handle holds the bytes of a stand-alone handle created on
+ * that data set's data with chain_id_offset = c.  Every call that takes a handle of potus_set_datasets_ex takes this one and works with the
+ * chain's or the data set's model: potus_write_array[_device], potus_timeline*, potus_cv_*, potus_optimize, potus_laplace, potus_pathfinder,
+ * potus_advi.  potus_sbc_ranks, potus_constrain and potus_simulate_prior refuse it as they refuse potus_set_datasets_ex's; so do the pooled
+ * calls. */
+#define POTUS_N_SCALES 9
+int potus_set_datasets_grid(int handle, int n_datasets, const int32_t *n_democrat_state, const int32_t *n_democrat_national,
+                            const int32_t *n_two_share_state, const int32_t *n_two_share_national,
+                            const double *mu_b_prior /*[n][S] or NULL*/, const double *mu_b_T_scale /*[n] or NULL*/,
+                            const double *scales /*[n][POTUS_N_SCALES] or NULL*/);
+/* The distance between two sets of draws, per column (potus_sens.hpp, k_sg_distance).  a [n_a][n_cols] and b [n_b][n_cols] are blocks in the
+ * memory of GPU `device`, draw-major: the layout of a data set's slice of potus_timeline_scores_device.  out [n_cols][3] (host) = w1, ks, cjs:
+ *   x_1 < ... < x_m are the distinct values of the union of the two samples.
+ *   P_j = #{a <= x_j} / n_a.  Q_j is likewise for b.
+ *   Delta_j = x_{j+1} - x_j for j < m.
+ *   w1  = sum_j Delta_j |P_j - Q_j|.  This is the Wasserstein-1 distance, in the column's own units.
+ *   ks  = max_j |P_j - Q_j|.
+ *   cjs = max(c(a, b), c(-a, -b)), defined as follows.
+ *     c(a, b) = sqrt(max(0, C(P||Q) + C(Q||P)) / sum_j Delta_j (P_j + Q_j)).
+ *     C(P||Q) = sum_j Delta_j P_j log2(P_j / ((P_j + Q_j)/2)) + (1 / (2 ln 2)) sum_j Delta_j (Q_j - P_j), with 0 * log 0 = 0.
+ *     c = 0 when m = 1.
+ *     This is the cumulative Jensen-Shannon distance of Nguyen & Vemuri (2015), which Kallioinen et al. (2023) use for power-scaling
+ *     sensitivity.
+ *   A non-finite value in either sample of a column makes that column's three outputs NaN, and no other column's.
+ * Both samples of a column are sorted in LDS: n_a + n_b <= 16 384, more is refused with POTUS_ERR_UNSUPPORTED before the device is touched.
+ * Every sum runs in an order fixed by n_a and n_b: a column has the same bytes alone and among any number of others. */
+int potus_ecdf_distance_device(int device, const void *a, int n_a, const void *b, int n_b, int n_cols, double *out /*[n_cols][3]*/);
+/* Every data set of a handle against data set `base` (0-based), over the post-warm-up draws and per day of [day_begin, day_end): the three
+ * distances above for S + 2 columns -- the S state scores (predicted_score), the state_weights-weighted national vote and the Democratic
+ * electoral votes sum_s ev[s] 1[score > 0.5] of a draw.  out [n_datasets][days][S + 2][3]; n_draws_out [n_datasets] as potus_timeline's.
+ * Row `base` is 0, 0, 0.  A data set with a failed chain gets NaN, and so does every row if `base` failed; the others are unaffected.
+ * Equal to potus_ecdf_distance_device on the slices of potus_timeline_scores_device.  Refusals are potus_timeline's, and base outside
+ * [0, n_datasets) (POTUS_ERR_ARG); 2 x draws per data set <= 16 384. */
+int potus_grid_compare(int handle, int base, int day_begin, int day_end, const double *ev /*[S]*/, int ev_to_win,
+                       double *out, int32_t *n_draws_out);
+/* Milliseconds (HIP events) of the calling thread's last potus_grid_compare: the scores kernel, the distance kernel; after
+ * potus_ecdf_distance_device: 0, the distance kernel. */
+int potus_grid_timing(double *ms /*[2]*/);
 /* Per data set of a handle (of potus_set_datasets or potus_set_datasets_ex; a handle without either is one data set) and per day of
  * [day_begin, day_end) (0-based), over the data set's post-warm-up draws (warm-up rows of save_warmup = 1 are left out):
  *   state_out [n][days][S][4]   low 2.5 %, high 97.5 %, mean, P(> 0.5) of predicted_score; quantiles are R's type 7
@@ -386,8 +434,9 @@ int potus_timeline_timing(double *ms /*[2]*/);
 /* ---- exact cross-validation: held-out polls under the draws of the data set that did not see them ----
  * A fold of K-fold cross-validation, or a run date of leave-future-out, is a data set of potus_set_datasets_ex whose held-out polls have
  * n_two_share = 0.  For every (data set, poll) pair the masks name, the calls evaluate log p(y | n, draw) on the data set's post-warm-up draws
- * (warm-up rows of save_warmup = 1 are left out) with the data set's own model -- its prior and scale -- and the y, n and sigma of the data
- * given to potus_create.  integrate = 1: the poll's noise coordinate integrated over its N(0,1) prior, the exact predictive density of a poll
+ * (warm-up rows of save_warmup = 1 are left out) with the data set's own model -- its prior and scales -- and the y and n of the data
+ * given to potus_create.  The poll's measurement-noise sigma is the data set's own: on a handle of potus_set_datasets_grid the one of its
+ * scales, on every other handle the one given to potus_create.  integrate = 1: the poll's noise coordinate integrated over its N(0,1) prior, the exact predictive density of a poll
  * the data set has not seen; integrate = 0: at the draw's own noise coordinate.  Handles of potus_set_datasets[_ex], and a plain handle,
  * which counts as one data set (in-sample values: those of potus_log_lik_device, byte for byte).  Refused before any kernel runs: a NULL mask or
  * output (POTUS_ERR_ARG; out_device = NULL is the exception below), a handle that is not initialised or has no post-warm-up draw saved
@@ -856,6 +905,11 @@ void potus_R_set_datasets_ex(int *handle, int *n_datasets, int *n_democrat_state
                              int *has_prior, double *mu_b_prior, int *has_scale, double *mu_b_T_scale, int *status);
 void potus_R_timeline(int *handle, int *day_begin, int *day_end, double *ev, int *ev_to_win, double *state_out, double *natl_out, double *ev_out,
                       int *n_draws_out, int *status);
+void potus_R_set_datasets_grid(int *handle, int *n_datasets, int *n_democrat_state, int *n_democrat_national, int *n_two_share_state, int *n_two_share_national,
+                               int *has /*[3]: mu_b_prior, mu_b_T_scale, scales given*/, double *mu_b_prior, double *mu_b_T_scale, double *scales /*[n][9]*/,
+                               int *status);
+void potus_R_grid_compare(int *handle, int *iargs /*[4]: base (0-based), day_begin, day_end, ev_to_win*/, double *ev, double *out /*[n][days][S + 2][3]*/,
+                          int *n_draws_out, int *status);
 void potus_R_cv_lpd(int *handle, int *held_state, int *held_national, int *integrate, double *lpd_out, int *n_draws_out, int *status);
 void potus_R_optimize(int *handle, int *iopts /*[7]: jacobian, history_size, iter, path_offset, n_paths, q0 given, rows wanted*/,
                       double *dopts /*[6]: init_alpha, tol_obj, tol_rel_obj, tol_grad, tol_rel_grad, tol_param*/, double *q0, double *q_out, double *lp_out,

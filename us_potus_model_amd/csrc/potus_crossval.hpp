@@ -4,8 +4,9 @@
 // A fold of K-fold cross-validation, and a run date of leave-future-out, is a data set of potus_set_datasets_ex: the polls it holds out
 // stay in the design with n_two_share = 0.  The held-out log predictive density of poll k under data set d is
 //   lpd[d][k] = log (1 / n) sum_draws p(y_k | n_k, draw),
-// with the data set's own model (its prior and scale) and the y, n, log C(n, y) and sigma of the data given to potus_create -- the data
-// set's own y and n of such a poll are 0.  integrate = 1 integrates the poll's noise coordinate over its N(0,1) prior (the fold never saw
+// with the data set's own model (its prior and scales, the poll's measurement-noise sigma among them: on a handle of
+// potus_set_datasets_grid that is the data set's, elsewhere the one given to potus_create) and the y, n and log C(n, y) of the data given to
+// potus_create -- the data set's own y and n of such a poll are 0.  integrate = 1 integrates the poll's noise coordinate over its N(0,1) prior (the fold never saw
 // the poll, so the prior IS its posterior there): the exact predictive density, by loo_poll_ll's Gauss-Hermite form.  integrate = 0
 // evaluates at the draw's own noise coordinate (checkable to the bit against the logit_pi columns).
 // Kernels:
@@ -30,7 +31,7 @@
 struct CvParams {
   RowSrc src;
   int ncols, n_post, chains_per_ds, integrate;   // post-warm-up rows src.first .. src.first + n_post - 1 of every chain
-  const double *pd0;     // [4][Npad] y, n, unadjusted, sigma of the data given to potus_create, in the model's poll order
+  const double *pd0;     // [4][Npad] y, n, unadjusted (and sigma, not read: the data set's own is) of the data given to potus_create, in the model's poll order
   const double *lc;      // [Npoll] log C(n, y) of that data, same order
   const int *off;        // [n_datasets + 1] offsets of the data sets' held lists
   const int *held;       // [off[n_datasets]] model poll index of every pair
@@ -63,7 +64,7 @@ __global__ __launch_bounds__(256) void k_cv_loglik(const DevModel *Mg, CvParams 
       const int s = M.pi[i], qi = M.pi[5 * Np + i];
       double eta = row_poll_eta(M, c, row, P.pd0 + 2 * Np, i);
       eta += s == M.S ? row[c.nat_polling_bias] : row[c.polling_bias + s];
-      P.out[(size_t)(j - P.p0) * nd + at] = P.lc[i] + loo_poll_ll(P.pd0[i], P.pd0[Np + i], eta, P.pd0[3 * Np + i], q[qi], P.integrate);
+      P.out[(size_t)(j - P.p0) * nd + at] = P.lc[i] + loo_poll_ll(P.pd0[i], P.pd0[Np + i], eta, M.pd[3 * Np + i], q[qi], P.integrate);
     }
     __syncthreads();
   }

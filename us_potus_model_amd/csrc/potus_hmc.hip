@@ -759,6 +759,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, c
 #include "potus_outcomes.hpp"   // joint election outcomes: EV histogram, tipping point, joint win counts
 #include "potus_scenario.hpp"   // conditional forecasts and the covariance of the state scores
 #include "potus_timeline.hpp"   // run dates as the data sets of one handle: their rows, scores and summaries
+#include "potus_sens.hpp"       // prior sensitivity by refit: the distance between two sets of draws, per column
 #include "potus_crossval.hpp"   // exact cross-validation: held-out polls under the draws of the data set that did not see them
 #include "potus_loo_mm.hpp"     // moment matching for PSIS-LOO: the pass under an affine map, weighted moments, PSIS of general ratios
 #include "potus_loo_mm_rules.hpp"
@@ -935,6 +936,9 @@ struct Sampler {
   bool ds_ex = false, ds_own_prior = false;
   std::vector<double> h_mat, h_cov, h_w_raw;   // host copies for the per-data-set models: the packed mat, state_covariance_0, state_weights as given
   double h_nsd = 0, h_rw_scale = 0, h_T_scale = 0;   // sqrt(w' cov w), random_walk_scale, mu_b_T_scale
+  double h_scales[9] = {};                             // the nine scales as given to potus_create (data_scales)
+  std::vector<int> h_seg_src;                          // per segment of seg_scale: the scale it holds, -1 = 1.0 (seg_scales)
+  bool ds_grid = false;                                // potus_set_datasets_grid with scales: every data set has all of these of its own
   int chains_per_ds() const { return n_ds ? R.chains / n_ds : R.chains; }
   // potus_laplace: the rows [lp__, six NaN, x] of the last call's draws, [lap_modes][lap_draws][7 + D]; apart from chain state
   double *lap_rows = nullptr;
@@ -1092,6 +1096,43 @@ bool prior_blocks(const std::vector<double> &cov, double nsd, const std::vector<
   return true;
 }
 
+// What random_walk_scale and polling_bias_scale put into DevModel::mat: Lw_ext [SE][SP] (L_W [s][k], then the row v = L_W' w), LB_t [k][s], LB [s][k].
+// build_model packs them; potus_set_datasets_grid rebuilds them per data set with the same code.  LW and LB are the column-major factors.
+struct ScaleBlocks { std::vector<double> LW, LB, Lw_ext, LB_t, LBr; };
+bool scale_blocks(const std::vector<double> &cov, double nsd, const std::vector<double> &w, int S, int SE, int SP, double random_walk_scale, double polling_bias_scale, ScaleBlocks &B) {
+  if (!scaled_chol(cov, nsd, polling_bias_scale, S, B.LB) || !scaled_chol(cov, nsd, random_walk_scale, S, B.LW)) return false;
+  auto at = [&](const std::vector<double> &Lm, int i, int j) { return Lm[i + (size_t)j * S]; };
+  B.Lw_ext.assign((size_t)SE * SP, 0.0); B.LB_t.resize((size_t)S * S); B.LBr.resize((size_t)S * S);
+  for (int s = 0; s < S; s++) for (int k = 0; k < S; k++) {
+    B.Lw_ext[(size_t)s * SP + k] = at(B.LW, s, k);
+    B.LB_t[(size_t)k * S + s] = at(B.LB, s, k); B.LBr[(size_t)s * S + k] = at(B.LB, s, k);
+  }
+  for (int k = 0; k < S; k++) { double v = 0; for (int s = k; s < S; s++) v += at(B.LW, s, k) * w[s]; B.Lw_ext[(size_t)S * SP + k] = v; }
+  return true;
+}
+// The scales of a model in the order of hash_data's sc[9] (POTUS_N_SCALES, potus_hmc.h), as given: the no-mode variant never reads sc[1], sc[2], sc[5].
+enum { SC_C = 0, SC_M, SC_POP, SC_NOISE_NATIONAL, SC_NOISE_STATE, SC_E_BIAS, SC_RANDOM_WALK, SC_MU_B_T, SC_POLLING_BIAS };
+void data_scales(const potus_data *d, double *sc) {
+  sc[SC_C] = d->sigma_c; sc[SC_M] = d->sigma_m; sc[SC_POP] = d->sigma_pop; sc[SC_NOISE_NATIONAL] = d->sigma_measure_noise_national;
+  sc[SC_NOISE_STATE] = d->sigma_measure_noise_state; sc[SC_E_BIAS] = d->sigma_e_bias; sc[SC_RANDOM_WALK] = d->random_walk_scale;
+  sc[SC_MU_B_T] = d->mu_b_T_scale; sc[SC_POLLING_BIAS] = d->polling_bias_scale;
+}
+// ... what they put into the scalar fields of DevModel
+void model_scales(DevModel &M, const double *sc) {
+  M.sigma_c = sc[SC_C]; M.sigma_m = sc[SC_M]; M.sigma_pop = sc[SC_POP]; M.sigma_e = sc[SC_E_BIAS];
+  M.sigma_ns = sc[SC_NOISE_STATE]; M.sigma_nn = sc[SC_NOISE_NATIONAL];
+  // (stan:50-52 uses square(scale): the sign of a scale does not reach the factors, chol(c^2 A) = |c| chol(A))
+  M.aT = std::fabs(sc[SC_MU_B_T] / sc[SC_RANDOM_WALK]); M.aB = std::fabs(sc[SC_POLLING_BIAS] / sc[SC_RANDOM_WALK]);
+}
+// ... into the sigma slot of a poll in pd
+double poll_sigma(const double *sc, bool national) { return sc[national ? SC_NOISE_NATIONAL : SC_NOISE_STATE]; }
+// ... and into seg_scale: src names the scale of every segment (-1: none, 1.0)
+std::vector<double> seg_scales(const std::vector<int> &src, const double *sc) {
+  std::vector<double> v(src.size());
+  for (size_t i = 0; i < src.size(); i++) v[i] = src[i] < 0 ? 1.0 : sc[src[i]];
+  return v;
+}
+
 int build_model(Sampler *sp, const potus_data *d) {
   const bool full = d->variant == POTUS_VARIANT_FULL;
   const int S = d->S, T = d->T, Ns = d->N_state_polls, Nn = d->N_national_polls;
@@ -1105,8 +1146,9 @@ int build_model(Sampler *sp, const potus_data *d) {
   M.SE = S + 1; M.SP = S | 1; M.TP = T | 1;
   M.o_zT = L.o_zT; M.o_Z = L.o_Z; M.o_c = L.o_c; M.o_m = L.o_m; M.o_pop = L.o_pop; M.o_mue = L.o_mue; M.o_rho = L.o_rho;
   M.o_ze = L.o_ze; M.o_nn = L.o_nn; M.o_ns = L.o_ns; M.o_zb = L.o_zb; M.nmid = L.o_nn - L.o_c;
-  M.sigma_c = d->sigma_c; M.sigma_m = d->sigma_m; M.sigma_pop = d->sigma_pop; M.sigma_e = d->sigma_e_bias;
-  M.sigma_ns = d->sigma_measure_noise_state; M.sigma_nn = d->sigma_measure_noise_national;
+  double *sc = sp->h_scales;
+  data_scales(d, sc);
+  model_scales(M, sc);
 
   // transformed data (stan:42-55)
   std::vector<double> w(d->state_weights, d->state_weights + S), cov(d->state_covariance_0, d->state_covariance_0 + (size_t)S * S);
@@ -1114,18 +1156,12 @@ int build_model(Sampler *sp, const potus_data *d) {
   for (int i = 0; i < S; i++) for (int j = 0; j < S; j++) nsd2 += w[i] * cov[i + (size_t)j * S] * w[j];
   const double nsd = std::sqrt(nsd2);
   PriorBlocks pb;
-  if (!scaled_chol(cov, nsd, d->polling_bias_scale, S, sp->LB) || !prior_blocks(cov, nsd, w, S, d->mu_b_prior, d->mu_b_T_scale, pb) || !scaled_chol(cov, nsd, d->random_walk_scale, S, sp->LW))
+  ScaleBlocks sb;
+  if (!scale_blocks(cov, nsd, w, S, M.SE, M.SP, d->random_walk_scale, d->polling_bias_scale, sb) || !prior_blocks(cov, nsd, w, S, d->mu_b_prior, d->mu_b_T_scale, pb))
     return fail(POTUS_ERR_ARG, "state_covariance_0 is not positive definite");
-  sp->LT = pb.LT;
+  sp->LT = pb.LT; sp->LW = sb.LW; sp->LB = sb.LB;
   sp->h_cov = cov; sp->h_w_raw = w; sp->h_nsd = nsd; sp->h_rw_scale = d->random_walk_scale; sp->h_T_scale = d->mu_b_T_scale;
-  auto at = [&](const std::vector<double> &Lm, int i, int j) { return Lm[i + (size_t)j * S]; };
-
-  std::vector<double> Lw_ext((size_t)M.SE * M.SP, 0.0), LB_t((size_t)S * S), LBr((size_t)S * S);
-  for (int s = 0; s < S; s++) for (int k = 0; k < S; k++) {
-    Lw_ext[(size_t)s * M.SP + k] = at(sp->LW, s, k);
-    LB_t[(size_t)k * S + s] = at(sp->LB, s, k); LBr[(size_t)s * S + k] = at(sp->LB, s, k);
-  }
-  for (int k = 0; k < S; k++) { double v = 0; for (int s = k; s < S; s++) v += at(sp->LW, s, k) * w[s]; Lw_ext[(size_t)S * M.SP + k] = v; }
+  const std::vector<double> &Lw_ext = sb.Lw_ext, &LB_t = sb.LB_t, &LBr = sb.LBr;
 
   // polls merged and sorted by day (then state); national polls carry the pseudo-state S
   struct Poll { int s, t, p, m, pop, qidx; double y, n, unadj, sig; };
@@ -1133,11 +1169,11 @@ int build_model(Sampler *sp, const potus_data *d) {
   for (int i = 0; i < Ns; i++)
     polls.push_back({d->state[i] - 1, d->day_state[i] - 1, d->poll_state[i] - 1, full ? d->poll_mode_state[i] - 1 : 0,
                      full ? d->poll_pop_state[i] - 1 : 0, L.o_ns + i, (double)d->n_democrat_state[i], (double)d->n_two_share_state[i],
-                     full ? d->unadjusted_state[i] : 0.0, d->sigma_measure_noise_state});
+                     full ? d->unadjusted_state[i] : 0.0, poll_sigma(sc, false)});
   for (int j = 0; j < Nn; j++)
     polls.push_back({S, d->day_national[j] - 1, d->poll_national[j] - 1, full ? d->poll_mode_national[j] - 1 : 0,
                      full ? d->poll_pop_national[j] - 1 : 0, L.o_nn + j, (double)d->n_democrat_national[j],
-                     (double)d->n_two_share_national[j], full ? d->unadjusted_national[j] : 0.0, d->sigma_measure_noise_national});
+                     (double)d->n_two_share_national[j], full ? d->unadjusted_national[j] : 0.0, poll_sigma(sc, true)});
   std::stable_sort(polls.begin(), polls.end(), [](const Poll &a, const Poll &b) { return a.t != b.t ? a.t < b.t : a.s < b.s; });
   const int Np = (int)polls.size();
   std::vector<int> ps(Np), pt(Np), pp(Np), pm(Np), ppop(Np), pq(Np), day_ptr(T + 1, 0);
@@ -1179,9 +1215,10 @@ int build_model(Sampler *sp, const potus_data *d) {
   // two-level segment sums: level-1 tasks of <= PT_SUBLEN polls (padded with the zero slot Npoll),
   // level-2 one thread per segment
   std::vector<int> sub16, seg_ptr{0}, seg_kind, seg_index;
-  std::vector<double> seg_scale, sub_wt16;
+  std::vector<int> &seg_src = sp->h_seg_src;   // the scale of every segment (seg_scales)
+  std::vector<double> sub_wt16;
   int nsub = 0;
-  auto add_group = [&](int nseg, int kind, int index0, double scale, bool weighted, auto key) {
+  auto add_group = [&](int nseg, int kind, int index0, int scale, bool weighted, auto key) {
     std::vector<std::vector<int>> lists(nseg);
     for (int i = 0; i < Np; i++) { const int k = key(i); if (k >= 0) lists[k].push_back(i); }
     for (int sgi = 0; sgi < nseg; sgi++) {
@@ -1194,17 +1231,18 @@ int build_model(Sampler *sp, const potus_data *d) {
         nsub++;
       }
       seg_ptr.push_back(nsub);
-      seg_kind.push_back(kind); seg_index.push_back(index0 + sgi); seg_scale.push_back(scale);
+      seg_kind.push_back(kind); seg_index.push_back(index0 + sgi); seg_src.push_back(scale);
     }
   };
-  add_group(d->P, 0, L.o_c, d->sigma_c, false, [&](int i) { return pp[i]; });
+  add_group(d->P, 0, L.o_c, SC_C, false, [&](int i) { return pp[i]; });
   if (full) {
-    add_group(d->M, 0, L.o_m, d->sigma_m, false, [&](int i) { return pm[i]; });
-    add_group(d->Pop, 0, L.o_pop, d->sigma_pop, false, [&](int i) { return ppop[i]; });
+    add_group(d->M, 0, L.o_m, SC_M, false, [&](int i) { return pm[i]; });
+    add_group(d->Pop, 0, L.o_pop, SC_POP, false, [&](int i) { return ppop[i]; });
   }
-  add_group(S + 1, 1, 0, 1.0, false, [&](int i) { return ps[i]; });
+  add_group(S + 1, 1, 0, -1, false, [&](int i) { return ps[i]; });
   M.sub_weighted_begin = nsub;
-  if (full) add_group(T, 2, 0, 1.0, true, [&](int i) { return pt[i]; });
+  if (full) add_group(T, 2, 0, -1, true, [&](int i) { return pt[i]; });
+  const std::vector<double> seg_scale = seg_scales(seg_src, sc);
   M.nsub = nsub;
   M.nseg = (int)seg_kind.size();
   seg_ptr.push_back(nsub); // so that seg_ptr[seg + 1] is loadable for every seg
@@ -1236,8 +1274,6 @@ int build_model(Sampler *sp, const potus_data *d) {
   M.m_prior = app(pb.prior); M.m_w = app(w);
   M.m_priorx = app(pb.px);
   sp->h_mat = mat;
-  // (stan:50-52 uses square(scale): the sign of a scale does not reach the factors, chol(c^2 A) = |c| chol(A))
-  M.aT = std::fabs(d->mu_b_T_scale / d->random_walk_scale); M.aB = std::fabs(d->polling_bias_scale / d->random_walk_scale);
   M.Npad = (Np + 15) & ~15;
   std::vector<int> pi((size_t)6 * M.Npad, 0);
   std::vector<double> pdv((size_t)4 * M.Npad, 0.0);
@@ -4666,12 +4702,16 @@ int potus_write_stan_csv(int handle, const char *dir, const char *basename) {
 }
 
 // ------------------------------------------------------------------------ simulation-based calibration (DESIGN.md "Simulation-based calibration")
-// potus_set_datasets and potus_set_datasets_ex (ex: the four arrays may be null, the poll sizes and the prior may differ per data set, ds_ex is set)
+// potus_set_datasets, potus_set_datasets_ex (ex: the four arrays may be null, the poll sizes and the prior may differ per data set, ds_ex is set)
+// and potus_set_datasets_grid (ex with scales [n][POTUS_N_SCALES]: every piece of the model that a scale reaches is the data set's own)
+static const char *const kScaleNames[POTUS_N_SCALES] = {"sigma_c", "sigma_m", "sigma_pop", "sigma_measure_noise_national", "sigma_measure_noise_state",
+                                                        "sigma_e_bias", "random_walk_scale", "mu_b_T_scale", "polling_bias_scale"};
 static int set_datasets_impl(const char *what, Sampler *sp, int n_datasets, const int32_t *y_state, const int32_t *y_national, const int32_t *n_state,
-                             const int32_t *n_national, const double *mu_b_prior, const double *mu_b_T_scale, bool ex) {
+                             const int32_t *n_national, const double *mu_b_prior, const double *mu_b_T_scale, bool ex, const double *scales = nullptr) {
   if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
   const int Ns = sp->M.Ns, Nn = sp->M.Nn, Np = Ns + Nn, Npad = sp->M.Npad, S = sp->M.S;
   if (n_datasets < 1) return fail(POTUS_ERR_ARG, "%s: n_datasets = %d, at least 1", what, n_datasets);
+  if (scales && mu_b_T_scale) return fail(POTUS_ERR_ARG, "%s: both mu_b_T_scale[] and scales are given: scales[][%d] is mu_b_T_scale, pass one of the two", what, (int)SC_MU_B_T);
   if (!ex && ((Ns && !y_state) || (Nn && !y_national))) return fail(POTUS_ERR_ARG, "%s: null outcome array", what);
   if (sp->inited) return fail(POTUS_ERR_STATE, "%s: the handle is already initialised (call it between potus_create and potus_init)", what);
   if (sp->n_ds) return fail(POTUS_ERR_STATE, "%s: the handle already holds %d data sets", what, sp->n_ds);
@@ -4680,6 +4720,18 @@ static int set_datasets_impl(const char *what, Sampler *sp, int n_datasets, cons
   if (sp->R.chains % n_datasets) return fail(POTUS_ERR_ARG, "%s: chains = %d is not a multiple of n_datasets = %d", what, sp->R.chains, n_datasets);
   if (mu_b_prior) for (size_t i = 0; i < (size_t)n_datasets * S; i++) if (!std::isfinite(mu_b_prior[i])) return fail(POTUS_ERR_ARG, "%s: data set %d: mu_b_prior is not finite", what, (int)(i / S) + 1);
   if (mu_b_T_scale) for (int k = 0; k < n_datasets; k++) if (!(mu_b_T_scale[k] > 0) || !std::isfinite(mu_b_T_scale[k])) return fail(POTUS_ERR_ARG, "%s: data set %d: mu_b_T_scale = %g, must be positive and finite", what, k + 1, mu_b_T_scale[k]);
+  // the scales of every data set: the no-mode variant keeps the handle's own where it reads none (potus_create ignores them there).  potus_create
+  // itself tests a scale only through the factorisation below; a grid names the data set and the scale before that
+  std::vector<double> scs;
+  if (scales) {
+    scs.assign(scales, scales + (size_t)n_datasets * POTUS_N_SCALES);
+    for (int k = 0; k < n_datasets; k++)
+      for (int j = 0; j < POTUS_N_SCALES; j++) {
+        double &v = scs[(size_t)k * POTUS_N_SCALES + j];
+        if (!sp->M.full && (j == SC_M || j == SC_POP || j == SC_E_BIAS)) { v = sp->h_scales[j]; continue; }
+        if (!(v > 0) || !std::isfinite(v)) return fail(POTUS_ERR_ARG, "%s: data set %d: %s = %g, must be positive and finite", what, k + 1, kScaleNames[j], v);
+      }
+  }
   DeviceLocks lock(sp->device);
   HIP_TRY(hipSetDevice(sp->device));
   std::vector<double> base((size_t)4 * Npad);
@@ -4698,27 +4750,58 @@ static int set_datasets_impl(const char *what, Sampler *sp, int n_datasets, cons
       if (ex && n < 0) return fail(POTUS_ERR_ARG, "%s: data set %d: n_two_share_%s[%d] = %d is negative", what, k + 1, nat ? "national" : "state", j + 1, (int)n);
       if (y < 0 || y > n) return fail(POTUS_ERR_ARG, "%s: data set %d: n_democrat_%s[%d] = %d outside [0,%d]", what, k + 1, nat ? "national" : "state", j + 1, (int)y, (int)n);
       blk[i] = y; blk[(size_t)Npad + i] = n;
+      if (scales) blk[(size_t)3 * Npad + i] = poll_sigma(&scs[(size_t)k * POTUS_N_SCALES], nat);
     }
   }
   const double *dpd = nullptr;
   if (const int rc = upload(sp, pd, &dpd)) return rc;
   std::vector<DevModel> ms(n_datasets, sp->M);
   for (int k = 0; k < n_datasets; k++) ms[k].pd = dpd + (size_t)k * 4 * Npad;
-  if (mu_b_prior || mu_b_T_scale) {   // own mat and aT: the blocks build_model derives from the prior and the scale, by its code
+  if (scales) {   // own sigma fields, aT, aB and seg_scale, by build_model's code.  Sizes, offsets, the LDS layout and the schedule are the handle's: no scale reaches them
+    const size_t nseg = sp->h_seg_src.size();
+    if ((int)nseg != sp->M.nseg) return fail(POTUS_ERR_STATE, "%s: internal: %zu segment scales for %d segments", what, nseg, sp->M.nseg);
+    std::vector<double> segs;
+    for (int k = 0; k < n_datasets; k++) {
+      const double *sc = &scs[(size_t)k * POTUS_N_SCALES];
+      const DevModel before = ms[k];
+      model_scales(ms[k], sc);
+      const std::vector<double> one = seg_scales(sp->h_seg_src, sc);
+      segs.insert(segs.end(), one.begin(), one.end());
+      DevModel same = ms[k];   // everything but the eight scalars is untouched
+      same.sigma_c = before.sigma_c; same.sigma_m = before.sigma_m; same.sigma_pop = before.sigma_pop; same.sigma_e = before.sigma_e;
+      same.sigma_ns = before.sigma_ns; same.sigma_nn = before.sigma_nn; same.aT = before.aT; same.aB = before.aB;
+      if (std::memcmp(&same, &before, sizeof(DevModel)) != 0) return fail(POTUS_ERR_STATE, "%s: internal: a scale changed the layout of data set %d", what, k + 1);
+    }
+    const double *dseg = nullptr;
+    if (const int rc = upload(sp, segs, &dseg)) return rc;
+    for (int k = 0; k < n_datasets; k++) ms[k].seg_scale = dseg + (size_t)k * nseg;
+  }
+  if (mu_b_prior || mu_b_T_scale || scales) {   // own mat and aT: the blocks build_model derives from the prior and the scales, by its code
     const size_t nm = sp->h_mat.size();
     std::vector<double> mats((size_t)n_datasets * nm);
     for (int k = 0; k < n_datasets; k++) {
       double *m = mats.data() + (size_t)k * nm;
       std::copy(sp->h_mat.begin(), sp->h_mat.end(), m);
       PriorBlocks pb;
-      const double scale = mu_b_T_scale ? mu_b_T_scale[k] : sp->h_T_scale;
+      const double *sc = scales ? &scs[(size_t)k * POTUS_N_SCALES] : nullptr;
+      const double scale = sc ? sc[SC_MU_B_T] : mu_b_T_scale ? mu_b_T_scale[k] : sp->h_T_scale;
       const double *prior = mu_b_prior ? mu_b_prior + (size_t)k * S : sp->h_mat.data() + sp->M.m_prior;
       if (!prior_blocks(sp->h_cov, sp->h_nsd, sp->h_w_raw, S, prior, scale, pb)) return fail(POTUS_ERR_ARG, "%s: data set %d: the covariance scaled by mu_b_T_scale = %g is not positive definite", what, k + 1, scale);
       std::copy(pb.LT_t.begin(), pb.LT_t.end(), m + sp->M.m_LTt);
       std::copy(pb.LTr.begin(), pb.LTr.end(), m + sp->M.m_LT);
-      ms[k].aT = std::fabs(scale / sp->h_rw_scale);
+      if (!sc) ms[k].aT = std::fabs(scale / sp->h_rw_scale);
       std::copy(pb.prior.begin(), pb.prior.end(), m + sp->M.m_prior);
       std::copy(pb.px.begin(), pb.px.end(), m + sp->M.m_priorx);
+      if (sc) {   // Lw_ext (mat starts with it), LB_t and LB
+        ScaleBlocks sb;
+        if (!scale_blocks(sp->h_cov, sp->h_nsd, sp->h_w_raw, S, sp->M.SE, sp->M.SP, sc[SC_RANDOM_WALK], sc[SC_POLLING_BIAS], sb))
+          return fail(POTUS_ERR_ARG, "%s: data set %d: the covariance scaled by random_walk_scale = %g or polling_bias_scale = %g is not positive definite", what, k + 1, sc[SC_RANDOM_WALK], sc[SC_POLLING_BIAS]);
+        if (sb.Lw_ext.size() > (size_t)sp->M.m_LTt || sp->M.m_LBt + sb.LB_t.size() > nm || sp->M.m_LB + sb.LBr.size() > nm)
+          return fail(POTUS_ERR_STATE, "%s: internal: the blocks of data set %d do not fit the handle's mat", what, k + 1);
+        std::copy(sb.Lw_ext.begin(), sb.Lw_ext.end(), m);
+        std::copy(sb.LB_t.begin(), sb.LB_t.end(), m + sp->M.m_LBt);
+        std::copy(sb.LBr.begin(), sb.LBr.end(), m + sp->M.m_LB);
+      }
     }
     const double *dmat = nullptr;
     if (const int rc = upload(sp, mats, &dmat)) return rc;
@@ -4730,6 +4813,7 @@ static int set_datasets_impl(const char *what, Sampler *sp, int n_datasets, cons
   sp->dMs = const_cast<DevModel *>(dms);
   sp->n_ds = n_datasets;
   if (ex) sp->ds_ex = true;
+  if (scales) sp->ds_grid = true;
   return 0;
 }
 
@@ -4742,6 +4826,14 @@ int potus_set_datasets_ex(int handle, int n_datasets, const int32_t *n_democrat_
                           const int32_t *n_two_share_state, const int32_t *n_two_share_national, const double *mu_b_prior, const double *mu_b_T_scale) {
   return set_datasets_impl("potus_set_datasets_ex", get(handle), n_datasets, n_democrat_state, n_democrat_national, n_two_share_state, n_two_share_national,
                            mu_b_prior, mu_b_T_scale, true);
+}
+
+// Prior settings as data sets: potus_set_datasets_ex, and every data set with the nine scales of its own.
+int potus_set_datasets_grid(int handle, int n_datasets, const int32_t *n_democrat_state, const int32_t *n_democrat_national,
+                            const int32_t *n_two_share_state, const int32_t *n_two_share_national, const double *mu_b_prior, const double *mu_b_T_scale,
+                            const double *scales) {
+  return set_datasets_impl("potus_set_datasets_grid", get(handle), n_datasets, n_democrat_state, n_democrat_national, n_two_share_state, n_two_share_national,
+                           mu_b_prior, mu_b_T_scale, true, scales);
 }
 
 namespace {
@@ -4834,6 +4926,95 @@ int potus_timeline(int handle, int day_begin, int day_end, const double *ev, int
 
 int potus_timeline_timing(double *ms) {
   return timing_out("potus_timeline_timing", g_tl_ms, 2, ms);
+}
+
+// ---------------------------------------------------------------------------------------------- prior sensitivity by refit (potus_sens.hpp)
+namespace {
+thread_local double g_sg_ms[2] = {0.0, 0.0};   // the last call of this thread: k_tl_scores, k_sg_distance / k_sg_grid (HIP events)
+constexpr int SG_MAX_GRID = 512;               // workgroups of a launch: with the largest samples one is resident per CU, more columns are grid-strided
+
+int sg_check_sizes(const char *what, long long n_a, long long n_b) {
+  if (n_a < 1 || n_b < 1) return fail(POTUS_ERR_ARG, "%s: n_a = %lld, n_b = %lld, at least one draw each", what, n_a, n_b);
+  if (n_a + n_b > SG_MAX_N)
+    return fail(POTUS_ERR_UNSUPPORTED, "%s: n_a + n_b = %lld + %lld = %lld: both samples of a column are sorted in LDS, at most %d draws together", what, n_a, n_b,
+                n_a + n_b, SG_MAX_N);
+  return 0;
+}
+} // namespace
+
+int potus_ecdf_distance_device(int device, const void *a, int n_a, const void *b, int n_b, int n_cols, double *out) {
+  const char *what = "potus_ecdf_distance_device";
+  if (!a || !b || !out || n_cols < 1) return fail(POTUS_ERR_ARG, "%s: bad argument", what);
+  if (const int rc_ = sg_check_sizes(what, n_a, n_b)) return rc_;
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, device, a, "block a")) return rc_;
+  if (const int rc_ = mm_also_device(what, device, b, "block b")) return rc_;
+  DevBufs tmp;
+  double *dout = nullptr;
+  if (const int rc_ = tmp.get(&dout, (size_t)n_cols * 3 * 8, what)) return rc_;
+  const size_t lds = (size_t)(n_a + n_b) * 8;
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sg_distance), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  EventTimer t;
+  HIP_TRY(t.made);
+  HIP_TRY(t.start(0));
+  hipLaunchKernelGGL(k_sg_distance, dim3((unsigned)std::min(n_cols, SG_MAX_GRID)), dim3(SG_THREADS), lds, 0, (const double *)a, n_a, (const double *)b, n_b, n_cols, dout);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(t.stop(0));
+  HIP_TRY(hipMemcpy(out, dout, (size_t)n_cols * 3 * 8, hipMemcpyDeviceToHost));
+  double ms = 0;
+  if (const int rc_ = t.elapsed_or_fail(&ms)) return rc_;
+  g_sg_ms[0] = 0.0; g_sg_ms[1] = ms;
+  return 0;
+}
+
+int potus_grid_compare(int handle, int base, int day_begin, int day_end, const double *ev, int ev_to_win, double *out, int32_t *n_draws_out) {
+  const char *what = "potus_grid_compare";
+  (void)ev_to_win;   // the electoral votes of a draw are compared as a count; the threshold is part of potus_timeline's summary only
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  if (!ev || !out || !n_draws_out) return fail(POTUS_ERR_ARG, "%s: null argument", what);
+  TlPlan pl;
+  if (const int rc_ = tl_check_args(what, sp, day_begin, day_end, pl)) return rc_;
+  if (base < 0 || base >= pl.n_ds) return fail(POTUS_ERR_ARG, "%s: base = %d outside the handle's %d data sets", what, base, pl.n_ds);
+  DeviceGuard guard;
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  if (const int rc_ = ds_plan(what, sp, pl)) return rc_;
+  const int S = sp->M.S, nd = pl.nd, n = pl.cpd * pl.n_post, n_ds = pl.n_ds;
+  if (const int rc_ = sg_check_sizes(what, n, n)) return rc_;
+  DevBufs tmp;
+  EventTimer e0, e1;
+  HIP_TRY(e0.made); HIP_TRY(e1.made);
+  double *x = nullptr, *dw = nullptr, *dev_ = nullptr, *dout = nullptr;
+  int *dskip = nullptr;
+  int rc;
+  const size_t n_out = (size_t)n_ds * nd * (S + 2) * 3;
+  if ((rc = tmp.get(&x, (size_t)n_ds * n * nd * S * 8, what)) || (rc = tmp.get(&dw, (size_t)S * 8, what)) || (rc = tmp.get(&dev_, (size_t)S * 8, what)) ||
+      (rc = tmp.get(&dout, n_out * 8, what)) || (rc = tmp.get(&dskip, (size_t)n_ds * 4, what))) return rc;
+  HIP_TRY(hipMemcpyAsync(dskip, pl.skip.data(), (size_t)n_ds * 4, hipMemcpyHostToDevice, sp->stream));
+  HIP_TRY(hipMemcpyAsync(dw, sp->h_w.data(), (size_t)S * 8, hipMemcpyHostToDevice, sp->stream));
+  HIP_TRY(hipMemcpyAsync(dev_, ev, (size_t)S * 8, hipMemcpyHostToDevice, sp->stream));
+  HIP_TRY(e0.start(sp->stream));
+  if ((rc = tl_scores(sp, pl, day_begin, day_end, dskip, x))) return rc;
+  HIP_TRY(e0.stop(sp->stream));
+  const size_t lds = (size_t)2 * n * 8;
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_sg_grid), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  SgGridParams Q{x, n_ds, n, nd, S, base, dw, dev_, dskip, dout};
+  HIP_TRY(e1.start(sp->stream));
+  hipLaunchKernelGGL(k_sg_grid, dim3((unsigned)std::min<long long>((long long)n_ds * nd * (S + 2), SG_MAX_GRID)), dim3(SG_THREADS), lds, sp->stream, Q);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(e1.stop(sp->stream));
+  HIP_TRY(hipMemcpyAsync(out, dout, n_out * 8, hipMemcpyDeviceToHost, sp->stream));
+  HIP_TRY(hipStreamSynchronize(sp->stream));
+  double ms0 = 0, ms1 = 0;
+  if ((rc = e0.elapsed_or_fail(&ms0)) || (rc = e1.elapsed_or_fail(&ms1))) return rc;
+  g_sg_ms[0] = ms0; g_sg_ms[1] = ms1;
+  for (int k = 0; k < n_ds; k++) n_draws_out[k] = pl.skip[k] || pl.skip[base] ? 0 : n;
+  return 0;
+}
+
+int potus_grid_timing(double *ms) {
+  return timing_out("potus_grid_timing", g_sg_ms, 2, ms);
 }
 
 // ---------------------------------------------------------------------------------------------- exact cross-validation (potus_crossval.hpp)
@@ -6904,6 +7085,14 @@ void potus_R_set_datasets_ex(int *handle, int *n_datasets, int *n_democrat_state
                              int *has_prior, double *mu_b_prior, int *has_scale, double *mu_b_T_scale, int *status) {
   *status = potus_set_datasets_ex(*handle, *n_datasets, n_democrat_state, n_democrat_national, n_two_share_state, n_two_share_national,
                                   *has_prior ? mu_b_prior : nullptr, *has_scale ? mu_b_T_scale : nullptr);
+}
+void potus_R_set_datasets_grid(int *handle, int *n_datasets, int *n_democrat_state, int *n_democrat_national, int *n_two_share_state, int *n_two_share_national,
+                               int *has /*[3]: mu_b_prior, mu_b_T_scale, scales given*/, double *mu_b_prior, double *mu_b_T_scale, double *scales, int *status) {
+  *status = potus_set_datasets_grid(*handle, *n_datasets, n_democrat_state, n_democrat_national, n_two_share_state, n_two_share_national,
+                                    has[0] ? mu_b_prior : nullptr, has[1] ? mu_b_T_scale : nullptr, has[2] ? scales : nullptr);
+}
+void potus_R_grid_compare(int *handle, int *iargs /*[4]: base, day_begin, day_end, ev_to_win*/, double *ev, double *out, int *n_draws_out, int *status) {
+  *status = potus_grid_compare(*handle, iargs[0], iargs[1], iargs[2], ev, iargs[3], out, n_draws_out);
 }
 void potus_R_timeline(int *handle, int *day_begin, int *day_end, double *ev, int *ev_to_win, double *state_out, double *natl_out, double *ev_out, int *n_draws_out, int *status) {
   *status = potus_timeline(*handle, *day_begin, *day_end, ev, *ev_to_win, state_out, natl_out, ev_out, n_draws_out);

@@ -152,6 +152,14 @@ def load_library():
         L.potus_timeline.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, dp, dp, i32p]
         L.potus_timeline_scores_device.argtypes = [C.c_int, C.c_int, C.c_int, C.c_void_p]
         L.potus_timeline_timing.argtypes = [dp]
+    if hasattr(L, "potus_grid_compare"):                # prior settings as the data sets of one handle (sensitivity.py)
+        i32p = C.POINTER(C.c_int32)
+        L.potus_set_datasets_grid.argtypes = [C.c_int, C.c_int, i32p, i32p, i32p, i32p, dp, dp, dp]
+        L.potus_ecdf_distance_device.argtypes = [C.c_int, C.c_void_p, C.c_int, C.c_void_p, C.c_int, C.c_int, dp]
+        L.potus_grid_compare.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, i32p]
+        L.potus_grid_timing.argtypes = [dp]
+        L.potus_R_set_datasets_grid.argtypes = [ip, ip, ip, ip, ip, ip, ip, dp, dp, dp, ip]
+        L.potus_R_grid_compare.argtypes = [ip, ip, dp, dp, ip, ip]
     if hasattr(L, "potus_cv_lpd"):                      # exact cross-validation (crossval.py)
         i32p = C.POINTER(C.c_int32)
         L.potus_cv_log_lik_device.argtypes = [C.c_int, i32p, i32p, C.c_int, C.c_void_p, C.POINTER(C.c_longlong)]
@@ -213,6 +221,7 @@ EXPORTS = [
     "potus_diagnostics", "potus_diagnostics_device", "potus_check_convergence",
     "potus_set_datasets", "potus_simulate_prior", "potus_constrain", "potus_sbc_ranks",
     "potus_set_datasets_ex", "potus_timeline", "potus_timeline_scores_device", "potus_timeline_timing",
+    "potus_set_datasets_grid", "potus_ecdf_distance_device", "potus_grid_compare", "potus_grid_timing",
     "potus_log_lik_device", "potus_loo_device", "potus_loo",
     "potus_default_loo_mm_opts", "potus_loo_moment_match", "potus_loo_mm_timing", "potus_loo_mm_ratios_device", "potus_loo_mm_moments_device",
     "potus_psis_device", "potus_R_loo_moment_match",
@@ -232,8 +241,28 @@ EXPORTS = [
     "potus_R_create", "potus_R_init", "potus_R_run", "potus_R_run_many", "potus_R_num_columns", "potus_R_saved_count",
     "potus_R_write_array", "potus_R_write_stan_csv", "potus_R_posterior_summary", "potus_R_diagnostics", "potus_R_check_convergence", "potus_R_backtest_scores", "potus_R_last_error", "potus_R_destroy",
     "potus_R_set_datasets", "potus_R_simulate_prior", "potus_R_sbc_ranks", "potus_R_constrain", "potus_R_loo", "potus_R_outcomes", "potus_R_monitor", "potus_R_scenario",
-    "potus_R_set_datasets_ex", "potus_R_timeline", "potus_R_cv_lpd", "potus_R_optimize",
+    "potus_R_set_datasets_ex", "potus_R_timeline", "potus_R_cv_lpd", "potus_R_optimize", "potus_R_set_datasets_grid", "potus_R_grid_compare",
 ]
+
+
+# the nine hand-set prior scales of the data, in the order of potus_set_datasets_grid's scales[n][POTUS_N_SCALES]
+SCALE_NAMES = ("sigma_c", "sigma_m", "sigma_pop", "sigma_measure_noise_national", "sigma_measure_noise_state", "sigma_e_bias",
+               "random_walk_scale", "mu_b_T_scale", "polling_bias_scale")
+N_SCALES = len(SCALE_NAMES)
+
+
+def ecdf_distance_device(a, b, L=None):
+    """potus_ecdf_distance_device: a [n_a, n_cols] and b [n_b, n_cols], float64 torch tensors on one GPU, draw-major.  Returns [n_cols, 3] =
+    (w1, ks, cjs) per column (numpy)."""
+    import torch
+    L = L or load_library()
+    if a.dtype != torch.float64 or b.dtype != torch.float64 or a.dim() != 2 or b.dim() != 2 or a.shape[1] != b.shape[1]:
+        raise ValueError("ecdf_distance_device: two float64 blocks [n_a, n_cols] and [n_b, n_cols] are expected")
+    a, b = a.contiguous(), b.contiguous()
+    out = np.zeros((a.shape[1], 3))
+    torch.cuda.current_stream(a.device).synchronize()
+    _check(L, L.potus_ecdf_distance_device(a.device.index or 0, C.c_void_p(a.data_ptr()), a.shape[0], C.c_void_p(b.data_ptr()), b.shape[0], a.shape[1], _dp(out)))
+    return out
 
 
 def _dp(a):
@@ -450,15 +479,16 @@ class Handle:
         self.n_datasets = n
 
     def set_datasets_ex(self, n_democrat_state=None, n_democrat_national=None, n_two_share_state=None, n_two_share_national=None,
-                        mu_b_prior=None, mu_b_T_scale=None, n=None):
+                        mu_b_prior=None, mu_b_T_scale=None, n=None, scales=None, _grid=False):
         """potus_set_datasets_ex: data sets that may differ in the poll outcomes and sizes ([n, N_state_polls], [n, N_national_polls];
         n_two_share = 0: the data set has not seen the poll), mu_b_prior [n, S] and mu_b_T_scale [n].  None = the handle's own for every data set."""
+        what = "set_datasets_grid" if _grid else "set_datasets_ex"
         Ns, Nn, S = int(self.data["N_state_polls"]), int(self.data["N_national_polls"]), int(self.data["S"])
         given = [(a, w) for a, w in ((n_democrat_state, Ns), (n_two_share_state, Ns), (n_democrat_national, Nn), (n_two_share_national, Nn),
-                                     (mu_b_prior, S), (mu_b_T_scale, 1)) if a is not None and w]
+                                     (mu_b_prior, S), (mu_b_T_scale, 1), (scales, N_SCALES)) if a is not None and w]
         counts = {np.asarray(a).reshape(-1, w).shape[0] for a, w in given} | ({int(n)} if n is not None else set())
         if len(counts) != 1:
-            raise ValueError(f"set_datasets_ex: the arrays give {sorted(counts)} data sets (pass n when every array is None)")
+            raise ValueError(f"{what}: the arrays give {sorted(counts)} data sets (pass n when every array is None)")
         n = counts.pop()
         keep = []
 
@@ -473,9 +503,32 @@ class Handle:
                 return None
             keep.append(np.ascontiguousarray(np.asarray(a, dtype=np.float64).reshape(n, w)))
             return _dp(keep[-1])
-        _check(self.L, self.L.potus_set_datasets_ex(self.h, n, ints(n_democrat_state, Ns), ints(n_democrat_national, Nn), ints(n_two_share_state, Ns),
-                                                    ints(n_two_share_national, Nn), dbls(mu_b_prior, S), dbls(mu_b_T_scale, 1)))
+        args = (self.h, n, ints(n_democrat_state, Ns), ints(n_democrat_national, Nn), ints(n_two_share_state, Ns), ints(n_two_share_national, Nn),
+                dbls(mu_b_prior, S), dbls(mu_b_T_scale, 1))
+        _check(self.L, self.L.potus_set_datasets_grid(*args, dbls(scales, N_SCALES)) if _grid else self.L.potus_set_datasets_ex(*args))
         self.n_datasets = n
+
+    def set_datasets_grid(self, scales=None, **datasets):
+        """potus_set_datasets_grid: set_datasets_ex (same keywords) and scales [n, 9], the nine prior scales of every data set in the order of
+        SCALE_NAMES.  None = the handle's own for every data set; mu_b_T_scale and scales together are refused."""
+        self.set_datasets_ex(scales=scales, _grid=True, **datasets)
+
+    def grid_compare(self, ev, base=0, days=None, ev_to_win=270):
+        """potus_grid_compare: every data set against data set `base` over the post-warm-up draws, per day of `days` = (begin, end) (0-based,
+        default: election day only): dict(distance [n, days, S + 2, 3] = (w1, ks, cjs) of the S state scores, the national vote and the
+        electoral votes of a draw; n_draws [n]).  A data set with a failed chain has NaN, and so has every row if `base` failed."""
+        S = int(self.data["S"])
+        t0, t1 = self._day_range(days)
+        n, nd = self.n_datasets, max(t1 - t0, 0)
+        ev = np.ascontiguousarray(ev, dtype=np.float64).reshape(S)
+        out, cnt = np.zeros((n, nd, S + 2, 3)), np.zeros(n, np.int32)
+        _check(self.L, self.L.potus_grid_compare(self.h, int(base), t0, t1, _dp(ev), int(ev_to_win), _dp(out), _ip(cnt)))
+        return dict(distance=out, n_draws=cnt)
+
+    def grid_timing(self):
+        ms = np.zeros(2)
+        _check(self.L, self.L.potus_grid_timing(_dp(ms)))
+        return dict(scores_ms=float(ms[0]), distance_ms=float(ms[1]))
 
     def _day_range(self, days):
         """days = (begin, end), 0-based; None: election day only."""

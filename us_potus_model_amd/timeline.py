@@ -18,7 +18,7 @@ from __future__ import annotations
 import numpy as np
 
 from . import _abi
-from .sampler import Handle, PotusError, device_diagnostics_of_block
+from .sampler import SCALE_NAMES, Handle, PotusError, device_diagnostics_of_block
 
 _BATCHED = dict(cus_per_chain=1, twin=0)     # what potus_set_datasets_ex needs: one workgroup per chain
 MAX_DRAWS = 16384                            # post-warm-up draws per date that potus_timeline sorts in LDS
@@ -57,10 +57,14 @@ def design_of(data, keep_state, keep_national, mu_b_prior=None, mu_b_T_scale=Non
 
 
 def data_of(design, d):
-    """The `data` dict of run date d of a design (mask applied)."""
-    return mask(design["data"], design["keep_state"][d], design["keep_national"][d],
-                None if design.get("mu_b_prior") is None else design["mu_b_prior"][d],
-                None if design.get("mu_b_T_scale") is None else design["mu_b_T_scale"][d])
+    """The `data` dict of run date d of a design (mask applied; with the prior scales of setting d where the design has a grid of them,
+    sensitivity.grid)."""
+    out = mask(design["data"], design["keep_state"][d], design["keep_national"][d],
+               None if design.get("mu_b_prior") is None else design["mu_b_prior"][d],
+               None if design.get("mu_b_T_scale") is None else design["mu_b_T_scale"][d])
+    if design.get("scales") is not None:
+        out.update({name: float(v) for name, v in zip(SCALE_NAMES, design["scales"][d])})
+    return out
 
 
 def set_design(handle, design):
@@ -72,6 +76,11 @@ def set_design(handle, design):
     for name, k in (("state", ks), ("national", kn)):
         for f in ("n_two_share", "n_democrat"):
             arr[f"{f}_{name}"] = np.where(k, np.asarray(data[f"{f}_{name}"], dtype=np.int32)[None, :], 0).astype(np.int32)
+    if design.get("scales") is not None:      # prior settings (sensitivity.grid): potus_set_datasets_grid
+        handle.set_datasets_grid(design["scales"], n_democrat_state=arr["n_democrat_state"], n_democrat_national=arr["n_democrat_national"],
+                                 n_two_share_state=arr["n_two_share_state"], n_two_share_national=arr["n_two_share_national"],
+                                 mu_b_prior=design.get("mu_b_prior"), mu_b_T_scale=design.get("mu_b_T_scale"), n=n)
+        return
     handle.set_datasets_ex(arr["n_democrat_state"], arr["n_democrat_national"], arr["n_two_share_state"], arr["n_two_share_national"],
                            design.get("mu_b_prior"), design.get("mu_b_T_scale"), n=n)
 
@@ -163,7 +172,7 @@ class Timeline:
         self.handle.close()
 
 
-def fit(design, variant="full", chains_per_date=4, **opts):
+def fit(design, variant="full", chains_per_date=4, _cls=None, **opts):
     """Fit every run date of a design as chains of one launch.  opts: the sampler options of Handle (num_warmup, num_samples, seed, ...)."""
     import time
     n = int(design["keep_state"].shape[0])
@@ -184,7 +193,7 @@ def fit(design, variant="full", chains_per_date=4, **opts):
     except Exception:
         h.close()
         raise
-    return Timeline(h, design, chains_per_date, wall)
+    return (_cls or Timeline)(h, design, chains_per_date, wall)
 
 
 def modes(design, variant="full", paths_per_date=1, device=0, seed=1843, init_radius=2.0, **opts):
