@@ -762,3 +762,30 @@ potus_scenario_cor <- function(scenario, day = dim(scenario$cov)[1]) {
   s <- ifelse(diag(v) > 0, 1 / sqrt(diag(v)), NaN)
   v * outer(s, s)
 }
+
+# ---- proper scoring rules of the joint forecast against the result (us_potus_model_amd/scoring.py is the same in Python; DESIGN.md section 4u) ----
+# What scoringRules gives as crps_sample, es_sample, vs_sample and dss_sample, on the device over the post-warm-up draws of every chain of the fit.
+# actual: the certified two-party share per state; the national share and the Democratic electoral votes of the result are derived with the
+# fit's normalised state weights and ev unless given.  use: logical [S], the states of the multivariate scores (NULL: all); days: c(first, last)
+# 1-based, NULL = election day alone.  Returns crps, pit_lo, pit_hi, dss, interval, ae_median, se_mean [days, S + 2] (columns: the states, the
+# national vote, the electoral votes), energy, variogram, dss_joint [days], rmse (root mean se_mean of the used states on the last day), n_draws.
+potus_forecast_scores <- function(fit, actual, ev, use = NULL, vs_p = 0.5, days = NULL, actual_national = NULL, actual_ev = NULL, ev_to_win = 270L) {
+  S <- as.integer(fit$data$S); nT <- as.integer(fit$data$T)
+  if (length(actual) != S || length(ev) != S) stop("potus_forecast_scores: actual and ev have one entry per state")
+  if (is.null(use)) use <- rep(TRUE, S)
+  if (is.null(days)) days <- c(nT, nT)
+  w <- fit$data$state_weights / sum(fit$data$state_weights)
+  if (is.null(actual_national)) actual_national <- sum(w * actual)
+  if (is.null(actual_ev)) actual_ev <- sum(ev[actual > 0.5])
+  n <- as.integer(days[2] - days[1] + 1L)
+  r <- .C("potus_R_forecast_scores", as.integer(fit$handles), length(fit$handles), as.integer(c(days[1] - 1L, days[2], ev_to_win)), as.double(ev),
+          as.double(c(actual, actual_national, actual_ev)), as.integer(use), as.double(vs_p), uni = double(max(n, 1L) * (S + 2L) * 7L),
+          multi = double(max(n, 1L) * 3L), n_draws = double(1), status = integer(1))
+  .potus_check(r$status)
+  uni <- aperm(array(r$uni, c(7L, S + 2L, n)), c(3, 2, 1))
+  multi <- matrix(r$multi, n, 3L, byrow = TRUE)
+  out <- list(n_draws = r$n_draws, days = days, use = as.logical(use), vs_p = vs_p, energy = multi[, 1], variogram = multi[, 2], dss_joint = multi[, 3])
+  for (k in 1:7) out[[c("crps", "pit_lo", "pit_hi", "dss", "interval", "ae_median", "se_mean")[k]]] <- matrix(uni[, , k], n, S + 2L)
+  out$rmse <- sqrt(mean(out$se_mean[n, seq_len(S)][as.logical(use)]))
+  out
+}

@@ -869,6 +869,49 @@ int potus_scenario_device(int device, const void *block /*[n_draws][n_days][S]*/
  * out of it (host clock), keeping and compacting (host clock), the moments (HIP events), the counting kernel (HIP events). */
 int potus_scenario_timing(double *ms /*[5]*/);
 
+/* ---- proper scoring rules of the joint forecast against the result ----
+ * What scoringRules gives an R user as crps_sample, es_sample, vs_sample and dss_sample, for the n draws of predicted_score of every day.
+ * INPUT: a block x [n_draws][n_days][S], draws in canonical order (the block of potus_outcomes_device and potus_scenario_device); w [S] the
+ *   normalised national weights and ev [S] the electoral votes; actual [S + 2] = the certified two-party share per state, the national share,
+ *   the Democratic electoral votes; use [S] of 0 / 1: the m states that enter the multivariate scores; vs_p in (0, 2].
+ * UNIVARIATE, uni_out [days][S + 2][7], per day and column c -- the S states, the national vote sum_s w[s] x[s] and the electoral votes
+ *   sum_s ev[s] 1[x[s] > 0.5] of a draw (ev_to_win is taken for symmetry with potus_timeline and not used: the votes are scored as a count) -- over the
+ *   column's draws sorted ascending, x_(1..n), y = actual[c]:
+ *     [0] crps       (2 / n^2) sum_i (x_(i) - y)(n 1[y < x_(i)] - i + 1/2)  =  mean|x - y| - sum_i sum_j |x_i - x_j| / (2 n^2)   (crps_sample, edf)
+ *     [1] pit_lo     #{x < y} / n
+ *     [2] pit_hi     #{x <= y} / n
+ *     [3] dss        log v + (y - mean)^2 / v, v the variance (ddof 1, two passes); NaN when v = 0 (every draw the same value) or n = 1
+ *     [4] interval   (u - l) + 40 (l - y)+ + 40 (y - u)+, l and u the type-7 quantiles at 0.025 and 0.975
+ *     [5] ae_median  |median - y|, the type-7 median
+ *     [6] se_mean    (mean - y)^2
+ * MULTIVARIATE, multi_out [days][3], per day over the m used states, x_i and y in R^m:
+ *     [0] energy     (1 / n) sum_i |x_i - y| - (1 / (2 n^2)) sum_i sum_j |x_i - x_j|, Euclidean norm, every pair by direct differences
+ *     [1] variogram  sum_{a < b} (|y_a - y_b|^p - (1 / n) sum_i |x_ia - x_ib|^p)^2, p = vs_p; 0 when m = 1
+ *     [2] dss        log det Sigma + (y - mu)' Sigma^-1 (y - mu), Sigma the ddof-1 covariance by two passes (potus_scenario's); NaN when n <= m or
+ *                    a Cholesky pivot is not positive, with status OK
+ * NOT FINITE: a value that is not finite in a column makes that (day, column)'s seven outputs NaN; in a state it also makes that day's national and
+ *   electoral-vote rows NaN and, if the state is used, that day's three multivariate outputs.  No other day is affected.
+ * Every sum runs in an order fixed by (n, the used states) and two constants of the library (tiles of 128 draws, chunks of 64): a day has the same
+ *   bytes alone and inside a range, for any launch shape.  No floating-point atomics.
+ * REFUSED before the device is touched: S > 63 and more than 16 384 draws per block or data set (POTUS_ERR_UNSUPPORTED); an actual that is not
+ *   finite or a share outside [0, 1], use all zero, vs_p outside (0, 2], a bad day range, a null argument (POTUS_ERR_ARG). */
+int potus_forecast_scores_device(int device, const void *block /*[n_draws][n_days][S]*/, long long n_draws, int n_days, int S, const double *w,
+                                 const double *ev, int ev_to_win, const double *actual /*[S + 2]*/, const int32_t *use /*[S]*/, double vs_p,
+                                 double *uni_out, double *multi_out);
+/* The same over the pooled post-warm-up draws of handles that hold one posterior, pooled exactly as potus_scenario pools them (canonical
+ * order, warm-up rows left out, handles with data sets refused with POTUS_ERR_STATE), days [day_begin, day_end). */
+int potus_forecast_scores(const int *handles, int n_handles, int day_begin, int day_end, const double *ev, int ev_to_win,
+                          const double *actual, const int32_t *use, double vs_p, double *uni_out, double *multi_out, long long *n_draws_out);
+/* The same for every data set of one handle (run dates, prior settings) in one call, on potus_timeline's scores: the columns, the energy and
+ * the variogram score of all data sets in one launch each; the joint dss data set after data set (its moments are potus_scenario's kernels, which
+ * take one block of draws).  uni_out [n][days][S + 2][7], multi_out [n][days][3], n_draws_out [n].  A data set with a failed chain gets NaN and
+ * n_draws_out = 0. */
+int potus_forecast_scores_datasets(int handle, int day_begin, int day_end, const double *ev, int ev_to_win, const double *actual,
+                                   const int32_t *use, double vs_p, double *uni_out, double *multi_out, int32_t *n_draws_out);
+/* Milliseconds (HIP events) of the calling thread's last potus_forecast_scores[_device|_datasets]: the columns, the energy score, the variogram
+ * score, the joint DSS (moments, factor and solve). */
+int potus_forecast_scores_timing(double *ms /*[4]*/);
+
 /* ---- .C()-callable wrappers (int* / double* / char** only) ---- */
 void potus_R_create(int *dims /*[8]: N_nat,N_state,T,S,P,M,Pop,variant*/,
                     int *state, int *day_state, int *day_national, int *poll_state,
@@ -944,6 +987,9 @@ void potus_R_outcomes(int *handles, int *n_handles, int *iopts /*[4]: day_begin,
 /* counts as doubles, like potus_R_outcomes; n [2] = n_kept, n_draws; mean and cov are written when iopts[5], the counts when iopts[6] */
 void potus_R_scenario(int *handles, int *n_handles, int *iopts /*[7]: cond_day, day_begin, day_end, ev_to_win, bounds given, moments wanted, counts wanted*/,
                       double *lo, double *hi, int *ev, double *n /*[2]*/, double *mean, double *cov, double *ev_hist, double *tipping, double *joint, int *status);
+/* potus_forecast_scores; n_draws as a double */
+void potus_R_forecast_scores(int *handles, int *n_handles, int *iopts /*[3]: day_begin, day_end, ev_to_win*/, double *ev, double *actual /*[S + 2]*/,
+                             int *use, double *vs_p, double *uni_out, double *multi_out, double *n_draws, int *status);
 
 #ifdef __cplusplus
 }

@@ -769,6 +769,7 @@ __global__ __launch_bounds__(PT_THREADS) void k_run_ds(const DevModel *Mg_all, c
 #include "potus_advi.hpp"       // mean-field ADVI: stochastic-gradient tracks, the ELBO on a chip-wide grid, draws
 #include "potus_eloo.hpp"       // E_loo: expectations under the leave-one-out posteriors, pointwise and as a product on the matrix cores (included last: potus_loo_mm.hpp's reason)
 #include "potus_ppc.hpp"        // posterior predictive checks: replicated polls, PIT and LOO-PIT sums, group statistics (after potus_eloo.hpp: it adds kernels only)
+#include "potus_fscore.hpp"     // proper scoring rules of the joint forecast: CRPS, energy, variogram, Dawid-Sebastiani (it adds kernels only)
 
 // ======================================================================== host
 namespace {
@@ -4367,6 +4368,50 @@ int sc_check(const char *what, int S, const double *lo, const double *hi, const 
   return oc_check(what, S, ev, ev_to_win, nullptr, ev_sum);
 }
 
+// The two-pass moments of the S + 1 coordinates of x [n][n_days][S] (w [S] on the device), in blocks of days that fit the scratch budget:
+// *dmean [n_days][S + 1] and (want_cov) *dcov [n_days][S + 1][S + 1] on the device, owned by tmp; span times the kernels.  Queued on st, not waited for.
+int sc_moments(const char *what, hipStream_t st, DevBufs &tmp, const double *x, long long n, int n_days, int S, const double *dw, bool want_cov, EventTimer &span,
+               double **dmean_out, double **dcov_out) {
+  const int C = S + 1;
+  const size_t n_mean = (size_t)n_days * C, n_cov = (size_t)n_days * C * C;
+  if (n > 65535ll * SC_CHUNK) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld kept draws (the moments take at most %lld)", what, n, 65535ll * SC_CHUNK);
+  const int nchunks = (int)((n + SC_CHUNK - 1) / SC_CHUNK);
+  const size_t per_day = ((size_t)n + (size_t)nchunks * (C + (want_cov ? (size_t)C * C : 0))) * 8;
+  size_t budget = SC_SCRATCH_BUDGET;
+  if (const char *e = getenv("POTUS_SCENARIO_SCRATCH_BUDGET")) budget = std::max<size_t>(1, (size_t)atoll(e));
+  const int dblk = (int)std::min<size_t>((size_t)n_days, std::max<size_t>(1, budget / per_day));
+  double *scratch = nullptr, *dmean = nullptr, *dcov = nullptr;
+  if (const int rc_ = tmp.get(&scratch, per_day * dblk, what)) return rc_;
+  if (const int rc_ = tmp.get(&dmean, n_mean * 8, what)) return rc_;
+  if (want_cov) if (const int rc_ = tmp.get(&dcov, n_cov * 8, what)) return rc_;
+  ScParams P{x, n, n_days, S, 0, nchunks, dw, scratch, scratch + (size_t)dblk * n, scratch + (size_t)dblk * n + (size_t)dblk * nchunks * C, dmean, dcov};
+  const int NT = (C + 15) / 16;
+  HIP_TRY(span.start(st));
+  for (int d0 = 0; d0 < n_days; d0 += dblk) {
+    P.day0 = d0;
+    const dim3 grid((unsigned)std::min(dblk, n_days - d0), (unsigned)nchunks);
+    hipLaunchKernelGGL(k_sc_nat, grid, dim3(SC_THREADS), 0, st, P);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_sc_sum, grid, dim3(SC_THREADS), 0, st, P);
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_sc_finish_mean, dim3(grid.x), dim3(64), 0, st, P);
+    HIP_TRY(hipGetLastError());
+    if (!want_cov) continue;
+    switch (NT) {
+      case 1: hipLaunchKernelGGL(k_sc_gram<1>, grid, dim3(SC_THREADS), 0, st, P); break;
+      case 2: hipLaunchKernelGGL(k_sc_gram<2>, grid, dim3(SC_THREADS), 0, st, P); break;
+      case 3: hipLaunchKernelGGL(k_sc_gram<3>, grid, dim3(SC_THREADS), 0, st, P); break;
+      default: hipLaunchKernelGGL(k_sc_gram<4>, grid, dim3(SC_THREADS), 0, st, P); break;
+    }
+    HIP_TRY(hipGetLastError());
+    hipLaunchKernelGGL(k_sc_finish_cov, dim3(grid.x), dim3(SC_THREADS), 0, st, P);
+    HIP_TRY(hipGetLastError());
+  }
+  HIP_TRY(span.stop(st));
+  *dmean_out = dmean; *dcov_out = dcov;
+  return 0;
+}
+
 // items [nd][n_days][S] on the current device, in canonical order; the condition day's item of draw d at cond + d * cstride.
 // Everything the call returns, in the caller's host arrays (any of them may be null).
 int sc_compute(const char *what, hipStream_t st, const double *items, long long nd, int n_days, int S, const double *cond, long long cstride, const double *w,
@@ -4421,40 +4466,8 @@ int sc_compute(const char *what, hipStream_t st, const double *items, long long 
   if (o.mean && !want_mean) std::fill(o.mean, o.mean + n_mean, nan);
   if (o.cov && !want_cov) std::fill(o.cov, o.cov + n_cov, nan);
   if (want_mean || want_cov) {
-    if (n > 65535ll * SC_CHUNK) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld kept draws (the moments take at most %lld)", what, n, 65535ll * SC_CHUNK);
-    const int nchunks = (int)((n + SC_CHUNK - 1) / SC_CHUNK);
-    const size_t per_day = ((size_t)n + (size_t)nchunks * (C + (want_cov ? (size_t)C * C : 0))) * 8;
-    size_t budget = SC_SCRATCH_BUDGET;
-    if (const char *e = getenv("POTUS_SCENARIO_SCRATCH_BUDGET")) budget = std::max<size_t>(1, (size_t)atoll(e));
-    const int dblk = (int)std::min<size_t>((size_t)n_days, std::max<size_t>(1, budget / per_day));
-    double *scratch = nullptr, *dmean = nullptr, *dcov = nullptr;
-    if (const int rc_ = tmp.get(&scratch, per_day * dblk, what)) return rc_;
-    if (const int rc_ = tmp.get(&dmean, n_mean * 8, what)) return rc_;
-    if (want_cov) if (const int rc_ = tmp.get(&dcov, n_cov * 8, what)) return rc_;
-    ScParams P{kept, n, n_days, S, 0, nchunks, dw, scratch, scratch + (size_t)dblk * n, scratch + (size_t)dblk * n + (size_t)dblk * nchunks * C, dmean, dcov};
-    const int NT = (C + 15) / 16;
-    HIP_TRY(e.start(st));
-    for (int d0 = 0; d0 < n_days; d0 += dblk) {
-      P.day0 = d0;
-      const dim3 grid((unsigned)std::min(dblk, n_days - d0), (unsigned)nchunks);
-      hipLaunchKernelGGL(k_sc_nat, grid, dim3(SC_THREADS), 0, st, P);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_sc_sum, grid, dim3(SC_THREADS), 0, st, P);
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_sc_finish_mean, dim3(grid.x), dim3(64), 0, st, P);
-      HIP_TRY(hipGetLastError());
-      if (!want_cov) continue;
-      switch (NT) {
-        case 1: hipLaunchKernelGGL(k_sc_gram<1>, grid, dim3(SC_THREADS), 0, st, P); break;
-        case 2: hipLaunchKernelGGL(k_sc_gram<2>, grid, dim3(SC_THREADS), 0, st, P); break;
-        case 3: hipLaunchKernelGGL(k_sc_gram<3>, grid, dim3(SC_THREADS), 0, st, P); break;
-        default: hipLaunchKernelGGL(k_sc_gram<4>, grid, dim3(SC_THREADS), 0, st, P); break;
-      }
-      HIP_TRY(hipGetLastError());
-      hipLaunchKernelGGL(k_sc_finish_cov, dim3(grid.x), dim3(SC_THREADS), 0, st, P);
-      HIP_TRY(hipGetLastError());
-    }
-    HIP_TRY(e.stop(st));
+    double *dmean = nullptr, *dcov = nullptr;
+    if (const int rc_ = sc_moments(what, st, tmp, kept, n, n_days, S, dw, want_cov, e, &dmean, &dcov)) return rc_;
     if (want_mean) HIP_TRY(hipMemcpyAsync(o.mean, dmean, n_mean * 8, hipMemcpyDeviceToHost, st));
     if (want_cov) HIP_TRY(hipMemcpyAsync(o.cov, dcov, n_cov * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(hipStreamSynchronize(st));
@@ -5015,6 +5028,192 @@ int potus_grid_compare(int handle, int base, int day_begin, int day_end, const d
 
 int potus_grid_timing(double *ms) {
   return timing_out("potus_grid_timing", g_sg_ms, 2, ms);
+}
+
+// ---------------------------------------------------------------------------------------------- scoring rules of the joint forecast (potus_fscore.hpp)
+namespace {
+thread_local double g_fs_ms[4] = {0.0, 0.0, 0.0, 0.0};   // the last call of this thread: columns, energy, variogram, joint DSS (HIP events)
+constexpr int FS_MAX_GRID = 4096;                        // workgroups of the tile launch; more tiles are grid-strided
+
+// everything about S, ev, actual, use and vs_p: no device needed.  used = the used states, ascending
+int fs_check(const char *what, int S, const double *ev, const double *actual, const int32_t *use, double vs_p, std::vector<int> &used) {
+  if (S < 1 || S > FS_MAX_S) return fail(POTUS_ERR_UNSUPPORTED, "%s: S = %d (the used states of a draw sit in the registers of a lane: 1 .. %d)", what, S, FS_MAX_S);
+  if (!ev || !actual || !use) return fail(POTUS_ERR_ARG, "%s: null ev, actual or use", what);
+  for (int s = 0; s < S; s++) if (!std::isfinite(ev[s])) return fail(POTUS_ERR_ARG, "%s: ev[%d] is not finite", what, s);
+  for (int c = 0; c < S + 2; c++) {
+    if (!std::isfinite(actual[c])) return fail(POTUS_ERR_ARG, "%s: actual[%d] is not finite", what, c);
+    if (c <= S && !(actual[c] >= 0.0 && actual[c] <= 1.0)) return fail(POTUS_ERR_ARG, "%s: actual[%d] = %g outside [0, 1]", what, c, actual[c]);
+  }
+  used.clear();
+  for (int s = 0; s < S; s++) {
+    if (use[s] != 0 && use[s] != 1) return fail(POTUS_ERR_ARG, "%s: use[%d] = %d (0 or 1)", what, s, use[s]);
+    if (use[s]) used.push_back(s);
+  }
+  if (used.empty()) return fail(POTUS_ERR_ARG, "%s: use is all zero (no state enters the multivariate scores)", what);
+  if (!(vs_p > 0.0 && vs_p <= 2.0)) return fail(POTUS_ERR_ARG, "%s: vs_p = %g outside (0, 2]", what, vs_p);
+  return 0;
+}
+int fs_check_draws(const char *what, long long n) {
+  if (n < 1) return fail(POTUS_ERR_ARG, "%s: %lld draws (at least one)", what, n);
+  if (n > PS_RUN) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld draws: a column's draws are sorted in LDS, at most %d", what, n, PS_RUN);
+  return 0;
+}
+
+// x [n_ds][n][nd][S] on the current device, every data set's draws in canonical order -> uni_out [n_ds][nd][S + 2][7], multi_out [n_ds][nd][3] on the host
+int fs_compute(const char *what, hipStream_t st, const double *x, int n_ds, int n, int nd, int S, const double *w, const double *ev, const double *actual,
+               const std::vector<int> &used, double vs_p, double *uni_out, double *multi_out) {
+  const int m = (int)used.size();
+  const long long days = (long long)n_ds * nd;
+  const int nt = (n + FS_TILE - 1) / FS_TILE, tiles = nt * (nt + 1) / 2;
+  if (days * tiles > (1ll << 31) || days > (1 << 24)) return fail(POTUS_ERR_UNSUPPORTED, "%s: %lld days of %d tiles of pairs (at most 2^31 tiles)", what, days, tiles);
+  const size_t n_uni = (size_t)days * (S + 2) * FS_NUNI, n_multi = (size_t)days * FS_NMULTI;
+  DevBufs tmp;
+  EventTimer e[3];   // the columns, the energy score, the variogram score
+  for (EventTimer &t : e) HIP_TRY(t.made);
+  double *dw = nullptr, *dev_ = nullptr, *dact = nullptr, *duni = nullptr, *dmulti = nullptr, *part = nullptr;
+  int *duidx = nullptr, *dflag = nullptr;
+  int rc;
+  if ((rc = tmp.get(&dw, (size_t)S * 8, what)) || (rc = tmp.get(&dev_, (size_t)S * 8, what)) || (rc = tmp.get(&dact, (size_t)(S + 2) * 8, what)) ||
+      (rc = tmp.get(&duidx, (size_t)m * 4, what)) || (rc = tmp.get(&duni, n_uni * 8, what)) || (rc = tmp.get(&dmulti, n_multi * 8, what)) ||
+      (rc = tmp.get(&dflag, (size_t)days * 4, what)) || (rc = tmp.get(&part, (size_t)days * tiles * 2 * 8, what))) return rc;
+  HIP_TRY(hipMemcpyAsync(dw, w, (size_t)S * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dev_, ev, (size_t)S * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(dact, actual, (size_t)(S + 2) * 8, hipMemcpyHostToDevice, st));
+  HIP_TRY(hipMemcpyAsync(duidx, used.data(), (size_t)m * 4, hipMemcpyHostToDevice, st));
+  const FsParams P{x, n_ds, n, nd, S, m, dw, dev_, dact, duidx, vs_p, vs_p == 0.5 ? 1 : vs_p == 1.0 ? 2 : vs_p == 2.0 ? 3 : 0};
+  // ---- the columns
+  const size_t lds = (size_t)n * 8;
+  HIP_TRY(hipFuncSetAttribute(reinterpret_cast<const void *>(k_fs_column), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
+  HIP_TRY(e[0].start(st));
+  hipLaunchKernelGGL(k_fs_column, dim3((unsigned)std::min<long long>(days * (S + 2), 65535)), dim3(PS_THREADS), lds, st, P, duni);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(e[0].stop(st));
+  // ---- the variogram score, and the flag of every day
+  HIP_TRY(e[2].start(st));
+  hipLaunchKernelGGL(k_fs_variogram, dim3((unsigned)std::min<long long>(days, 65535)), dim3(FS_VTHREADS), 0, st, P, dmulti, dflag);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(e[2].stop(st));
+  // ---- the energy score: the tiles, then their partials in tile order
+  const unsigned grid = (unsigned)std::min<long long>(days * tiles, FS_MAX_GRID);
+  HIP_TRY(e[1].start(st));
+  switch ((m + 7) / 8) {   // the used states of a draw, padded to a multiple of eight, are the registers of a lane
+    case 1: hipLaunchKernelGGL(k_fs_energy<8>, dim3(grid), dim3(FS_ETHREADS), 0, st, P, part); break;
+    case 2: hipLaunchKernelGGL(k_fs_energy<16>, dim3(grid), dim3(FS_ETHREADS), 0, st, P, part); break;
+    case 3: hipLaunchKernelGGL(k_fs_energy<24>, dim3(grid), dim3(FS_ETHREADS), 0, st, P, part); break;
+    case 4: hipLaunchKernelGGL(k_fs_energy<32>, dim3(grid), dim3(FS_ETHREADS), 0, st, P, part); break;
+    case 5: hipLaunchKernelGGL(k_fs_energy<40>, dim3(grid), dim3(FS_ETHREADS), 0, st, P, part); break;
+    case 6: hipLaunchKernelGGL(k_fs_energy<48>, dim3(grid), dim3(FS_ETHREADS), 0, st, P, part); break;
+    case 7: hipLaunchKernelGGL(k_fs_energy<56>, dim3(grid), dim3(FS_ETHREADS), 0, st, P, part); break;
+    default: hipLaunchKernelGGL(k_fs_energy<64>, dim3(grid), dim3(FS_ETHREADS), 0, st, P, part); break;
+  }
+  HIP_TRY(hipGetLastError());
+  hipLaunchKernelGGL(k_fs_energy_finish, dim3((unsigned)days), dim3(64), 0, st, (const double *)part, n, tiles, (const int *)dflag, dmulti);
+  HIP_TRY(hipGetLastError());
+  HIP_TRY(e[1].stop(st));
+  // ---- the joint Dawid-Sebastiani score, data set after data set: scenario's two-pass moments, then one workgroup per day.  The moments'
+  // scratch (up to SC_SCRATCH_BUDGET), mean and covariance are one data set's at a time: given back before the next one takes its own.
+  // (n <= m: no covariance of full rank, the score is NaN whatever the draws are)
+  std::vector<std::unique_ptr<EventTimer>> ed;   // per data set: its moments, its factor and solve
+  for (int k = 0; k < n_ds && n > m; k++) {
+    for (int j = 0; j < 2; j++) { ed.emplace_back(new EventTimer()); HIP_TRY(ed.back()->made); }
+    EventTimer &e_mom = *ed[2 * k], &e_fac = *ed[2 * k + 1];
+    double *dmean = nullptr, *dcov = nullptr;
+    DevBufs own;
+    FsParams Pk = P;
+    Pk.x = x + (size_t)k * n * nd * S;
+    if ((rc = sc_moments(what, st, own, Pk.x, n, nd, S, dw, true, e_mom, &dmean, &dcov))) return rc;
+    HIP_TRY(e_fac.start(st));
+    hipLaunchKernelGGL(k_fs_dss, dim3((unsigned)nd), dim3(256), 0, st, Pk, (const double *)dmean, (const double *)dcov, (const int *)(dflag + (size_t)k * nd),
+                       dmulti + (size_t)k * nd * FS_NMULTI);
+    HIP_TRY(hipGetLastError());
+    HIP_TRY(e_fac.stop(st));
+    HIP_TRY(hipStreamSynchronize(st));   // before `own` frees what the kernels read
+  }
+  HIP_TRY(hipMemcpyAsync(uni_out, duni, n_uni * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipMemcpyAsync(multi_out, dmulti, n_multi * 8, hipMemcpyDeviceToHost, st));
+  HIP_TRY(hipStreamSynchronize(st));
+  if (n <= m) for (long long d = 0; d < days; d++) multi_out[d * FS_NMULTI + 2] = std::numeric_limits<double>::quiet_NaN();
+  double ms[4] = {0.0, 0.0, 0.0, 0.0};
+  for (int k = 0; k < 3; k++) if ((rc = e[k].elapsed_or_fail(&ms[k]))) return rc;
+  for (auto &t : ed) { double v = 0.0; if ((rc = t->elapsed_or_fail(&v))) return rc; ms[3] += v; }
+  std::copy(ms, ms + 4, g_fs_ms);
+  return 0;
+}
+} // namespace
+
+int potus_forecast_scores_device(int device, const void *block, long long n_draws, int n_days, int S, const double *w, const double *ev, int ev_to_win,
+                                 const double *actual, const int32_t *use, double vs_p, double *uni_out, double *multi_out) {
+  const char *what = "potus_forecast_scores_device";
+  (void)ev_to_win;   // the electoral votes of a draw are scored as a count
+  if (!block || !w || !uni_out || !multi_out) return fail(POTUS_ERR_ARG, "%s: null block, weights or output", what);
+  if (n_days < 1) return fail(POTUS_ERR_ARG, "%s: %d days (at least one): a bad day range", what, n_days);
+  std::vector<int> used;
+  if (const int rc_ = fs_check(what, S, ev, actual, use, vs_p, used)) return rc_;
+  if (const int rc_ = fs_check_draws(what, n_draws)) return rc_;
+  for (int s = 0; s < S; s++) if (!std::isfinite(w[s])) return fail(POTUS_ERR_ARG, "%s: w[%d] is not finite", what, s);
+  DeviceBlock dev;
+  if (const int rc_ = dev.open(what, device, block)) return rc_;
+  return fs_compute(what, 0, (const double *)block, 1, (int)n_draws, n_days, S, w, ev, actual, used, vs_p, uni_out, multi_out);
+}
+
+// Pooled over the post-warm-up draws of every listed sampler in CANONICAL order, exactly as potus_scenario pools them.
+int potus_forecast_scores(const int *handles, int n_handles, int day_begin, int day_end, const double *ev, int ev_to_win, const double *actual,
+                          const int32_t *use, double vs_p, double *uni_out, double *multi_out, long long *n_draws_out) {
+  const char *what = "potus_forecast_scores";
+  (void)ev_to_win;
+  if (!handles || n_handles < 1) return fail(POTUS_ERR_ARG, "%s: null handle list", what);
+  if (!uni_out || !multi_out) return fail(POTUS_ERR_ARG, "%s: null output", what);
+  Pool P;
+  if (const int rc_ = P.resolve(handles, n_handles, what)) return rc_;
+  if (const int rc_ = P.same_posterior("the scores pool the chains of one")) return rc_;
+  Sampler *s0 = P.s0;
+  const int S = s0->M.S, T = s0->M.T;
+  std::vector<int> used;
+  if (const int rc_ = fs_check(what, S, ev, actual, use, vs_p, used)) return rc_;
+  if (day_begin < 0 || day_end > T || day_begin >= day_end) return fail(POTUS_ERR_ARG, "%s: bad day range [%d,%d) of %d days", what, day_begin, day_end, T);
+  long long most = 0;
+  for (const Sampler *sp : P.sps) most += (long long)sp->R.chains * sp->R.num_samples;
+  if (const int rc_ = fs_check_draws(what, std::max<long long>(most, 1))) return rc_;
+  DeviceGuard guard;
+  DeviceLocks lock(P.devs);
+  DayItems g;
+  if (const int rc_ = gather_days(P, day_begin, day_end, true, -1, g)) return rc_;
+  if (const int rc_ = fs_check_draws(what, g.nd)) return rc_;
+  if (n_draws_out) *n_draws_out = g.nd;
+  return fs_compute(what, s0->stream, g.items, 1, (int)g.nd, day_end - day_begin, S, s0->h_w.data(), ev, actual, used, vs_p, uni_out, multi_out);
+}
+
+// Every data set of one handle, on k_tl_scores' block, in one launch of every kernel.
+int potus_forecast_scores_datasets(int handle, int day_begin, int day_end, const double *ev, int ev_to_win, const double *actual, const int32_t *use,
+                                   double vs_p, double *uni_out, double *multi_out, int32_t *n_draws_out) {
+  const char *what = "potus_forecast_scores_datasets";
+  (void)ev_to_win;
+  Sampler *sp = get(handle);
+  if (!sp) return fail(POTUS_ERR_STATE, "bad handle");
+  if (!uni_out || !multi_out || !n_draws_out) return fail(POTUS_ERR_ARG, "%s: null output", what);
+  std::vector<int> used;
+  if (const int rc_ = fs_check(what, sp->M.S, ev, actual, use, vs_p, used)) return rc_;
+  TlPlan pl;
+  if (const int rc_ = tl_check_args(what, sp, day_begin, day_end, pl)) return rc_;
+  DeviceGuard guard;
+  DeviceLocks lock(sp->device);
+  HIP_TRY(hipSetDevice(sp->device));
+  if (const int rc_ = ds_plan(what, sp, pl)) return rc_;
+  const int S = sp->M.S, nd = pl.nd, n = pl.cpd * pl.n_post, n_ds = pl.n_ds;
+  DevBufs tmp;
+  double *x = nullptr;
+  int *dskip = nullptr;
+  int rc;
+  if ((rc = tmp.get(&x, (size_t)n_ds * n * nd * S * 8, what)) || (rc = tmp.get(&dskip, (size_t)n_ds * 4, what))) return rc;
+  HIP_TRY(hipMemcpyAsync(dskip, pl.skip.data(), (size_t)n_ds * 4, hipMemcpyHostToDevice, sp->stream));
+  if ((rc = tl_scores(sp, pl, day_begin, day_end, dskip, x))) return rc;   // NaN scores for a data set with a failed chain: every score of it is NaN
+  if ((rc = fs_compute(what, sp->stream, x, n_ds, n, nd, S, sp->h_w.data(), ev, actual, used, vs_p, uni_out, multi_out))) return rc;
+  for (int k = 0; k < n_ds; k++) n_draws_out[k] = pl.skip[k] ? 0 : n;
+  return 0;
+}
+
+int potus_forecast_scores_timing(double *ms) {
+  return timing_out("potus_forecast_scores_timing", g_fs_ms, 4, ms);
 }
 
 // ---------------------------------------------------------------------------------------------- exact cross-validation (potus_crossval.hpp)
@@ -7225,6 +7424,14 @@ void potus_R_scenario(int *handles, int *n_handles, int *iopts /*[7]: cond_day, 
   for (size_t i = 0; i < t.size(); i++) tipping[i] = (double)t[i];
   for (size_t i = 0; i < j.size(); i++) joint[i] = (double)j[i];
   n[0] = (double)nk; n[1] = (double)nd;
+}
+
+void potus_R_forecast_scores(int *handles, int *n_handles, int *iopts /*[3]: day_begin, day_end, ev_to_win*/, double *ev, double *actual, int *use, double *vs_p,
+                             double *uni_out, double *multi_out, double *n_draws, int *status) {
+  if (!handles || !n_handles || !iopts || !vs_p || !n_draws) { *status = fail(POTUS_ERR_ARG, "potus_R_forecast_scores: null argument"); return; }
+  long long nd = 0;
+  *status = potus_forecast_scores(handles, *n_handles, iopts[0], iopts[1], ev, iopts[2], actual, use, *vs_p, uni_out, multi_out, &nd);
+  if (!*status) *n_draws = (double)nd;
 }
 
 } // extern "C"

@@ -146,6 +146,14 @@ def load_library():
         L.potus_scenario_device.argtypes = [C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int, dp, C.c_int, dp, dp, i32p, C.c_int, llp, dp, dp, llp, llp, llp]
         L.potus_scenario_timing.argtypes = [dp]
         L.potus_R_scenario.argtypes = [ip, ip, ip, dp, dp, ip, dp, dp, dp, dp, dp, dp, ip]
+    if hasattr(L, "potus_forecast_scores"):             # proper scoring rules of the joint forecast (scoring.py)
+        i32p, llp = C.POINTER(C.c_int32), C.POINTER(C.c_longlong)
+        L.potus_forecast_scores_device.argtypes = [C.c_int, C.c_void_p, C.c_longlong, C.c_int, C.c_int, dp, dp, C.c_int, dp, i32p, C.c_double, dp, dp]
+        L.potus_forecast_scores.argtypes = [ip, C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, i32p, C.c_double, dp, dp, llp]
+        L.potus_forecast_scores_datasets.argtypes = [C.c_int, C.c_int, C.c_int, dp, C.c_int, dp, i32p, C.c_double, dp, dp, i32p]
+        L.potus_forecast_scores_timing.argtypes = [dp]
+        L.potus_R_forecast_scores.argtypes = [ip, ip, ip, dp, dp, ip, dp, dp, dp, dp, ip]
+        L.potus_R_forecast_scores.restype = None
     if hasattr(L, "potus_timeline"):                    # run dates as the data sets of one handle (timeline.py)
         i32p = C.POINTER(C.c_int32)
         L.potus_set_datasets_ex.argtypes = [C.c_int, C.c_int, i32p, i32p, i32p, i32p, dp, dp]
@@ -238,6 +246,7 @@ EXPORTS = [
     "potus_outcomes", "potus_outcomes_device", "potus_outcomes_timing",
     "potus_monitor", "potus_monitor_device",
     "potus_scenario", "potus_scenario_device", "potus_scenario_timing",
+    "potus_forecast_scores", "potus_forecast_scores_device", "potus_forecast_scores_datasets", "potus_forecast_scores_timing", "potus_R_forecast_scores",
     "potus_R_create", "potus_R_init", "potus_R_run", "potus_R_run_many", "potus_R_num_columns", "potus_R_saved_count",
     "potus_R_write_array", "potus_R_write_stan_csv", "potus_R_posterior_summary", "potus_R_diagnostics", "potus_R_check_convergence", "potus_R_backtest_scores", "potus_R_last_error", "potus_R_destroy",
     "potus_R_set_datasets", "potus_R_simulate_prior", "potus_R_sbc_ranks", "potus_R_constrain", "potus_R_loo", "potus_R_outcomes", "potus_R_monitor", "potus_R_scenario",
@@ -1053,6 +1062,11 @@ class Handle:
         from .scenario import scenario
         return scenario([self], ev=ev, given=given, day=day, days=days, ev_to_win=ev_to_win, states=states)
 
+    def forecast_scores(self, ev, actual, **kw):
+        """CRPS, energy, variogram and Dawid-Sebastiani scores of this handle's post-warm-up draws against the result (us_potus_model_amd.scoring.score)."""
+        from .scoring import score
+        return score([self], ev, actual, **kw)
+
     def monitor(self, pars=None, cols=None, probs=(0.025, 0.25, 0.5, 0.75, 0.975)):
         """The summary table of this handle's post-warm-up draws: mean, sd, mad, mcse, R-hat, ESS, quantiles (us_potus_model_amd.monitor)."""
         from .monitor import monitor
@@ -1258,6 +1272,11 @@ class StanFit:
         from .scenario import scenario
         return scenario(self._hs, ev=ev, given=given, day=day, days=days, ev_to_win=ev_to_win, states=states)
 
+    def forecast_scores(self, ev, actual, **kw):
+        """Proper scoring rules of the joint forecast against the result, over every chain of the fit (us_potus_model_amd.scoring.score)."""
+        from .scoring import score
+        return score(self._hs, ev, actual, **kw)
+
     def monitor(self, pars=None, cols=None, probs=(0.025, 0.25, 0.5, 0.75, 0.975)):
         """fit$summary() / print(stanfit) / rstan::monitor over every chain of the fit, on the device (us_potus_model_amd.monitor)."""
         from .monitor import monitor
@@ -1412,6 +1431,12 @@ class Laplace:
         from .scenario import scenario_of_block
         return scenario_of_block(self.scores(days).contiguous(), self._h.data["state_weights"], ev=ev, given=given, day=day, ev_to_win=ev_to_win, states=states)
 
+    def forecast_scores(self, ev, actual, days=None, **kw):
+        """Proper scoring rules of the draws against the result (us_potus_model_amd.scoring.score_of_block on their scores)."""
+        from .scoring import score_of_block
+        T = int(self._h.data["T"])
+        return score_of_block(self.scores(days).contiguous(), self._h.data["state_weights"], ev, actual, days=(T - 1, T) if days is None else days, **kw)
+
     def close(self):
         self._h.close()
 
@@ -1476,6 +1501,12 @@ class Pathfinder:
         """Conditional forecast over the pooled draws (potus_scenario_device on their scores); `day` indexes the range `days`."""
         from .scenario import scenario_of_block
         return scenario_of_block(self.scores(days).contiguous(), self._h.data["state_weights"], ev=ev, given=given, day=day, ev_to_win=ev_to_win, states=states)
+
+    def forecast_scores(self, ev, actual, days=None, **kw):
+        """Proper scoring rules of the draws against the result (us_potus_model_amd.scoring.score_of_block on their scores)."""
+        from .scoring import score_of_block
+        T = int(self._h.data["T"])
+        return score_of_block(self.scores(days).contiguous(), self._h.data["state_weights"], ev, actual, days=(T - 1, T) if days is None else days, **kw)
 
     def close(self):
         self._h.close()
@@ -1544,6 +1575,12 @@ class Variational:
         """Conditional forecast over the pooled draws (potus_scenario_device on their scores); `day` indexes the range `days`."""
         from .scenario import scenario_of_block
         return scenario_of_block(self.scores(days).contiguous(), self._h.data["state_weights"], ev=ev, given=given, day=day, ev_to_win=ev_to_win, states=states)
+
+    def forecast_scores(self, ev, actual, days=None, **kw):
+        """Proper scoring rules of the draws against the result (us_potus_model_amd.scoring.score_of_block on their scores)."""
+        from .scoring import score_of_block
+        T = int(self._h.data["T"])
+        return score_of_block(self.scores(days).contiguous(), self._h.data["state_weights"], ev, actual, days=(T - 1, T) if days is None else days, **kw)
 
     def close(self):
         self._h.close()

@@ -168,6 +168,12 @@ class Timeline:
         from .scenario import scenario_of_block
         return scenario_of_block(self._block(d, self._days(days)), self._w, ev=ev, given=given, day=day, ev_to_win=ev_to_win, states=states)
 
+    def forecast_scores(self, ev, actual, days=None, **kw):
+        """Proper scoring rules of every run date's forecast against the result in one call (potus_forecast_scores_datasets): a ForecastScores
+        whose scores are [dates, days, ...]; days default: election day alone.  A date with a failed chain has NaN scores and n_draws 0."""
+        from .scoring import score_datasets
+        return score_datasets(self.handle, ev, actual, days=self._days(days), **kw)
+
     def close(self):
         self.handle.close()
 
